@@ -1,9 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- batched BM25 top-k throughput of the HIP engine on synthetic corpora (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c1|c4|c5] [--no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c1|c4|c5] [--full [--no-cpu-baseline]]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run builds the index, warms up, times the K steps, writes the last step's rows if --dump-outputs is given and
+prints the result line.  --full adds every other leg: the PCIe-inclusive and steady-state legs, the CPU baseline, the
+oracle checks, and at N > 1 the eager steps that time the kernels for the roofline.  Without --full the fields those
+legs fill are null (config.pcie_inclusive_qps / pcie_inclusive_ms_per_step / steady_state, roofline.pcie_inclusive_frac,
+cpu_baseline; at N > 1 with HIP-graph steps the whole roofline), and there is no parity_check.
+
+--dump-outputs DIR writes what the timed path returned in its last step (rank 0): DIR/doc_ids.npy (float64, exact for the
+int32 ids, -1 = empty slot), DIR/scores.npy (float32), DIR/counts.npy (float64) and DIR/query_index.npy (float64: the
+query of each row).  A batch whose rows exceed 64 MB is cut to a fixed, seeded sample of queries.  The inputs are seeded,
+so two builds run with the same arguments can be compared array for array.
 
 A *step* is one pass of the hot path (srx_search: scoring kernels + merge kernel; for N > 1 also the RCCL exchange of
 the per-shard top-k and the final merge) over one query batch resident in HBM.  Default workload "c3" is the corpus
@@ -29,7 +41,7 @@ Rank 0 prints ONE JSON line (contract in the task statement).  Fields beyond the
                                when that pass profiled THIS kernel source (sha256 of csrc/*.hip + srx_common.h), else null
   cpu_baseline                 the oracle (C/OpenMP restatement of the reference's full-CSR-scan scorer + top-k) timed on
                                this box's host cores on a bounded sample of the same batch
-Every run checks its GPU results against the oracle on a sample of the timed batch and exits non-zero on a mismatch:
+Every --full run checks its GPU results against the oracle on a sample of the timed batch and exits non-zero on a mismatch:
 at N = 1 the sample of the cpu_baseline leg; at N > 1 every rank scores a 32-query sample on its own shard's host CSR,
 rank 0 merges the per-shard lists on the host by (score desc, doc asc) and compares them with the exchanged rows.
 """
@@ -96,6 +108,27 @@ WORKLOADS = {
 }
 HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
 N_CHECK = 32            # N > 1: queries of the timed batch verified against the per-shard oracle
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20250
+
+
+def dump_outputs(path, res, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the (doc ids, scores, counts) rows of one step -> path/{doc_ids,scores,counts,query_index}.npy.
+    Ids and counts go out as float64 (exact for int32), scores as float32.  If the rows exceed max_bytes, a fixed, seeded
+    sample of queries (in batch order) is written instead; query_index.npy names the query of every row."""
+    d, s, c = (x.contiguous().cpu().numpy() for x in res)
+    nq, k = d.shape
+    row_bytes = k * (8 + 4) + 8 + 8
+    rows = np.arange(nq)
+    if nq * row_bytes > max_bytes:
+        rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        rows = np.sort(rng.choice(nq, max_bytes // row_bytes, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "doc_ids.npy"), d[rows].astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), s[rows].astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), c[rows].astype(np.float64))
+    np.save(os.path.join(path, "query_index.npy"), rows.astype(np.float64))
+    log(f"[bench] wrote the last step's rows of {len(rows)} of {nq} queries to {path}")
 
 
 def log(*a):
@@ -217,7 +250,7 @@ def main():
     ap.add_argument("--unit-tiles", type=int, default=0)
     ap.add_argument("--build-unit-tiles", type=int, default=-1,
                     help="tiles per padded run of the posting layout (index build); -1 = the workload's, 0 = automatic")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline AND every oracle check (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline AND every oracle check (profiling runs)")
     ap.add_argument("--debug", type=int, default=0, help="kernel ablation flags (timing experiments only; results are wrong)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget")
     ap.add_argument("--exchange", default="a2a", choices=["a2a", "allgather"], help="N > 1: how per-shard top-k lists meet")
@@ -239,6 +272,10 @@ def main():
                     help="batches kept in flight on separate HIP streams in the steady-state leg (0 = 4 for batches of <= 2048 queries, none otherwise)")
     ap.add_argument("--self-launch", action="store_true",
                     help="dev: take the launcher path (child ranks under torch.distributed.run) even at --gpus 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the PCIe-inclusive and steady-state legs, the CPU baseline, the oracle checks and (N > 1) the eager kernel timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the rows the timed path returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.self_launch):
@@ -278,7 +315,7 @@ def main():
     if args.build_unit_tiles < 0:
         args.build_unit_tiles = w.get("unit_tiles", 0)
     n_docs, V, k, nq = w["n_docs"], w["vocab"], w["k"], w["n_queries"]
-    want_check = not args.no_cpu_baseline          # oracle checks (and, at N = 1, the timed CPU baseline)
+    want_check = args.full and not args.no_cpu_baseline  # oracle checks (and, at N = 1, the timed CPU baseline)
     # --emulate-world: the emulated corpus-wide bounds cut this shard's rows below its own top-k (the other shards' docs
     # would fill them), so the rows are checked as what they must be -- a PREFIX of the oracle's ranked list for the shard
     # that holds every row at or above the query's initial threshold (emulated_bound_check) -- and no CPU baseline is timed
@@ -434,7 +471,14 @@ def main():
     prof = ix.profile_read()
     calls_per_step = calls["n"] / max(1, args.steps)
     kernel_timing = "hipEvents on the search stream around the kernels of every %d-th timed step" % max(1, args.profile_every)
-    if want_graph:
+    if args.dump_outputs and rank == 0:
+        searcher.wait()
+        torch.cuda.synchronize(dev)
+        dump_outputs(args.dump_outputs, res)
+    have_kernel_times = not want_graph or args.full  # graph replays record no events: their kernels are timed by --full only
+    if want_graph and not args.full:
+        result_graph = bool(searcher.graph)  # False if the capture was refused and the eager path ran
+    elif want_graph:
         # the timed steps were graph replays without event records: time the same kernels on a few eager steps now
         searcher.wait()
         torch.cuda.synchronize(dev)
@@ -457,7 +501,7 @@ def main():
 
     # ---- PCIe-inclusive: the same steps fed from host batches through the pinned double-buffered pipeline ----------
     pcie_qps = pcie_ms = None
-    if dist is None:
+    if dist is None and args.full:
         pipe = sparse_rx.HostBatchPipeline(ix, nq, len(q_term), k, depth=args.pipe_depth, zero_copy_queries=not args.pipe_copy,
                                            zero_copy_results=not args.pipe_copy)
         n_p = max(20, min(2 * args.steps, 60))
@@ -497,7 +541,7 @@ def main():
     #      (a) device-resident batches, (b) host batches through the multi-stream HostBatchPipeline ----
     steady = None
     n_streams = args.streams if args.streams > 0 else (4 if (nq <= 2048 and elapsed / args.steps < 0.5e-3) else 0)  # small, short batches only
-    if dist is None and n_streams > 1:
+    if dist is None and n_streams > 1 and args.full:
         ix.set_opts(supertile_log2=args.supertile_log2, target_blocks=args.target_blocks, profile=False, debug=args.debug, unit_tiles=args.unit_tiles)
         n_b = max(200, 20 * args.steps)
         slots = [(torch.cuda.Stream(device=dev), torch.empty(max(ix.workspace_bytes(nq, k), 1 << 16), dtype=torch.uint8, device=dev),
@@ -611,6 +655,8 @@ def main():
                      "batch_achieved": batch_achieved, "batch_frac": batch_achieved / (HBM_PEAK_GBPS * world),
                      "pcie_inclusive_frac": (alg_total / (pcie_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if pcie_ms else None},
     }
+    if not have_kernel_times:
+        result["roofline"] = None
 
     oracle_mode = None
     if want_check:

@@ -67,9 +67,9 @@ sha = sparse_rx._capi.kernel_sources_sha256()
 lines.append(f"kernel sources sha256 (csrc/*.hip + srx_common.h) = {sha}")
 args = open(out + "/args.txt").read().strip() if os.path.exists(out + "/args.txt") else ""
 open(f"profiles/{name}_rocprofv3_summary.txt", "w").write(
-    f"# rocprofv3 --kernel-trace --stats of: python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline {args} (3 warm-up + 20 timed "
+    f"# rocprofv3 --kernel-trace --stats of: python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline {args} (3 warm-up + 20 timed "
     "launches, then the PCIe-inclusive loop), then separate --pmc passes of: python3 bench.py --steps 5 --warmup 1 "
-    f"--no-cpu-baseline {args}; workload key {wkey}, 1 x MI355X\n"
+    f"--full --no-cpu-baseline {args}; workload key {wkey}, 1 x MI355X\n"
     + "\n".join(lines) + "\n")
 tj = {}
 if os.path.exists("profiles/traffic.json"):
