@@ -599,6 +599,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
         // wave's stores (write-through, straight to memory) must be acknowledged: an explicit s_waitcnt -- a workgroup-scope
         // release fence compiles to NOTHING here (a workgroup of one wave is its own scope), which let the last split read
         // lists that were still in flight (caught by bench.py's multi-stream parity check on C2).
+        // This hand-off is outside the HIP memory model; it rests on three properties of gfx950, and
+        // tests/test_search_plans.py (split queries on several streams at once) is its regression guard:
+        //   * global stores are counted in vmcnt, so vmcnt(0) means this wave's list stores have been acknowledged;
+        //   * agent-scope relaxed stores write through the XCD's L2 to memory: an acknowledged store is visible device-wide;
+        //   * agent-scope relaxed loads are coherent across the XCD L2s: the merging wave, on any XCD, reads memory, not a
+        //     stale line of its own L2.
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         unsigned old = 0;

@@ -161,6 +161,8 @@ class ShardedSearcher:
     torch-tensor functions on one device.  The product wiring is :meth:`for_device_index` (HIP engine:
     ``srx_search`` + ``srx_merge_topk_packed``); tests inject CPU callables to exercise the protocol under gloo."""
 
+    LANE_KEYS = 4  # graph lanes: the tensor sets whose captured graphs are kept (_search_graph)
+
     def __init__(self, local_search: Callable, pack: Callable, merge: Callable, group=None,
                  local_search_packed: Callable = None, merge_packed_out: Callable = None):
         self.local_search = local_search
@@ -246,15 +248,28 @@ class ShardedSearcher:
         without a single event between them, and a step costs the host one graph launch (measured on one GPU, RCCL group of
         one rank: the eager overlap path needs ~0.25 ms of Python + launches per step -- more than the 0.21 ms the GPU needs).
         The rows of batch i stay valid until lane i & 1 is replayed again (two batches later); :meth:`wait` joins both lanes.
+        A replay is ordered after the work the caller has queued on its current stream (the refill of the fixed query
+        buffers, typically).  Graphs are kept for the last ``LANE_KEYS`` tensor sets; an older set's graphs are released.
         Returns None (and switches itself off) when the capture is not possible on this stack: the eager path then runs."""
         import torch
         dev = q_ptr.device
         key = (q_ptr.data_ptr(), q_term.data_ptr(), q_weight.data_ptr(), int(q_ptr.shape[0]), int(q_term.shape[0]), k, self.mode, world)
         if getattr(self, "_lanes", None) is None:
             self._lanes, self._lane_step = {}, 0
+        cur = torch.cuda.current_stream(dev)
         lanes = self._lanes.get(key)
         if lanes is None:
-            cur = torch.cuda.current_stream(dev)
+            if getattr(self, "_lane_streams", None) is None:
+                # Two streams for every tensor set: lane i of every set shares its send / receive buffers (self._buf is
+                # keyed by shape), so all of them must run on one stream.
+                self._lane_streams = [torch.cuda.Stream(device=dev) for _ in range(2)]
+            while len(self._lanes) >= self.LANE_KEYS:
+                # Lanes are keyed by data_ptr: a caller with fresh tensors every batch would capture two graphs per call.
+                # Drop the oldest set once its replays are done.
+                old = self._lanes.pop(next(iter(self._lanes)))
+                for st_old, g_old, *_ in old:
+                    st_old.synchronize()
+                    g_old.reset()
             lanes = []
             try:
                 import torch.distributed as dist
@@ -265,7 +280,7 @@ class ShardedSearcher:
                     ranks = dist.get_process_group_ranks(self.group) if self.group is not None else list(range(dist.get_world_size()))
                     self._lane_groups = [dist.new_group(ranks=ranks) for _ in range(2)]
                 for li in range(2):
-                    st = torch.cuda.Stream(device=dev)
+                    st = self._lane_streams[li]
                     ws = torch.empty(max(int(self.workspace_bytes(q_ptr.shape[0] - 1, k)), 1 << 16), dtype=torch.uint8, device=dev)
                     st.wait_stream(cur)
                     with torch.cuda.stream(st):
@@ -285,6 +300,7 @@ class ShardedSearcher:
             self._lanes[key] = lanes
         st, g, out, _ = lanes[self._lane_step & 1]
         self._lane_step += 1
+        st.wait_stream(cur)  # the caller's query tensors: the replay reads them in place
         with torch.cuda.stream(st):
             g.replay()
         return out
@@ -385,19 +401,15 @@ class ShardedSearcher:
         side = getattr(self, "_side", None)
         if side is not None:
             torch.cuda.current_stream(side.device).wait_stream(side)
-        for lanes in (getattr(self, "_lanes", None) or {}).values():
-            for st, *_ in lanes:
-                torch.cuda.current_stream(st.device).wait_stream(st)
+        for st in getattr(self, "_lane_streams", None) or []:
+            torch.cuda.current_stream(st.device).wait_stream(st)
 
     def close(self) -> None:
         """Join the lanes and drop their captured graphs (they hold RCCL work: destroy them BEFORE the process group)."""
         import torch
-        lanes = getattr(self, "_lanes", None)
-        if lanes:
-            for ls in lanes.values():
-                for st, *_ in ls:
-                    st.synchronize()
-            self._lanes = {}
+        for st in getattr(self, "_lane_streams", None) or []:
+            st.synchronize()
+        self._lanes = {}
         if getattr(self, "_side", None) is not None:
             self._side.synchronize()
         self._buf = None

@@ -110,3 +110,83 @@ def np_compact_blocks(post, unit_docs, val_dtype=np.float32):
     out[:, 1] = (loc[:, 2] | (loc[:, 3] << 16)).astype(np.uint32).view(np.int32)
     out[:, 2:] = b[:, 4:]
     return out.reshape(-1)
+
+
+# ---- the search planner, restated (csrc/sparse_rx.hip: make_plan, srx_search_workspace_bytes, search_impl) -----------------
+# Constants of csrc/srx_common.h / sparse_rx.hip.  The GPU tests pin this restatement to the library through
+# DeviceIndex.workspace_bytes, which is a function of the plan: a planner change that moves a case to another bucket fails
+# the case instead of letting it test something else silently.
+PLAN_DEFAULT_TARGET = 3072  # make_plan: wave-sized work items per batch when target_blocks is 0
+PLAN_MERGE_CANDIDATES = 4096  # MERGE_NPT * THREADS: the merge takes <= 4096 candidates (2 tiers x splits x k)
+PLAN_MAX_TPS = 64  # MAX_TPS
+W1_KMAX = 112  # largest k tier 1 ranks (larger k: every work item goes to tier 2)
+W_KMAX = 128  # largest k the merge wave kernel ranks
+MW_CAP = 1024  # merge wave kernel: lists_per_q * k candidates at most
+W1_LCAP = 256  # tier 1's list capacity: the in-kernel merge selects down to k when count + c2 would exceed it
+T2_GRID_MAX = 1024  # tier 2's persistent grid: min(items, 1024) workgroups ...
+T2_GRID_SMALL = 128  # ... or 128 when the previous search of the index left the worklist empty
+
+
+def plan(n_tiles, unit_tiles, nq, k, target_blocks=0):
+    """make_plan for an index searched with the unit it was built for.  Returns a dict with n_super, n_splits, n_whole,
+    lists_per_q, items (tier-1 work items = the grid of the wave kernel), ovf_words, merge_kernel ("wave" |
+    "block" | None when no query is split), in_kernel_merge (the last split to arrive merges the query inside tier 1,
+    unless a split handed work to tier 2), t2_everything (tier 1 ranks nothing: every item goes to tier 2) and t2_full
+    (tier 2's full grid)."""
+    tpu = min(max(int(unit_tiles), 1), PLAN_MAX_TPS)
+    n_super = (int(n_tiles) + tpu - 1) // tpu
+    target = target_blocks if target_blocks > 0 else PLAN_DEFAULT_TARGET
+    ns = target // (nq if nq > 0 else 1)
+    n_whole = 0
+    if nq > target:
+        n_whole = nq // target * target
+        tail = nq - n_whole
+        ns = target // tail if tail > 0 else 1
+        ns = max(min(ns, 4), 2)
+        if tail == 0:
+            ns = 1
+    ns = max(ns, 1)
+    ns = min(ns, n_super)
+    ns = min(ns, PLAN_MERGE_CANDIDATES // (2 * (k if k > 0 else 1)))
+    ns = max(ns, 1)
+    if ns == 1:
+        n_whole = 0
+    lists_per_q = 2 * ns
+    merge = None
+    if nq - n_whole > 0:
+        merge = "wave" if (k <= W_KMAX and lists_per_q * k <= MW_CAP and lists_per_q <= 256) else "block"
+    items = n_whole + (nq - n_whole) * ns
+    return {"n_super": n_super, "n_splits": ns, "n_whole": n_whole, "tail": nq - n_whole if ns > 1 else 0,
+            "lists_per_q": lists_per_q, "items": items, "ovf_words": (n_super + 31) // 32, "merge_kernel": merge,
+            "in_kernel_merge": ns > 1 and k <= W1_KMAX, "t2_everything": k > W1_KMAX, "t2_full": min(items, T2_GRID_MAX)}
+
+
+def plan_workspace_bytes(p, nq, k):
+    """srx_search_workspace_bytes of a plan: candidate lists, counts, overflow bitmaps, arrival counters, worklist."""
+    lists = nq * p["lists_per_q"]
+    items = p["items"]
+    return lists * k * 8 + lists * 4 + items * p["ovf_words"] * 4 + 4 * (1 + (nq - p["n_whole"])) + 4 * items + 256
+
+
+def t2_grid(p, hint):
+    """The tier-2 grid search_impl launches for plan `p` when the index's hint word (the worklist length of a recent
+    search) reads `hint`."""
+    return T2_GRID_SMALL if (hint == 0 and not p["t2_everything"] and p["t2_full"] > T2_GRID_SMALL) else p["t2_full"]
+
+
+def plan_label(p, k):
+    """A case's name in the bucket terms of the planner."""
+    if p["n_splits"] == 1:
+        shape = "whole"
+    elif p["n_whole"] > 0:
+        shape = f"mixed{p['n_whole']}+{p['tail']}x{p['n_splits']}"
+    else:
+        shape = f"split{p['n_splits']}"
+    parts = [shape, f"k{k}"]
+    if p["merge_kernel"]:
+        parts.append(f"merge-{p['merge_kernel']}")
+    if p["in_kernel_merge"]:
+        parts.append("inkernel")
+    if p["t2_everything"]:
+        parts.append("t2all")
+    return "-".join(parts)

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle  # noqa: E402  (checker only)
-from parity import assert_canonical_order, assert_ranked_equal  # noqa: E402
+from parity import assert_canonical_order, assert_ranked_equal, plan, plan_workspace_bytes  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -496,8 +496,8 @@ def test_larger_properties(rx):
 
 def test_c3_full_size_properties(rx):
     """BASELINE config C3 at FULL size (10 M docs x 100 k vocab, 10^9 postings, 10 k queries x 8 terms, k = 100), corpus
-    generated on the device like bench.py does.  The oracle's full-CSR scan is bench.py's job at this size (it checks a
-    sample of every run); here the size-independent properties: canonical order, doc-unique rows, k-prefix property,
+    generated on the device like bench.py does.  The oracle on 16 whole queries and 32 queries of the split tail (the batch
+    is 9 216 whole queries + 784 queries in 3 splits each), and the size-independent properties: canonical order, doc-unique rows, k-prefix property,
     idempotence, and -- the strong one -- every query of a 96-query sub-batch returns bit-identical rows when searched
     alone (64 doc-range splits + tier-2 lists + merge kernel) and inside the 10 k batch (unsplit, ranked by tier 1)."""
     import torch
@@ -513,6 +513,10 @@ def test_c3_full_size_properties(rx):
     df = torch.bincount(cols, minlength=V).cpu().numpy()
     idf = torch.as_tensor(np.log((n_docs - df + 0.5) / (df + 0.5)).astype(np.float32), device=dev)
     avgdl = float(np.mean(dl.cpu().numpy()))
+    indptr = torch.zeros(n_docs + 1, dtype=torch.int64, device=dev)  # the doc-major CSR on the host, for the oracle samples
+    indptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_docs), 0)
+    host = (indptr.cpu().numpy(), cols.cpu().numpy(), tf.cpu().numpy(), dl.cpu().numpy())
+    del indptr
     ix = rx.DeviceIndex.from_coo(rows, cols, tf, idf, n_docs, doc_lengths=dl, avgdl=avgdl, device=dev, tile_log2=14)
     del rows, cols, tf
     assert ix.post16 is not None and ix.nnz > 990_000_000
@@ -525,6 +529,17 @@ def test_c3_full_size_properties(rx):
     assert np.array_equal(d, d2) and np.array_equal(s.view(np.uint32), s2.view(np.uint32)) and np.array_equal(n, n2)
     d10, s10, n10 = ix.search(*q, 10)
     assert np.array_equal(d10, d[:, :10]) and np.array_equal(s10.view(np.uint32), s[:, :10].view(np.uint32))
+    # the oracle on the two kinds of queries of the batch's plan: whole queries (ranked inside tier 1) and the tail of the
+    # last partial round, each query cut into 3 doc-range splits and merged by the split that arrives last
+    p = plan(ix.n_tiles, ix.unit_tiles, nq, k)
+    assert plan_workspace_bytes(p, nq, k) == ix.workspace_bytes(nq, k)
+    assert (p["n_whole"], p["n_splits"], p["in_kernel_merge"]) == (9216, 3, True)
+    idf_np = idf.cpu().numpy()
+    for lo, hi in ((0, 16), (9216, 9232), (9984, 10_000)):
+        qs = _sub_batch(q, lo, hi)
+        exp = oracle.search_batch(host[0], host[1], host[2], host[3], idf_np, qs[0], qs[1], qs[2], k, 1.2, 0.75, avgdl, native=True)
+        _assert_exact((d[lo:hi], s[lo:hi], n[lo:hi]), exp, f"c3 oracle sample, queries {lo}..{hi - 1}")
+    del host
     lo, hi = 5000, 5096                                          # a sub-batch: other work-item plan (splits + merge)
     qs = ((q[0][lo: hi + 1] - q[0][lo]).astype(np.int32), q[1][q[0][lo]: q[0][hi]], q[2][q[0][lo]: q[0][hi]])
     ds, ss, ns = ix.search(*qs, k)
