@@ -122,12 +122,10 @@ typedef struct {
     int32_t profile;        /* N > 0: bracket the kernels of every N-th search with hipEvents (read with srx_profile_read); an
                              * event record between two kernels costs the stream a few microseconds, so sampling keeps the
                              * timed steps close to unprofiled ones */
-    int32_t reserved;       /* debug bits.  Exact results: 8 = every query through the tier-2 (block) kernel, 16 = ignore
-                             * term_bound, 128 = no flat-tile path in tier 2, 256 = block merge kernel only, 2048 = no wave-level
-                             * dense tiles, 4096 = their masked form even on one-tile units, 8192 = their general selection.  Timing
-                             * experiments with WRONG results (bench ablations): 1 = no multi-term doc resolution, 2 = no
-                             * candidate screening, 4 = loads only, 32 = no final ranking, 512 = multi-term docs located but
-                             * not summed, 1024 = ... summed but not appended. */
+    int32_t reserved;       /* debug bits: alternative paths with the same, exact results.  8 = every query through the
+                             * tier-2 (block) kernel, 16 = ignore term_bound, 128 = no flat-tile path in tier 2, 256 = block
+                             * merge kernel only, 2048 = no wave-level dense tiles, 4096 = their masked form even on one-tile
+                             * units, 8192 = their general selection.  Any other bit: SRX_ERR_INVALID. */
     int32_t unit_tiles;     /* docs per unit = unit_tiles * 2^tile_log2 (1..64, need not be a power of two); 0 = the index's.
                                Takes precedence over supertile_log2. */
 } srx_search_opts;
@@ -264,7 +262,6 @@ int srx_build_compact(int32_t device, int32_t val_type, const int32_t *post, int
  * (the host-side mirror measured ~1 ms per copy call that way: more than a whole C2 search). */
 int srx_memcpy_async(void *dst, const void *src, int64_t bytes, void *stream);
 
-/* ---- profiling (bench.py roofline leg) ------------------------------------------------------------ */
 /* Dense INT8 side of the same service.  Replaces quantized_dot_product_batch
  * (rag_system/core/retriever_registry.py:90-117; NumPy twin :538-548) + the top-k that follows it (:505-519):
  *   score[q][d] = f32( f64(sum_i queries[q][i] * corpus[d][i]) * query_scale[q] * corpus_scale[d] )   (int8 x int8 -> int32,

@@ -12,12 +12,8 @@
 namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-#ifndef SRX_DENSE_NW_LONG
-#define SRX_DENSE_NW_LONG 4  // waves per workgroup of the filter kernel on rows longer than 384 bytes (8: measured, no gain)
-#endif
-#ifndef SRX_DENSE_PF
-#define SRX_DENSE_PF 6  // LDS reads of query fragments in flight ahead of the MFMAs
-#endif
+constexpr int DENSE_NW_LONG = 4;  // waves per workgroup of the filter kernel on rows longer than 384 bytes (8: measured, no gain)
+constexpr int DENSE_PF = 6;       // LDS reads of query fragments in flight ahead of the MFMAs
 constexpr int DENSE_CNT_STRIDE = 32;  // ints between two queries' candidate counters: one 128-byte line each (all waves
                                       // add to these: counters sharing a line serialise in one L2 channel)
 
@@ -116,24 +112,6 @@ struct DenseTab {    // per query of the pass (<= 1 024)
     unsigned tau[1024];
     float qs[1024];
 };
-// In-kernel stamps of the filter kernel (diagnostic build -DSRX_DSTAMP, tools/dense_stamp_run.py): s_memtime ticks per phase,
-// summed over waves.
-#ifdef SRX_DSTAMP
-__device__ unsigned long long g_dstamp[16];
-#define DSTAMP(i)                                                                        \
-    do {                                                                                 \
-        unsigned long long t_;                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                               \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");        \
-        __builtin_amdgcn_sched_barrier(0);                                               \
-        dst_acc[i] += t_ - dst_prev;                                                     \
-        dst_prev = t_;                                                                   \
-    } while (0)
-#else
-#define DSTAMP(i) \
-    do {          \
-    } while (0)
-#endif
 // ds_read_b128 with a compile-time offset, issued where it stands (the scheduler sinks plain LDS reads down to one MFMA before
 // their use); the consumer waits with lds_wait<N>, which also ties the value to the wait
 template <int OFF>
@@ -157,7 +135,7 @@ __device__ __forceinline__ void static_for(F &&f) {
 // screen the tile before, a barrier per phase -- 12-30 % slower: the screening phase (staging issue + screen + wait) is
 // 1.7 x the MFMA phase, and a lock-step pair runs at the pace of the longer one.)
 template <int KS>
-constexpr int dense_filter_waves() { return KS > 12 ? SRX_DENSE_NW_LONG : 4; }
+constexpr int dense_filter_waves() { return KS > 12 ? DENSE_NW_LONG : 4; }
 
 template <int KS>
 __global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgpu_waves_per_eu(2))) void srx_dense_i8_filter_kernel(const int8_t *__restrict__ corpus,
@@ -186,10 +164,6 @@ __global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgp
     const int64_t d0 = ((int64_t)blockIdx.x * NW + wv) * (32 * DT);  // may lie past the corpus: the wave then only helps
     constexpr int DIM = KS * 32;                                      // staging and takes part in the barriers
     const int n_qt = (nq + 31) / 32;
-#ifdef SRX_DSTAMP
-    unsigned long long dst_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dst_prev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dst_prev)::"memory");
-#endif
     // global -> LDS without a trip through registers (global_load_lds_dwordx4: lane l of a wave writes 16 bytes at the wave's
     // LDS base + 16 l): wave w copies the 64-fragment rows w, w + NW, ... of the tile -- EXACTLY ROWS loads per wave and tile
     // (a wave with a row too many re-copies the last row of its share: same bytes, same place), so that the wait for a tile can
@@ -270,7 +244,7 @@ __global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgp
     // reads one ahead and puts each group's bounds right before their use: four more LDS round trips per tile).  LDS reads
     // return in order, so before step s at most min(PF - 1, KS - 1 - s) younger reads may still be out.
     auto do_mfma = [&](int tile) __attribute__((always_inline)) {
-        constexpr int PF = KS < SRX_DENSE_PF ? KS : SRX_DENSE_PF;
+        constexpr int PF = KS < DENSE_PF ? KS : DENSE_PF;
         v4i Ab[PF];
 #pragma unroll
         for (int t = 0; t < DT; ++t) acc[t] = (v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -356,15 +330,11 @@ __global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgp
     auto phase_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    DSTAMP(0);  // prologue: B fragments, table, first tiles staged
     for (int qt = 0; qt < n_qt; ++qt) {
         const bool more = qt + PD < n_qt;                  // uniform
         if (more) stage_tile(qt + PD, (qt + PD) % NBUF);  // that buffer was last read in tile qt - 1: one barrier ago
-        DSTAMP(1);  // stage issue
         do_mfma(qt);
-        DSTAMP(2);  // MFMA loop (to the issue of the last one)
         do_epilogue(qt);
-        DSTAMP(3);  // epilogue (waits for the accumulators first)
         if (cnt >= DENSE_CB / 2) flush();  // uniform
         // my share of tile qt + 1 has landed (with three buffers it was issued a whole tile ago, and the loads of tile qt + 2
         // stay in flight).  Loads return in order; stores / atomics of mine (a flush) may not, so after one everything is drained.
@@ -373,18 +343,9 @@ __global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgp
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         dirty = false;
-        DSTAMP(4);  // flush, wait for the staged tile
         phase_barrier();  // every wave's share of tile qt + 1 is in LDS; tile qt's buffer is free
-        DSTAMP(5);  // barrier
     }
     if (cnt > 0) flush();
-    DSTAMP(6);  // final flush
-#ifdef SRX_DSTAMP
-    if (lane == 0) {
-        for (int i = 0; i < 7; ++i) atomicAdd(&g_dstamp[i], dst_acc[i]);
-        atomicAdd(&g_dstamp[8], 1ull);
-    }
-#endif
 }
 
 // Row top-k: one workgroup per (query, split of the doc range) folds its slice of the score row into an exact lazy
@@ -490,10 +451,6 @@ int64_t dense_sample(int64_t n_docs, int k) {
     // the sample pass itself is what counts (k = 10: 1.14 -> 1.11 ms at 4 096, sweep in profiles/r03_dense_filter_variants.log)
     const int64_t floor_s = 164ll * k < 4096 ? 4096 : (164ll * k > 16384 ? 16384 : 164ll * k);
     if (S < floor_s) S = floor_s;
-#ifdef SRX_DENSE_KNOBS  // dev build: scale the sample (tools/r3_run33.sh)
-    if (const char *e = getenv("SRX_DENSE_SAMPLE_MULT")) S = (int64_t)((double)S * atof(e));
-    if (S < 2048) S = 2048;
-#endif
     S = (S + 127) / 128 * 128;
     return (S * 4 <= n_docs) ? S : 0;
 }
@@ -605,7 +562,7 @@ int dense_search_i8_impl(int32_t device, const int8_t *corpus, const float *corp
             // sample's) is the threshold of the second round over [S1, n): about k (S1 / S + n / S1) survivors per query instead
             // of k n / S -- 4x fewer exact-path rows and buffer appends at 1 M docs.  Both rounds append to the same buffers.
             const int ks = dim / 32;
-            const int filter_waves = ks > 12 ? SRX_DENSE_NW_LONG : 4;  // = dense_filter_waves<KS>()
+            const int filter_waves = ks > 12 ? DENSE_NW_LONG : 4;  // = dense_filter_waves<KS>()
             const int filter_threads = 64 * filter_waves;
             const int64_t docs_per_block = (ks <= 12 ? 64 : 32) * filter_waves;
             int64_t S1 = (int64_t)sqrt((double)S * (double)n_docs);
@@ -842,12 +799,3 @@ int dense_rows_search(const char *who, int32_t device, const void *rows, const f
     return SRX_OK;
 }
 }  // namespace
-
-#ifdef SRX_DSTAMP
-extern "C" __attribute__((visibility("default"))) int srx_debug_read_dstamps(unsigned long long *h_out16) {
-    HIP_TRY(hipMemcpyFromSymbol(h_out16, HIP_SYMBOL(g_dstamp), sizeof(unsigned long long) * 16));
-    unsigned long long z[16] = {0};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dstamp), z, sizeof(z)));
-    return SRX_OK;
-}
-#endif

@@ -25,35 +25,6 @@
 
 thread_local char srx_g_err[512] = "";
 
-#ifdef SRX_STAMP2
-__device__ unsigned long long g_stamp2[16];
-#define T2_T0() unsigned long long t2_prev = __builtin_amdgcn_s_memtime()
-#define T2(i)                                                                    \
-    do {                                                                         \
-        if (threadIdx.x == 0) {                                                  \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();           \
-            atomicAdd(&g_stamp2[i], t_ - t2_prev);                                \
-            t2_prev = t_;                                                        \
-        }                                                                        \
-    } while (0)
-#define T2C(i) do { if (threadIdx.x == 0) atomicAdd(&g_stamp2[i], 1ull); } while (0)
-#define T2L_T0() unsigned long long t2l_prev = __builtin_amdgcn_s_memtime()
-#define T2L(i)                                                                   \
-    do {                                                                         \
-        if (threadIdx.x == 0) {                                                  \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();           \
-            atomicAdd(&g_stamp2[i], t_ - t2l_prev);                               \
-            t2l_prev = t_;                                                       \
-        }                                                                        \
-    } while (0)
-#else
-#define T2L_T0() do { } while (0)
-#define T2L(i) do { } while (0)
-#define T2_T0() do { } while (0)
-#define T2(i) do { } while (0)
-#define T2C(i) do { } while (0)
-#endif
-
 namespace {
 
 // Scoring kernel: one workgroup per (query, split of the doc range).
@@ -72,9 +43,6 @@ struct ScoreShared {
     int n_grp;
     unsigned ub_bits;  // srx_search_after: only candidates ranked strictly AFTER (ub_bits, ub_doc) in (score desc, doc asc)
     int ub_doc;        // order are collected; ub_bits = 0xFFFFFFFF: no bound (every score's bit pattern is below it)
-#ifdef SRX_T2_PAD_WORDS
-    int occupancy_pad[SRX_T2_PAD_WORDS];  // dev experiment: more LDS per workgroup = fewer workgroups per CU
-#endif
 };
 
 // srx_search_after's exclusive upper bound on (score bits, shard-local doc): true when the candidate ranks after it
@@ -139,7 +107,7 @@ struct Tier2Final {
 // CP: the index dropped its canonical blocks -- postings come from the compact copy (16-bit local ids + ubase = the unit's
 // first doc); every posting of a call then lies in ONE build unit (the host refuses unit overrides on such an index).
 template <typename VT, bool AFTER, bool CP>
-__device__ void hash_unit(ScoreShared &S, const IndexView &ix, int nt, int my_len, int k, int ubase, int dbg = 0) {
+__device__ void hash_unit(ScoreShared &S, const IndexView &ix, int nt, int my_len, int k, int ubase) {
     const int tid = threadIdx.x;
     int *keys = reinterpret_cast<int *>(S.tbl);
     float *vals = reinterpret_cast<float *>(S.tbl + SLOTS);
@@ -179,7 +147,7 @@ __device__ void hash_unit(ScoreShared &S, const IndexView &ix, int nt, int my_le
             if (s < n_steps) {
                 const int i = S.st_term[s];
                 if (s > 0 && S.st_term[s - 1] != i) __syncthreads();  // next term: order adds per doc
-                if (d[r] >= 0 && !(dbg & 2)) {
+                if (d[r] >= 0) {
                     const float c = (v[r] * S.m_idf[i]) * S.m_qw[i];
                     unsigned h = ((unsigned)d[r] * 0x9E3779B1u) >> (32 - 13);
                     for (;;) {
@@ -220,7 +188,7 @@ __device__ void hash_unit(ScoreShared &S, const IndexView &ix, int nt, int my_le
         }
     }
     __syncthreads();  // table is free from here: vals region doubles as the radix histogram
-    if (!(dbg & 1)) topk_fold<NPT_HASH, true>(ubits, udoc, k, S.tk, S.tbl + SLOTS);
+    topk_fold<NPT_HASH, true>(ubits, udoc, k, S.tk, S.tbl + SLOTS);
 }
 
 // Dense-accumulate one tile of G docs [tile_base, tile_base + G) described by m_start/m_len.
@@ -237,15 +205,12 @@ __device__ void dense_tile_accumulate(ScoreShared &S, const IndexView &ix, int n
         __syncthreads();
     }
     // Batches of 2048 postings (two stripes of whole blocks = 8 postings per thread) are enumerated term-major; a ring
-    // of SRX_DENSE_DEPTH batches is in flight, across term boundaries too, so a term's load latency hides behind the
+    // of K = 4 batches is in flight, across term boundaries too, so a term's load latency hides behind the
     // previous terms' work (one batch ahead left the dense tiles latency-bound).  A barrier separates consecutive
     // batches of different terms (the next term may touch the same doc).  A tile's run [start, start + len) starts at
     // an arbitrary padded position: the batches cover the blocks from start & ~3 on, postings outside the run and
     // sentinels (doc -1) are blanked.
-#ifndef SRX_DENSE_NB
-#define SRX_DENSE_NB 8
-#endif
-    constexpr int NB = SRX_DENSE_NB;      // postings per thread per batch (whole blocks of 4)
+    constexpr int NB = 8;                 // postings per thread per batch (whole blocks of 4)
     constexpr int BATCH = THREADS * NB;
     auto next_term = [&](int i) {  // first term index >= i with postings in this tile (uniform), nt if none
         while (i < nt && S.m_len[i] == 0) ++i;
@@ -300,10 +265,7 @@ __device__ void dense_tile_accumulate(ScoreShared &S, const IndexView &ix, int n
     // K batches in flight: register set j holds batch n with n % K == j; after batch n has been accumulated its set is
     // refilled with batch n + K.  (One batch ahead left a many-term tile -- 50 terms of < 1 batch each -- paying one full
     // memory round trip per term: profiles/r02_c4_*.)
-#ifndef SRX_DENSE_DEPTH
-#define SRX_DENSE_DEPTH 4
-#endif
-    constexpr int K = SRX_DENSE_DEPTH;
+    constexpr int K = 4;
     int qi[K], qo[K];  // term / offset of the batch in set j (qi == nt: none)
     int dq[K][NB];
     float vq[K][NB];
@@ -611,10 +573,7 @@ __device__ void wave_dense_accumulate(ScoreShared &S, const IndexView &ix, int n
 #pragma unroll
         for (int c = 0; c < 4; ++c) *slot[c] = a[c] + (b.v[c] * b.idf) * b.qw;
     };
-#ifndef SRX_WDENSE_DEPTH
-#define SRX_WDENSE_DEPTH 4
-#endif
-    constexpr int K = SRX_WDENSE_DEPTH;  // blocks in flight per lane
+    constexpr int K = 4;  // blocks in flight per lane
     Blk q[K];
     bool live[K];
 #pragma unroll
@@ -766,7 +725,6 @@ __device__ void dense_tile_select(ScoreShared &S, const IndexView &ix, int tile_
     const int tid = threadIdx.x;
     const float *acc = reinterpret_cast<const float *>(S.tbl);
     const int G = span_tiles << ix.tile_log2;  // accumulators in LDS: span_tiles consecutive tiles
-    T2L_T0();
     if (n_old_in >= 0) {
         unsigned *ovf_bits = reinterpret_cast<unsigned *>(S.m_start);
         int *ovf_doc = reinterpret_cast<int *>(ovf_bits + OVF_CAP);
@@ -829,18 +787,14 @@ __device__ void dense_tile_select(ScoreShared &S, const IndexView &ix, int tile_
             for (; i < n4r; i += THREADS) append4(i, i < n4 ? acc4[i] : zero4);
             __syncthreads();
             const unsigned n_total = S.tk.count;
-            T2L(6);
             if (n_total <= (unsigned)(KMAX + ovf_cap)) return;  // uniform.  The list stays lazy: no selection until it is full
             // The area is full: drop this scan's appends, shrink what was there before to the k best (tau rises) and scan
             // again.  Still too many (a query's first tiles), or nothing to shrink: the general path below.
-            T2C(14);
             __syncthreads();
             if (tid == 0) S.tk.count = n_old;
             __syncthreads();
             if (n_old <= (unsigned)k) break;
-            T2C(13);
             list_compact_select(S, k, n_old, ovf_bits, ovf_doc);
-            T2L(7);
             n_old = (unsigned)k;
         }
     }
@@ -940,10 +894,7 @@ __device__ void dense_tile_select(ScoreShared &S, const IndexView &ix, int tile_
     __syncthreads();
 }
 
-#ifndef SRX_DENSE_MIN
-#define SRX_DENSE_MIN 4096
-#endif
-constexpr int DENSE_MIN = SRX_DENSE_MIN < HASH_CAP ? SRX_DENSE_MIN : HASH_CAP;  // a tile with more postings than this is accumulated densely
+constexpr int DENSE_MIN = HASH_CAP;  // a tile with more postings than this is accumulated densely
 
 template <typename VT, bool AFTER, bool CP>
 __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const int32_t *__restrict__ q_ptr,
@@ -954,7 +905,6 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                             const int32_t *__restrict__ after_doc, const float *__restrict__ after_score, int64_t doc_base,
                             const Tier2Final &fin) {
     const int tid = threadIdx.x;
-    T2_T0();
     int q, split, nsq;
     decode_item(bid, n_whole, n_splits, q, split, nsq);
     if (q >= nq) return;
@@ -1054,16 +1004,13 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                 const int a = mine ? a_n : 0, b = mine ? b_n : 0;
                 a_n = gload_i32(wskip + min(j + WAVES, jlast));
                 b_n = gload_i32(wskip + min(j + WAVES, jlast) + 1);
-                T2(0);
                 if (wd_aligned)
                     wave_dense_accumulate<VT, true, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + a, b - a, w_idf, w_qw);
                 else
                     wave_dense_accumulate<VT, false, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + a, b - a, w_idf, w_qw);
                 const int n_old = (int)S.tk.count;  // stable here: nothing appends before the barrier
                 __syncthreads();
-                T2(3); T2C(11);
-                if (!(dbg & 16384)) dense_tile_select<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES, (dbg & 8192) ? -1 : n_old, OVF_CAP);
-                T2(4);
+                dense_tile_select<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES, (dbg & 8192) ? -1 : n_old, OVF_CAP);
             }
             if (S.tk.count > (unsigned)KMAX)  // uniform (stable since the last barrier): the overflow area goes back to its owners
                 list_compact_select(S, k, S.tk.count, reinterpret_cast<unsigned *>(S.m_start), reinterpret_cast<int *>(S.m_start) + OVF_CAP);
@@ -1093,9 +1040,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                     S.m_len[tid] = my_len;
                 }
                 __syncthreads();
-                T2(0);
                 served = flat_tile<VT, AFTER, CP>(S, ix, nt, my_len, su << ix.tile_log2, k);
-                T2(1); T2C(9);
                 for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;  // back to hash mode
                 __syncthreads();
             }
@@ -1106,9 +1051,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                     S.m_len[tid] = my_len;
                 }
                 __syncthreads();
-                T2(0);
-                hash_unit<VT, AFTER, CP>(S, ix, nt, my_len, k, (su * tps) << ix.tile_log2, dbg);
-                T2(2); T2C(10);
+                hash_unit<VT, AFTER, CP>(S, ix, nt, my_len, k, (su * tps) << ix.tile_log2);
             } else if (P > 0 && wave_dense) {
                 dense_quads(su * tps, min(su * tps + tps, ix.n_tiles));
             } else if (P > 0) {
@@ -1161,16 +1104,11 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                     const int n_old = (int)S.tk.count;  // stable here: nothing appends before the barrier
                     __syncthreads();
                     if (GP <= (unsigned)DENSE_MIN) {
-                        T2(0);
-                        hash_unit<VT, AFTER, CP>(S, ix, nt, glen, k, (su * tps) << ix.tile_log2, dbg);
-                        T2(2); T2C(10);
+                        hash_unit<VT, AFTER, CP>(S, ix, nt, glen, k, (su * tps) << ix.tile_log2);
                     } else {  // one dense tile (gb == ga + 1 by construction)
                         const int tile_base = ga << ix.tile_log2;
-                        T2(0);
                         dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, true, (su * tps) << ix.tile_log2);
-                        T2(3); T2C(11);
                         dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & 8192) ? -1 : n_old, 0);  // m_start / m_len are live: no overflow area
-                        T2(4);
                         for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;  // back to hash mode
                         __syncthreads();
                     }
@@ -1206,9 +1144,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
 
     // ---- emit this split's list (unordered; the merge kernel ranks) ----
     __syncthreads();
-    T2(0);
     topk_shrink(k, S.tk, S.tbl);
-    T2(5); T2C(12);
     if (nsq == 1 && fin.out_doc != nullptr) {
         // An unsplit query is ONE work item: this block holds everything tier 1 did not score.  Fold tier 1's list of the
         // same query in (it was complete before this kernel started; its docs come from other units), rank, and write the
@@ -1633,6 +1569,8 @@ SRX_API int srx_index_set_opts(srx_index *ix, const srx_search_opts *o) {
         return fail(SRX_ERR_INVALID, "srx_index_set_opts: supertile_log2 must be in [tile_log2, tile_log2+6]%s");
     if (o->unit_tiles < 0 || o->unit_tiles > MAX_TPS) return fail(SRX_ERR_INVALID, "srx_index_set_opts: unit_tiles must be in [0, 64]%s");
     if (o->target_blocks < 0) return fail(SRX_ERR_INVALID, "srx_index_set_opts: target_blocks < 0%s");
+    if (o->reserved & ~(8 | 16 | 128 | 256 | 2048 | 4096 | 8192))
+        return fail(SRX_ERR_INVALID, "srx_index_set_opts: reserved takes only the bits 8, 16, 128, 256, 2048, 4096, 8192%s");
     ix->opts = *o;
     return SRX_OK;
 }
@@ -2184,12 +2122,3 @@ SRX_API int srx_build_blocks(int32_t device, int32_t val_type, const int64_t *te
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }
-
-#ifdef SRX_STAMP2
-SRX_API int srx_debug_read_stamps2(unsigned long long *h_out16) {
-    HIP_TRY(hipMemcpyFromSymbol(h_out16, HIP_SYMBOL(g_stamp2), sizeof(unsigned long long) * 16));
-    unsigned long long z[16] = {0};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp2), z, sizeof(z)));
-    return SRX_OK;
-}
-#endif

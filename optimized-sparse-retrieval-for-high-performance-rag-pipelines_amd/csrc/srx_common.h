@@ -18,23 +18,6 @@
 
 #define SRX_API extern "C" __attribute__((visibility("default")))
 
-#ifdef SRX_STAMP
-__device__ unsigned long long g_stamp[32];
-#define STAMP(i)                                                                         \
-    do {                                                                                 \
-        unsigned long long t_;                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                               \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");        \
-        __builtin_amdgcn_sched_barrier(0);                                               \
-        st_acc[i] += t_ - st_prev;                                                       \
-        st_prev = t_;                                                                    \
-    } while (0)
-#else
-#define STAMP(i) \
-    do {         \
-    } while (0)
-#endif
-
 extern thread_local char srx_g_err[512];
 #define g_err srx_g_err
 
@@ -59,10 +42,7 @@ constexpr int MAX_TPS = 64;                 // tiles per supertile handled by th
 constexpr int MERGE_NPT = 16;               // merge kernel: candidates per thread (4096 per workgroup)
 constexpr int EMPTY_KEY = -1;
 // tier 1 (one wavefront per (query, split))
-#ifndef SRX_W_WPE
-#define SRX_W_WPE 4
-#endif
-constexpr int W_WAVES_PER_EU = SRX_W_WPE;   // tier-1 waves per SIMD the kernel is compiled for (its register budget).  The kernel needs 94 VGPRs
+constexpr int W_WAVES_PER_EU = 4;           // tier-1 waves per SIMD the kernel is compiled for (its register budget).  The kernel needs 94 VGPRs
                                             // and 8.25 KB of LDS per wave, so 19 waves are resident per CU.  Built for 5 (192-entry list, 7.75 KB:
                                             // 20 waves per CU) it measured 1 % slower on C3 and 4 % slower on a 1.25 M-doc shard (more selections)
 constexpr int W_UNIT_MAX_DOCS = 49152;      // a unit covers <= 49152 docs (3 tiles of 16384): its local doc ids are the bit positions of
@@ -71,18 +51,12 @@ constexpr int W_SENT_BASE = 49152;          // ... and the sentinels of the comp
                                             // W_SENT_BASE + 32 j, j < 64 (a word of their own each)
 constexpr int W_BM_WORDS = (W_SENT_BASE + 64 * 32) / 32;  // 1600 words = 6.25 KiB
 constexpr unsigned W_BM_ADR_MASK = 0x1FFCu; // byte offset of a bitmap word from a 16-bit id >> 3 (ids stay below 51200 by construction)
-#ifndef SRX_W_R
-#define SRX_W_R 12
-#endif
-constexpr int W_R = SRX_W_R;                // postings per lane per unit held in registers (8 or 12)
+constexpr int W_R = 12;                     // postings per lane per unit held in registers
 constexpr int W_CAP = W_R * 64;             // hence <= 768 postings per tier-1 unit
 constexpr int W_DUPCAP = 48;                // dup postings per unit resolved in tier 1 (more: the unit is dense -> tier 2)
 constexpr int W_LCAP = 384;                 // lazy top-k list capacity of the merge wave kernel's callers (entries; a multiple of 64)
 constexpr int W_KMAX = 128;                 // largest k ranked by one wavefront (wave_rank_emit: 2 keys per lane)
-#ifndef SRX_W_LCAP
-#define SRX_W_LCAP (SRX_W_WPE >= 5 ? 192 : 256)
-#endif
-constexpr int W1_LCAP = SRX_W_LCAP;         // tier 1's lazy top-k list capacity (entries; a multiple of 64)
+constexpr int W1_LCAP = 256;                // tier 1's lazy top-k list capacity (entries; a multiple of 64)
 constexpr int W1_KMAX = W1_LCAP - W_DUPCAP - 32 < 112 ? W1_LCAP - W_DUPCAP - 32 : 112;  // largest k tier 1 serves: next to k entries the
                                             // list keeps room for a unit's multi-term docs and >= 32 single-term candidates
 constexpr int W_MAXT = 64;                  // query terms (each owns 64 / 2^ceil(log2 nt) lanes)

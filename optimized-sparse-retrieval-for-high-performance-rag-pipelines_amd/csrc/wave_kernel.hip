@@ -30,22 +30,12 @@
 
 #include "srx_common.h"
 
-#ifdef SRX_STAMP
-#define CNT(i) (++st_cnt[i])
-#else
-#define CNT(i) \
-    do {       \
-    } while (0)
-#endif
-
 namespace {
 
 enum { U_OK = 0, U_DENSE = 1, U_FULL = 2 };  // outcome of scoring one unit (see process)
 
-#ifndef SRX_W_DEPTH
-#define SRX_W_DEPTH 2  // register sets: units in flight + the one being scored
-#endif
-struct WaveShared2 {  // 6400 + 8 LCAP bytes: 7936 at 5 waves per SIMD (20 x 7936 <= 160 KB), 8448 at 4
+constexpr int W_DEPTH = 2;  // register sets: units in flight + the one being scored
+struct WaveShared2 {  // 6400 + 8 LCAP bytes = 8448
     static constexpr int LCAP = W1_LCAP;
     static constexpr bool HIST_ALIASES_ZEROED_LDS = true;
     union {
@@ -60,8 +50,9 @@ static_assert(sizeof(WaveShared2) * 4 * W_WAVES_PER_EU <= 160 * 1024, "tier-1 LD
 
 // The unit-local doc ids stay PACKED in registers the way the compact copy stores them (two 16-bit ids per word: slot r
 // lives in half r & 1 of word r >> 1): a register set is W_R / 2 + W_R VGPRs instead of 2 W_R, which is what pays for the
-// third set in flight (SRX_W_DEPTH).  Pass 1 reads the halves with shifts that cost what the unpacked form's did.
+// third set in flight (W_DEPTH).  Pass 1 reads the halves with shifts that cost what the unpacked form's did.
 constexpr int W_RP = W_R / 2;
+static_assert(W_R == 12, "score() dispatches units of 1, 2 or 3 load steps");
 __device__ __forceinline__ unsigned slot_id(const unsigned (&dp)[W_RP], int r) {  // r: compile-time constant after unrolling
     return (r & 1) ? dp[r >> 1] >> 16 : dp[r >> 1] & 0xFFFFu;
 }
@@ -82,10 +73,8 @@ __device__ __forceinline__ int lane_reg(const unsigned (&dp)[W_RP], int rs, int 
     return (int)((rs & 1) ? w >> 16 : w & 0xFFFFu);
 }
 
-// DBG: the ablation build of the same kernel (bench.py --debug: timing experiments with WRONG results).  The shipped instance
-// (DBG = false) carries none of those tests in its unit loop.
-template <typename VT, bool DBG>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE))) void srx_wave_kernel(const srx_wave_launch a) {
+template <typename VT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W_WAVES_PER_EU))) void srx_wave_kernel(const srx_wave_launch a) {
     __shared__ WaveShared2 S;
     constexpr int BW = CompactWords<VT>::value;  // tier 1 streams the compact copy (16-bit unit-local docs)
     const IndexView &ix = a.ix;
@@ -129,12 +118,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
     for (int i = lane; i < W_BM_WORDS / 4; i += 64) reinterpret_cast<uint4 *>(S.bm)[i] = make_uint4(0u, 0u, 0u, 0u);
     wsync();
     WaveTopk tk = {0u, 0u};  // wave-uniform lazy top-k list state
-    int sink = 0;            // DBG only
-    const int dbg = DBG ? a.dbg : 0;
-#ifdef SRX_STAMP
-    unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev = __builtin_amdgcn_s_memtime();
-    unsigned st_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     bool flagged = false;    // wave-uniform: some unit of this block was handed to tier 2
     int lg = 0;
     while ((1 << lg) < nt) ++lg;
@@ -152,7 +135,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
         unsigned skip_boff = 0;  // BYTE offset of my term's skip row (the table is < 4 GiB: tier1_cannot_serve): one VGPR, and the
                                  // loads take the table's base from SGPRs (global_load ... v_off, s[base])
         float my_idf = 0.f, my_qw = 0.f, my_bnd = 0.f;
-        constexpr int NBQ = SRX_W_DEPTH + 2;
+        constexpr int NBQ = W_DEPTH + 2;
         int bq[NBQ];             // bq[i] = boundary (next unit to issue) + i of my term, in padded postings
         const int col = bound_column(k);
         const bool use_bound = ix.term_bound != nullptr && col >= 0;
@@ -264,7 +247,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
 
         // unit boundary j of my term in padded POSTINGS from the term's start (#padded postings with doc < j * tpu * G; a
         // multiple of 4).  Loaded by every lane without a branch (lanes without a term read term 0's row: valid memory,
-        // masked where the run length is formed) and consumed SRX_W_DEPTH + 1 fetches later: a load inside a divergent
+        // masked where the run length is formed) and consumed W_DEPTH + 1 fetches later: a load inside a divergent
         // branch made the compiler finish it on the spot with s_waitcnt vmcnt(0), which also drained the posting loads of
         // the next unit issued just before it -- the wave then had nothing in flight while it scored.
         auto bound = [&](int j) __attribute__((always_inline)) -> int {
@@ -321,15 +304,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
             for (int r = 0; r < NR; ++r) acc |= t[r];
             bool dense = false;
             const bool anydup = __ballot(acc != 0u) != 0ull;
-            STAMP(2);  // wait for the unit's postings + pass 1
-            CNT(0);
             // ---- the bitmap words go back to zero (measured: clearing the whole 8 KB bitmap with 8 wide stores per lane
             //      instead, which needs no addresses, costs the batch 14 % -- LDS write bandwidth) ----
 #pragma unroll
             for (int r = 0; r < NR; ++r) *reinterpret_cast<unsigned *>(reinterpret_cast<char *>(S.bm) + adr[r]) = 0u;
-            STAMP(4);  // restore
-            if (anydup && !(dbg & 1)) {  // uniform: some doc of this unit is matched by several terms (~3 units in 4 on C3)
-                CNT(1);
+            if (anydup) {  // uniform: some doc of this unit is matched by several terms (~3 units in 4 on C3)
                 // Lanes with a flagged posting (typically one or two) are visited one after the other: fm = the lane's
                 // flagged slots; the doc of its lowest flagged slot is broadcast, every lane picks up and blanks its
                 // posting of that doc (a doc occurs at most once per term, hence at most once per lane; sentinels carry
@@ -348,13 +327,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
                     const unsigned fms = (unsigned)__builtin_amdgcn_readlane((int)fm, src);
                     const int rs = __ffs((int)fms) - 1;                 // uniform: lane src's lowest flagged slot
                     const int dd = lane_reg<NR>(d, rs, src);            // its doc, wave-uniform
-                    CNT(2);
-                    if (dbg & 512) {  // timing experiment: locate the docs only
-                        sink += dd;
-                        fm = (lane == src) ? (fm & (fm - 1u)) : fm;
-                        m = __ballot(fm != 0u);
-                        continue;
-                    }
                     float myv = 0.0f;
 #pragma unroll
                     for (int r2 = 0; r2 < NR; ++r2) {
@@ -371,7 +343,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
                         mm &= mm - 1ull;
                     }
                     const unsigned b = __float_as_uint(sum);
-                    if (sum > 0.0f && b >= tk.tau && !(dbg & 1024)) {  // uniform; room for W_DUPCAP entries was made above
+                    if (sum > 0.0f && b >= tk.tau) {  // uniform; room for W_DUPCAP entries was made above
                         if (lane == 0) {
                             S.lbits[tk.count] = b;
                             S.ldoc[tk.count] = ubase + dd;
@@ -387,9 +359,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
                     m = __ballot(fm != 0u);
                 }
             }
-            STAMP(3);  // multi-term docs
             if (dense) return U_DENSE;
-            if (dbg & 2) return U_OK;  // timing experiment: no candidate screening (results are wrong)
             // ---- single-term docs.  Almost no posting can beat tau once the list has warmed up, so a conservative
             //      per-lane threshold on the stored value (vthr <= the smallest v whose contribution could reach tau, and
             //      > 0 so that blanked registers and sentinels never pass) screens them with one compare; the exact fp32
@@ -405,9 +375,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
             for (int r = 1; r + 1 < NR; r += 2) vmax = fmaxf(fmaxf(vmax, v[r]), v[r + 1]);
             if constexpr (NR % 2 == 0) vmax = fmaxf(vmax, v[NR - 1]);
             const bool anycand = __ballot(vmax >= vthr) != 0ull;
-            STAMP(5);  // screening
             if (anycand) {  // uniform, rare after warm-up
-                CNT(3);
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
                     const bool pass = v[r] >= vthr;
@@ -427,13 +395,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
                             S.ldoc[pz] = ubase + (int)slot_id(d, r);
                         }
                         tk.count += n2;
-#ifdef SRX_STAMP
-                        st_cnt[5] += n2;
-#endif
                     }
                 }
             }
-            STAMP(6);  // candidates (appends)
             return U_OK;
         };
 
@@ -442,7 +406,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
             flagged = true;
         };
 
-        // ---- software pipeline over units: SRX_W_DEPTH register sets rotate; while unit u is scored from registers, the
+        // ---- software pipeline over units: W_DEPTH register sets rotate; while unit u is scored from registers, the
         //      loads of units u+1 .. u+DEPTH-1 are in flight (a wave has no other way to keep memory requests outstanding:
         //      with one unit ahead the data arrives long before the unit before it has been scored, and nothing is in
         //      flight for the rest of that time) ----
@@ -451,18 +415,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
         // length has to stay in a register while the unit is in flight.
         // returns true when the list was full: the unit has NOT been scored
         auto score = [&](int su, int steps, unsigned (&d)[W_RP], float (&v)[W_R]) __attribute__((always_inline)) -> bool {
-            if (dbg & 4) {  // timing experiment: loads only (results are wrong)
-#pragma unroll
-                for (int r = 0; r < W_R; ++r) sink += (int)(d[r >> 1] ^ __float_as_uint(v[r]));
-            } else if (steps > W_R / 4) {
+            if (steps > W_R / 4) {
                 flag_tier2(su);
             } else if (steps > 0) {
                 int rc;
                 const int ubase = (su * tpu) << ix.tile_log2;
-                if (W_R > 12 && steps == 4)
-                    rc = process(IntC<(W_R > 12 ? 16 : 4)>{}, ubase, d, v);
-                else if (W_R > 8 && steps == 3)
-                    rc = process(IntC<(W_R > 8 ? 12 : 4)>{}, ubase, d, v);
+                if (steps == 3)
+                    rc = process(IntC<12>{}, ubase, d, v);
                 else if (steps == 2)
                     rc = process(IntC<8>{}, ubase, d, v);
                 else
@@ -479,9 +438,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
             int steps = 0;  // uniform
 #pragma unroll
             for (int s4 = 0; s4 <= W_R / 4; ++s4) steps += (__ballot(len > (s4 << LPT_LOG2)) != 0ull) ? 1 : 0;
-            STAMP(0);  // loop overhead / previous tail
             issue(bq[0] >> 2, steps > W_R / 4 ? 0 : len, d, v);
-            STAMP(1);  // issue
 #pragma unroll
             for (int i = 0; i < NBQ - 1; ++i) bq[i] = bq[i + 1];
             ++su_issue;
@@ -493,9 +450,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
         // The pipeline is (re)started at unit su_start: once per item, and again after every selection of the lazy list --
         // the units in flight at that moment are fetched a second time (L2 hits), a few times per query while the threshold
         // warms up and hardly ever after.
-        constexpr int DEPTH = SRX_W_DEPTH;
+        constexpr int DEPTH = W_DEPTH;
         int su_start = su_lo;
-        STAMP(8);  // prologue: item decode, bitmap clear, term metadata, initial threshold
         for (;;) {
             su_issue = su_start;
             const bool first_start = SCALAR_PROLOGUE && su_start == su_lo;  // uniform: bq[0], bq[1] came with the scalar prologue
@@ -521,8 +477,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
                 }
             }
             if (su_full < 0) break;
-            STAMP(0);
-            CNT(4);
             // ---- no register set is live here: shrink the list to its k best (tau rises) and redo unit su_full.  A unit that
             //      does not fit next to a list of k entries either goes to tier 2 ----
             if (tk.count > (unsigned)k) {
@@ -533,7 +487,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
                 flag_tier2(su_full);
                 su_start = su_full + 1;
             }
-            STAMP(9);  // list selection between restarts
         }
     };
     switch (6 - lg) {
@@ -545,29 +498,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
         case 5: run(IntC<5>{}); break;
         default: run(IntC<6>{}); break;
     }
-    if ((dbg & (4 | 512)) && sink == 0x7F123457) a.cand_count[list] = sink;  // keeps the loads of the timing experiment alive
     unsigned count = tk.count;
-    if (dbg & 32) count = 0;  // timing experiment: no final selection / ranking
     if (count > (unsigned)k) {
         wave_list_select(S, count, k);
         count = (unsigned)k;
     }
-    STAMP(7);  // epilogue (final select)
-#ifdef SRX_STAMP
-#define STAMP_FLUSH()                                                                              \
-    do {                                                                                           \
-        STAMP(10); /* rank + row / list write */                                                   \
-        if (lane == 0) {                                                                           \
-            for (int i = 0; i < 12; ++i) atomicAdd(&g_stamp[i], st_acc[i]);                        \
-            atomicAdd(&g_stamp[12], 1ull);                                                         \
-            for (int i = 0; i < 8; ++i) atomicAdd(&g_stamp[13 + i], (unsigned long long)st_cnt[i]); \
-        }                                                                                          \
-    } while (0)
-#else
-#define STAMP_FLUSH() \
-    do {              \
-    } while (0)
-#endif
     if (nsq == 1 && !flagged && a.out_doc != nullptr) {
         // This wave holds the query's complete top-k (one split, nothing handed to tier 2): rank it here and write
         // the final row, so the merge kernel can skip the query.
@@ -577,7 +512,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
             a.out_count[(int64_t)q * a.out_cnt_stride] = (int)count;
             a.cand_count[list] = -1;  // tells the merge kernel this query is final
         }
-        STAMP_FLUSH();
         return;
     }
     // A split's list is read by another wave of this grid (below), possibly on another XCD with an L2 of its own: its
@@ -639,34 +573,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SRX_W_WPE)))
             }
         }
     }
-    STAMP_FLUSH();
 }
 
 }  // namespace
 
 int srx_launch_wave_kernel(const srx_wave_launch &a, int val_type, int64_t blocks, hipStream_t stream) {
     if (blocks <= 0) return SRX_OK;
-    const bool ablate = (a.dbg & (1 | 2 | 4 | 32 | 512 | 1024)) != 0;  // timing experiments: the DBG instance
-    if (val_type == SRX_VAL_F32) {
-        if (ablate)
-            hipLaunchKernelGGL((srx_wave_kernel<float, true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-        else
-            hipLaunchKernelGGL((srx_wave_kernel<float, false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-    } else {
-        if (ablate)
-            hipLaunchKernelGGL((srx_wave_kernel<__half, true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-        else
-            hipLaunchKernelGGL((srx_wave_kernel<__half, false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-    }
+    if (val_type == SRX_VAL_F32)
+        hipLaunchKernelGGL((srx_wave_kernel<float>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+    else
+        hipLaunchKernelGGL((srx_wave_kernel<__half>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }
-
-#ifdef SRX_STAMP
-extern "C" __attribute__((visibility("default"))) int srx_debug_read_stamps(unsigned long long *h_out16) {
-    HIP_TRY(hipMemcpyFromSymbol(h_out16, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 32));
-    unsigned long long z[32] = {0};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z)));
-    return SRX_OK;
-}
-#endif

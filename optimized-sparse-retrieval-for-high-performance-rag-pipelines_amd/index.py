@@ -467,12 +467,15 @@ class DeviceIndex:
     # -- search ----------------------------------------------------------------------------------------
     def set_opts(self, supertile_log2: int = 0, target_blocks: int = 0, profile: int = 0, debug: int = 0,
                  unit_tiles: int = 0) -> None:
-        """profile = N > 0: every N-th search is bracketed with hipEvents (True = every search)."""
+        """profile = N > 0: every N-th search is bracketed with hipEvents (True = every search).
+        debug = an OR of the exact-result path bits of srx_search_opts.reserved: 8, 16, 128, 256, 2048, 4096, 8192
+        (include/sparse_rx.h); any other bit raises ValueError and leaves the options as they were."""
         if self.post is None and (supertile_log2 or unit_tiles):
             raise ValueError("this index keeps no canonical blocks (drop_canonical): it is searched with the unit it was built for")
-        self._opts = _capi.SearchOpts(supertile_log2=supertile_log2, target_blocks=target_blocks, profile=int(profile),
-                                      reserved=int(debug), unit_tiles=int(unit_tiles))
-        _capi.check(_capi.lib().srx_index_set_opts(self._h, ctypes.byref(self._opts)), "srx_index_set_opts")
+        opts = _capi.SearchOpts(supertile_log2=supertile_log2, target_blocks=target_blocks, profile=int(profile),
+                                reserved=int(debug), unit_tiles=int(unit_tiles))
+        _capi.check(_capi.lib().srx_index_set_opts(self._h, ctypes.byref(opts)), "srx_index_set_opts")
+        self._opts = opts
 
     def workspace_bytes(self, nq: int, k: int) -> int:
         return _capi.check(_capi.lib().srx_search_workspace_bytes(self._h, nq, k), "srx_search_workspace_bytes")

@@ -686,6 +686,8 @@ def test_one_copy_of_the_postings(rx, tmp_path):
             for dbg in (2048, 4096, 8192, 128):
                 ix.set_opts(debug=dbg)
                 _assert_exact(ix.search(*qs, 1000), exp, f"one copy splade {vd} tile={tl} ut={ut} debug={dbg}")
+            with pytest.raises(ValueError, match="reserved"):  # only the exact-result bits are accepted
+                ix.set_opts(debug=4)
         ix.close()
     ce = synth.zipf_corpus_np(5_000, 700, 30, seed=3)            # a > 256-term query: the general path
     _, idfe, avgdle = synth.corpus_stats(ce)
