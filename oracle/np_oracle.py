@@ -73,13 +73,18 @@ def topk_ranked(scores: np.ndarray, k: int):
 def int8_similarities(queries_int8, corpus_int8, query_scales, corpus_scales):
     """retriever_registry.py:538-548 (the NumPy twin of quantized_dot_product_batch :90-117, symmetric scheme):
     similarities[q, d] = f32( int32 dot * query_scale (f32) * doc_scale (f32) ) with NumPy scalar promotion
-    (int32 * float32 -> float64, * float32 -> float64, stored into a float32 array)."""
-    q = np.asarray(queries_int8).astype(np.int32)
-    c = np.asarray(corpus_int8).astype(np.int32)
-    dots = q @ c.T  # exact: |dot| <= dim * 127 * 127 < 2^31
+    (int32 * float32 -> float64, * float32 -> float64, stored into a float32 array).
+    The int32 dot is taken as a float64 matmul (BLAS; NumPy's integer matmul is a slow loop): every product and partial sum
+    is an integer of magnitude <= 1024 * 128^2 < 2^53, so it is exact in any summation order."""
+    q = np.asarray(queries_int8).astype(np.float64)
+    c = np.asarray(corpus_int8)
+    dots = np.empty((q.shape[0], c.shape[0]), np.float64)
+    step = max(1, (1 << 24) // max(1, c.shape[1]))  # the float64 copy of the corpus is made in slices of <= 128 MB
+    for lo in range(0, c.shape[0], step):
+        dots[:, lo:lo + step] = q @ c[lo:lo + step].astype(np.float64).T
     qs = np.asarray(query_scales, dtype=np.float32).astype(np.float64)[:, None]
     cs = np.asarray(corpus_scales, dtype=np.float32).astype(np.float64)[None, :]
-    return ((dots.astype(np.float64) * qs) * cs).astype(np.float32)
+    return ((dots * qs) * cs).astype(np.float32)
 
 
 def dense_topk(similarities, k):

@@ -190,3 +190,167 @@ def plan_label(p, k):
     if p["t2_everything"]:
         parts.append("t2all")
     return "-".join(parts)
+
+
+# ---- the dense side, restated (csrc/dense.hip) --------------------------------------------------------------------------
+# Dispatch: dense_qb, dense_splits, dense_sample, the first filter round's S1 and dense_ws (the workspace layout), with the
+# constants of csrc/srx_common.h / dense.hip.  The GPU suite (test_dense_kernels.py) pins this to the library through
+# srx_dense_workspace_bytes (QB through the score region, filtered-vs-matrix through the candidate buffers) and reads the
+# overflow flags and survivor counts out of the workspace at the offsets restated here.
+DENSE_DIMS = (32, 64, 96, 128, 192, 256, 384, 512, 768, 1024)  # the INT8 kernels' instantiations: KS = dim / 32
+DENSE_CAP = 65536  # candidate buffer entries per query of the filtered path
+DENSE_CNT_STRIDE = 32  # ints between two queries' candidate counters
+DENSE_SPLIT_DOCS = 256 * 16 * 4  # THREADS * DENSE_NPT * 4: docs per split of a score row at least
+DENSE_MERGE_CANDIDATES = 4096  # MERGE_NPT * THREADS
+F32_QP = 4  # queries per pass of the f32 / u8 matvec
+
+
+def dense_qb(n_docs):
+    """Queries per pass: the score matrix (queries x n_docs x 4 B) within 4 GiB, 32 .. 1024, a multiple of 32."""
+    q = (4 << 30) // (((n_docs + 63) // 64 * 64) * 4)
+    return int(min(max(q // 32 * 32, 32), 1024))
+
+
+def dense_splits(n_docs, nq, k):
+    """Doc-range splits of a score row: 2048 // nq, at most n_docs // 16384, at most one merge level (4096 // k)."""
+    s = 2048 // (nq if nq > 0 else 1)
+    s = min(s, n_docs // DENSE_SPLIT_DOCS, DENSE_MERGE_CANDIDATES // (k if k > 0 else 1))
+    return max(s, 1)
+
+
+def dense_sample(n_docs, k):
+    """Sample size S of the threshold pass of the filtered path; 0 = the matrix path (n_docs < 65 536 or 4 S > n_docs)."""
+    if n_docs < 65536:
+        return 0
+    S = (3 * k * n_docs + DENSE_CAP - 1) // DENSE_CAP
+    S = max(S, min(max(164 * k, 4096), 16384))
+    S = (S + 127) // 128 * 128
+    return S if S * 4 <= n_docs else 0
+
+
+def dense_ks_params(dim):
+    """Per-instantiation constants of srx_dense_i8_filter_kernel<KS>: doc tiles per wave (DT), survivor list entries per
+    wave (DENSE_CB), query tiles in LDS (NBUF), waves per workgroup (NW) and docs per workgroup."""
+    ks = dim // 32
+    nw = 4  # DENSE_NW_LONG = 4 too
+    dt = 2 if ks <= 12 else 1
+    cb = 512 if ks <= 12 else (256 if ks <= 24 else 128)
+    nbuf = 3 if ks <= 16 else 2
+    return {"KS": ks, "DT": dt, "DENSE_CB": cb, "NBUF": nbuf, "NW": nw, "docs_per_block": 32 * dt * nw}
+
+
+def dense_s1(n_docs, S, dim):
+    """Docs of the first filter round: sqrt(S n), rounded up to whole rounds of the chip (512 workgroups) once it reaches
+    one, else to whole workgroups; n_docs (one round) when twice that exceeds the corpus.  Returns (S1, chip_rounded)."""
+    import math
+    dpb = dense_ks_params(dim)["docs_per_block"]
+    s1 = int(math.sqrt(float(S) * float(n_docs)))
+    chip = dpb * (2048 // 4)
+    chip_rounded = s1 >= chip
+    s1 = (s1 + chip - 1) // chip * chip if chip_rounded else (s1 + dpb - 1) // dpb * dpb
+    if s1 * 2 > n_docs:
+        return n_docs, False
+    return s1, chip_rounded
+
+
+def dense_ws(nq, n_docs, k):
+    """dense_ws: byte offsets of the workspace regions (each rounded up to 256 B) and the total srx_dense_workspace_bytes."""
+    QB = dense_qb(n_docs)
+    qb = min(nq, QB)
+    ld = (n_docs + 63) // 64 * 64
+    ns = dense_splits(n_docs, qb, k)
+    filt = dense_sample(n_docs, k) > 0
+    off, w = 0, {}
+    for name, nbytes in (("scores", qb * ld * 4), ("cand_doc", qb * ns * k * 4), ("cand_score", qb * ns * k * 4),
+                         ("cand_count", qb * ns * 4), ("tau", qb * 4), ("buf_cnt", (qb * DENSE_CNT_STRIDE + qb + 1) * 4),
+                         ("buf_doc", qb * DENSE_CAP * 4 if filt else 0), ("buf_score", qb * DENSE_CAP * 4 if filt else 0),
+                         ("apack", (qb + 31) // 32 * 32 * 1024)):
+        w[name] = off
+        off += (nbytes + 255) // 256 * 256
+    w["ovf"] = w["buf_cnt"] + qb * DENSE_CNT_STRIDE * 4
+    w["any_ovf"] = w["ovf"] + qb * 4
+    w["bytes"] = off + 256
+    w["qb"] = qb
+    return w
+
+
+def dense_f32_ws_bytes(nq, n_docs, k):
+    """srx_dense_f32_workspace_bytes: the score rows of one pass of F32_QP queries, their candidate lists and counts."""
+    ld = (n_docs + 63) // 64 * 64
+    ns = dense_splits(n_docs, F32_QP, k)
+    return F32_QP * ld * 4 + F32_QP * ns * k * 8 + F32_QP * ns * 4 + 1024
+
+
+def dense_plan(nq, n_docs, k, dim):
+    """The dispatch of one srx_dense_search_i8 call: passes, path, rounds, S, S1 and the splits of the score-row ranking
+    (the matrix path and the overflow fallback)."""
+    QB = dense_qb(n_docs)
+    S = dense_sample(n_docs, k)
+    p = {"KS": dim // 32, "QB": QB, "passes": (nq + QB - 1) // QB, "S": S, "ns": dense_splits(n_docs, min(nq, QB), k),
+         "path": "filtered" if S else "matrix", "rounds": 0, "S1": 0, "chip": False}
+    if S:
+        p["S1"], p["chip"] = dense_s1(n_docs, S, dim)
+        p["rounds"] = 1 if p["S1"] >= n_docs else 2
+    return p
+
+
+def dense_plan_label(p, k):
+    parts = [f"ks{p['KS']}", p["path"]]
+    if p["path"] == "filtered":
+        parts.append(f"r{p['rounds']}" + ("chip" if p["chip"] else ""))
+    parts += [f"p{p['passes']}", f"ns{p['ns']}", f"k{k}"]
+    return "-".join(parts)
+
+
+def dense_rows_scores(rows, queries, scale_min=None, score_offset=0.0):
+    """srx_dense_f32_scores_kernel / srx_dense_u8_scores_kernel restated bit for bit (fp32, no contraction): lane l of the
+    doc's wave sums r[l + 64 i] * q[l + 64 i] over the 16 slices i in order (slices past dim / 64 add 0 * 0), the xor
+    butterfly 32, 16, 8, 4, 2, 1 adds the lanes, lane 0's value + score_offset is the score.  u8 rows (scale_min given) are
+    de-quantized first with one fp32 multiply and one add: u8 * scale_min[2 d] + scale_min[2 d + 1].
+    rows f32 / u8 [n, dim], queries f32 [nq, dim], dim a multiple of 64 <= 1024.  Returns f32 [nq, n]."""
+    f = np.float32
+    q = np.asarray(queries, dtype=f)
+    R = np.asarray(rows)
+    n, dim = R.shape
+    assert q.shape[1] == dim and dim % 64 == 0 and 0 < dim <= 1024
+    nsl = dim // 64
+    sm = None if scale_min is None else np.asarray(scale_min, dtype=f).reshape(-1)
+    qv = q.reshape(len(q), nsl, 64)[:, None]  # [nq, 1, slice, lane]
+    out = np.empty((len(q), n), f)
+    chunk = max(1, (1 << 22) // (dim * max(1, len(q))))
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        r = R[lo:hi]
+        if sm is None:
+            r = r.astype(f, copy=False)
+        else:
+            r = r.astype(f) * sm[2 * lo:2 * hi:2, None] + sm[2 * lo + 1:2 * hi:2, None]
+        r = r.reshape(hi - lo, nsl, 64)[None]  # [1, docs, slice, lane]
+        a = np.zeros((len(q), hi - lo, 64), f)
+        for i in range(nsl):
+            a = a + r[:, :, i, :] * qv[:, :, i, :]
+        if nsl < 16:
+            a = a + f(0.0)  # the zero slices: -0 becomes +0, nothing else changes
+        for o in (32, 16, 8, 4, 2, 1):  # lanes l and l ^ o hold the same sum after a step: lane 0's chain is this
+            a = a[:, :, :o] + a[:, :, o:2 * o]
+        out[:, lo:hi] = a[:, :, 0] + f(score_offset) if sm is None else a[:, :, 0]
+    return out
+
+
+def dense_topk_rows(similarities, k):
+    """np_oracle.dense_topk (score > 0 only, (score desc, doc asc), padded with -1 / 0) through a partition: only the
+    candidates at or above each row's k-th largest value are sorted.  Same rows; fast on wide corpora."""
+    s = np.asarray(similarities, dtype=np.float32)
+    nq, n = s.shape
+    out_d = np.full((nq, k), -1, np.int32)
+    out_s = np.zeros((nq, k), np.float32)
+    out_n = np.zeros(nq, np.int32)
+    kk = min(k, n)
+    thr = -np.partition(-s, kk - 1, axis=1)[:, kk - 1]
+    for i in range(nq):
+        c = np.flatnonzero((s[i] >= thr[i]) & (s[i] > 0))
+        c = c[np.lexsort((c, -s[i, c].astype(np.float64)))][:k]
+        out_d[i, : len(c)] = c
+        out_s[i, : len(c)] = s[i, c]
+        out_n[i] = len(c)
+    return out_d, out_s, out_n
