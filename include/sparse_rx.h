@@ -15,6 +15,8 @@
  *   srx_build_blocks      whole doc-major CSR per query, retrieval.py:55-72)
  *   srx_merge_topk        the (score desc, doc asc) merge of per-shard / per-split top-k lists
  *                         (multi-GPU: after the RCCL all-gather; no reference counterpart)
+ *   srx_fuse_topk         hybrid retrieval: one fused ranking from a sparse and a dense top-k list (the reference
+ *                         configures a `hybrid` retriever but does not implement it)
  *
  * Conventions
  *   - extern "C", plain pointers and sizes, no C++ / torch types.  Every array pointer is a DEVICE
@@ -312,6 +314,37 @@ int srx_dense_search_f32(int32_t device, const float *emb, int64_t n_docs, int32
 int srx_dense_search_u8(int32_t device, const uint8_t *corpus, const float *corpus_scales, int64_t n_docs, int32_t dim,
                         const float *queries, int32_t nq, int32_t k, int64_t doc_base, int32_t *out_doc, float *out_score,
                         int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Hybrid retrieval: fuse two ranked lists per query -- A = the sparse side (srx_search rows), B = the dense side
+ * (srx_dense_search_* rows over the same row ids) -- into one ranked top-k list.  Replaces nothing in the reference: its
+ * `hybrid` retriever type is configured (rag_system/configs/ms_marco_paper_results.yaml:108-120, sparse_weight 0.3,
+ * dense_weight 0.7) and listed as a next step (bench/utils.py:158) but RetrieverRegistry.create rejects it
+ * (rag_system/core/retriever_registry.py:596-599).  Added without a version bump: SRX_VERSION stays 301.
+ * Inputs in the engine's own output form: x_doc i32[nq][kx], x_score f32[nq][kx], x_count i32[nq], 1 <= ka, kb <= 1024.
+ * Entry r of a list is used iff r < min(max(count, 0), kx), doc >= 0 and score > 0; its rank is its position r either
+ * way.  PRECONDITION, not checked on the device: no doc id twice inside one list.  Doc ids are taken as they are.
+ * Contribution of a used entry, fp32, every operation rounded on its own (IEEE divide, denormals kept):
+ *   SRX_FUSE_WEIGHTED   c = weight_x * (score / x_score[q][0])   -- divided by the list's best score; a list whose entry 0
+ *                       is not used counts as empty in this mode
+ *   SRX_FUSE_RRF        c = weight_x / (rrf_c + (float)(r + 1))   -- reciprocal rank fusion; rrf_c is ignored otherwise
+ * Fused score of a doc = c_A + c_B when both lists hold it, else its one contribution.  Row q of the outputs
+ * (out_doc / out_score [nq][k], out_count [nq], 1 <= k <= 1024): the k best docs with fused score > 0, ranked (fused score
+ * descending, doc ascending), padded with doc -1 / score 0; out_count[q] <= min(k, docs in either list).
+ * Note: with one weight 0 the fused SET is the other list's, but score / best can round two different scores to the
+ * same quotient, and such ties then rank by doc id -- the order can differ from that list's own.
+ * Refused with SRX_ERR_INVALID before anything touches a device: ka, kb or k out of range, an unknown mode, a weight that
+ * is negative or not finite, both weights 0, rrf_c not finite or <= 0 in mode SRX_FUSE_RRF, a NULL pointer with nq > 0.
+ * nq == 0 returns SRX_OK without a launch.  Asynchronous on `stream`, allocates nothing, needs no workspace.
+ */
+typedef enum {
+    SRX_FUSE_WEIGHTED = 0, /* weighted sum of the scores, each list normalised by its best score */
+    SRX_FUSE_RRF = 1       /* weighted reciprocal rank fusion */
+} srx_fuse_mode;
+int srx_fuse_topk(int32_t device, const int32_t *a_doc, const float *a_score, const int32_t *a_count, int32_t ka,
+                  const int32_t *b_doc, const float *b_score, const int32_t *b_count, int32_t kb, int32_t nq, int32_t k,
+                  int32_t mode, float weight_a, float weight_b, float rrf_c, int32_t *out_doc, float *out_score,
+                  int32_t *out_count, void *stream);
 
 /* Average over the profiled srx_search calls since the last read (at most the latest 256): h_ms[0] = tier-1
  * wave kernel, h_ms[1] = tier-2 block kernel, h_ms[2] = merge kernel, h_ms[3] = whole call (milliseconds,

@@ -54,44 +54,6 @@ __device__ __forceinline__ bool after_bound(const ScoreShared &S, unsigned b, in
     return b < S.ub_bits || (b == S.ub_bits && doc > S.ub_doc);
 }
 
-// Rank the block's final list (tk.count <= k entries, unordered) by (score desc, doc asc) -- bitonic sort of 64-bit keys
-// score bits : 0x7FFFFFFF - doc in `sortkey` (KMAX words of LDS) -- and write the padded result row.
-__device__ void block_rank_emit(const TopkShared &tk, unsigned long long *sortkey, int k, int64_t doc_base,
-                                int32_t *__restrict__ row_doc, float *__restrict__ row_score, int32_t *__restrict__ row_count) {
-    const int tid = threadIdx.x;
-    const unsigned cnt = tk.count;
-    unsigned n = 1;
-    while (n < cnt) n <<= 1;
-    for (unsigned i = tid; i < n; i += THREADS)
-        sortkey[i] = i < cnt ? (((unsigned long long)tk.bits[i] << 32) | (0x7FFFFFFFu - (unsigned)tk.doc[i])) : 0ull;
-    __syncthreads();
-    for (unsigned size = 2; size <= n; size <<= 1) {
-        for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
-            for (unsigned i = tid; i < (n >> 1); i += THREADS) {
-                const unsigned pos = 2 * i - (i & (stride - 1));
-                const unsigned long long a = sortkey[pos], b = sortkey[pos + stride];
-                const bool desc = (pos & size) == 0;
-                if (desc ? (a < b) : (a > b)) {
-                    sortkey[pos] = b;
-                    sortkey[pos + stride] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (unsigned i = tid; i < (unsigned)k; i += THREADS) {
-        if (i < cnt) {
-            const unsigned long long x = sortkey[i];
-            row_doc[i] = (int32_t)(doc_base + (int64_t)(0x7FFFFFFFu - (unsigned)(x & 0xFFFFFFFFull)));
-            row_score[i] = __uint_as_float((unsigned)(x >> 32));
-        } else {
-            row_doc[i] = -1;
-            row_score[i] = 0.0f;
-        }
-    }
-    if (tid == 0) *row_count = (int)cnt;
-}
-
 // Where the tier-2 kernel writes FINAL rows (queries that are one work item: nothing is left for the merge kernel) and the
 // worklist length it reports back to the host (pinned word, read without synchronisation by the next call: a hint only).
 struct Tier2Final {

@@ -1,7 +1,7 @@
 // srx_common.h -- shared device primitives of libsparse_rx.so (gfx950): constants, the index view, wave / block
 // reductions, the exact radix selections and the running top-k lists used by the scoring, merge and dense kernels.
 // Everything here has internal linkage (anonymous namespace): each translation unit (sparse_rx.hip, wave_kernel.hip,
-// dense.hip) compiles its own copy; only the few host functions declared at the end cross units.
+// dense.hip, fuse.hip) compiles its own copy; only the few host functions declared at the end cross units.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off  (no fused multiply-add: the reference's arithmetic is
 // separate fp32 multiply / add / IEEE divide).
@@ -418,6 +418,44 @@ __device__ void topk_shrink(int k, TopkShared &tk, unsigned *hist) {
     const int none_d[1] = {0};
     __syncthreads();
     topk_fold<1, false>(none_b, none_d, k, tk, hist);
+}
+
+// Rank the block's final list (tk.count <= k entries, unordered) by (score desc, doc asc) -- bitonic sort of 64-bit keys
+// score bits : 0x7FFFFFFF - doc in `sortkey` (KMAX words of LDS) -- and write the padded result row.
+__device__ void block_rank_emit(const TopkShared &tk, unsigned long long *sortkey, int k, int64_t doc_base,
+                                int32_t *__restrict__ row_doc, float *__restrict__ row_score, int32_t *__restrict__ row_count) {
+    const int tid = threadIdx.x;
+    const unsigned cnt = tk.count;
+    unsigned n = 1;
+    while (n < cnt) n <<= 1;
+    for (unsigned i = tid; i < n; i += THREADS)
+        sortkey[i] = i < cnt ? (((unsigned long long)tk.bits[i] << 32) | (0x7FFFFFFFu - (unsigned)tk.doc[i])) : 0ull;
+    __syncthreads();
+    for (unsigned size = 2; size <= n; size <<= 1) {
+        for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+            for (unsigned i = tid; i < (n >> 1); i += THREADS) {
+                const unsigned pos = 2 * i - (i & (stride - 1));
+                const unsigned long long a = sortkey[pos], b = sortkey[pos + stride];
+                const bool desc = (pos & size) == 0;
+                if (desc ? (a < b) : (a > b)) {
+                    sortkey[pos] = b;
+                    sortkey[pos + stride] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (unsigned i = tid; i < (unsigned)k; i += THREADS) {
+        if (i < cnt) {
+            const unsigned long long x = sortkey[i];
+            row_doc[i] = (int32_t)(doc_base + (int64_t)(0x7FFFFFFFu - (unsigned)(x & 0xFFFFFFFFull)));
+            row_score[i] = __uint_as_float((unsigned)(x >> 32));
+        } else {
+            row_doc[i] = -1;
+            row_score[i] = 0.0f;
+        }
+    }
+    if (tid == 0) *row_count = (int)cnt;
 }
 
 

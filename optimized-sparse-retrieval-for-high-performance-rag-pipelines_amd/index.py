@@ -773,6 +773,98 @@ def merge_topk_device(in_doc, in_score, in_count, k: int, gathered: bool = False
     return out
 
 
+FUSE_MODES = {"weighted": _capi.SRX_FUSE_WEIGHTED, "rrf": _capi.SRX_FUSE_RRF}
+
+
+def check_fuse_args(mode, weights, rrf_c) -> Tuple[int, float, float, float]:
+    """The argument rules of ``srx_fuse_topk`` on the host: (mode code, weight_a, weight_b, rrf_c) or ``ValueError``."""
+    if mode not in FUSE_MODES:
+        raise ValueError(f"fusion must be one of {sorted(FUSE_MODES)}, got {mode!r}")
+    try:
+        wa, wb = (float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise ValueError("weights must be a pair of numbers (sparse, dense)") from None
+    if not (np.isfinite(wa) and np.isfinite(wb)) or wa < 0 or wb < 0:
+        raise ValueError(f"fusion weights must be finite and >= 0, got {(wa, wb)}")
+    if wa == 0 and wb == 0:
+        raise ValueError("fusion weights are both 0")
+    rrf_c = float(rrf_c)
+    if mode == "rrf" and not (np.isfinite(rrf_c) and rrf_c > 0):
+        raise ValueError(f"rrf_c must be finite and > 0, got {rrf_c}")
+    return FUSE_MODES[mode], wa, wb, rrf_c
+
+
+def fuse_topk_device(a, b, k: int, mode: str = "weighted", weights=(0.3, 0.7), rrf_c: float = 60.0):
+    """``srx_fuse_topk`` on device tensors: one fused ranking per query from two ranked lists over the same doc ids.
+    ``a`` (sparse side) and ``b`` (dense side) are ``(doc i32[nq, kx], score f32[nq, kx], count i32[nq])`` as the
+    ``search_device`` of either engine returns them; the result is the same triple with ``k`` columns.  ``mode``
+    "weighted": ``w * (score / best score of the list)``; "rrf": ``w / (rrf_c + rank)``, rank from 1; a doc in both
+    lists gets the sum (include/sparse_rx.h has the exact arithmetic).  Asynchronous on the current stream of the
+    tensors' device."""
+    torch = _torch()
+    code, wa, wb, rrf_c = check_fuse_args(mode, weights, rrf_c)
+    max_k = _capi.limits()["max_k"]
+    (a_doc, a_score, a_count), (b_doc, b_score, b_count) = a, b
+    if a_doc.dim() != 2 or b_doc.dim() != 2 or a_doc.shape != a_score.shape or b_doc.shape != b_score.shape:
+        raise ValueError("fuse_topk_device: doc / score must be [nq, k] tensors of one shape per list")
+    nq, ka, kb = int(a_doc.shape[0]), int(a_doc.shape[1]), int(b_doc.shape[1])
+    if int(b_doc.shape[0]) != nq or a_count.numel() != nq or b_count.numel() != nq:
+        raise ValueError("fuse_topk_device: the two lists must cover the same queries")
+    if not (1 <= ka <= max_k and 1 <= kb <= max_k and 1 <= int(k) <= max_k):
+        raise ValueError(f"fuse_topk_device: list widths and k must be in [1, {max_k}], got {ka}, {kb}, {k}")
+    dev = a_doc.device
+    for t, dt in ((a_doc, torch.int32), (a_score, torch.float32), (a_count, torch.int32), (b_doc, torch.int32),
+                  (b_score, torch.float32), (b_count, torch.int32)):
+        if t.dtype != dt or t.device != dev:
+            raise ValueError("fuse_topk_device: doc / count must be int32, score float32, all on one device")
+    if dev.type != "cuda":
+        raise ValueError("fuse_topk_device: the lists must be device tensors")
+    L = _capi.lib()
+    with torch.cuda.device(dev):
+        out = (torch.empty((nq, k), dtype=torch.int32, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev),
+               torch.empty((nq,), dtype=torch.int32, device=dev))
+        a_doc, a_score, a_count = a_doc.contiguous(), a_score.contiguous(), a_count.contiguous()
+        b_doc, b_score, b_count = b_doc.contiguous(), b_score.contiguous(), b_count.contiguous()
+        rc = L.srx_fuse_topk(dev.index or 0, _ptr(a_doc), _ptr(a_score), _ptr(a_count), ka, _ptr(b_doc), _ptr(b_score),
+                             _ptr(b_count), kb, nq, int(k), code, wa, wb, rrf_c, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                             _stream_ptr(torch, dev))
+        _capi.check(rc, "srx_fuse_topk")
+    return out
+
+
+def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, ka: int, kb: int, k: int, mode: str, weights,
+                  rrf_c: float):
+    """The hybrid pipeline of the API mirrors: sparse search of a host CSR batch on ``index`` (``ka`` rows per query),
+    ``dense_search(kb)`` -> the dense side's device triple for the same queries, ``fuse_topk_device``; the three steps
+    stay on the device, then one synchronisation and one copy back.  Returns host (doc, score, count)."""
+    torch = _torch()
+    check_fuse_args(mode, weights, rrf_c)
+    index.validate_queries(q_ptr, q_term, q_weight)
+    dev = index.device
+    qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
+    qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
+    qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
+    a = index.search_device(qp, qt, qw, ka)
+    b = dense_search(kb)
+    packed = pack_results(*fuse_topk_device(a, b, k, mode=mode, weights=weights, rrf_c=rrf_c))
+    torch.cuda.synchronize(dev)
+    rows = packed.cpu().numpy()
+    return rows[:, :k], rows[:, k:2 * k].view(np.float32), rows[:, 2 * k]
+
+
+def hybrid_depths(top_k: int, candidates, n_docs: int) -> Tuple[int, int]:
+    """(k, rows fetched from each side) for a hybrid search, or ``ValueError``.  ``top_k`` > max_k is refused: paging a
+    fused ranking deeper than the engine's lists is out of scope, and a silently shorter list would be worse."""
+    max_k = 1024  # SRX_MAX_K
+    top_k = int(top_k)
+    if top_k > max_k:
+        raise ValueError(f"hybrid search returns at most {max_k} rows per query, got top_k={top_k}")
+    if candidates is not None and int(candidates) < 1:
+        raise ValueError(f"candidates must be >= 1, got {candidates}")
+    cand = top_k if candidates is None else int(candidates)
+    return min(top_k, n_docs), min(cand, n_docs, max_k)
+
+
 def combine_term_bounds(fine_tables, world: int = None):
     """Corpus-wide score bounds from the shards' tables.  ``fine_tables``: tensor [W, V, len(FINE_KS)] (or a list of
     [V, F] tensors), shard r's K-th largest stored value per term for K in DeviceIndex.FINE_KS (0 = fewer than K

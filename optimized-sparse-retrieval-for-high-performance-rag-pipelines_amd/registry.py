@@ -6,7 +6,8 @@ Mirrors, on the HIP engine, the two other call sites of the reference's hot path
     (``bm25*`` types score with ``simd_bm25_score``, every other type with ``simd_tfidf_score`` and
     idf = log(N/(df+1)), :257-278, :378-399; index cache ``.rag_cache/{method}_index_{hash}.npz``, :189-200, :280-312)
 so that the YAML experiments and ``benchmark_efficiency`` (objects with ``build_index_from_corpus`` + ``search``) run
-unmodified.  The registry's dense types (dpr / contriever / splade) go to the ``QuantizedEmbeddingRetriever`` mirror.
+unmodified.  The registry's dense types (dpr / contriever / splade) go to the ``QuantizedEmbeddingRetriever`` mirror, and
+the ``hybrid`` type the reference configures without implementing it to ``HybridRetriever`` (sparse + dense, fused on the GPU).
 
 ``top_k``: any value, like the reference (deep rankings are paged with ``srx_search_after``); ``top_k <= 0`` gives ``{}``.
 """
@@ -21,7 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from .backend import SparseBackend
-from .index import DeviceIndex, HostIndex, encode_queries
+from .index import DeviceIndex, HostIndex, check_fuse_args, encode_queries, hybrid_depths, hybrid_search
 
 _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
 
@@ -279,6 +280,120 @@ class QuantizedEmbeddingRetriever:
         return results
 
 
+class HybridRetriever:
+    """The ``hybrid`` retriever type the reference configures (configs/ms_marco_paper_results.yaml:108-120: ``model:
+    {sparse, dense}``, ``params: {sparse_weight: 0.3, dense_weight: 0.7, ...}``) but does not implement
+    (retriever_registry.py:596-599 rejects it).  Composes the two mirrors above over one corpus dict -- row i is the same
+    document on both sides -- and fuses their top lists on the GPU (``srx_fuse_topk``, include/sparse_rx.h).
+
+    ``fusion``: "weighted" (each side's scores divided by its best score, then the weighted sum) or "rrf" (weighted
+    reciprocal rank fusion with constant ``rrf_c``).  ``candidates``: rows fetched from each side (default ``top_k``; each
+    side is capped at ``min(candidates, n_docs, 1024)``).  A doc only one side retrieved scores with that side alone.
+    With one weight 0 the result is the other side's SET, but equal normalised scores rank by doc id, so the order can
+    differ from that side's own.  ``top_k`` > 1024 raises ``ValueError``: fused rankings deeper than the engine's lists
+    are not paged, and a silently shorter list would be worse than an error.  The dense side is the symmetric INT8 engine
+    whatever the embeddings' origin.  Needs the whole index on one GPU."""
+
+    def __init__(self, model=None, sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted",
+                 rrf_c: float = 60.0, candidates: Optional[int] = None, embedding_dim: int = 768, device: Optional[str] = None,
+                 k1: float = 1.2, b: float = 0.75, tile_log2: int = 14, **kwargs):
+        model = model or {}
+        if not isinstance(model, dict):
+            raise ValueError("hybrid retriever: model must be a dict {sparse: ..., dense: ...}")
+        fusion = str(fusion).lower()
+        check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
+        if candidates is not None and int(candidates) < 1:
+            raise ValueError(f"candidates must be >= 1, got {candidates}")
+        self.method = "hybrid"
+        self.sparse_weight, self.dense_weight = float(sparse_weight), float(dense_weight)
+        self.fusion, self.rrf_c, self.candidates = fusion, float(rrf_c), candidates
+        # top_k, use_numba, cache_matrices of the reference's config block are accepted and mean nothing here
+        sparse, dense = str(model.get("sparse", "bm25")), str(model.get("dense", "dpr"))
+        group = {key: kwargs[key] for key in ("group", "sharded", "shard_searcher_factory") if key in kwargs}
+        if sparse.lower() == "tfidf":
+            self.sparse = OptimizedBM25Retriever(method="tfidf", model=sparse, k1=1000, b=0, device=device, tile_log2=tile_log2,
+                                                 cache_queries=False, **group)
+        else:  # a bm25 type name, or a model name for the default type
+            self.sparse = OptimizedBM25Retriever(method=sparse if sparse.lower() in _BM25_TYPES else "bm25", model=sparse, k1=k1, b=b,
+                                                 device=device, tile_log2=tile_log2, cache_queries=False, **group)
+        self.dense = QuantizedEmbeddingRetriever(method=dense if dense.lower() in ("dpr", "contriever", "splade") else "dpr",
+                                                 model=dense, embedding_dim=embedding_dim, device=self.sparse.device)
+        self.device = self.sparse.device
+
+    @property
+    def doc_ids(self):
+        return self.sparse.doc_ids
+
+    def _refuse_sharded(self):
+        if self.sparse._be.sharded():
+            raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
+
+    def build_index_from_corpus(self, corpus: Dict[str, Dict], embeddings=None) -> None:
+        """``embeddings``: f32[n_docs, dim], row i = the i-th corpus key; ``None`` = the dense mirror's simulated
+        vectors (what the reference's dense types index).  Either way the rows are quantised into one INT8 index."""
+        from .dense import DenseInt8Index, quantize_symmetric
+        self._refuse_sharded()
+        if not corpus:
+            raise ValueError("Empty corpus provided")
+        if embeddings is not None:
+            emb = np.asarray(embeddings, dtype=np.float32)
+            if emb.ndim != 2 or emb.shape[0] != len(corpus):
+                raise ValueError("embeddings must be [n_docs, dim] with one row per document")
+        self.sparse.build_index_from_corpus(corpus)
+        d = self.dense
+        if embeddings is None:
+            emb = d.synthetic_embeddings(len(corpus))
+        d.embedding_dim = int(emb.shape[1])
+        d.doc_ids = list(corpus.keys())
+        d.use_quantization, d.quantization_method = True, "symmetric"
+        d.corpus_embeddings_int8, d.corpus_scales = quantize_symmetric(emb)
+        d._index = DenseInt8Index(d.corpus_embeddings_int8, d.corpus_scales, device=self.device)
+
+    def search(self, queries: Dict[str, str], top_k: int = 10, query_embeddings=None) -> Dict[str, Dict[str, float]]:
+        """``{qid: {doc_id: fused score}}`` in rank order.  ``query_embeddings``: ``{qid: f32[dim]}``; ``None`` = the dense
+        mirror's simulated query vectors (seeded by ``hash(text)``: they differ between processes, like the reference's)."""
+        from .dense import quantize_query_symmetric
+        self._refuse_sharded()
+        if self.sparse.host is None or self.dense._index is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
+        n_docs = len(self.doc_ids)
+        k, cand = hybrid_depths(top_k, self.candidates, n_docs)
+        live = [(qid, text) for qid, text in queries.items() if text]
+        if k <= 0 or not live:
+            return results
+        embs = []
+        for qid, text in live:
+            if query_embeddings is None:
+                e = self.dense._generate_query_embedding(text)
+            else:
+                if qid not in query_embeddings:
+                    raise ValueError(f"no query embedding for {qid!r}")
+                e = np.asarray(query_embeddings[qid], dtype=np.float32)
+                if e.shape != (self.dense.embedding_dim,):
+                    raise ValueError(f"query embedding of {qid!r} has shape {e.shape}, expected ({self.dense.embedding_dim},)")
+            embs.append(e)
+        qq = [quantize_query_symmetric(e) for e in embs]
+        q_i8, q_scale = np.stack([a for a, _ in qq]), np.array([s for _, s in qq], dtype=np.float32)
+        q_ptr, q_term, q_w = encode_queries([text for _, text in live], self.sparse.host.vocabulary)
+
+        def dense_search(kb):
+            import torch
+            return self.dense._index.search_device(torch.as_tensor(np.ascontiguousarray(q_i8, dtype=np.int8), device=self.device),
+                                                   torch.as_tensor(q_scale, device=self.device), kb)
+
+        doc, score, count = hybrid_search(self.sparse.dev, q_ptr, q_term, q_w, dense_search, cand, cand, k, self.fusion,
+                                          (self.sparse_weight, self.dense_weight), self.rrf_c)
+        ids = self.doc_ids
+        for i, (qid, _) in enumerate(live):
+            results[qid] = {ids[int(doc[i, j])]: float(score[i, j]) for j in range(int(count[i]))}
+        return results
+
+    def close(self):
+        self.sparse.close()
+        self.dense._index = None
+
+
 class RetrieverRegistry:
     """retriever_registry.py:562-599."""
 
@@ -307,6 +422,8 @@ class RetrieverRegistry:
             p2 = dict(params)
             embedding_dim = p2.pop("embedding_dim", 768)
             return QuantizedEmbeddingRetriever(method=method, model=model or f"quantized_{method}", embedding_dim=embedding_dim, **p2)
+        if m == "hybrid":  # configured by the reference, implemented here only (HybridRetriever)
+            return HybridRetriever(model=model, **params)
         if method in cls._retrievers:
             return cls._retrievers[method](**params)
         raise ValueError(f"Unknown retriever method: {method}")
@@ -314,4 +431,4 @@ class RetrieverRegistry:
     @classmethod
     def list_available(cls):
         return {"optimized_sparse": ["bm25", "bm25_custom", "tfidf"], "quantized_dense": ["dpr", "contriever", "splade"],
-                "registered_custom": list(cls._retrievers.keys())}
+                "hybrid": ["hybrid"],                 "registered_custom": list(cls._retrievers.keys())}

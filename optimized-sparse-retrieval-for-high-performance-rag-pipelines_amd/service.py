@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .backend import SparseBackend
-from .index import DeviceIndex, HostIndex, encode_queries
+from .index import DeviceIndex, HostIndex, check_fuse_args, encode_queries, hybrid_depths, hybrid_search
 
 logger = logging.getLogger(__name__)
 
@@ -196,12 +196,7 @@ class RetrievalService:
         that every doc is rankable; its k rows are re-scored on the host with ``np.dot`` (fp32, the reference's own
         expression) and re-ranked, so the shift never shows in the result.  The shift coarsens that pass's ranking to
         ulp(offset): docs whose true scores differ by less can swap places at the k-th boundary (scores <= 0 only)."""
-        if getattr(self, "_dense", None) is None and self.embedding_path and os.path.exists(str(self.embedding_path)) and self.doc_ids:
-            n = len(self.doc_ids)
-            dim = os.path.getsize(str(self.embedding_path)) // (n * 4)  # retrieval.py:324-328
-            self.set_embeddings(np.memmap(str(self.embedding_path), dtype="float32", mode="r", shape=(n, dim)))
-        if getattr(self, "_dense", None) is None:
-            raise ValueError("No embedding index available")
+        self._ensure_dense()
         q = np.asarray(query_vector, dtype=np.float32)
         kk = max(1, min(int(k), self._dense.n_docs))
         d, s, n = self._dense.search(q, kk)
@@ -225,6 +220,65 @@ class RetrievalService:
                 results.append({"doc_id": self.doc_ids[int(i)], "score": float(score)})
             elif not self.doc_ids:
                 results.append({"doc_id": str(int(i)), "score": float(score)})
+        return results
+
+    def _ensure_dense(self) -> None:
+        if getattr(self, "_dense", None) is None and self.embedding_path and os.path.exists(str(self.embedding_path)) and self.doc_ids:
+            n = len(self.doc_ids)
+            dim = os.path.getsize(str(self.embedding_path)) // (n * 4)  # retrieval.py:324-328
+            self.set_embeddings(np.memmap(str(self.embedding_path), dtype="float32", mode="r", shape=(n, dim)))
+        if getattr(self, "_dense", None) is None:
+            raise ValueError("No embedding index available")
+
+    def search_hybrid(self, queries: Dict[str, str], query_vectors: Dict[str, np.ndarray], top_k: int = 10, *,
+                      sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted", rrf_c: float = 60.0,
+                      candidates: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+        """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
+        the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
+        ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
+        arithmetic).  ``fusion`` "weighted": each side's scores divided by its best score, then
+        ``sparse_weight * s + dense_weight * d``; "rrf": ``weight / (rrf_c + rank)`` per side.  A doc only one side
+        retrieved scores with that side alone; a query without in-vocabulary terms is the dense list re-scored.
+        ``candidates``: rows fetched from each side (default ``top_k``, capped at ``min(candidates, n_docs, 1024)``).
+        All queries of the call run as one batch: sparse search, dense search and fusion stay on the device, followed by
+        one synchronisation and one copy back.  Returns ``{qid: {doc_id: fused score}}`` in rank order, ``{}`` for a blank
+        query; ``top_k <= 0`` gives ``{}`` per query.  ``top_k`` > 1024 raises ``ValueError``: a fused ranking deeper
+        than the engine's lists is not paged, and a silently shorter list would be worse than an error.  With one weight
+        0 the result is the other side's set, but equal normalised scores rank by doc id.  The query cache is not used.
+        Needs the whole index on one GPU."""
+        fusion = str(fusion).lower()
+        check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
+        k, cand = hybrid_depths(top_k, candidates, self._be.n_docs_total)
+        if self._be.sharded():
+            raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        self._ensure_dense()
+        results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
+        live = [(qid, text) for qid, text in queries.items() if text and text.strip()]
+        if k <= 0 or not live:
+            return results
+        vecs = []
+        for qid, _ in live:
+            if qid not in query_vectors:
+                raise ValueError(f"no query vector for {qid!r}")
+            v = np.asarray(query_vectors[qid], dtype=np.float32)
+            if v.shape != (self._dense.dim,):
+                raise ValueError(f"query vector of {qid!r} has shape {v.shape}, expected ({self._dense.dim},)")
+            vecs.append(v)
+        if (self.k1, self.b) != self._built_k1b:
+            self._upload()
+        q_ptr, q_term, q_weight = encode_queries([text for _, text in live], self.host.vocabulary)
+
+        def dense_search(kb):
+            import torch
+            return self._dense.search_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), kb)
+
+        doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
+                                          (sparse_weight, dense_weight), rrf_c)
+        ids = self.host.doc_ids
+        for i, (qid, _) in enumerate(live):
+            results[qid] = {ids[int(doc[i, j])]: float(score[i, j]) for j in range(int(count[i]))}
         return results
 
     def clear_cache(self) -> None:
