@@ -17,6 +17,8 @@
  *                         (multi-GPU: after the RCCL all-gather; no reference counterpart)
  *   srx_fuse_topk         hybrid retrieval: one fused ranking from a sparse and a dense top-k list (the reference
  *                         configures a `hybrid` retriever but does not implement it)
+ *   srx_score_docs        the exact score of caller-given (query, doc) pairs, same arithmetic as srx_search (the reference
+ *                         can only rank: no counterpart)
  *
  * Conventions
  *   - extern "C", plain pointers and sizes, no C++ / torch types.  Every array pointer is a DEVICE
@@ -345,6 +347,35 @@ int srx_fuse_topk(int32_t device, const int32_t *a_doc, const float *a_score, co
                   const int32_t *b_doc, const float *b_score, const int32_t *b_count, int32_t kb, int32_t nq, int32_t k,
                   int32_t mode, float weight_a, float weight_b, float rrf_c, int32_t *out_doc, float *out_score,
                   int32_t *out_count, void *stream);
+
+/*
+ * Exact sparse scores of caller-given candidate docs: out_score[q][c] = what doc cand_doc[q][c] scores for query q, with the
+ * arithmetic of srx_search, so a row srx_search returned scores to its own bits.  Replaces nothing in the reference (it
+ * can only rank); the expression is its per-posting contribution and summation order (srx_index_desc above:
+ * retrieval.py:41-76 / evaluate_rag_pipeline.py:95-121, 436-479).  Takes the DESCRIPTOR (a host struct), not a handle, and
+ * reads whichever copy of the postings it has: the compact copy (post16) when present, else the canonical blocks (post);
+ * both value types.  Added without a version bump: SRX_VERSION stays 301.
+ * Queries are the CSR batch of srx_search with the same PRECONDITIONS, not checked on the device: q_ptr[0] == 0 and q_ptr
+ * non-decreasing; 0 <= q_term < vocab; no term twice in one query.  The order of a query's terms is the order of the additions.
+ * cand_doc i32[nq][m]: GLOBAL row ids (doc_base + local row, what srx_search returns); m >= 1, nq * m <= 2^31 - 1, no other
+ * limit on m (m = n_docs gives a full score vector).  cand_count i32[nq] or NULL: with it, entries c >= max(cand_count[q], 0)
+ * are padding -- the (doc, score, count) triple of either search engine can be passed as it is, -1 padding included.
+ * out_score[q * m + c], f32:
+ *   +0.0f  if the entry is padding, or if cand_doc - doc_base (computed in 64 bits) is outside [0, n_docs): -1, rows of
+ *          another shard;
+ *   else   s = +0.0f, then for i = q_ptr[q] .. q_ptr[q + 1] - 1 in that order: if term q_term[i] has a posting for the doc with
+ *          stored value v, s = s + ((v * idf[t]) * q_weight[i]), every operation rounded to fp32 on its own, fp16 values
+ *          widened exactly.  (A stored value of exactly 0 may be added or skipped: starting from +0.0f the bits are the same.)
+ * There is NO score > 0 filter: negative scores (negative idf) and zeros are returned as they are -- scoring is not
+ * retrieval.  Duplicates in a row are legal; each is scored.
+ * Refused with SRX_ERR_INVALID before anything touches a device: a NULL descriptor; bad val_type; n_docs / vocab / tile_log2 /
+ * n_tiles / unit_tiles out of range or inconsistent (the rules of srx_index_create); neither post nor post16; post16 with
+ * a unit of more than 49152 docs; NULL term_ptr / tile_skip / idf; nq < 0, m < 1, nq * m > 2^31 - 1; NULL q_ptr / cand_doc /
+ * out_score with nq > 0.  nq == 0 returns SRX_OK without a launch.  Asynchronous on `stream`, allocates nothing, needs no
+ * workspace and writes nothing but out_score.
+ */
+int srx_score_docs(const srx_index_desc *h_desc, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
+                   const int32_t *cand_doc, const int32_t *cand_count, int32_t m, float *out_score, void *stream);
 
 /* Average over the profiled srx_search calls since the last read (at most the latest 256): h_ms[0] = tier-1
  * wave kernel, h_ms[1] = tier-2 block kernel, h_ms[2] = merge kernel, h_ms[3] = whole call (milliseconds,

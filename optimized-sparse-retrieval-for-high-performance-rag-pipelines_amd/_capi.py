@@ -15,7 +15,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
-SOURCES = ["wave_kernel.hip", "sparse_rx.hip", "dense.hip", "fuse.hip"]   # one translation unit each, compiled in parallel
+SOURCES = ["wave_kernel.hip", "sparse_rx.hip", "dense.hip", "fuse.hip", "score_docs.hip"]   # one translation unit each, compiled in parallel
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
@@ -76,6 +76,7 @@ SYMBOLS = {
     "srx_dense_search_u8": (ctypes.c_int, [_I32, _VP, _VP, _I64, _I32, _VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _I64, _VP]),
     "srx_fuse_topk": (ctypes.c_int, [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, ctypes.c_float, ctypes.c_float,
                                      ctypes.c_float, _VP, _VP, _VP, _VP]),
+    "srx_score_docs": (ctypes.c_int, [ctypes.POINTER(IndexDesc), _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP]),
     "srx_build_impacts": (ctypes.c_int, [_I32, _VP, _VP, _VP, _I64, _DBL, _DBL, _DBL, _VP, _VP]),
     "srx_build_tile_skip": (ctypes.c_int, [_I32, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "srx_memcpy_async": (ctypes.c_int, [_VP, _VP, _I64, _VP]),

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .index import DeviceIndex, HostIndex, build_host_index, deep_search, validate_query_batch
+from .index import DeviceIndex, HostIndex, build_host_index, deep_search, validate_candidates, validate_query_batch
 
 
 class SparseBackend:
@@ -123,6 +123,63 @@ class SparseBackend:
             self.searcher.wait()
             torch.cuda.synchronize(dev)
         return d.cpu().numpy(), s.cpu().numpy(), c.cpu().numpy()
+
+    def score_arrays(self, q_ptr, q_term, q_weight, cand_doc, cand_count=None) -> np.ndarray:
+        """Host CSR batch + host candidate block (cand_doc int[nq, m] GLOBAL row ids, cand_count int[nq] or None) -> the exact
+        scores f32[nq, m] (``srx_score_docs``): on the one shard, or scored on every shard and summed
+        (distributed.ShardedSearcher.score_docs)."""
+        if self.searcher is None:
+            return self.dev.score_docs(q_ptr, q_term, q_weight, cand_doc, cand_count)
+        import torch
+        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
+        nq = len(q_ptr) - 1
+        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
+        if nq == 0:
+            return np.zeros((0, cand_doc.shape[1]), np.float32)
+        dev = self.dev.device if self.dev is not None else torch.device("cpu")
+        qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
+        qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
+        qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
+        cd = torch.as_tensor(cand_doc, device=dev)
+        cc = None if cand_count is None else torch.as_tensor(cand_count, device=dev)
+        out = self.searcher.score_docs(qp, qt, qw, cd, cc)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
+
+    def score_dicts(self, queries, candidates, order: str = "term"):
+        """The dict form the API mirrors share: ``queries`` {qid: text}, ``candidates`` {qid: sequence of doc ids} ->
+        {qid: {doc_id: exact score}} with every listed candidate in the caller's order (0.0 where no query term matches,
+        and for a blank or all-OOV query); a qid without candidates gives {}; an unknown doc id raises ValueError.  One
+        batch: ragged lists are padded with -1 and passed with their lengths (``cand_count``)."""
+        from .index import encode_queries
+        ids = self.host.doc_ids
+        if getattr(self, "_row_of_ids", None) is not ids:
+            self._row_of, self._row_of_ids = {d: i for i, d in enumerate(ids)}, ids
+        results = {qid: {} for qid in queries}
+        live, rows = [], []
+        for qid, text in queries.items():
+            cands = list(candidates.get(qid, ()) or ())
+            if not cands:
+                continue
+            try:
+                rows.append([self._row_of[d] for d in cands])
+            except KeyError as e:
+                raise ValueError(f"unknown doc id {e.args[0]!r} among the candidates of {qid!r}") from None
+            live.append((qid, text or "", cands))
+        if not live:
+            return results
+        m = max(len(r) for r in rows)
+        cand_doc = np.full((len(rows), m), -1, dtype=np.int32)
+        cand_count = np.zeros(len(rows), dtype=np.int32)
+        for i, r in enumerate(rows):
+            cand_doc[i, : len(r)] = r
+            cand_count[i] = len(r)
+        q_ptr, q_term, q_weight = encode_queries([text for _, text, _ in live], self.host.vocabulary, order=order)
+        scores = self.score_arrays(q_ptr, q_term, q_weight, cand_doc, cand_count)
+        for i, (qid, _, cands) in enumerate(live):
+            results[qid] = {d: float(scores[i, c]) for c, d in enumerate(cands)}
+        return results
 
     def close(self) -> None:
         if self.dev is not None:

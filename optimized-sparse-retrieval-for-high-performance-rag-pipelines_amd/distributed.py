@@ -164,8 +164,11 @@ class ShardedSearcher:
     LANE_KEYS = 4  # graph lanes: the tensor sets whose captured graphs are kept (_search_graph)
 
     def __init__(self, local_search: Callable, pack: Callable, merge: Callable, group=None,
-                 local_search_packed: Callable = None, merge_packed_out: Callable = None):
+                 local_search_packed: Callable = None, merge_packed_out: Callable = None, local_score: Callable = None):
         self.local_search = local_search
+        # local_score(q_ptr, q_term, q_weight, cand_doc i32[nq, m] GLOBAL ids, cand_count i32[nq] | None) -> f32[nq, m]: this
+        # shard's exact scores, +0 for padding and for rows of other shards (:meth:`score_docs`)
+        self.local_score = local_score
         self.pack = pack
         self.merge = merge
         self.group = group
@@ -181,7 +184,8 @@ class ShardedSearcher:
     def for_device_index(cls, index, group=None) -> "ShardedSearcher":
         from .index import merge_topk_packed_device, merge_topk_packed_out_device, pack_results
         s = cls(index.search_device, pack_results, merge_topk_packed_device, group,
-                local_search_packed=index.search_packed_device, merge_packed_out=merge_topk_packed_out_device)
+                local_search_packed=index.search_packed_device, merge_packed_out=merge_topk_packed_out_device,
+                local_score=index.score_docs_device)
         s.workspace_bytes = index.workspace_bytes  # lets the graph lanes give every lane a workspace of its own
         return s
 
@@ -239,6 +243,23 @@ class ShardedSearcher:
             for t in o:
                 t.record_stream(main)
         return tuple(torch.cat([o[j] for o in outs]) for j in range(3))
+
+    def score_docs(self, q_ptr, q_term, q_weight, cand_doc, cand_count=None):
+        """Exact scores f32[nq, m] of the candidate block ``cand_doc`` i32[nq, m] (GLOBAL row ids; ``cand_count`` i32[nq]
+        or None marks the padding), identical on every rank and identical to the one-shard result.
+
+        Every rank scores the WHOLE block on its shard (``local_score``: rows of other shards and padding come back
+        ``+0.0``), then ONE ``all_reduce(SUM)`` of f32[nq, m].  That is exact: each pair has one owning shard and every
+        other addend is ``+0.0``; ``x + (+0) = x`` bit for bit in any association order, and an own score is never ``-0``
+        because its sum starts at ``+0``.  Eager path only (the graph lanes serve the searches)."""
+        import torch.distributed as dist
+        if self.local_score is None:
+            raise ValueError("this ShardedSearcher was built without local_score: it cannot score given docs")
+        out = self.local_score(q_ptr, q_term, q_weight, cand_doc, cand_count)
+        exchange = (dist.is_initialized() and dist.get_world_size(self.group) > 1) or getattr(self, "force_exchange", False)
+        if exchange:
+            dist.all_reduce(out, op=dist.ReduceOp.SUM, group=self.group)
+        return out
 
     def _search_graph(self, q_ptr, q_term, q_weight, k: int, world: int):
         """Steady-state submission for a caller that searches the SAME device tensors batch after batch (a serving loop with

@@ -157,6 +157,35 @@ def validate_query_batch(q_ptr, q_term, q_weight, vocab: int) -> None:
                 raise ValueError("a query lists the same term twice (merge duplicates into one weight)")
 
 
+def validate_candidates(cand_doc, cand_count, nq: int) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """The candidate block of ``srx_score_docs`` (include/sparse_rx.h) as host arrays, checked before anything is launched:
+    ``cand_doc`` is a 2-D integer array with ``nq`` rows and ``m >= 1`` columns whose values are int32-representable
+    (GLOBAL row ids; ``-1`` and any other id outside the index are legal and score ``+0``), ``nq * m <= 2**31 - 1``;
+    ``cand_count`` is ``None`` or a 1-D integer array of length ``nq`` with int32-representable values (entries
+    ``c >= max(cand_count[q], 0)`` of row q are padding).  Returns them as contiguous int32 arrays.  Raises ValueError."""
+    d = np.asarray(cand_doc)
+    if d.ndim != 2 or d.dtype.kind not in "iu":
+        raise ValueError("cand_doc must be a 2-D integer array [nq, m]")
+    if d.shape[0] != nq:
+        raise ValueError(f"cand_doc has {d.shape[0]} rows for {nq} queries")
+    if d.shape[1] < 1:
+        raise ValueError("cand_doc needs m >= 1 columns")
+    if nq * d.shape[1] > 2 ** 31 - 1:
+        raise ValueError("nq * m must be <= 2**31 - 1")
+    i32 = np.iinfo(np.int32)
+    if d.size and (int(d.min()) < i32.min or int(d.max()) > i32.max):
+        raise ValueError("cand_doc holds ids that are not int32-representable")
+    c = None
+    if cand_count is not None:
+        c = np.asarray(cand_count)
+        if c.ndim != 1 or c.dtype.kind not in "iu" or len(c) != nq:
+            raise ValueError(f"cand_count must be a 1-D integer array of length {nq}")
+        if c.size and (int(c.min()) < i32.min or int(c.max()) > i32.max):
+            raise ValueError("cand_count holds values that are not int32-representable")
+        c = np.ascontiguousarray(c, dtype=np.int32)
+    return np.ascontiguousarray(d, dtype=np.int32), c
+
+
 # ---------------------------------------------------------------------------------------------------------
 # device index
 # ---------------------------------------------------------------------------------------------------------
@@ -247,6 +276,7 @@ class DeviceIndex:
         if self._h:
             _capi.lib().srx_index_destroy(self._h)
         self._h = h
+        self._desc = d  # the handle-free entry points (srx_score_docs) take the descriptor itself
 
     def set_term_bound(self, table) -> None:
         """Replace the score-bound table (f32[V, 4], K = 1, 10, 100, 1000).  Any table of valid LOWER bounds of the K-th
@@ -563,6 +593,55 @@ class DeviceIndex:
         d, s, c = deep_search(self.search_device, qp, qt, qw, k, _capi.limits()["max_k"])
         torch.cuda.synchronize(dev)
         return d.cpu().numpy(), s.cpu().numpy(), c.cpu().numpy()
+
+    # -- scores of given docs ------------------------------------------------------------------------------
+    def score_docs_device(self, q_ptr, q_term, q_weight, cand_doc, cand_count=None, out=None):
+        """``srx_score_docs`` on device tensors: the exact score of every (query, candidate) pair, with the arithmetic of the
+        search (a row ``search_device`` returned scores to its own bits).  q_ptr i32[nq+1], q_term i32, q_weight f32 as in
+        :meth:`search_device`; cand_doc i32[nq, m] GLOBAL row ids; cand_count i32[nq] or None (entries ``c >= cand_count[q]``
+        are padding) -- the (doc, score, count) triple of a search can be passed as it is.  Returns f32[nq, m] (``out`` when
+        given): ``+0`` for padding and for ids outside this shard, no ``score > 0`` filter.  Asynchronous on the current
+        stream.  Precondition (NOT checked here, the tensors never leave the device): q_ptr starts at 0 and is
+        non-decreasing, 0 <= q_term < vocab, no term twice inside a query -- :meth:`score_docs` checks host batches."""
+        torch = _torch()
+        nq = q_ptr.numel() - 1
+        if cand_doc.dim() != 2 or int(cand_doc.shape[0]) != nq or cand_doc.dtype != torch.int32:
+            raise ValueError("score_docs_device: cand_doc must be an int32 tensor [nq, m]")
+        m = int(cand_doc.shape[1])
+        if m < 1:
+            raise ValueError("score_docs_device: cand_doc needs m >= 1 columns")
+        if cand_count is not None and (cand_count.dtype != torch.int32 or cand_count.numel() != nq):
+            raise ValueError("score_docs_device: cand_count must be an int32 tensor [nq]")
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty((nq, m), dtype=torch.float32, device=self.device)
+            if out.dtype != torch.float32 or tuple(out.shape) != (nq, m) or not out.is_contiguous():
+                raise ValueError("score_docs_device: out must be a contiguous float32 tensor [nq, m]")
+            cand_doc = cand_doc.contiguous()
+            cand_count = None if cand_count is None else cand_count.contiguous()
+            rc = _capi.lib().srx_score_docs(ctypes.byref(self._desc), _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, _ptr(cand_doc),
+                                            _ptr(cand_count), m, _ptr(out), _stream_ptr(torch, self.device))
+            _capi.check(rc, "srx_score_docs")
+        return out
+
+    def score_docs(self, q_ptr: np.ndarray, q_term: np.ndarray, q_weight: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
+        """Host arrays in, f32[nq, m] out.  The batch (``validate_queries``) and the candidates
+        (:func:`validate_candidates`) are validated first; then one launch, one synchronisation and one copy."""
+        torch = _torch()
+        nq = len(q_ptr) - 1
+        self.validate_queries(q_ptr, q_term, q_weight)
+        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
+        if nq == 0:
+            return np.zeros((0, cand_doc.shape[1]), np.float32)
+        dev = self.device
+        qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
+        qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
+        qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
+        cd = torch.as_tensor(cand_doc, device=dev)
+        cc = None if cand_count is None else torch.as_tensor(cand_count, device=dev)
+        out = self.score_docs_device(qp, qt, qw, cd, cc)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
 
     def profile_read(self):
         """Average kernel durations (ms) over the profiled searches since the last read."""

@@ -115,6 +115,15 @@ class _SparseRetrieverBase:
                     results[qid] = dict(d)
         return results
 
+    def score(self, queries: Dict[str, str], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
+        """The exact score of caller-named documents: ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in
+        the caller's order and the arithmetic of :meth:`search` (``srx_score_docs``; the accumulation order is this
+        retriever's ``term_order``).  No ``score > 0`` filter: 0.0 where no query term matches and for a blank or
+        all-OOV query; ``{}`` for a qid without candidates; ``ValueError`` for an unknown doc id.  One batch, no cache."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        return self._be.score_dicts(queries, candidates, order=self.term_order)
+
     def _to_dict(self, idx, sc):
         ids = self.host.doc_ids
         return {ids[int(i)]: float(s) for i, s in zip(idx, sc) if s > 0}

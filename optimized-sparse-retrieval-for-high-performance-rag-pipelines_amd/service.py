@@ -27,7 +27,7 @@ import logging
 import os
 import threading
 import time
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -166,6 +166,19 @@ class RetrievalService:
                 for qid in pending[key]:
                     results[qid] = dict(d)
         return results
+
+    def score_bm25(self, queries: Dict[str, str], candidates: Dict[str, Sequence[str]]) -> Dict[str, Dict[str, float]]:
+        """The exact BM25 score of caller-named documents (no reference counterpart: it can only rank):
+        ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in the caller's order, scored with the arithmetic
+        of :meth:`search_bm25` (``srx_score_docs``: a row ``search_bm25`` returned scores to the same float).  There is no
+        ``score > 0`` filter: a doc no query term matches scores 0.0, as does every doc for a blank or all-OOV query; a qid
+        without candidates gives ``{}``; an unknown doc id raises ``ValueError``.  All queries of the call run as one batch
+        (ragged lists padded); the query cache is not used.  Sharded: every rank makes the same call and gets the same dict."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        if (self.k1, self.b) != self._built_k1b:
+            self._upload()
+        return self._be.score_dicts(queries, candidates, order="term")
 
     def _to_dict(self, idx: np.ndarray, sc: np.ndarray) -> Dict[str, float]:
         ids = self.host.doc_ids
