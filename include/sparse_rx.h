@@ -170,6 +170,17 @@ int srx_search(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const
  * gathered == 1: [n_lists][nq][k] and [n_lists][nq] -- the layout an all-gather of per-rank srx_search
  * outputs produces.  Doc ids are taken as they are (global).  workspace may be NULL when
  * n_lists*k <= 4096, otherwise srx_merge_workspace_bytes() bytes.
+ * The same contract in every layout and for the packed forms below (tests/merge_ref.py restates it, tests/test_merge_gpu.py
+ * pins it bit for bit): entry r of a list is used iff r < min(max(count, 0), k) and score > 0 -- NaN, -0.0, 0 and negative
+ * scores are not, +inf and denormals are; whatever lies behind count is not read.  A negative count is an empty list, in
+ * the first list of a query as in any other; a count above k means k entries.  The order of the entries inside a list is
+ * irrelevant (the lists need not be ranked).  Result row: the k best used entries by (score bits descending, doc
+ * ascending), then doc -1 / score +0.0; every word of the row and the count are written for every query.
+ * PRECONDITIONS, not checked on the device: no doc id twice in one query (the merge does not de-duplicate: both copies
+ * would be returned); 0 <= doc <= 2^31 - 2 for used entries.
+ * Refused before anything touches a device: nq < 0, n_lists <= 0, k outside 1..SRX_MAX_K, a NULL pointer with nq > 0 (a
+ * NULL packed buffer: always) -- SRX_ERR_INVALID; a workspace that is needed and NULL or too small -- SRX_ERR_NOMEM.
+ * nq == 0 returns SRX_OK without a launch.
  */
 int64_t srx_merge_workspace_bytes(int32_t nq, int32_t n_lists, int32_t k);
 int srx_merge_topk(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count,

@@ -585,7 +585,7 @@ int dense_search_i8_impl(int32_t device, const int8_t *corpus, const float *corp
                                w.cand_score, w.cand_count, (unsigned *)nullptr, 0);
             HIP_TRY(hipGetLastError());
             int rc = srx_merge_impl(device, w.cand_doc, w.cand_score, w.cand_count, qb, 1, k, 0, (int64_t)k, (int64_t)1, od, os, oc,
-                                (int64_t)k, (int64_t)1, nullptr, 0, stream_v);
+                                (int64_t)k, (int64_t)1, nullptr, 0, stream_v, nullptr, 1);
             if (rc != SRX_OK) return rc;
             // ---- fallback for queries whose buffer overflowed (degenerate score distributions): through the score
             //      matrix; both kernels return at once unless the any-overflow flag is set ----
@@ -596,7 +596,7 @@ int dense_search_i8_impl(int32_t device, const int8_t *corpus, const float *corp
                                (const int *)w.any_ovf, w.cand_doc, w.cand_score, w.cand_count, (unsigned *)nullptr, 0);
             HIP_TRY(hipGetLastError());
             rc = srx_merge_impl(device, w.cand_doc, w.cand_score, w.cand_count, qb, ns, k, 0, (int64_t)k, (int64_t)1, od, os, oc,
-                            (int64_t)k, (int64_t)1, nullptr, 0, stream_v, (const int *)w.any_ovf);
+                            (int64_t)k, (int64_t)1, nullptr, 0, stream_v, (const int *)w.any_ovf, 1);
             if (rc != SRX_OK) return rc;
         } else {
             SRX_DENSE_DISPATCH(srx_dense_i8_scores_kernel, blocks_for(n_docs), THREADS, corpus, corpus_scale, n_docs, (const v4i *)w.apack, qs, qb, w.scores, ld, no_gate, packed);

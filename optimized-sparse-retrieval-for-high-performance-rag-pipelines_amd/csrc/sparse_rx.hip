@@ -1191,13 +1191,15 @@ __global__ __launch_bounds__(THREADS) void srx_merge_wave_kernel(const int32_t *
                                                                  int32_t *__restrict__ out_doc,
                                                                  float *__restrict__ out_score,
                                                                  int32_t *__restrict__ out_count, int64_t out_row_stride,
-                                                                 int64_t out_cnt_stride, const int *__restrict__ gate, int q0) {
+                                                                 int64_t out_cnt_stride, const int *__restrict__ gate, int q0,
+                                                                 int skip_final) {
     __shared__ MergeWaveShared MW[WAVES];
     const int lane = threadIdx.x & 63;
     const int q = q0 + blockIdx.x * WAVES + (threadIdx.x >> 6);  // q0: first query this launch covers (the split ones of a search)
     if (q >= nq) return;
     if (gate != nullptr && *gate == 0) return;  // optional device-side switch (dense fallback pass)
-    if (!gathered && in_count[(int64_t)q * n_lists * cnt_stride] < 0) return;  // tier 1 already wrote this query's final row
+    // skip_final (plain layout only): a negative count in the query's first list marks a row its producer already wrote
+    if (skip_final && in_count[(int64_t)q * n_lists * cnt_stride] < 0) return;
     MergeWaveShared &S = MW[threadIdx.x >> 6];
     // list lengths first (one round trip), then every candidate slot of the query in one batch of loads (a second
     // round trip), then a ballot compaction of the positive scores into the LDS list
@@ -1255,14 +1257,15 @@ __global__ __launch_bounds__(THREADS) void srx_merge_kernel(const int32_t *__res
                                                             int64_t doc_base, int32_t *__restrict__ out_doc,
                                                             float *__restrict__ out_score,
                                                             int32_t *__restrict__ out_count, int64_t out_row_stride,
-                                                            int64_t out_cnt_stride, const int *__restrict__ gate, int q0) {
+                                                            int64_t out_cnt_stride, const int *__restrict__ gate, int q0, int skip_final) {
     __shared__ MergeShared M;
     const int tid = threadIdx.x;
     const int q = q0 + blockIdx.x / n_groups;
     const int g = blockIdx.x - (q - q0) * n_groups;
     if (q >= nq) return;
     if (gate != nullptr && *gate == 0) return;  // optional device-side switch (dense fallback pass)
-    if (!gathered && in_count[(int64_t)q * n_lists * cnt_stride] < 0) return;  // tier 1 already wrote this query's final row
+    // skip_final (plain layout only): a negative count in the query's first list marks a row its producer already wrote
+    if (skip_final && in_count[(int64_t)q * n_lists * cnt_stride] < 0) return;
     const int l0 = g * lists_per_group;
     const int l1 = min(l0 + lists_per_group, n_lists);
     if (tid == 0) {
@@ -1699,11 +1702,11 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
         if (k <= W_KMAX && (int64_t)p.lists_per_q * k <= MW_CAP && p.lists_per_q <= 256 && !(dbg & 256))
             hipLaunchKernelGGL(srx_merge_wave_kernel, dim3((unsigned)((nq_m + WAVES - 1) / WAVES)), dim3(THREADS), 0, stream, cand_doc,
                                cand_score, cand_count, nq, p.lists_per_q, k, 0, (int64_t)k, (int64_t)1, ix->d.doc_base, out_doc,
-                               out_score, out_count, ors, ocs, (const int *)nullptr, p.n_whole);
+                               out_score, out_count, ors, ocs, (const int *)nullptr, p.n_whole, 1);
         else
             hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)nq_m), dim3(THREADS), 0, stream, cand_doc, cand_score, cand_count, nq,
                                p.lists_per_q, k, p.lists_per_q, 1, 1, 0, (int64_t)k, (int64_t)1, ix->d.doc_base, out_doc, out_score,
-                               out_count, ors, ocs, (const int *)nullptr, p.n_whole);
+                               out_count, ors, ocs, (const int *)nullptr, p.n_whole, 1);
         HIP_TRY(hipGetLastError());
     }
     if (prof) {
@@ -1784,12 +1787,13 @@ SRX_API int64_t srx_merge_workspace_bytes(int32_t nq, int32_t n_lists, int32_t k
 int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count, int32_t nq,
                    int32_t n_lists, int32_t k, int lay, int64_t row_stride, int64_t cnt_stride, int32_t *out_doc,
                    float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, void *workspace, int64_t workspace_bytes,
-                   void *stream_v, const int *gate) {
+                   void *stream_v, const int *gate, int skip_marked) {
     if (nq < 0 || n_lists <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_merge_topk: bad argument%s");
     if (nq == 0) return SRX_OK;
     if (!in_doc || !in_score || !in_count || !out_doc || !out_score || !out_count)
         return fail(SRX_ERR_INVALID, "srx_merge_topk: null pointer%s");
     const int64_t need = srx_merge_workspace_bytes(nq, n_lists, k);
+    if (skip_marked && (lay != 0 || need > 0)) return fail(SRX_ERR_INVALID, "srx_merge_topk: marked rows need the plain layout and a single pass%s");
     if (need > 0 && (!workspace || workspace_bytes < need)) return fail(SRX_ERR_NOMEM, "srx_merge_topk: workspace too small%s");
     HIP_TRY(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_v;
@@ -1808,7 +1812,7 @@ int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score,
         int32_t *oc = (int32_t *)(os + (int64_t)nq * groups * k);
         hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)((int64_t)nq * groups)), dim3(THREADS), 0, stream, cur_doc,
                            cur_score, cur_count, nq, lists, k, fan, groups, 0, lay, row_stride, cnt_stride, (int64_t)0, od, os,
-                           oc, (int64_t)k, (int64_t)1, gate, 0);
+                           oc, (int64_t)k, (int64_t)1, gate, 0, 0);
         HIP_TRY(hipGetLastError());
         lay = 0;
         row_stride = k;
@@ -1822,10 +1826,10 @@ int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score,
     if (k <= W_KMAX && (int64_t)lists * k <= MW_CAP && lists <= 256)
         hipLaunchKernelGGL(srx_merge_wave_kernel, dim3((unsigned)((nq + WAVES - 1) / WAVES)), dim3(THREADS), 0, stream, cur_doc,
                            cur_score, cur_count, nq, lists, k, lay, row_stride, cnt_stride, (int64_t)0, out_doc, out_score,
-                           out_count, ors, ocs, gate, 0);
+                           out_count, ors, ocs, gate, 0, skip_marked);
     else
         hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)nq), dim3(THREADS), 0, stream, cur_doc, cur_score, cur_count, nq,
-                           lists, k, lists, 1, 1, lay, row_stride, cnt_stride, (int64_t)0, out_doc, out_score, out_count, ors, ocs, gate, 0);
+                           lists, k, lists, 1, 1, lay, row_stride, cnt_stride, (int64_t)0, out_doc, out_score, out_count, ors, ocs, gate, 0, skip_marked);
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }

@@ -791,8 +791,10 @@ struct srx_wave_launch {
 };
 // tier 1 (wave_kernel.hip): one wavefront per (query, split); `blocks` work items
 int srx_launch_wave_kernel(const srx_wave_launch &a, int val_type, int64_t blocks, hipStream_t stream);
-// exact merge of candidate lists (sparse_rx.hip), also used by the dense side
+// exact merge of candidate lists (sparse_rx.hip), also used by the dense side.  A negative count is an empty list.  skip_marked
+// (plain layout, n_lists * k <= 4096 only): a query whose FIRST list has a negative count is left alone instead -- its output
+// row was written by an earlier pass (the dense side's filtered pass and its fallback share one set of rows).
 int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count, int32_t nq,
                    int32_t n_lists, int32_t k, int lay, int64_t row_stride, int64_t cnt_stride, int32_t *out_doc,
                    float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, void *workspace, int64_t workspace_bytes,
-                   void *stream_v, const int *gate = nullptr);
+                   void *stream_v, const int *gate = nullptr, int skip_marked = 0);

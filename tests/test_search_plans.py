@@ -186,12 +186,22 @@ def test_plan_vs_oracle(env, case):
     label = _case_id(case)
     ix = env.index(name)
     ix.set_opts(target_blocks=target)
-    _pinned_plan(ix, name, nq, k, target, expect)
+    p = _pinned_plan(ix, name, nq, k, target, expect)
     q = env.queries(name, nq, qk, seed=1000 + nq + 7 * k + target)
     exp = env.oracle(name, q, k)
     rows, packed = _search_layouts(ix, q, k)
     _assert_exact(rows, exp, f"{label} search_device")
     _assert_exact(packed, exp, f"{label} search_packed_device")
+    if p["merge_kernel"] == "wave":
+        # the same batch with the block merge kernel in the wave kernel's place (debug bit 256): the block kernel on a split
+        # tail that starts at query n_whole, with the index's doc_base, which it otherwise only sees for k > 128
+        ix.set_opts(target_blocks=target, debug=256)
+        try:
+            rows, packed = _search_layouts(ix, q, k)
+        finally:
+            ix.set_opts(target_blocks=target, debug=0)
+        _assert_exact(rows, exp, f"{label} search_device, block merge kernel")
+        _assert_exact(packed, exp, f"{label} search_packed_device, block merge kernel")
 
 
 def test_search_after_pages_on_a_mixed_plan(env):
