@@ -15,7 +15,8 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
-SOURCES = ["wave_kernel.hip", "sparse_rx.hip", "dense.hip", "fuse.hip", "score_docs.hip"]   # one translation unit each, compiled in parallel
+SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
+           "score_docs.hip"]                                    # one translation unit each, compiled in parallel
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
@@ -92,11 +93,12 @@ _lib: Optional[ctypes.CDLL] = None
 
 
 def kernel_sources_sha256() -> str:
-    """sha256 over the sparse path's kernel sources (wave_kernel.hip, sparse_rx.hip, srx_common.h): identifies the build a
-    profile was taken from."""
+    """sha256 over the sources of the kernels a sparse search launches (wave_kernel.hip, tier2_kernel.hip, merge.hip and
+    srx_common.h): identifies the build a profile was taken from.  The driver (sparse_rx.hip) and the index build
+    (build.hip) are not part of it: an edit there does not change what a search runs on the GPU."""
     import hashlib
     h = hashlib.sha256()
-    for f in ["wave_kernel.hip", "sparse_rx.hip", "srx_common.h"]:
+    for f in ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "srx_common.h"]:
         with open(os.path.join(CSRC_DIR, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()

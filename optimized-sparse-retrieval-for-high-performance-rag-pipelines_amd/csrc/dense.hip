@@ -1,6 +1,6 @@
 // dense.hip -- the dense side of the same service: INT8 MFMA GEMM + fused top-k filter, and the f32
 // streaming matvec of search_by_vector.  Shares the block top-k machinery and the merge kernels (srx_common.h,
-// sparse_rx.hip).
+// merge.hip).
 
 #include "srx_common.h"
 

@@ -1,7 +1,8 @@
 // srx_common.h -- shared device primitives of libsparse_rx.so (gfx950): constants, the index view, wave / block
 // reductions, the exact radix selections and the running top-k lists used by the scoring, merge and dense kernels.
-// Everything here has internal linkage (anonymous namespace): each translation unit (sparse_rx.hip, wave_kernel.hip,
-// dense.hip, fuse.hip) compiles its own copy; only the few host functions declared at the end cross units.
+// Everything here has internal linkage (anonymous namespace): each translation unit (wave_kernel.hip, tier2_kernel.hip,
+// merge.hip, build.hip, sparse_rx.hip, dense.hip, fuse.hip, score_docs.hip) compiles its own copy; only the few host
+// functions declared at the end cross units.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off  (no fused multiply-add: the reference's arithmetic is
 // separate fp32 multiply / add / IEEE divide).
@@ -481,7 +482,7 @@ __device__ __forceinline__ void load_block(const int32_t *blk, __half, int (&d)[
 }
 
 // The one rule both tiers apply: tier 1 (wave_kernel.hip) serves a query of nt > 0 terms iff this is false; tier 2
-// (sparse_rx.hip) then takes the whole query instead of the flagged units only.
+// (tier2_kernel.hip) then takes the whole query instead of the flagged units only.
 __device__ __forceinline__ bool tier1_cannot_serve(const IndexView &ix, int nt, int k, int tpu, int dbg) {
     return nt > W_MAXT || k > W1_KMAX || (tpu << ix.tile_log2) > W_UNIT_MAX_DOCS || ix.post16 == nullptr || (dbg & 8) != 0 ||
            ix.vocab * (int64_t)(ix.n_tiles + 1) >= (1ll << 30);  // tier 1 addresses the skip table with 32-bit byte offsets
@@ -791,7 +792,35 @@ struct srx_wave_launch {
 };
 // tier 1 (wave_kernel.hip): one wavefront per (query, split); `blocks` work items
 int srx_launch_wave_kernel(const srx_wave_launch &a, int val_type, int64_t blocks, hipStream_t stream);
-// exact merge of candidate lists (sparse_rx.hip), also used by the dense side.  A negative count is an empty list.  skip_marked
+// tier 2 (tier2_kernel.hip): the parameters of srx_score_kernel; `grid` persistent workgroups drain the worklist `work`
+struct srx_score_launch {
+    IndexView ix;
+    const int32_t *q_ptr, *q_term;
+    const float *q_weight;
+    int nq, k, n_splits, n_whole, tpu, n_super, dbg;
+    const unsigned *ovf;
+    int ovf_words, lists_per_q;
+    const int *work;
+    int32_t *cand_doc;
+    float *cand_score;
+    int32_t *cand_count;
+    const int32_t *after_doc;  // srx_search_after's bounds (both null: a plain search)
+    const float *after_score;
+    int64_t doc_base;
+    int32_t *out_doc;    // final rows of the queries that are one work item
+    float *out_score;
+    int32_t *out_count;
+    int64_t out_row_stride, out_cnt_stride;
+    int *hint;           // device address of the pinned word that receives the worklist length (may be null)
+};
+int srx_launch_score_kernel(const srx_score_launch &a, int val_type, unsigned grid, hipStream_t stream);
+// the last merge level (merge.hip): the `lists` lists of every query in [q0, nq) -> its ranked final row; skip_final leaves
+// a query alone whose first list has a negative count; force_block takes the workgroup kernel where one wavefront would do
+int srx_launch_final_merge(const int32_t *in_doc, const float *in_score, const int32_t *in_count, int nq, int lists, int k,
+                           int lay, int64_t row_stride, int64_t cnt_stride, int64_t doc_base, int32_t *out_doc,
+                           float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, const int *gate, int q0,
+                           int skip_final, bool force_block, hipStream_t stream);
+// exact merge of candidate lists (merge.hip), also used by the dense side.  A negative count is an empty list.  skip_marked
 // (plain layout, n_lists * k <= 4096 only): a query whose FIRST list has a negative count is left alone instead -- its output
 // row was written by an earlier pass (the dense side's filtered pass and its fallback share one set of rows).
 int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count, int32_t nq,

@@ -26,7 +26,7 @@
 //     conservative per-lane threshold screens them; survivors get the exact fp32 test and go to a lazy LDS list that an
 //     exact wave-level radix select shrinks when it fills (srx_common.h).
 // Units that do not fit (a run longer than W_R / 4 blocks per lane, more than W_DUPCAP multi-term docs) are flagged
-// for tier 2, as are queries with > 64 terms and k > W1_KMAX.
+// for tier 2 (tier2_kernel.hip), as are queries with > 64 terms and k > W1_KMAX.
 
 #include "srx_common.h"
 

@@ -113,7 +113,7 @@ def np_compact_blocks(post, unit_docs, val_dtype=np.float32):
 
 
 # ---- the search planner, restated (csrc/sparse_rx.hip: make_plan, srx_search_workspace_bytes, search_impl) -----------------
-# Constants of csrc/srx_common.h / sparse_rx.hip.  The GPU tests pin this restatement to the library through
+# Constants of csrc/srx_common.h / sparse_rx.hip / merge.hip (srx_launch_final_merge).  The GPU tests pin this restatement to the library through
 # DeviceIndex.workspace_bytes, which is a function of the plan: a planner change that moves a case to another bucket fails
 # the case instead of letting it test something else silently.
 PLAN_DEFAULT_TARGET = 3072  # make_plan: wave-sized work items per batch when target_blocks is 0
