@@ -24,6 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-f
 
 SRX_VAL_F32, SRX_VAL_F16 = 0, 1
 SRX_FUSE_WEIGHTED, SRX_FUSE_RRF = 0, 1
+SRX_MAX_K = 1024  # rows per query list inside the engine (limits()["max_k"]; pinned to the library by tests/test_capi_cpu.py)
 
 
 class SparseRxUnavailable(RuntimeError):

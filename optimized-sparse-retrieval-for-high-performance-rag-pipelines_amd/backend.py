@@ -15,12 +15,11 @@ corpus / query dicts (SPMD) and
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import _capi
-from .index import DeviceIndex, HostIndex, build_host_index, deep_search, validate_candidates, validate_query_batch
+from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, score_host_batch, search_host_batch
 
 
 class SparseBackend:
@@ -104,25 +103,17 @@ class SparseBackend:
             self.searcher.force_exchange = self._force_sharded
 
     # -- search -----------------------------------------------------------------------------------------
+    def _batch_device(self):
+        """The device the batches go to: the index's, or the CPU for a test searcher (CPU tensors, no synchronisation)."""
+        import torch
+        return self.dev.device if self.dev is not None else torch.device("cpu")
+
     def search_arrays(self, q_ptr, q_term, q_weight, k: int):
         """Host CSR batch -> host rows (doc i32[nq, k] GLOBAL row ids, score f32[nq, k], count i32[nq]); any k >= 1."""
         if self.searcher is None:
             return self.dev.search(q_ptr, q_term, q_weight, k)
-        import torch
-        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
-        nq = len(q_ptr) - 1
-        if nq == 0:
-            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
-        dev = self.dev.device if self.dev is not None else torch.device("cpu")
-        qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
-        qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
-        qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
-        page = _capi.limits()["max_k"] if self.dev is not None else 1024
-        d, s, c = deep_search(self.searcher.search, qp, qt, qw, k, page)
-        if dev.type == "cuda":
-            self.searcher.wait()
-            torch.cuda.synchronize(dev)
-        return d.cpu().numpy(), s.cpu().numpy(), c.cpu().numpy()
+        return search_host_batch(self.searcher.search, q_ptr, q_term, q_weight, k, self.host.vocab_size, self._batch_device(),
+                                 wait=self.searcher.wait)
 
     def score_arrays(self, q_ptr, q_term, q_weight, cand_doc, cand_count=None) -> np.ndarray:
         """Host CSR batch + host candidate block (cand_doc int[nq, m] GLOBAL row ids, cand_count int[nq] or None) -> the exact
@@ -130,29 +121,77 @@ class SparseBackend:
         (distributed.ShardedSearcher.score_docs)."""
         if self.searcher is None:
             return self.dev.score_docs(q_ptr, q_term, q_weight, cand_doc, cand_count)
-        import torch
-        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
-        nq = len(q_ptr) - 1
-        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
-        if nq == 0:
-            return np.zeros((0, cand_doc.shape[1]), np.float32)
-        dev = self.dev.device if self.dev is not None else torch.device("cpu")
-        qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
-        qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
-        qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
-        cd = torch.as_tensor(cand_doc, device=dev)
-        cc = None if cand_count is None else torch.as_tensor(cand_count, device=dev)
-        out = self.searcher.score_docs(qp, qt, qw, cd, cc)
-        if dev.type == "cuda":
-            torch.cuda.synchronize(dev)
-        return out.cpu().numpy()
+        return score_host_batch(self.searcher.score_docs, q_ptr, q_term, q_weight, cand_doc, cand_count, self.host.vocab_size,
+                                self._batch_device())
+
+    def to_dict(self, idx: np.ndarray, sc: np.ndarray) -> Dict[str, float]:
+        """Ranked rows -> {doc_id: score}, ``score > 0`` only (retrieval.py:292-296)."""
+        ids = self.host.doc_ids
+        return {ids[int(i)]: float(s) for i, s in zip(idx, sc) if s > 0}
+
+    def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
+                     blank: str = "empty"):
+        """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
+        in the caller's order, one batched search for all texts the cache does not hold (equal texts share one row).  What
+        the call sites of the reference do differently is named here:
+
+          * ``blank``      "empty": only a false text (``""``, ``None``) is answered ``{}`` unsearched
+                           (retriever_registry.py:237-239); "whitespace": so is a text of white space only (retrieval.py:211-213)
+                           -- which "empty" searches as an empty row;
+          * ``strip_key``  the cache key is ``f"{text.strip()}:{top_k}"`` (retrieval.py:216) or the text as it is
+                           (evaluate_rag_pipeline.py:340);
+          * ``cache``      the caller's dict (entries: (rows i64, scores f32), read and written under ``lock``), at most
+                           1 000 entries (retrieval.py:288); ``None`` = every call searches;
+          * ``order``      the accumulation order of :func:`index.encode_queries`.
+
+        A row without in-vocabulary terms gives ``{}`` and is not cached (retrieval.py:237-238, :251-252).  ``top_k`` beyond
+        the corpus asks for ``n_docs`` rows; ``top_k <= 0`` keeps nothing (the reference's ``argpartition(...)[:0]``), cache
+        hits aside."""
+        k_eff = min(int(top_k), self.n_docs_total)  # any depth: search_arrays pages past the engine's 1024-row lists
+        results: Dict[str, Dict[str, float]] = {}
+        pending: Dict[str, List[str]] = {}  # cache key -> the qids waiting for it
+        texts: List[str] = []
+        keys: List[str] = []
+        for qid, text in queries.items():
+            if not text or (blank == "whitespace" and not text.strip()):
+                results[qid] = {}
+                continue
+            key = f"{text.strip() if strip_key else text}:{top_k}"
+            hit = None
+            if cache is not None:
+                with lock:
+                    hit = cache.get(key)
+            if hit is not None:
+                results[qid] = self.to_dict(*hit)
+                continue
+            results[qid] = {}  # keeps the caller's qid order; filled below
+            if key not in pending:
+                pending[key] = []
+                texts.append(text)
+                keys.append(key)
+            pending[key].append(qid)
+        if texts and k_eff > 0:
+            q_ptr, q_term, q_weight = encode_queries(texts, self.host.vocabulary, order=order)
+            docs, scores, counts = self.search_arrays(q_ptr, q_term, q_weight, k_eff)
+            for i, key in enumerate(keys):
+                if q_ptr[i + 1] == q_ptr[i]:
+                    continue
+                c = int(counts[i])
+                entry = (docs[i, :c].astype(np.int64), scores[i, :c].copy())
+                if cache is not None:
+                    with lock:
+                        if len(cache) < 1000:
+                            cache[key] = entry
+                d = self.to_dict(*entry)
+                for qid in pending[key]:
+                    results[qid] = dict(d)
+        return results
 
     def score_dicts(self, queries, candidates, order: str = "term"):
         """The dict form the API mirrors share: ``queries`` {qid: text}, ``candidates`` {qid: sequence of doc ids} ->
         {qid: {doc_id: exact score}} with every listed candidate in the caller's order (0.0 where no query term matches,
         and for a blank or all-OOV query); a qid without candidates gives {}; an unknown doc id raises ValueError.  One
         batch: ragged lists are padded with -1 and passed with their lengths (``cand_count``)."""
-        from .index import encode_queries
         ids = self.host.doc_ids
         if getattr(self, "_row_of_ids", None) is not ids:
             self._row_of, self._row_of_ids = {d: i for i, d in enumerate(ids)}, ids
@@ -186,3 +225,35 @@ class SparseBackend:
             self.dev.close()
             self.dev = None
         self.searcher = None
+
+
+class SparseIndexViews:
+    """The reference's attribute names as read-only views of ``self._be`` (a :class:`SparseBackend`): shared by
+    ``RetrievalService`` and the registry mirrors."""
+
+    @property
+    def host(self) -> Optional[HostIndex]:
+        return self._be.host  # sharded: this rank's rows, corpus-wide vocabulary / idf / avgdl / doc ids
+
+    @property
+    def dev(self) -> Optional[DeviceIndex]:
+        return self._be.dev
+
+    @property
+    def vocabulary(self) -> Dict[str, int]:
+        return self.host.vocabulary if self.host else {}
+
+    @property
+    def doc_ids(self) -> List[str]:
+        return self.host.doc_ids if self.host else []
+
+    @property
+    def corpus_tf(self):
+        if self.host is None:
+            return None
+        from scipy.sparse import csr_matrix
+        h = self.host
+        return csr_matrix((h.data, h.indices, h.indptr), shape=(h.n_docs, h.vocab_size))
+
+    def _to_dict(self, idx, sc) -> Dict[str, float]:
+        return self._be.to_dict(idx, sc)

@@ -10,7 +10,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from .index import _ptr, _stream_ptr, _torch
+from .index import _check_k, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, rows_to_dict
 
 DIMS = (32, 64, 96, 128, 192, 256, 384, 512, 768, 1024)  # row lengths the kernel is instantiated for
 
@@ -62,18 +62,60 @@ def _pad_dim(dim: int) -> int:
     raise ValueError(f"embedding dim {dim} > {DIMS[-1]} is not supported by the INT8 engine")
 
 
-class DenseInt8Index:
+class _DenseIndex:
+    """What the three dense indexes share; each keeps how its corpus is stored and which entry point it calls."""
+
+    _workspace_fn = "srx_dense_f32_workspace_bytes"
+    _entry = None  # the search entry point ``_launch`` calls, as ``_capi.check`` names it
+
+    def _open(self, device):
+        """The no-GPU refusal, the library and the device: first step of every constructor."""
+        torch = _torch()
+        if not torch.cuda.is_available():
+            raise _capi.SparseRxUnavailable(f"no HIP device visible: {type(self).__name__} needs a GPU (there is no CPU fallback)")
+        _capi.lib()
+        self.device = torch.device(device)
+        self._ws = None
+        return torch
+
+    def _pad64(self, engine: str) -> int:
+        """Row length rounded up to the 64 columns the f32 / uint8 kernels step by."""
+        dim_pad = (self.dim + 63) // 64 * 64
+        if dim_pad > 1024:
+            raise ValueError(f"embedding dim {self.dim} > 1024 is not supported by the {engine} engine")
+        return dim_pad
+
+    def _search_device(self, queries, dtype, k: int, *extra):
+        """k check, the query block zero-padded to ``dim_pad``, the output triple and the workspace, then the class's
+        ``_launch(L, q, nq, k, out, ws, stream, *extra)`` -> the entry point's return code.  An empty batch launches nothing."""
+        torch = _torch()
+        _check_k(k)
+        nq = int(queries.shape[0])
+        L = _capi.lib()
+        with torch.cuda.device(self.device):
+            q = torch.zeros((nq, self.dim_pad), dtype=dtype, device=self.device)
+            q[:, : self.dim] = queries
+            out = _empty_topk(torch, nq, k, self.device)
+            if nq == 0:
+                return out
+            ws = _grow_ws(torch, self, _capi.check(getattr(L, self._workspace_fn)(nq, self.n_docs, k), self._workspace_fn))
+            _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), self._entry)
+        return out
+
+    def _host(self, out):
+        return _to_host(_torch(), self.device, out)
+
+
+class DenseInt8Index(_DenseIndex):
     """INT8 corpus resident in HBM: ``corpus_int8`` i8[n_docs, dim] (rows zero-padded to a supported length) and
     ``corpus_scales`` f32[n_docs] -- the state ``QuantizedEmbeddingRetriever.build_index_from_corpus`` keeps
     (retriever_registry.py:389-392).  By default the matrix is kept in MFMA-fragment order only (``srx_dense_pack_i8``:
     same bytes; a wave's B-fragment loads are contiguous); ``packed=False`` keeps the row-major matrix and searches that."""
 
+    _workspace_fn, _entry = "srx_dense_workspace_bytes", "srx_dense_search_i8"
+
     def __init__(self, corpus_int8, corpus_scales, device="cuda:0", doc_base: int = 0, packed: bool = True):
-        torch = _torch()
-        if not torch.cuda.is_available():
-            raise _capi.SparseRxUnavailable("no HIP device visible: DenseInt8Index needs a GPU (there is no CPU fallback)")
-        _capi.lib()
-        self.device = torch.device(device)
+        torch = self._open(device)
         c = corpus_int8 if isinstance(corpus_int8, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(corpus_int8, dtype=np.int8))
         assert c.dtype == torch.int8 and c.dim() == 2
         self.n_docs, self.dim = int(c.shape[0]), int(c.shape[1])
@@ -96,60 +138,38 @@ class DenseInt8Index:
             self.scales = s.to(device=self.device, dtype=torch.float32).contiguous()
         assert self.scales.numel() == self.n_docs
         self.doc_base = int(doc_base)
-        self._ws = None
 
     def search_device(self, queries_int8, query_scales, k: int):
         """queries i8[nq, dim] + f32[nq] on the device -> (doc i32[nq,k], score f32[nq,k], count i32[nq]); asynchronous."""
-        torch = _torch()
-        if not (1 <= k <= _capi.limits()["max_k"]):
-            raise ValueError(f"top_k must be in [1, {_capi.limits()['max_k']}] for the HIP engine, got {k}")
-        nq = int(queries_int8.shape[0])
-        L = _capi.lib()
-        with torch.cuda.device(self.device):
-            q = torch.zeros((nq, self.dim_pad), dtype=torch.int8, device=self.device)
-            q[:, : self.dim] = queries_int8
-            qs = query_scales.to(device=self.device, dtype=torch.float32).contiguous()
-            out = (torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
-                   torch.empty((nq,), dtype=torch.int32, device=self.device))
-            if nq == 0:
-                return out
-            need = _capi.check(L.srx_dense_workspace_bytes(nq, self.n_docs, k), "srx_dense_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            fn = L.srx_dense_search_i8_packed if self.packed else L.srx_dense_search_i8
-            rc = fn(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad,
-                    _ptr(q), _ptr(qs), nq, k, self.doc_base, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                    _ptr(self._ws), self._ws.numel(), _stream_ptr(torch, self.device))
-            _capi.check(rc, "srx_dense_search_i8")
-        return out
+        return self._search_device(queries_int8, _torch().int8, k, query_scales)
+
+    def _launch(self, L, q, nq, k, out, ws, stream, query_scales):
+        qs = query_scales.to(device=self.device, dtype=_torch().float32).contiguous()
+        fn = L.srx_dense_search_i8_packed if self.packed else L.srx_dense_search_i8
+        return fn(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad, _ptr(q), _ptr(qs), nq, k,
+                  self.doc_base, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream)
 
     def search(self, queries_int8: np.ndarray, query_scales: np.ndarray, k: int):
         """Host arrays in, host arrays out."""
         torch = _torch()
-        d, s, n = self.search_device(torch.as_tensor(np.ascontiguousarray(queries_int8, dtype=np.int8), device=self.device),
-                                     torch.as_tensor(np.ascontiguousarray(query_scales, dtype=np.float32), device=self.device), k)
-        torch.cuda.synchronize(self.device)
-        return d.cpu().numpy(), s.cpu().numpy(), n.cpu().numpy()
+        return self._host(self.search_device(torch.as_tensor(np.ascontiguousarray(queries_int8, dtype=np.int8), device=self.device),
+                                             torch.as_tensor(np.ascontiguousarray(query_scales, dtype=np.float32), device=self.device), k))
 
 
-class DenseUint8Index:
+class DenseUint8Index(_DenseIndex):
     """Asymmetric-scheme corpus resident in HBM: ``corpus_uint8`` u8[n_docs, dim] and the reference's ``corpus_scales``
     table f32[2 n_docs] unchanged (retriever_registry.py:449-462); ``search`` replaces the de-quantize + ``np.dot`` loop of
     ``_numpy_quantized_similarity`` (:550-559) + the top-k for a batch of de-quantized query vectors
     (``srx_dense_search_u8``, which indexes the table the way the reference's reader does)."""
 
+    _entry = "srx_dense_search_u8"
+
     def __init__(self, corpus_uint8, corpus_scales, device="cuda:0", doc_base: int = 0):
-        torch = _torch()
-        if not torch.cuda.is_available():
-            raise _capi.SparseRxUnavailable("no HIP device visible: DenseUint8Index needs a GPU (there is no CPU fallback)")
-        _capi.lib()
-        self.device = torch.device(device)
+        torch = self._open(device)
         c = torch.as_tensor(np.ascontiguousarray(corpus_uint8, dtype=np.uint8))
         assert c.dim() == 2
         self.n_docs, self.dim = int(c.shape[0]), int(c.shape[1])
-        self.dim_pad = (self.dim + 63) // 64 * 64
-        if self.dim_pad > 1024:
-            raise ValueError(f"embedding dim {self.dim} > 1024 is not supported by the uint8 engine")
+        self.dim_pad = self._pad64("uint8")
         s = np.ascontiguousarray(corpus_scales, dtype=np.float32).reshape(-1)
         if s.size != 2 * self.n_docs:
             raise ValueError("corpus_scales must hold 2 * n_docs floats (retriever_registry.py:459)")
@@ -158,37 +178,19 @@ class DenseUint8Index:
             self.corpus[:, : self.dim] = c.to(self.device)
             self.scales = torch.as_tensor(s).to(self.device)
         self.doc_base = int(doc_base)
-        self._ws = None
 
     def search_device(self, queries_f32, k: int):
-        torch = _torch()
-        if not (1 <= k <= _capi.limits()["max_k"]):
-            raise ValueError(f"top_k must be in [1, {_capi.limits()['max_k']}] for the HIP engine, got {k}")
-        nq = int(queries_f32.shape[0])
-        L = _capi.lib()
-        with torch.cuda.device(self.device):
-            q = torch.zeros((nq, self.dim_pad), dtype=torch.float32, device=self.device)
-            q[:, : self.dim] = queries_f32
-            out = (torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
-                   torch.empty((nq,), dtype=torch.int32, device=self.device))
-            if nq == 0:
-                return out
-            need = _capi.check(L.srx_dense_f32_workspace_bytes(nq, self.n_docs, k), "srx_dense_f32_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            rc = L.srx_dense_search_u8(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad, _ptr(q),
-                                       nq, k, self.doc_base, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(self._ws),
-                                       self._ws.numel(), _stream_ptr(torch, self.device))
-            _capi.check(rc, "srx_dense_search_u8")
-        return out
+        return self._search_device(queries_f32, _torch().float32, k)
+
+    def _launch(self, L, q, nq, k, out, ws, stream):
+        return L.srx_dense_search_u8(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad, _ptr(q),
+                                     nq, k, self.doc_base, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream)
 
     def search(self, queries_uint8: np.ndarray, query_scales: np.ndarray, k: int):
         """queries u8[nq, dim] + f32[nq, 2] (scale, min) as the reference's search builds them (:486-491); host arrays out."""
         torch = _torch()
         qf = np.stack([dequantize_query_asymmetric(q, s) for q, s in zip(np.asarray(queries_uint8), np.asarray(query_scales))])
-        d, s, n = self.search_device(torch.as_tensor(np.ascontiguousarray(qf, dtype=np.float32), device=self.device), k)
-        torch.cuda.synchronize(self.device)
-        return d.cpu().numpy(), s.cpu().numpy(), n.cpu().numpy()
+        return self._host(self.search_device(torch.as_tensor(np.ascontiguousarray(qf, dtype=np.float32), device=self.device), k))
 
 
 class QuantizedEmbeddingIndex:
@@ -217,26 +219,22 @@ class QuantizedEmbeddingIndex:
         qq = [quantize_query_symmetric(query_embeddings[q]) for q in qids]
         k = min(top_k, len(self.doc_ids))
         d, s, n = self.index.search(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), k)
-        return {qid: {self.doc_ids[int(d[i, j])]: float(s[i, j]) for j in range(int(n[i]))} for i, qid in enumerate(qids)}
+        return {qid: rows_to_dict(self.doc_ids, d, s, n, i) for i, qid in enumerate(qids)}
 
 
-class DenseF32Index:
+class DenseF32Index(_DenseIndex):
     """f32 embedding matrix resident in HBM: the ``embedding_index`` of ``RetrievalService`` (retrieval.py:329-335);
     ``search`` replaces ``np.dot(self.embedding_index, query_vector)`` + top-k of ``search_by_vector`` (:411-423) for a
     batch of query vectors (``srx_dense_search_f32``)."""
 
+    _entry = "srx_dense_search_f32"
+
     def __init__(self, embeddings, device="cuda:0", doc_base: int = 0):
-        torch = _torch()
-        if not torch.cuda.is_available():
-            raise _capi.SparseRxUnavailable("no HIP device visible: DenseF32Index needs a GPU (there is no CPU fallback)")
-        _capi.lib()
-        self.device = torch.device(device)
+        torch = self._open(device)
         e = embeddings
         assert len(e.shape) == 2 and (not isinstance(e, torch.Tensor) or e.dtype == torch.float32)
         self.n_docs, self.dim = int(e.shape[0]), int(e.shape[1])
-        self.dim_pad = (self.dim + 63) // 64 * 64
-        if self.dim_pad > 1024:
-            raise ValueError(f"embedding dim {self.dim} > 1024 is not supported by the f32 engine")
+        self.dim_pad = self._pad64("f32")
         with torch.cuda.device(self.device):
             self.emb = torch.zeros((self.n_docs, self.dim_pad), dtype=torch.float32, device=self.device)
             if isinstance(e, torch.Tensor):
@@ -250,7 +248,6 @@ class DenseF32Index:
                     chunk = np.array(e[lo: lo + rows], dtype=np.float32)
                     self.emb[lo: lo + chunk.shape[0], : self.dim] = torch.from_numpy(chunk).to(self.device)
         self.doc_base = int(doc_base)
-        self._ws = None
         self._max_norm = None
 
     def max_row_norm(self) -> float:
@@ -269,32 +266,15 @@ class DenseF32Index:
 
     def search_device(self, queries, k: int, score_offset: float = 0.0):
         """Top-k of (score + score_offset) > 0 per query (include/sparse_rx.h); the returned scores carry the offset."""
-        torch = _torch()
-        if not (1 <= k <= _capi.limits()["max_k"]):
-            raise ValueError(f"top_k must be in [1, {_capi.limits()['max_k']}] for the HIP engine, got {k}")
-        nq = int(queries.shape[0])
-        L = _capi.lib()
-        with torch.cuda.device(self.device):
-            q = torch.zeros((nq, self.dim_pad), dtype=torch.float32, device=self.device)
-            q[:, : self.dim] = queries
-            out = (torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
-                   torch.empty((nq,), dtype=torch.int32, device=self.device))
-            if nq == 0:
-                return out
-            need = _capi.check(L.srx_dense_f32_workspace_bytes(nq, self.n_docs, k), "srx_dense_f32_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            rc = L.srx_dense_search_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k, self.doc_base,
-                                        _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(self._ws), self._ws.numel(),
-                                        _stream_ptr(torch, self.device), float(score_offset))
-            _capi.check(rc, "srx_dense_search_f32")
-        return out
+        return self._search_device(queries, _torch().float32, k, score_offset)
+
+    def _launch(self, L, q, nq, k, out, ws, stream, score_offset):
+        return L.srx_dense_search_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k, self.doc_base,
+                                      _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream, float(score_offset))
 
     def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0):
         torch = _torch()
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
-        d, s, n = self.search_device(torch.as_tensor(q, device=self.device), k, score_offset)
-        torch.cuda.synchronize(self.device)
-        return d.cpu().numpy(), s.cpu().numpy(), n.cpu().numpy()
+        return self._host(self.search_device(torch.as_tensor(q, device=self.device), k, score_offset))

@@ -172,8 +172,19 @@ class ShardedSearcher:
         self.pack = pack
         self.merge = merge
         self.group = group
-        self._buf = None
-        self.mode = "a2a"
+        # the switches, set by plain assignment from outside (backend.SparseBackend, bench.py, the tests)
+        self.mode = "a2a"             # the exchange: "a2a" or "allgather" (:meth:`_exchange`)
+        self.graph = False            # replay the step from captured HIP graphs (:meth:`_search_graph`; needs workspace_bytes)
+        self.overlap = False          # exchange + merge on a second stream (:meth:`_search_packed`)
+        self.force_exchange = False   # run the exchange even in a group of one rank
+        self.workspace_bytes = None   # (nq, k) -> bytes of one search: lets every graph lane own a workspace
+        # state the methods create on first use
+        self._buf = {}                # exchange buffers by (kind, world, nq, k, device, slot)
+        self._side = self._score = None  # the overlap streams, and the events that guard their double-buffered slots
+        self._slot_ev = {}
+        self._step = 0
+        self._lanes, self._lane_step = {}, 0  # graph lanes by tensor set
+        self._lane_streams = self._lane_groups = None
         # Optional in-place variants (no packing / unpacking kernels around the exchange):
         # local_search_packed(q_ptr, q_term, q_weight, k, out i32[nq, 2k+1]) and
         # merge_packed_out(packed i32[W, nq, 2k+1], k, out i32[nq, 2k+1]) fill `out` rows [k docs][k score bits][count].
@@ -195,9 +206,8 @@ class ShardedSearcher:
         same q_ptr on the host (NumPy / CPU tensor), to cut sub-batches without a device-to-host sync."""
         import torch
         import torch.distributed as dist
-        exchange = (dist.is_initialized() and dist.get_world_size(self.group) > 1) or getattr(self, "force_exchange", False)
         kw = {} if after is None else {"after": after}  # srx_search_after: the bound is a GLOBAL (doc, score) row, the same on every shard
-        if not exchange:
+        if not self._exchanging():
             return self.local_search(q_ptr, q_term, q_weight, k, **kw)
         if after is not None:
             chunks = 1  # deep pages: plain path
@@ -206,8 +216,8 @@ class ShardedSearcher:
         on_gpu = q_ptr.is_cuda
         if chunks <= 0:
             chunks = 1  # measured on one GPU: cutting the batch costs more (under-filled launches) than it can hide
-        if (on_gpu and after is None and getattr(self, "graph", False) and self.local_search_packed is not None
-                and self.merge_packed_out is not None and getattr(self, "workspace_bytes", None) is not None):
+        if (on_gpu and after is None and self.graph and self.local_search_packed is not None
+                and self.merge_packed_out is not None and self.workspace_bytes is not None):
             out = self._search_graph(q_ptr, q_term, q_weight, k, world)
             if out is not None:
                 return out
@@ -221,7 +231,7 @@ class ShardedSearcher:
         bounds = [(nq * i) // chunks for i in range(chunks + 1)]
         qp_host = q_ptr_host if q_ptr_host is not None else q_ptr.cpu()  # the term offsets of the cut points
         main = torch.cuda.current_stream(dev)
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         side = self._side
         side.wait_stream(main)
@@ -256,10 +266,21 @@ class ShardedSearcher:
         if self.local_score is None:
             raise ValueError("this ShardedSearcher was built without local_score: it cannot score given docs")
         out = self.local_score(q_ptr, q_term, q_weight, cand_doc, cand_count)
-        exchange = (dist.is_initialized() and dist.get_world_size(self.group) > 1) or getattr(self, "force_exchange", False)
-        if exchange:
+        if self._exchanging():
             dist.all_reduce(out, op=dist.ReduceOp.SUM, group=self.group)
         return out
+
+    def _exchanging(self) -> bool:
+        """More than one rank, or ``force_exchange``: the per-shard results go through the collectives."""
+        import torch.distributed as dist
+        return (dist.is_initialized() and dist.get_world_size(self.group) > 1) or self.force_exchange
+
+    def _get_buf(self, key, make):
+        """The exchange buffers kept under ``key``, made by ``make()`` on first use."""
+        bufs = self._buf.get(key)
+        if bufs is None:
+            bufs = self._buf[key] = make()
+        return bufs
 
     def _search_graph(self, q_ptr, q_term, q_weight, k: int, world: int):
         """Steady-state submission for a caller that searches the SAME device tensors batch after batch (a serving loop with
@@ -275,12 +296,10 @@ class ShardedSearcher:
         import torch
         dev = q_ptr.device
         key = (q_ptr.data_ptr(), q_term.data_ptr(), q_weight.data_ptr(), int(q_ptr.shape[0]), int(q_term.shape[0]), k, self.mode, world)
-        if getattr(self, "_lanes", None) is None:
-            self._lanes, self._lane_step = {}, 0
         cur = torch.cuda.current_stream(dev)
         lanes = self._lanes.get(key)
         if lanes is None:
-            if getattr(self, "_lane_streams", None) is None:
+            if self._lane_streams is None:
                 # Two streams for every tensor set: lane i of every set shares its send / receive buffers (self._buf is
                 # keyed by shape), so all of them must run on one stream.
                 self._lane_streams = [torch.cuda.Stream(device=dev) for _ in range(2)]
@@ -294,7 +313,7 @@ class ShardedSearcher:
             lanes = []
             try:
                 import torch.distributed as dist
-                if getattr(self, "_lane_groups", None) is None:
+                if self._lane_groups is None:
                     # A communicator of its own per lane: the two lanes' collectives run on different streams with nothing
                     # ordering them against each other, which one RCCL communicator does not allow.  (Collective call: every
                     # rank builds its lanes at the same point of the same first search.)
@@ -339,18 +358,16 @@ class ShardedSearcher:
         nq = q_ptr.shape[0] - 1
         row = 2 * k + 1
         dev = q_ptr.device
-        if self._buf is None:
-            self._buf = {}
-        overlap = bool(getattr(self, "overlap", False)) and q_ptr.is_cuda and _lane is None
+        overlap = bool(self.overlap) and q_ptr.is_cuda and _lane is None
         slot = 0 if _lane is None else _lane
         lkw = {} if after is None else {"after": after}
         if _workspace is not None:
             lkw["workspace"] = _workspace
         if overlap:
-            self._step = getattr(self, "_step", 0) + 1
+            self._step += 1
             slot = self._step & 1
             cur = torch.cuda.current_stream(dev)
-            if getattr(self, "_side", None) is None:
+            if self._side is None:
                 # Two streams of the searcher's own: the scoring of batch i + 1 and the exchange of batch i only run side by
                 # side when NEITHER is the legacy default stream (measured, profiles/r03_exchange_timeline_*: with the search
                 # on the default stream every kernel of both streams ran back to back, the "overlap" only added event waits)
@@ -380,23 +397,17 @@ class ShardedSearcher:
             return allrows[:nq]
 
         if self.mode == "allgather":
-            key = ("pag", world, nq, k, dev, slot)
-            bufs = self._buf.get(key)
-            if bufs is None:
-                bufs = self._buf[key] = (torch.empty((nq, row), dtype=torch.int32, device=dev),
-                                         torch.empty((world, nq, row), dtype=torch.int32, device=dev))
-            mine, recv = bufs
+            mine, recv = self._get_buf(("pag", world, nq, k, dev, slot),
+                                       lambda: (torch.empty((nq, row), dtype=torch.int32, device=dev),
+                                                torch.empty((world, nq, row), dtype=torch.int32, device=dev)))
             send = mine
             with (torch.cuda.stream(main) if overlap else contextlib.nullcontext()):
                 self.local_search_packed(q_ptr, q_term, q_weight, k, mine, **lkw)
         else:
             blk = (nq + world - 1) // world
-            key = ("pa2a", world, nq, k, dev, slot)
-            bufs = self._buf.get(key)
-            if bufs is None:
-                bufs = self._buf[key] = (torch.zeros((world * blk, row), dtype=torch.int32, device=dev),  # send; rows >= nq stay empty
-                                         torch.empty((world, blk, row), dtype=torch.int32, device=dev))   # the lists of my query block
-            send, recv = bufs
+            send, recv = self._get_buf(("pa2a", world, nq, k, dev, slot),
+                                       lambda: (torch.zeros((world * blk, row), dtype=torch.int32, device=dev),  # send; rows >= nq stay empty
+                                                torch.empty((world, blk, row), dtype=torch.int32, device=dev)))  # the lists of my query block
             mine = send[:nq]
             with (torch.cuda.stream(main) if overlap else contextlib.nullcontext()):
                 self.local_search_packed(q_ptr, q_term, q_weight, k, mine, **lkw)
@@ -419,24 +430,23 @@ class ShardedSearcher:
     def wait(self) -> None:
         """Make the current stream wait for every exchange submitted with ``overlap`` / through the graph lanes (no-op otherwise)."""
         import torch
-        side = getattr(self, "_side", None)
-        if side is not None:
-            torch.cuda.current_stream(side.device).wait_stream(side)
-        for st in getattr(self, "_lane_streams", None) or []:
+        if self._side is not None:
+            torch.cuda.current_stream(self._side.device).wait_stream(self._side)
+        for st in self._lane_streams or []:
             torch.cuda.current_stream(st.device).wait_stream(st)
 
     def close(self) -> None:
         """Join the lanes and drop their captured graphs (they hold RCCL work: destroy them BEFORE the process group)."""
         import torch
-        for st in getattr(self, "_lane_streams", None) or []:
+        for st in self._lane_streams or []:
             st.synchronize()
         self._lanes = {}
-        if getattr(self, "_side", None) is not None:
+        if self._side is not None:
             self._side.synchronize()
-        self._buf = None
+        self._buf = {}
         if torch.cuda.is_available():
             torch.cuda.synchronize()
-        for g in getattr(self, "_lane_groups", None) or []:  # the lanes' own communicators
+        for g in self._lane_groups or []:  # the lanes' own communicators
             try:
                 import torch.distributed as dist
                 dist.destroy_process_group(g)
@@ -456,26 +466,19 @@ class ShardedSearcher:
         nq = count.shape[0]
         row = 2 * k + 1
         mine = self.pack(doc, score, count)  # [nq, 2k+1] i32: nq*(8k+4) bytes per rank
-        if self._buf is None:
-            self._buf = {}
         mode = self.mode
         if mode == "allgather":
-            key = ("ag", world, nq, k, mine.device, slot)
-            g = self._buf.get(key)
-            if g is None:
-                g = self._buf[key] = torch.empty((world, nq, row), dtype=torch.int32, device=mine.device)
+            g = self._get_buf(("ag", world, nq, k, mine.device, slot),
+                              lambda: torch.empty((world, nq, row), dtype=torch.int32, device=mine.device))
             # RCCL over xGMI on the GPU build; output = concatenation along dim 0 (the form every backend accepts)
             dist.all_gather_into_tensor(g.view(world * nq, row), mine, group=self.group)
             return self.merge(g, k)
         # ---- all-to-all: rank j merges query block j ----
         blk = (nq + world - 1) // world
-        key = ("a2a", world, nq, k, mine.device, slot)
-        bufs = self._buf.get(key)
-        if bufs is None:
-            bufs = self._buf[key] = (torch.zeros((world * blk, row), dtype=torch.int32, device=mine.device),   # send (padded)
-                                     torch.empty((world, blk, row), dtype=torch.int32, device=mine.device),    # lists of my block
-                                     torch.empty((world * blk, row), dtype=torch.int32, device=mine.device))   # merged rows, all blocks
-        send, recv, allrows = bufs
+        send, recv, allrows = self._get_buf(("a2a", world, nq, k, mine.device, slot), lambda: (
+            torch.zeros((world * blk, row), dtype=torch.int32, device=mine.device),    # send (padded)
+            torch.empty((world, blk, row), dtype=torch.int32, device=mine.device),     # lists of my block
+            torch.empty((world * blk, row), dtype=torch.int32, device=mine.device)))   # merged rows, all blocks
         send[:nq] = mine  # rows nq .. world*blk-1 stay zero = empty lists (count 0)
         dist.all_to_all_single(recv.view(world * blk, row), send, group=self.group)
         mdoc, mscore, mcount = self.merge(recv, k)  # my block: [blk, k]

@@ -202,6 +202,82 @@ def _stream_ptr(torch, device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _check_k(k) -> None:
+    if not (1 <= k <= _capi.SRX_MAX_K):
+        raise ValueError(f"top_k must be in [1, {_capi.SRX_MAX_K}] for the HIP engine, got {k}")
+
+
+def _empty_topk(torch, nq: int, k: int, device):
+    """The output triple of every top-k entry point, uninitialised: (doc i32[nq,k], score f32[nq,k], count i32[nq])."""
+    return (torch.empty((nq, k), dtype=torch.int32, device=device), torch.empty((nq, k), dtype=torch.float32, device=device),
+            torch.empty((nq,), dtype=torch.int32, device=device))
+
+
+def _batch_to_device(torch, q_ptr, q_term, q_weight, device):
+    """Host CSR batch -> (q_ptr i32, q_term i32, q_weight f32) tensors on ``device``."""
+    return (torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=device),
+            torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=device),
+            torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=device))
+
+
+def _grow_ws(torch, owner, need: int, floor: int = 0):
+    """``owner._ws``, the workspace an index object caches between searches, replaced when ``need`` bytes do not fit."""
+    if owner._ws is None or owner._ws.numel() < need:
+        owner._ws = torch.empty(max(need, floor), dtype=torch.uint8, device=owner.device)
+    return owner._ws
+
+
+def _merge_ws(torch, nq: int, n_lists: int, k: int, device):
+    need = _capi.check(_capi.lib().srx_merge_workspace_bytes(nq, n_lists, k), "srx_merge_workspace_bytes")
+    return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+
+
+def _after_ptrs(torch, after, nq: int):
+    """The bound row of ``srx_search_after`` (doc i32[nq] GLOBAL ids, score f32[nq]) as the two pointer arguments."""
+    a_doc, a_score = after
+    assert a_doc.dtype == torch.int32 and a_score.dtype == torch.float32 and a_doc.numel() == nq == a_score.numel()
+    return a_doc.data_ptr(), a_score.data_ptr()
+
+
+def _to_host(torch, device, tensors, wait=None):
+    """The tail of every host-array entry point: (``wait()``,) one synchronisation, NumPy copies.  CPU tensors (the test
+    searchers) need neither."""
+    if device.type == "cuda":
+        if wait is not None:
+            wait()
+        torch.cuda.synchronize(device)
+    return tuple(t.cpu().numpy() for t in tensors)
+
+
+def search_host_batch(search_fn, q_ptr, q_term, q_weight, k: int, vocab: int, device, wait=None):
+    """A host CSR batch through any ``search_fn`` of :func:`deep_search` (one index, a sharded searcher, a fused pipeline):
+    validate, upload to ``device``, search -- any k >= 1, rankings deeper than the engine's lists are paged --, ``wait()``
+    when given, synchronise, download.  Returns host (doc i32[nq, k], score f32[nq, k], count i32[nq])."""
+    torch = _torch()
+    validate_query_batch(q_ptr, q_term, q_weight, vocab)
+    if k < 1:
+        raise ValueError(f"top_k must be >= 1, got {k}")
+    if len(q_ptr) - 1 == 0:
+        return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
+    out = deep_search(search_fn, *_batch_to_device(torch, q_ptr, q_term, q_weight, device), k, _capi.SRX_MAX_K)
+    return _to_host(torch, device, out, wait)
+
+
+def score_host_batch(score_fn, q_ptr, q_term, q_weight, cand_doc, cand_count, vocab: int, device) -> np.ndarray:
+    """A host CSR batch and a host candidate block through any ``score_fn(q_ptr, q_term, q_weight, cand_doc, cand_count)``
+    on device tensors: validate both, upload, one launch, one synchronisation, one copy.  Returns f32[nq, m]."""
+    torch = _torch()
+    validate_query_batch(q_ptr, q_term, q_weight, vocab)
+    nq = len(q_ptr) - 1
+    cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
+    if nq == 0:
+        return np.zeros((0, cand_doc.shape[1]), np.float32)
+    cd = torch.as_tensor(cand_doc, device=device)
+    cc = None if cand_count is None else torch.as_tensor(cand_count, device=device)
+    out = score_fn(*_batch_to_device(torch, q_ptr, q_term, q_weight, device), cd, cc)
+    return _to_host(torch, device, (out,))[0]
+
+
 class DeviceIndex:
     """One doc-range shard resident in HBM: term-major postings + tile skip table + idf, plus the
     ``srx_index`` handle.  All tensors are owned here (PyTorch-ROCm is the allocator); the library only
@@ -517,29 +593,7 @@ class DeviceIndex:
         0 <= q_term < vocab, no term twice inside a query -- ``validate_queries`` / ``search`` check host batches.
         ``after`` = (doc i32[nq] GLOBAL ids, score f32[nq]) device tensors: ``srx_search_after`` -- only docs ranked
         strictly after that row in (score desc, doc asc) order (the next page of a ranking deeper than max_k)."""
-        torch = _torch()
-        nq = q_ptr.numel() - 1
-        if not (1 <= k <= _capi.limits()["max_k"]):
-            raise ValueError(f"top_k must be in [1, {_capi.limits()['max_k']}] for the HIP engine, got {k}")
-        with torch.cuda.device(self.device):
-            if out is None:
-                out = (torch.empty((nq, k), dtype=torch.int32, device=self.device),
-                       torch.empty((nq, k), dtype=torch.float32, device=self.device),
-                       torch.empty((nq,), dtype=torch.int32, device=self.device))
-            need = self.workspace_bytes(nq, k)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
-            if after is None:
-                rc = _capi.lib().srx_search(self._h, _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, k, _ptr(out[0]), _ptr(out[1]),
-                                            _ptr(out[2]), _ptr(self._ws), self._ws.numel(), _stream_ptr(torch, self.device))
-            else:
-                a_doc, a_score = after
-                assert a_doc.dtype == torch.int32 and a_score.dtype == torch.float32 and a_doc.numel() == nq == a_score.numel()
-                rc = _capi.lib().srx_search_after(self._h, _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, k, a_doc.data_ptr(),
-                                                  a_score.data_ptr(), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(self._ws),
-                                                  self._ws.numel(), _stream_ptr(torch, self.device))
-            _capi.check(rc, "srx_search")
-        return out
+        return self._search(False, q_ptr, q_term, q_weight, k, out, after, None, None)
 
     def search_packed_device(self, q_ptr, q_term, q_weight, k: int, out=None, stream=None, workspace=None, after=None):
         """``srx_search_packed``: the same search, each query's result written as one row
@@ -547,29 +601,33 @@ class DeviceIndex:
         sharded search, so no packing kernel runs.  Returns ``out``.  ``stream`` (a torch stream, default: the current
         one) and ``workspace`` (a uint8 tensor of ``workspace_bytes`` bytes, default: the index's own) let several
         searches of one index be in flight on different streams."""
+        return self._search(True, q_ptr, q_term, q_weight, k, out, after, stream, workspace)
+
+    def _search(self, packed: bool, q_ptr, q_term, q_weight, k: int, out, after, stream, workspace):
+        """The one body of :meth:`search_device` and :meth:`search_packed_device`: k check, output, workspace, stream, then
+        ``srx_search[_after][_packed]`` -- the four entry points differ in the bound row and in the output pointers."""
         torch = _torch()
         nq = q_ptr.numel() - 1
-        if not (1 <= k <= _capi.limits()["max_k"]):
-            raise ValueError(f"top_k must be in [1, {_capi.limits()['max_k']}] for the HIP engine, got {k}")
+        _check_k(k)
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((nq, 2 * k + 1), dtype=torch.int32, device=self.device)
-            assert out.dtype == torch.int32 and tuple(out.shape) == (nq, 2 * k + 1) and out.is_contiguous()
-            if workspace is None:
-                need = self.workspace_bytes(nq, k)
-                if self._ws is None or self._ws.numel() < need:
-                    self._ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
-                workspace = self._ws
-            sp = stream.cuda_stream if stream is not None else _stream_ptr(torch, self.device)
-            if after is None:
-                rc = _capi.lib().srx_search_packed(self._h, _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, k, _ptr(out),
-                                                   _ptr(workspace), workspace.numel(), sp)
+            if not packed:
+                outs = out = _empty_topk(torch, nq, k, self.device) if out is None else out
             else:
-                a_doc, a_score = after
-                assert a_doc.dtype == torch.int32 and a_score.dtype == torch.float32 and a_doc.numel() == nq == a_score.numel()
-                rc = _capi.lib().srx_search_after_packed(self._h, _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, k, a_doc.data_ptr(),
-                                                         a_score.data_ptr(), _ptr(out), _ptr(workspace), workspace.numel(), sp)
-            _capi.check(rc, "srx_search_packed")
+                if out is None:
+                    out = torch.empty((nq, 2 * k + 1), dtype=torch.int32, device=self.device)
+                assert out.dtype == torch.int32 and tuple(out.shape) == (nq, 2 * k + 1) and out.is_contiguous()
+                outs = (out,)
+            if workspace is None:
+                workspace = _grow_ws(torch, self, self.workspace_bytes(nq, k), 1 << 20)
+            sp = stream.cuda_stream if stream is not None else _stream_ptr(torch, self.device)
+            name = "srx_search_packed" if packed else "srx_search"
+            if after is None:
+                fn, bound = getattr(_capi.lib(), name), ()
+            else:
+                fn, bound = getattr(_capi.lib(), name.replace("srx_search", "srx_search_after")), _after_ptrs(torch, after, nq)
+            rc = fn(self._h, _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, k, *bound, *[_ptr(o) for o in outs], _ptr(workspace),
+                    workspace.numel(), sp)
+            _capi.check(rc, name)
         return out
 
     def validate_queries(self, q_ptr: np.ndarray, q_term: np.ndarray, q_weight: np.ndarray) -> None:
@@ -579,20 +637,7 @@ class DeviceIndex:
         """Host arrays in, host arrays out (doc, score, count).  The batch is validated first (``validate_queries``);
         ``search_device`` trusts its device tensors.  Any k >= 1: a ranking deeper than the engine's list capacity
         (``max_k`` = 1024) is paged with ``srx_search_after`` (:func:`deep_search`)."""
-        torch = _torch()
-        nq = len(q_ptr) - 1
-        self.validate_queries(q_ptr, q_term, q_weight)
-        if k < 1:
-            raise ValueError(f"top_k must be >= 1, got {k}")
-        if nq == 0:
-            return (np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32))
-        dev = self.device
-        qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
-        qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
-        qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
-        d, s, c = deep_search(self.search_device, qp, qt, qw, k, _capi.limits()["max_k"])
-        torch.cuda.synchronize(dev)
-        return d.cpu().numpy(), s.cpu().numpy(), c.cpu().numpy()
+        return search_host_batch(self.search_device, q_ptr, q_term, q_weight, k, self.vocab, self.device)
 
     # -- scores of given docs ------------------------------------------------------------------------------
     def score_docs_device(self, q_ptr, q_term, q_weight, cand_doc, cand_count=None, out=None):
@@ -627,21 +672,7 @@ class DeviceIndex:
     def score_docs(self, q_ptr: np.ndarray, q_term: np.ndarray, q_weight: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
         """Host arrays in, f32[nq, m] out.  The batch (``validate_queries``) and the candidates
         (:func:`validate_candidates`) are validated first; then one launch, one synchronisation and one copy."""
-        torch = _torch()
-        nq = len(q_ptr) - 1
-        self.validate_queries(q_ptr, q_term, q_weight)
-        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
-        if nq == 0:
-            return np.zeros((0, cand_doc.shape[1]), np.float32)
-        dev = self.device
-        qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
-        qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
-        qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
-        cd = torch.as_tensor(cand_doc, device=dev)
-        cc = None if cand_count is None else torch.as_tensor(cand_count, device=dev)
-        out = self.score_docs_device(qp, qt, qw, cd, cc)
-        torch.cuda.synchronize(dev)
-        return out.cpu().numpy()
+        return score_host_batch(self.score_docs_device, q_ptr, q_term, q_weight, cand_doc, cand_count, self.vocab, self.device)
 
     def profile_read(self):
         """Average kernel durations (ms) over the profiled searches since the last read."""
@@ -689,8 +720,7 @@ class HostBatchPipeline:
     def __init__(self, index: "DeviceIndex", max_queries: int, max_terms: int, k: int, depth: int = 3, validate: bool = True,
                  zero_copy_queries: bool = True, zero_copy_results: bool = True, multi_stream: bool = False):
         torch = _torch()
-        if not (1 <= k <= _capi.limits()["max_k"]):
-            raise ValueError(f"top_k must be in [1, {_capi.limits()['max_k']}] for the HIP engine, got {k}")
+        _check_k(k)
         self.index, self.k, self.depth, self.validate = index, int(k), int(depth), validate
         self.zero_copy = bool(zero_copy_queries)
         self.zero_copy_out = bool(zero_copy_results)
@@ -841,10 +871,8 @@ def merge_topk_device(in_doc, in_score, in_count, k: int, gathered: bool = False
     dev = in_doc.device
     L = _capi.lib()
     with torch.cuda.device(dev):
-        out = (torch.empty((nq, k), dtype=torch.int32, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev),
-               torch.empty((nq,), dtype=torch.int32, device=dev))
-        need = _capi.check(L.srx_merge_workspace_bytes(nq, n_lists, k), "srx_merge_workspace_bytes")
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        out = _empty_topk(torch, nq, k, dev)
+        ws = _merge_ws(torch, nq, n_lists, k, dev)
         in_doc, in_score, in_count = in_doc.contiguous(), in_score.contiguous(), in_count.contiguous()
         rc = L.srx_merge_topk(dev.index or 0, _ptr(in_doc), _ptr(in_score), _ptr(in_count), nq, n_lists, k, int(gathered),
                               _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), _stream_ptr(torch, dev))
@@ -882,7 +910,7 @@ def fuse_topk_device(a, b, k: int, mode: str = "weighted", weights=(0.3, 0.7), r
     tensors' device."""
     torch = _torch()
     code, wa, wb, rrf_c = check_fuse_args(mode, weights, rrf_c)
-    max_k = _capi.limits()["max_k"]
+    max_k = _capi.SRX_MAX_K
     (a_doc, a_score, a_count), (b_doc, b_score, b_count) = a, b
     if a_doc.dim() != 2 or b_doc.dim() != 2 or a_doc.shape != a_score.shape or b_doc.shape != b_score.shape:
         raise ValueError("fuse_topk_device: doc / score must be [nq, k] tensors of one shape per list")
@@ -900,8 +928,7 @@ def fuse_topk_device(a, b, k: int, mode: str = "weighted", weights=(0.3, 0.7), r
         raise ValueError("fuse_topk_device: the lists must be device tensors")
     L = _capi.lib()
     with torch.cuda.device(dev):
-        out = (torch.empty((nq, k), dtype=torch.int32, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev),
-               torch.empty((nq,), dtype=torch.int32, device=dev))
+        out = _empty_topk(torch, nq, k, dev)
         a_doc, a_score, a_count = a_doc.contiguous(), a_score.contiguous(), a_count.contiguous()
         b_doc, b_score, b_count = b_doc.contiguous(), b_score.contiguous(), b_count.contiguous()
         rc = L.srx_fuse_topk(dev.index or 0, _ptr(a_doc), _ptr(a_score), _ptr(a_count), ka, _ptr(b_doc), _ptr(b_score),
@@ -915,26 +942,19 @@ def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, k
                   rrf_c: float):
     """The hybrid pipeline of the API mirrors: sparse search of a host CSR batch on ``index`` (``ka`` rows per query),
     ``dense_search(kb)`` -> the dense side's device triple for the same queries, ``fuse_topk_device``; the three steps
-    stay on the device, then one synchronisation and one copy back.  Returns host (doc, score, count)."""
-    torch = _torch()
+    stay on the device, then one synchronisation and the copy back (:func:`search_host_batch`).  Returns host (doc, score, count)."""
     check_fuse_args(mode, weights, rrf_c)
-    index.validate_queries(q_ptr, q_term, q_weight)
-    dev = index.device
-    qp = torch.as_tensor(np.ascontiguousarray(q_ptr, dtype=np.int32), device=dev)
-    qt = torch.as_tensor(np.ascontiguousarray(q_term, dtype=np.int32), device=dev)
-    qw = torch.as_tensor(np.ascontiguousarray(q_weight, dtype=np.float32), device=dev)
-    a = index.search_device(qp, qt, qw, ka)
-    b = dense_search(kb)
-    packed = pack_results(*fuse_topk_device(a, b, k, mode=mode, weights=weights, rrf_c=rrf_c))
-    torch.cuda.synchronize(dev)
-    rows = packed.cpu().numpy()
-    return rows[:, :k], rows[:, k:2 * k].view(np.float32), rows[:, 2 * k]
+
+    def fused(qp, qt, qw, kk):
+        return fuse_topk_device(index.search_device(qp, qt, qw, ka), dense_search(kb), kk, mode=mode, weights=weights, rrf_c=rrf_c)
+
+    return search_host_batch(fused, q_ptr, q_term, q_weight, k, index.vocab, index.device)
 
 
 def hybrid_depths(top_k: int, candidates, n_docs: int) -> Tuple[int, int]:
     """(k, rows fetched from each side) for a hybrid search, or ``ValueError``.  ``top_k`` > max_k is refused: paging a
     fused ranking deeper than the engine's lists is out of scope, and a silently shorter list would be worse."""
-    max_k = 1024  # SRX_MAX_K
+    max_k = _capi.SRX_MAX_K
     top_k = int(top_k)
     if top_k > max_k:
         raise ValueError(f"hybrid search returns at most {max_k} rows per query, got top_k={top_k}")
@@ -980,6 +1000,11 @@ def pack_results(doc, score, count):
     return out
 
 
+def rows_to_dict(doc_ids, doc, score, count, i: int) -> Dict[str, float]:
+    """Row ``i`` of a host (doc, score, count) triple as ``{doc_id: score}`` in rank order."""
+    return {doc_ids[int(doc[i, j])]: float(score[i, j]) for j in range(int(count[i]))}
+
+
 def merge_topk_packed_out_device(packed, k: int, out=None):
     """``srx_merge_topk_packed_out``: gathered packed rows [n_lists, nq, 2k+1] -> packed rows ``out`` [nq, 2k+1]."""
     torch = _torch()
@@ -991,8 +1016,7 @@ def merge_topk_packed_out_device(packed, k: int, out=None):
         if out is None:
             out = torch.empty((nq, row), dtype=torch.int32, device=dev)
         assert out.dtype == torch.int32 and tuple(out.shape) == (nq, row) and out.is_contiguous()
-        need = _capi.check(L.srx_merge_workspace_bytes(nq, n_lists, k), "srx_merge_workspace_bytes")
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        ws = _merge_ws(torch, nq, n_lists, k, dev)
         rc = L.srx_merge_topk_packed_out(dev.index or 0, _ptr(packed), nq, n_lists, k, _ptr(out), _ptr(ws), ws.numel(),
                                          _stream_ptr(torch, dev))
         _capi.check(rc, "srx_merge_topk_packed_out")
@@ -1007,10 +1031,8 @@ def merge_topk_packed_device(packed, k: int):
     dev = packed.device
     L = _capi.lib()
     with torch.cuda.device(dev):
-        out = (torch.empty((nq, k), dtype=torch.int32, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev),
-               torch.empty((nq,), dtype=torch.int32, device=dev))
-        need = _capi.check(L.srx_merge_workspace_bytes(nq, n_lists, k), "srx_merge_workspace_bytes")
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        out = _empty_topk(torch, nq, k, dev)
+        ws = _merge_ws(torch, nq, n_lists, k, dev)
         packed = packed.contiguous()
         rc = L.srx_merge_topk_packed(dev.index or 0, _ptr(packed), nq, n_lists, k, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                      _ptr(ws), ws.numel(), _stream_ptr(torch, dev))

@@ -21,13 +21,13 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .backend import SparseBackend
-from .index import DeviceIndex, HostIndex, check_fuse_args, encode_queries, hybrid_depths, hybrid_search
+from .backend import SparseBackend, SparseIndexViews
+from .index import HostIndex, check_fuse_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
 
 _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
 
 
-class _SparseRetrieverBase:
+class _SparseRetrieverBase(SparseIndexViews):
     """Shared batched search: cache semantics of the reference call sites, one srx_search per call."""
 
     mode = "bm25"
@@ -43,77 +43,15 @@ class _SparseRetrieverBase:
         self.query_cache: Optional[Dict[str, Tuple[np.ndarray, np.ndarray]]] = {} if use_cache else None
         self.cache_lock = threading.RLock()
 
-    @property
-    def host(self) -> Optional[HostIndex]:
-        return self._be.host
-
-    @property
-    def dev(self) -> Optional[DeviceIndex]:
-        return self._be.dev
-
-    # reference attribute names
-    @property
-    def vocabulary(self):
-        return self.host.vocabulary if self.host else {}
-
-    @property
-    def doc_ids(self):
-        return self.host.doc_ids if self.host else []
-
-    @property
-    def corpus_tf(self):
-        if self.host is None:
-            return None
-        from scipy.sparse import csr_matrix
-        h = self.host
-        return csr_matrix((h.data, h.indices, h.indptr), shape=(h.n_docs, h.vocab_size))
-
     def _upload(self):
         self._be.upload(self.mode, self.k1, self.b)
 
     def search(self, queries: Dict[str, str], top_k: int = 10) -> Dict[str, Dict[str, float]]:
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        results: Dict[str, Dict[str, float]] = {}
-        pending: Dict[str, List[str]] = {}
-        texts, keys = [], []
-        for qid, text in queries.items():
-            if not text:  # retriever_registry.py:237-239
-                results[qid] = {}
-                continue
-            key = f"{text.strip() if self.strip_cache_key else text}:{top_k}"
-            hit = None
-            if self.query_cache is not None:
-                with self.cache_lock:
-                    hit = self.query_cache.get(key)
-            if hit is not None:
-                results[qid] = self._to_dict(*hit)
-                continue
-            results[qid] = {}
-            if key not in pending:
-                pending[key] = []
-                texts.append(text)
-                keys.append(key)
-            pending[key].append(qid)
-        if texts:
-            q_ptr, q_term, q_w = encode_queries(texts, self.host.vocabulary, order=self.term_order)
-            k_eff = min(int(top_k), self._be.n_docs_total)  # any depth: DeviceIndex.search pages past the engine's 1024-row lists
-            if k_eff <= 0:  # argpartition(...)[:0] keeps nothing (retriever_registry.py:304-312): {} per query, like the reference
-                return results
-            docs, scores, counts = self._be.search_arrays(q_ptr, q_term, q_w, k_eff)
-            for i, key in enumerate(keys):
-                if q_ptr[i + 1] == q_ptr[i]:
-                    continue
-                c = int(counts[i])
-                entry = (docs[i, :c].astype(np.int64), scores[i, :c].copy())
-                if self.query_cache is not None:
-                    with self.cache_lock:
-                        if len(self.query_cache) < 1000:
-                            self.query_cache[key] = entry
-                d = self._to_dict(*entry)
-                for qid in pending[key]:
-                    results[qid] = dict(d)
-        return results
+        # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional
+        return self._be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock,
+                                     strip_key=self.strip_cache_key, blank="empty")
 
     def score(self, queries: Dict[str, str], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
         """The exact score of caller-named documents: ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in
@@ -123,10 +61,6 @@ class _SparseRetrieverBase:
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         return self._be.score_dicts(queries, candidates, order=self.term_order)
-
-    def _to_dict(self, idx, sc):
-        ids = self.host.doc_ids
-        return {ids[int(i)]: float(s) for i, s in zip(idx, sc) if s > 0}
 
     def close(self):
         self._be.close()
@@ -285,7 +219,7 @@ class QuantizedEmbeddingRetriever:
         else:
             d, s, n = self._index.search(np.stack(embs), k)
         for i, (qid, _) in enumerate(live):
-            results[qid] = {self.doc_ids[int(d[i, j])]: float(s[i, j]) for j in range(int(n[i]))}  # score > 0 only (:515-519)
+            results[qid] = rows_to_dict(self.doc_ids, d, s, n, i)  # score > 0 only (:515-519)
         return results
 
 
@@ -393,9 +327,8 @@ class HybridRetriever:
 
         doc, score, count = hybrid_search(self.sparse.dev, q_ptr, q_term, q_w, dense_search, cand, cand, k, self.fusion,
                                           (self.sparse_weight, self.dense_weight), self.rrf_c)
-        ids = self.doc_ids
         for i, (qid, _) in enumerate(live):
-            results[qid] = {ids[int(doc[i, j])]: float(score[i, j]) for j in range(int(count[i]))}
+            results[qid] = rows_to_dict(self.doc_ids, doc, score, count, i)
         return results
 
     def close(self):

@@ -31,15 +31,15 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .backend import SparseBackend
-from .index import DeviceIndex, HostIndex, check_fuse_args, encode_queries, hybrid_depths, hybrid_search
+from .backend import SparseBackend, SparseIndexViews
+from .index import check_fuse_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
 
 logger = logging.getLogger(__name__)
 
 NUMBA_AVAILABLE = False  # kept for get_stats() key compatibility (retrieval.py:476)
 
 
-class RetrievalService:
+class RetrievalService(SparseIndexViews):
     """BM25 retrieval with the reference's API; scoring + top-k run on the GPU."""
 
     def __init__(self, index_path=None, embedding_path=None, num_workers: int = 4, cache_size: int = 1000, *,
@@ -66,23 +66,7 @@ class RetrievalService:
         self.cache_lock = threading.RLock()
         self.build_time = 0.0
 
-    # -- reference attribute names (read-only views) -----------------------------------------------------
-    @property
-    def host(self) -> Optional[HostIndex]:
-        return self._be.host  # sharded: this rank's rows, corpus-wide vocabulary / idf / avgdl / doc ids
-
-    @property
-    def dev(self) -> Optional[DeviceIndex]:
-        return self._be.dev
-
-    @property
-    def vocabulary(self) -> Dict[str, int]:
-        return self.host.vocabulary if self.host else {}
-
-    @property
-    def doc_ids(self) -> List[str]:
-        return self.host.doc_ids if self.host else []
-
+    # -- reference attribute names (read-only views; host, dev, vocabulary, doc_ids, corpus_tf: backend.SparseIndexViews) --
     @property
     def idf_weights(self):
         return self.host.idf if self.host else None
@@ -94,14 +78,6 @@ class RetrievalService:
     @property
     def avgdl(self) -> float:
         return self.host.avgdl if self.host else 0.0
-
-    @property
-    def corpus_tf(self):
-        if self.host is None:
-            return None
-        from scipy.sparse import csr_matrix
-        h = self.host
-        return csr_matrix((h.data, h.indices, h.indptr), shape=(h.n_docs, h.vocab_size))
 
     # -- build ------------------------------------------------------------------------------------------
     def build_bm25_index(self, corpus: Dict[str, Dict]) -> None:
@@ -124,48 +100,13 @@ class RetrievalService:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
-        # k >= n_docs -> everything, ranked (:281-284); any depth: past its 1024-row lists the engine pages with
-        # srx_search_after (index.deep_search)
-        k_eff = min(int(top_k), self._be.n_docs_total)
-        if k_eff <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
+        if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
             self._upload()  # k1 / b are plain attributes on the reference (:116-117): impacts depend on them
-        results: Dict[str, Dict[str, float]] = {}
-        pending: Dict[str, List[str]] = {}  # cache_key -> qids waiting for it
-        texts: List[str] = []
-        keys: List[str] = []
-        for qid, text in queries.items():
-            if not text or not text.strip():  # :211-213
-                results[qid] = {}
-                continue
-            key = f"{text.strip()}:{top_k}"  # :216
-            with self.cache_lock:
-                hit = self.query_cache.get(key)
-            if hit is not None:
-                results[qid] = self._to_dict(*hit)
-                continue
-            results[qid] = {}  # keeps the caller's qid order; filled below
-            if key not in pending:
-                pending[key] = []
-                texts.append(text)
-                keys.append(key)
-            pending[key].append(qid)
-        if texts:
-            q_ptr, q_term, q_weight = encode_queries(texts, self.host.vocabulary)
-            docs, scores, counts = self._be.search_arrays(q_ptr, q_term, q_weight, k_eff)
-            for i, key in enumerate(keys):
-                if q_ptr[i + 1] == q_ptr[i]:  # no token / no in-vocabulary term -> {} and nothing cached (:237-238, :251-252)
-                    continue
-                c = int(counts[i])
-                entry = (docs[i, :c].astype(np.int64), scores[i, :c].copy())
-                with self.cache_lock:
-                    if len(self.query_cache) < 1000:  # :288
-                        self.query_cache[key] = entry
-                d = self._to_dict(*entry)
-                for qid in pending[key]:
-                    results[qid] = dict(d)
-        return results
+        # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on
+        return self._be.search_dicts(queries, top_k, order="term", cache=self.query_cache, lock=self.cache_lock, strip_key=True,
+                                     blank="whitespace")
 
     def score_bm25(self, queries: Dict[str, str], candidates: Dict[str, Sequence[str]]) -> Dict[str, Dict[str, float]]:
         """The exact BM25 score of caller-named documents (no reference counterpart: it can only rank):
@@ -179,10 +120,6 @@ class RetrievalService:
         if (self.k1, self.b) != self._built_k1b:
             self._upload()
         return self._be.score_dicts(queries, candidates, order="term")
-
-    def _to_dict(self, idx: np.ndarray, sc: np.ndarray) -> Dict[str, float]:
-        ids = self.host.doc_ids
-        return {ids[int(i)]: float(s) for i, s in zip(idx, sc) if s > 0}  # :292-296
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
@@ -254,7 +191,7 @@ class RetrievalService:
         retrieved scores with that side alone; a query without in-vocabulary terms is the dense list re-scored.
         ``candidates``: rows fetched from each side (default ``top_k``, capped at ``min(candidates, n_docs, 1024)``).
         All queries of the call run as one batch: sparse search, dense search and fusion stay on the device, followed by
-        one synchronisation and one copy back.  Returns ``{qid: {doc_id: fused score}}`` in rank order, ``{}`` for a blank
+        one synchronisation and the copy back.  Returns ``{qid: {doc_id: fused score}}`` in rank order, ``{}`` for a blank
         query; ``top_k <= 0`` gives ``{}`` per query.  ``top_k`` > 1024 raises ``ValueError``: a fused ranking deeper
         than the engine's lists is not paged, and a silently shorter list would be worse than an error.  With one weight
         0 the result is the other side's set, but equal normalised scores rank by doc id.  The query cache is not used.
@@ -289,9 +226,8 @@ class RetrievalService:
 
         doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
                                           (sparse_weight, dense_weight), rrf_c)
-        ids = self.host.doc_ids
         for i, (qid, _) in enumerate(live):
-            results[qid] = {ids[int(doc[i, j])]: float(score[i, j]) for j in range(int(count[i]))}
+            results[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return results
 
     def clear_cache(self) -> None:

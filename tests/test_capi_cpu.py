@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
 def test_limits_and_error_strings():
     lim = _capi.limits()
     assert lim == {"max_k": 1024, "max_tile_log2": 14, "hash_cap": 4096, "threads": 256}
+    assert _capi.SRX_MAX_K == lim["max_k"]  # the constant the Python layer checks k against
     L = _capi.lib()
     assert L.srx_index_create(None, None) == -1
     assert b"null" in L.srx_last_error()
