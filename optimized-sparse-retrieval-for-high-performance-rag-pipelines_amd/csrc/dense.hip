@@ -12,7 +12,6 @@
 namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-constexpr int DENSE_NW_LONG = 4;  // waves per workgroup of the filter kernel on rows longer than 384 bytes (8: measured, no gain)
 constexpr int DENSE_PF = 6;       // LDS reads of query fragments in flight ahead of the MFMAs
 constexpr int DENSE_CNT_STRIDE = 32;  // ints between two queries' candidate counters: one 128-byte line each (all waves
                                       // add to these: counters sharing a line serialise in one L2 channel)
@@ -88,6 +87,17 @@ __global__ __launch_bounds__(THREADS) void srx_dense_i8_scores_kernel(const int8
     }
 }
 
+// Geometry of the filter kernel below at ks k-steps per row, for the kernel (constexpr) and its driver.  DT doc tiles of 32 per wave:
+// with two, every A fragment (query tile) feeds two MFMAs; both tiles' B fragments must fit the register file (rows <= 384 bytes).  NW waves
+// per workgroup, CB survivor list entries per wave, NBUF query tiles in LDS (one in use, one or two on their way): two workgroups per CU must fit.
+struct DenseFilterGeom {
+    int DT, NW, CB, NBUF, docs_per_block;
+};
+constexpr DenseFilterGeom dense_filter_geom(int ks) {
+    const int dt = ks <= 12 ? 2 : 1, nw = 4;
+    return {dt, nw, ks <= 12 ? 512 : (ks <= 24 ? 256 : 128), ks <= 16 ? 3 : 2, 32 * dt * nw};
+}
+
 // The same GEMM with the top-k filter fused in: instead of writing the score, a lane keeps it only if it can still
 // reach the query's top k (score > 0 and >= tau[q], a valid lower bound of the k-th best score taken from a sample of
 // the corpus) and appends (doc, score) to the query's candidate buffer.  A full buffer raises the query's overflow flag
@@ -135,10 +145,7 @@ __device__ __forceinline__ void static_for(F &&f) {
 // screen the tile before, a barrier per phase -- 12-30 % slower: the screening phase (staging issue + screen + wait) is
 // 1.7 x the MFMA phase, and a lock-step pair runs at the pace of the longer one.)
 template <int KS>
-constexpr int dense_filter_waves() { return KS > 12 ? DENSE_NW_LONG : 4; }
-
-template <int KS>
-__global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgpu_waves_per_eu(2))) void srx_dense_i8_filter_kernel(const int8_t *__restrict__ corpus,
+__global__ __launch_bounds__(64 * dense_filter_geom(KS).NW) __attribute__((amdgpu_waves_per_eu(2))) void srx_dense_i8_filter_kernel(const int8_t *__restrict__ corpus,
                                                                        const float *__restrict__ corpus_scale,
                                                                        int64_t n_docs, const v4i *__restrict__ apack,
                                                                        const float *__restrict__ query_scale, int nq,
@@ -147,13 +154,8 @@ __global__ __launch_bounds__(64 * dense_filter_waves<KS>()) __attribute__((amdgp
                                                                        float *__restrict__ buf_score,
                                                                        int *__restrict__ buf_cnt, int *__restrict__ ovf,
                                                                        int *__restrict__ any_ovf, int packed) {
-    // DT doc tiles of 32 per wave: with two, every A fragment (query tile) feeds two MFMAs; the B fragments of both
-    // tiles must fit the register file (KS <= 12, i.e. rows up to 384 bytes).
-    constexpr int DT = KS <= 12 ? 2 : 1;
-    constexpr int NW = dense_filter_waves<KS>();  // waves per workgroup
-    // LDS: two free-running workgroups of four waves per CU must fit (80 KiB each); one of eight waves may take more
-    constexpr int DENSE_CB = KS <= 12 ? 512 : (KS <= 24 ? 256 : 128);  // per-wave survivor list entries
-    constexpr int NBUF = (KS <= 16 || NW == 8) ? 3 : 2;  // query tiles in LDS: the one in use and one or two on their way
+    constexpr DenseFilterGeom G = dense_filter_geom(KS);
+    constexpr int DT = G.DT, NW = G.NW, DENSE_CB = G.CB, NBUF = G.NBUF;
     constexpr int PD = NBUF - 1;                         // tiles staged ahead
     constexpr int ROWS = (KS + NW - 1) / NW;             // 1 KiB fragment rows of a tile that one wave stages
     __shared__ v4i ldsA[NBUF][KS * 64];
@@ -421,14 +423,12 @@ __global__ __launch_bounds__(THREADS) void srx_dense_topk_kernel(const float *__
     }
 }
 
+int64_t dense_ld(int64_t n_docs) { return (n_docs + 63) / 64 * 64; }  // row length of the score matrix
 // Queries per pass: as many as keep the fallback's score matrix (queries x n_docs x 4 B) within 4 GiB, 32 .. 1024.
 // More queries per pass = the docs' B fragments are loaded once for more query tiles.
 int dense_qb(int64_t n_docs) {
-    int64_t q = (4ll << 30) / (((n_docs + 63) / 64 * 64) * 4);
-    q = q / 32 * 32;
-    if (q < 32) q = 32;
-    if (q > 1024) q = 1024;
-    return (int)q;
+    const int64_t q = (4ll << 30) / (dense_ld(n_docs) * 4) / 32 * 32;
+    return (int)(q < 32 ? 32 : q > 1024 ? 1024 : q);
 }
 constexpr int DENSE_CAP = 65536;  // candidate buffer entries per query of the filtered path
 int dense_splits(int64_t n_docs, int nq, int k) {
@@ -454,24 +454,39 @@ int64_t dense_sample(int64_t n_docs, int k) {
     S = (S + 127) / 128 * 128;
     return (S * 4 <= n_docs) ? S : 0;
 }
+// Two filter rounds (round 3): the sample's threshold lets about k n / S docs per query through; the first round filters only
+// the docs [0, S1), S1 = sqrt(S n), the k-th best of its survivors (a valid lower bound too, and never below the sample's) is
+// the threshold of the second round over [S1, n): about k (S1 / S + n / S1) survivors per query instead of k n / S -- 4x fewer
+// exact-path rows and buffer appends at 1 M docs.  Whole rounds of the chip at eight waves per CU; small corpus: one round.
+int64_t dense_s1(int64_t n_docs, int64_t S, int ks) {
+    const DenseFilterGeom g = dense_filter_geom(ks);
+    const int64_t root = (int64_t)sqrt((double)S * (double)n_docs), chip = (int64_t)g.docs_per_block * (2048 / g.NW);
+    const int64_t unit = root >= chip ? chip : g.docs_per_block, S1 = (root + unit - 1) / unit * unit;
+    return S1 * 2 > n_docs ? n_docs : S1;
+}
+struct DensePlan {  // the dispatch of one srx_dense_search_i8 call (tests/parity.py: dense_plan)
+    int QB, qb_max;  // queries per pass; of the largest pass
+    int64_t ld;
+    int ns;          // splits of a score row (matrix path, overflow fallback)
+    int64_t S;       // sample size of the threshold pass; 0 = matrix path
+};
+DensePlan dense_plan(int nq, int64_t n_docs, int k) {
+    const int QB = dense_qb(n_docs), qb_max = nq < QB ? nq : QB;
+    return {QB, qb_max, dense_ld(n_docs), dense_splits(n_docs, qb_max, k), dense_sample(n_docs, k)};
+}
 struct DenseWs {
     float *scores;
-    int32_t *cand_doc;
-    float *cand_score;
-    int32_t *cand_count;
+    srx_rows cand;  // [qb_max * ns] lists of k
     unsigned *tau;
-    int *buf_cnt, *ovf, *any_ovf;
+    int *buf_cnt, *ovf, *any_ovf;  // counts, overflow flags, any-overflow: zeroed_bytes, one memset
+    int64_t zeroed_bytes;
     int32_t *buf_doc;
     float *buf_score;
     v4i *apack;
     int64_t bytes;
 };
-DenseWs dense_ws(void *base, int nq, int64_t n_docs, int k) {
-    const int QB = dense_qb(n_docs);
-    const int qb = nq < QB ? nq : QB;
-    const int64_t ld = (n_docs + 63) / 64 * 64;
-    const int ns = dense_splits(n_docs, qb, k);
-    const bool filt = dense_sample(n_docs, k) > 0;
+DenseWs dense_ws(void *base, const DensePlan &pl, int k) {
+    const int qb = pl.qb_max;
     DenseWs w;
     char *p = (char *)base;
     auto take = [&](int64_t bytes) {
@@ -479,25 +494,64 @@ DenseWs dense_ws(void *base, int nq, int64_t n_docs, int k) {
         p += (bytes + 255) / 256 * 256;
         return r;
     };
-    w.scores = (float *)take((int64_t)qb * ld * 4);
-    w.cand_doc = (int32_t *)take((int64_t)qb * ns * k * 4);
-    w.cand_score = (float *)take((int64_t)qb * ns * k * 4);
-    w.cand_count = (int32_t *)take((int64_t)qb * ns * 4);
+    w.scores = (float *)take((int64_t)qb * pl.ld * 4);
+    int32_t *cand_doc = (int32_t *)take((int64_t)qb * pl.ns * k * 4);
+    float *cand_score = (float *)take((int64_t)qb * pl.ns * k * 4);
+    w.cand = srx_plain_rows(cand_doc, cand_score, (int32_t *)take((int64_t)qb * pl.ns * 4), k);
     w.tau = (unsigned *)take((int64_t)qb * 4);
-    w.buf_cnt = (int *)take((int64_t)(qb * DENSE_CNT_STRIDE + qb + 1) * 4);  // counts, overflow flags, any-overflow: one memset
+    w.zeroed_bytes = (int64_t)(qb * DENSE_CNT_STRIDE + qb + 1) * 4;
+    w.buf_cnt = (int *)take(w.zeroed_bytes);
     w.ovf = w.buf_cnt + qb * DENSE_CNT_STRIDE;
     w.any_ovf = w.ovf + qb;
-    w.buf_doc = (int32_t *)take(filt ? (int64_t)qb * DENSE_CAP * 4 : 0);
-    w.buf_score = (float *)take(filt ? (int64_t)qb * DENSE_CAP * 4 : 0);
+    w.buf_doc = (int32_t *)take(pl.S > 0 ? (int64_t)qb * DENSE_CAP * 4 : 0);
+    w.buf_score = (float *)take(pl.S > 0 ? (int64_t)qb * DENSE_CAP * 4 : 0);
     w.apack = (v4i *)take((int64_t)((qb + 31) / 32) * 32 * 1024);  // dim <= 1024 bytes per query row
     w.bytes = (int64_t)(p - (char *)base) + 256;
     return w;
 }
+
+// What one launch of srx_dense_topk_kernel ranks (the comment above the kernel); the defaults are the plain case.  A job that
+// ranks only some queries marks the others' first lists, and the merge after it leaves their rows alone
+enum { RANK_MATRIX = 0, RANK_BUFFERS = 1 };                          // mode
+enum { ALL_QUERIES = 0, ONLY_OVERFLOWED = 1, ONLY_THE_OTHERS = -1 };  // only_flag
+struct DenseTopkJob {
+    float *scores;
+    int64_t ld, n_docs;
+    int nq, k;
+    int64_t doc_base;
+    srx_rows cand;  // out: n_splits lists per query
+    int n_splits = 1, only = ALL_QUERIES, mode = RANK_MATRIX, cap = 0;  // RANK_BUFFERS: cap entries per query, the ids in
+    const int32_t *buf_doc = nullptr;                                   // buf_doc, buf_cnt[q] of them in use
+    const int *buf_cnt = nullptr, *ovf = nullptr, *gate = nullptr;
+};
+void launch_dense_topk(hipStream_t stream, const DenseTopkJob &j, unsigned *tau_out = nullptr, int tau_keep = 0) {
+    hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)((int64_t)j.nq * j.n_splits)), dim3(THREADS), 0, stream, j.scores, j.ld,
+                       j.n_docs, j.nq, j.k, j.n_splits, j.doc_base, j.mode, j.buf_doc, j.buf_cnt, j.cap, j.ovf, j.only, j.gate,
+                       j.cand.doc, j.cand.score, j.cand.count, tau_out, tau_keep);
+}
+// The job's lists, then their merge into the queries' rows of `out` behind the same gate
+int dense_rank_merge(int32_t device, void *stream_v, const DenseTopkJob &j, const srx_rows &out) {
+    launch_dense_topk((hipStream_t)stream_v, j);
+    HIP_TRY(hipGetLastError());
+    return srx_merge_impl(device, j.cand, j.nq, j.n_splits, j.k, 0, out, nullptr, 0, stream_v, j.gate, j.only != ALL_QUERIES);
+}
+
+// f(IntC<KS>) for the INT8 kernels' instantiation KS = ks; false: there is none
+template <typename F>
+bool dense_for_ks(int ks, F &&f) {
+    switch (ks) {
+#define SRX_KS(KS) case KS: f(IntC<KS>{}); return true;
+        SRX_KS(1) SRX_KS(2) SRX_KS(3) SRX_KS(4) SRX_KS(6) SRX_KS(8) SRX_KS(12) SRX_KS(16) SRX_KS(24) SRX_KS(32)
+#undef SRX_KS
+    }
+    return false;
+}
+bool dense_ks_supported(int ks) { return dense_for_ks(ks, [](auto) {}); }
 }  // namespace
 
 SRX_API int64_t srx_dense_workspace_bytes(int32_t nq, int64_t n_docs, int32_t k) {
     if (nq < 0 || n_docs <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_dense_workspace_bytes: bad argument%s");
-    return dense_ws(nullptr, nq, n_docs, k).bytes;
+    return dense_ws(nullptr, dense_plan(nq, n_docs, k), k).bytes;
 }
 
 namespace {
@@ -513,105 +567,59 @@ int dense_search_i8_impl(int32_t device, const int8_t *corpus, const float *corp
     if (!corpus || !corpus_scale || !queries || !query_scale || !out_doc || !out_score || !out_count)
         return fail(SRX_ERR_INVALID, "srx_dense_search_i8: null pointer%s");
     if (((uintptr_t)corpus | (uintptr_t)queries) & 15) return fail(SRX_ERR_INVALID, "srx_dense_search_i8: corpus / queries must be 16-byte aligned%s");
-    const int64_t need = srx_dense_workspace_bytes(nq, n_docs, k);
-    if (!workspace || workspace_bytes < need) return fail(SRX_ERR_NOMEM, "srx_dense_search_i8: workspace too small%s");
+    const DensePlan p = dense_plan(nq, n_docs, k);
+    const DenseWs w = dense_ws(workspace, p, k);
+    if (!workspace || workspace_bytes < w.bytes) return fail(SRX_ERR_NOMEM, "srx_dense_search_i8: workspace too small%s");
     HIP_TRY(hipSetDevice(device));
+    const int ks = dim / 32;
+    if (!dense_ks_supported(ks)) return fail(SRX_ERR_INVALID, "srx_dense_search_i8: dim must be 32, 64, 96, 128, 192, 256, 384, 512, 768 or 1024 (pad the rows with zeros)%s");
     hipStream_t stream = (hipStream_t)stream_v;
-    const int QB = dense_qb(n_docs);
-    const int qbmax = nq < QB ? nq : QB;
-    const int64_t ld = (n_docs + 63) / 64 * 64;
-    const int ns = dense_splits(n_docs, qbmax, k);
-    const int64_t S = dense_sample(n_docs, k);
-    const DenseWs w = dense_ws(workspace, nq, n_docs, k);
-    auto blocks_for = [](int64_t docs) { return (unsigned)((docs + 32 * WAVES - 1) / (32 * WAVES)); };
-    int ks_ok = 1;
-    // KERNEL<KS> dispatch on dim / 32
-#define SRX_DENSE_DISPATCH(KERNEL, GRID, BLOCK, ...)                                                                        \
-    switch (dim / 32) {                                                                                               \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;                \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;                \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;                \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;                \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;                \
-        case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;                \
-        case 12: hipLaunchKernelGGL(KERNEL<12>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;              \
-        case 16: hipLaunchKernelGGL(KERNEL<16>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;              \
-        case 24: hipLaunchKernelGGL(KERNEL<24>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;              \
-        case 32: hipLaunchKernelGGL(KERNEL<32>, dim3(GRID), dim3(BLOCK), 0, stream, __VA_ARGS__); break;              \
-        default: ks_ok = 0;                                                                                           \
-    }
-    for (int q0 = 0; q0 < nq; q0 += QB) {
-        const int qb = nq - q0 < QB ? nq - q0 : QB;
-        const int8_t *qp = queries + (int64_t)q0 * dim;
-        const float *qs = query_scale + q0;
-        int32_t *od = out_doc + (int64_t)q0 * k;
-        float *os = out_score + (int64_t)q0 * k;
-        int32_t *oc = out_count + q0;
-        const int *no_gate = nullptr;
-        hipLaunchKernelGGL(srx_dense_pack_queries_kernel, dim3(64), dim3(THREADS), 0, stream, qp, (int64_t)qb, (int)dim, w.apack);
-        if (S > 0) {
+    const DenseFilterGeom g = dense_filter_geom(ks);
+    const int64_t S1 = p.S > 0 ? dense_s1(n_docs, p.S, ks) : 0;
+    for (int q0 = 0; q0 < nq; q0 += p.QB) {
+        const int qb = nq - q0 < p.QB ? nq - q0 : p.QB;
+        const srx_rows out = srx_plain_rows(out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k, out_count + q0, k);
+        auto score_docs = [&](int64_t docs, int y, const int *gate) {  // docs [0, docs) into the score matrix, the query tiles over grid.y
+            dense_for_ks(ks, [&](auto KS) {
+                hipLaunchKernelGGL(srx_dense_i8_scores_kernel<decltype(KS)::value>, dim3((unsigned)((docs + 32 * WAVES - 1) / (32 * WAVES)), (unsigned)y),
+                                   dim3(THREADS), 0, stream, corpus, corpus_scale, docs, (const v4i *)w.apack, query_scale + q0, qb, w.scores, p.ld, gate, packed);
+            });
+        };
+        // every doc through the score matrix, the rows ranked in ns splits, the lists merged.  As the fallback for queries whose buffer
+        // overflowed (degenerate score distributions) all three kernels return at once unless some query did, and rank only those
+        auto through_matrix = [&](bool fallback) -> int {
+            DenseTopkJob job{w.scores, p.ld, n_docs, qb, k, doc_base, w.cand, p.ns};
+            if (fallback) {
+                job.ovf = w.ovf; job.only = ONLY_OVERFLOWED; job.gate = w.any_ovf;
+            }
+            score_docs(n_docs, 1, job.gate);
+            return dense_rank_merge(device, stream_v, job, out);
+        };
+        hipLaunchKernelGGL(srx_dense_pack_queries_kernel, dim3(64), dim3(THREADS), 0, stream, queries + (int64_t)q0 * dim, (int64_t)qb, (int)dim, w.apack);
+        int rc = SRX_OK;
+        if (p.S > 0) {
             // ---- filtered path: threshold from a sample, GEMM with the filter fused in, rank the candidate buffers ----
-            HIP_TRY(hipMemsetAsync(w.buf_cnt, 0, (size_t)(qbmax * DENSE_CNT_STRIDE + qbmax + 1) * 4, stream));
-            SRX_DENSE_DISPATCH(srx_dense_i8_scores_kernel, dim3(blocks_for(S), (unsigned)((qb + 127) / 128)), THREADS, corpus, corpus_scale, S, (const v4i *)w.apack, qs, qb, w.scores, ld, no_gate, packed);
-            if (!ks_ok) break;
-            hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)qb), dim3(THREADS), 0, stream, w.scores, ld, S, qb, k, 1, doc_base,
-                               0, (const int32_t *)nullptr, (const int *)nullptr, 0, (const int *)nullptr, 0, no_gate, w.cand_doc,
-                               w.cand_score, w.cand_count, w.tau, 0);
-            // Two rounds (round 3): the sample's threshold lets about k n / S docs per query through; the first round filters only
-            // the docs [0, S1), S1 = sqrt(S n), the k-th best of its survivors (a valid lower bound too, and never below the
-            // sample's) is the threshold of the second round over [S1, n): about k (S1 / S + n / S1) survivors per query instead
-            // of k n / S -- 4x fewer exact-path rows and buffer appends at 1 M docs.  Both rounds append to the same buffers.
-            const int ks = dim / 32;
-            const int filter_waves = ks > 12 ? DENSE_NW_LONG : 4;  // = dense_filter_waves<KS>()
-            const int filter_threads = 64 * filter_waves;
-            const int64_t docs_per_block = (ks <= 12 ? 64 : 32) * filter_waves;
-            int64_t S1 = (int64_t)sqrt((double)S * (double)n_docs);
-            const int64_t chip = docs_per_block * (2048 / filter_waves);  // whole rounds of the chip at eight waves per CU
-            S1 = S1 >= chip ? (S1 + chip - 1) / chip * chip : (S1 + docs_per_block - 1) / docs_per_block * docs_per_block;
-            if (S1 * 2 > n_docs) S1 = n_docs;  // small corpus: one round
-            for (int round = 0; round < 2; ++round) {
+            HIP_TRY(hipMemsetAsync(w.buf_cnt, 0, (size_t)w.zeroed_bytes, stream));
+            score_docs(p.S, (qb + 127) / 128, nullptr);
+            launch_dense_topk(stream, {w.scores, p.ld, p.S, qb, k, doc_base, w.cand}, w.tau);  // the sample's k-th best: the first threshold
+            const DenseTopkJob rank_buffers{w.buf_score, DENSE_CAP, n_docs, qb, k, doc_base, w.cand, 1, ALL_QUERIES, RANK_BUFFERS, DENSE_CAP, w.buf_doc, w.buf_cnt};
+            for (int round = 0; round < 2; ++round) {  // [0, S1) and [S1, n) (dense_s1); both append to the same buffers
                 const int64_t lo = round == 0 ? 0 : S1, hi = round == 0 ? S1 : n_docs;
                 if (lo >= hi) break;
-                SRX_DENSE_DISPATCH(srx_dense_i8_filter_kernel, (unsigned)((hi - lo + docs_per_block - 1) / docs_per_block), filter_threads, corpus + lo * dim,
-                                   corpus_scale + lo, hi - lo, (const v4i *)w.apack, qs, qb, w.tau, DENSE_CAP, doc_base + lo, w.buf_doc,
-                                   w.buf_score, w.buf_cnt, w.ovf, w.any_ovf, packed);
-                if (round == 0 && hi < n_docs)
-                    hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)qb), dim3(THREADS), 0, stream, w.buf_score, (int64_t)DENSE_CAP,
-                                       n_docs, qb, k, 1, doc_base, 1, w.buf_doc, w.buf_cnt, DENSE_CAP, (const int *)nullptr, 0, no_gate,
-                                       w.cand_doc, w.cand_score, w.cand_count, w.tau, 1);
+                dense_for_ks(ks, [&](auto KS) {
+                    hipLaunchKernelGGL(srx_dense_i8_filter_kernel<decltype(KS)::value>, dim3((unsigned)((hi - lo + g.docs_per_block - 1) / g.docs_per_block)),
+                                       dim3(64 * g.NW), 0, stream, corpus + lo * dim, corpus_scale + lo, hi - lo, (const v4i *)w.apack, query_scale + q0, qb, (const unsigned *)w.tau,
+                                       DENSE_CAP, doc_base + lo, w.buf_doc, w.buf_score, w.buf_cnt, w.ovf, w.any_ovf, packed);
+                });
+                if (round == 0 && hi < n_docs) launch_dense_topk(stream, rank_buffers, w.tau, 1);  // the survivors' k-th best, if higher: the second threshold
             }
-            hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)qb), dim3(THREADS), 0, stream, w.buf_score, (int64_t)DENSE_CAP,
-                               n_docs, qb, k, 1, doc_base, 1, w.buf_doc, w.buf_cnt, DENSE_CAP, w.ovf, -1, no_gate, w.cand_doc,
-                               w.cand_score, w.cand_count, (unsigned *)nullptr, 0);
-            HIP_TRY(hipGetLastError());
-            int rc = srx_merge_impl(device, w.cand_doc, w.cand_score, w.cand_count, qb, 1, k, 0, (int64_t)k, (int64_t)1, od, os, oc,
-                                (int64_t)k, (int64_t)1, nullptr, 0, stream_v, nullptr, 1);
-            if (rc != SRX_OK) return rc;
-            // ---- fallback for queries whose buffer overflowed (degenerate score distributions): through the score
-            //      matrix; both kernels return at once unless the any-overflow flag is set ----
-            SRX_DENSE_DISPATCH(srx_dense_i8_scores_kernel, blocks_for(n_docs), THREADS, corpus, corpus_scale, n_docs, (const v4i *)w.apack, qs, qb, w.scores, ld,
-                               (const int *)w.any_ovf, packed);
-            hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)((int64_t)qb * ns)), dim3(THREADS), 0, stream, w.scores, ld, n_docs,
-                               qb, k, ns, doc_base, 0, (const int32_t *)nullptr, (const int *)nullptr, 0, (const int *)w.ovf, 1,
-                               (const int *)w.any_ovf, w.cand_doc, w.cand_score, w.cand_count, (unsigned *)nullptr, 0);
-            HIP_TRY(hipGetLastError());
-            rc = srx_merge_impl(device, w.cand_doc, w.cand_score, w.cand_count, qb, ns, k, 0, (int64_t)k, (int64_t)1, od, os, oc,
-                            (int64_t)k, (int64_t)1, nullptr, 0, stream_v, (const int *)w.any_ovf, 1);
-            if (rc != SRX_OK) return rc;
-        } else {
-            SRX_DENSE_DISPATCH(srx_dense_i8_scores_kernel, blocks_for(n_docs), THREADS, corpus, corpus_scale, n_docs, (const v4i *)w.apack, qs, qb, w.scores, ld, no_gate, packed);
-            if (!ks_ok) break;
-            hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)((int64_t)qb * ns)), dim3(THREADS), 0, stream, w.scores, ld, n_docs,
-                               qb, k, ns, doc_base, 0, (const int32_t *)nullptr, (const int *)nullptr, 0, (const int *)nullptr, 0, no_gate,
-                               w.cand_doc, w.cand_score, w.cand_count, (unsigned *)nullptr, 0);
-            HIP_TRY(hipGetLastError());
-            const int rc = srx_merge_impl(device, w.cand_doc, w.cand_score, w.cand_count, qb, ns, k, 0, (int64_t)k, (int64_t)1, od, os, oc,
-                                      (int64_t)k, (int64_t)1, nullptr, 0, stream_v);
-            if (rc != SRX_OK) return rc;
+            DenseTopkJob others = rank_buffers;  // the overflowed queries' rows are the fallback's
+            others.ovf = w.ovf; others.only = ONLY_THE_OTHERS;
+            rc = dense_rank_merge(device, stream_v, others, out);
         }
+        if (rc == SRX_OK) rc = through_matrix(p.S > 0);
+        if (rc != SRX_OK) return rc;
     }
-#undef SRX_DENSE_DISPATCH
-    if (!ks_ok) return fail(SRX_ERR_INVALID, "srx_dense_search_i8: dim must be 32, 64, 96, 128, 192, 256, 384, 512, 768 or 1024 (pad the rows with zeros)%s");
     return SRX_OK;
 }
 }  // namespace
@@ -725,20 +733,57 @@ __global__ __launch_bounds__(THREADS) void srx_dense_u8_scores_kernel(const uint
         }
     }
 }
+// The workspace of a pass of F32_QP queries: their score rows, then the candidate lists and counts of their splits
+struct RowsWs {
+    DenseTopkJob rank;  // the score rows of a pass, its lists and their splits; nq is the caller's
+    int64_t bytes;
+};
+RowsWs rows_ws(void *base, int64_t n_docs, int k, int64_t doc_base = 0) {
+    const int ns = dense_splits(n_docs, F32_QP, k);
+    const int64_t ld = dense_ld(n_docs), lists = (int64_t)F32_QP * ns;
+    int32_t *cand_doc = (int32_t *)((float *)base + F32_QP * ld);
+    const srx_rows cand = srx_plain_rows(cand_doc, (float *)(cand_doc + lists * k), cand_doc + 2 * lists * k, k);
+    return {{(float *)base, ld, n_docs, 0, k, doc_base, cand, ns}, (int64_t)((char *)(cand.count + lists) - (char *)base) + 1024};
+}
 }  // namespace
 
 SRX_API int64_t srx_dense_f32_workspace_bytes(int32_t nq, int64_t n_docs, int32_t k) {
     if (nq < 0 || n_docs <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_dense_f32_workspace_bytes: bad argument%s");
-    const int64_t ld = (n_docs + 63) / 64 * 64;
-    const int ns = dense_splits(n_docs, F32_QP, k);
-    return (int64_t)F32_QP * ld * 4 + (int64_t)F32_QP * ns * k * 8 + (int64_t)F32_QP * ns * 4 + 1024;
+    return rows_ws(nullptr, n_docs, k).bytes;
 }
 
 namespace {
 // rows: f32 embeddings (u8_scale_min == nullptr) or uint8 rows de-quantized with u8_scale_min
 int dense_rows_search(const char *who, int32_t device, const void *rows, const float *u8_scale_min, int64_t n_docs, int32_t dim,
                       const float *queries, int32_t nq, int32_t k, int64_t doc_base, int32_t *out_doc, float *out_score,
-                      int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v, float score_offset);
+                      int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v, float score_offset) {
+    const float *emb = (const float *)rows;
+    if (nq < 0 || n_docs <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "%s: need n_docs > 0, 1 <= k <= 1024", who);
+    if (dim <= 0 || dim % 64 != 0 || dim > 64 * F32_MAXS)
+        return fail(SRX_ERR_INVALID, "%s: dim must be a multiple of 64, <= 1024 (pad the rows with zeros)", who);
+    if (doc_base < 0 || doc_base + n_docs >= 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: doc_base + n_docs must fit int32", who);
+    if (nq == 0) return SRX_OK;
+    if (!emb || !queries || !out_doc || !out_score || !out_count) return fail(SRX_ERR_INVALID, "%s: null pointer", who);
+    RowsWs w = rows_ws(workspace, n_docs, k, doc_base);
+    if (!workspace || workspace_bytes < w.bytes) return fail(SRX_ERR_NOMEM, "%s: workspace too small", who);
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    int64_t blocks = (n_docs + WAVES - 1) / WAVES;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    for (int q0 = 0; q0 < nq; q0 += F32_QP) {
+        const int qb = nq - q0 < F32_QP ? nq - q0 : F32_QP;
+        if (u8_scale_min == nullptr)
+            hipLaunchKernelGGL(srx_dense_f32_scores_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, emb, n_docs, (int)dim,
+                               queries + (int64_t)q0 * dim, qb, w.rank.scores, w.rank.ld, score_offset);
+        else
+            hipLaunchKernelGGL(srx_dense_u8_scores_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, (const uint8_t *)rows,
+                               u8_scale_min, n_docs, (int)dim, queries + (int64_t)q0 * dim, qb, w.rank.scores, w.rank.ld);
+        w.rank.nq = qb;
+        const int rc = dense_rank_merge(device, stream_v, w.rank, srx_plain_rows(out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k, out_count + q0, k));
+        if (rc != SRX_OK) return rc;
+    }
+    return SRX_OK;
+}
 }  // namespace
 
 SRX_API int srx_dense_search_f32(int32_t device, const float *emb, int64_t n_docs, int32_t dim, const float *queries, int32_t nq,
@@ -755,47 +800,3 @@ SRX_API int srx_dense_search_u8(int32_t device, const uint8_t *corpus, const flo
     return dense_rows_search("srx_dense_search_u8", device, corpus, corpus_scales, n_docs, dim, queries, nq, k, doc_base, out_doc,
                              out_score, out_count, workspace, workspace_bytes, stream_v, 0.0f);
 }
-
-namespace {
-int dense_rows_search(const char *who, int32_t device, const void *rows, const float *u8_scale_min, int64_t n_docs, int32_t dim,
-                      const float *queries, int32_t nq, int32_t k, int64_t doc_base, int32_t *out_doc, float *out_score,
-                      int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v, float score_offset) {
-    const float *emb = (const float *)rows;
-    if (nq < 0 || n_docs <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "%s: need n_docs > 0, 1 <= k <= 1024", who);
-    if (dim <= 0 || dim % 64 != 0 || dim > 64 * F32_MAXS)
-        return fail(SRX_ERR_INVALID, "%s: dim must be a multiple of 64, <= 1024 (pad the rows with zeros)", who);
-    if (doc_base < 0 || doc_base + n_docs >= 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: doc_base + n_docs must fit int32", who);
-    if (nq == 0) return SRX_OK;
-    if (!emb || !queries || !out_doc || !out_score || !out_count) return fail(SRX_ERR_INVALID, "%s: null pointer", who);
-    const int64_t need = srx_dense_f32_workspace_bytes(nq, n_docs, k);
-    if (!workspace || workspace_bytes < need) return fail(SRX_ERR_NOMEM, "%s: workspace too small", who);
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const int64_t ld = (n_docs + 63) / 64 * 64;
-    const int ns = dense_splits(n_docs, F32_QP, k);
-    float *scores = (float *)workspace;
-    int32_t *cand_doc = (int32_t *)(scores + (int64_t)F32_QP * ld);
-    float *cand_score = (float *)(cand_doc + (int64_t)F32_QP * ns * k);
-    int32_t *cand_count = (int32_t *)(cand_score + (int64_t)F32_QP * ns * k);
-    int64_t blocks = (n_docs + WAVES - 1) / WAVES;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    for (int q0 = 0; q0 < nq; q0 += F32_QP) {
-        const int qb = nq - q0 < F32_QP ? nq - q0 : F32_QP;
-        if (u8_scale_min == nullptr)
-            hipLaunchKernelGGL(srx_dense_f32_scores_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, emb, n_docs, (int)dim,
-                               queries + (int64_t)q0 * dim, qb, scores, ld, score_offset);
-        else
-            hipLaunchKernelGGL(srx_dense_u8_scores_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, (const uint8_t *)rows,
-                               u8_scale_min, n_docs, (int)dim, queries + (int64_t)q0 * dim, qb, scores, ld);
-        hipLaunchKernelGGL(srx_dense_topk_kernel, dim3((unsigned)((int64_t)qb * ns)), dim3(THREADS), 0, stream, scores, ld, n_docs, qb, k,
-                           ns, doc_base, 0, (const int32_t *)nullptr, (const int *)nullptr, 0, (const int *)nullptr, 0,
-                           (const int *)nullptr, cand_doc, cand_score, cand_count, (unsigned *)nullptr, 0);
-        HIP_TRY(hipGetLastError());
-        const int rc = srx_merge_impl(device, cand_doc, cand_score, cand_count, qb, ns, k, 0, (int64_t)k, (int64_t)1,
-                                  out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k, out_count + q0, (int64_t)k, (int64_t)1,
-                                  nullptr, 0, stream_v);
-        if (rc != SRX_OK) return rc;
-    }
-    return SRX_OK;
-}
-}  // namespace

@@ -161,19 +161,17 @@ __global__ __launch_bounds__(THREADS) void srx_merge_kernel(const int32_t *__res
 
 // The last merge level: `lists` lists per query -> the ranked final rows of queries [q0, nq).  One wavefront per query
 // when the candidates fit it, else one workgroup (lists * k <= 4096: the callers' tree levels / plan see to that).
-int srx_launch_final_merge(const int32_t *in_doc, const float *in_score, const int32_t *in_count, int nq, int lists, int k,
-                           int lay, int64_t row_stride, int64_t cnt_stride, int64_t doc_base, int32_t *out_doc,
-                           float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, const int *gate, int q0,
-                           int skip_final, bool force_block, hipStream_t stream) {
+int srx_launch_final_merge(const srx_const_rows &in, int nq, int lists, int k, int lay, int64_t doc_base, const srx_rows &out,
+                           const int *gate, int q0, int skip_final, bool force_block, hipStream_t stream) {
     const int n = nq - q0;
     if (k <= W_KMAX && (int64_t)lists * k <= MW_CAP && lists <= 256 && !force_block)
-        hipLaunchKernelGGL(srx_merge_wave_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(THREADS), 0, stream, in_doc,
-                           in_score, in_count, nq, lists, k, lay, row_stride, cnt_stride, doc_base, out_doc, out_score,
-                           out_count, ors, ocs, gate, q0, skip_final);
+        hipLaunchKernelGGL(srx_merge_wave_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(THREADS), 0, stream, in.doc,
+                           in.score, in.count, nq, lists, k, lay, in.row_stride, in.cnt_stride, doc_base, out.doc, out.score,
+                           out.count, out.row_stride, out.cnt_stride, gate, q0, skip_final);
     else
-        hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)n), dim3(THREADS), 0, stream, in_doc, in_score, in_count, nq,
-                           lists, k, lists, 1, 1, lay, row_stride, cnt_stride, doc_base, out_doc, out_score, out_count, ors,
-                           ocs, gate, q0, skip_final);
+        hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)n), dim3(THREADS), 0, stream, in.doc, in.score, in.count, nq,
+                           lists, k, lists, 1, 1, lay, in.row_stride, in.cnt_stride, doc_base, out.doc, out.score, out.count,
+                           out.row_stride, out.cnt_stride, gate, q0, skip_final);
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }
@@ -187,13 +185,11 @@ SRX_API int64_t srx_merge_workspace_bytes(int32_t nq, int32_t n_lists, int32_t k
     return 2 * ((int64_t)nq * g * k * 8 + (int64_t)nq * g * 4 + 256);
 }
 
-int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count, int32_t nq,
-                   int32_t n_lists, int32_t k, int lay, int64_t row_stride, int64_t cnt_stride, int32_t *out_doc,
-                   float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, void *workspace, int64_t workspace_bytes,
-                   void *stream_v, const int *gate, int skip_marked) {
+int srx_merge_impl(int32_t device, const srx_const_rows &in, int32_t nq, int32_t n_lists, int32_t k, int lay, const srx_rows &out,
+                   void *workspace, int64_t workspace_bytes, void *stream_v, const int *gate, int skip_marked) {
     if (nq < 0 || n_lists <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_merge_topk: bad argument%s");
     if (nq == 0) return SRX_OK;
-    if (!in_doc || !in_score || !in_count || !out_doc || !out_score || !out_count)
+    if (!in.doc || !in.score || !in.count || !out.doc || !out.score || !out.count)
         return fail(SRX_ERR_INVALID, "srx_merge_topk: null pointer%s");
     const int64_t need = srx_merge_workspace_bytes(nq, n_lists, k);
     if (skip_marked && (lay != 0 || need > 0)) return fail(SRX_ERR_INVALID, "srx_merge_topk: marked rows need the plain layout and a single pass%s");
@@ -201,56 +197,44 @@ int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score,
     HIP_TRY(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_v;
     const int fan = (MERGE_NPT * THREADS) / k;
-    const int32_t *cur_doc = in_doc;
-    const float *cur_score = in_score;
-    const int32_t *cur_count = in_count;
-    int lists = n_lists;
-    int level = 0;
+    srx_const_rows cur = in;
+    int lists = n_lists, level = 0;
     const int64_t half = need / 2;
     while (lists > fan) {  // tree levels: groups of `fan` lists -> one unordered list each (plain layout)
         const int groups = (lists + fan - 1) / fan;
-        char *buf = (char *)workspace + (level & 1) * half;
-        int32_t *od = (int32_t *)buf;
+        int32_t *od = (int32_t *)((char *)workspace + (level & 1) * half);
         float *os = (float *)(od + (int64_t)nq * groups * k);
-        int32_t *oc = (int32_t *)(os + (int64_t)nq * groups * k);
-        hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)((int64_t)nq * groups)), dim3(THREADS), 0, stream, cur_doc,
-                           cur_score, cur_count, nq, lists, k, fan, groups, 0, lay, row_stride, cnt_stride, (int64_t)0, od, os,
-                           oc, (int64_t)k, (int64_t)1, gate, 0, 0);
+        const srx_rows lvl = srx_plain_rows(od, os, (int32_t *)(os + (int64_t)nq * groups * k), k);
+        hipLaunchKernelGGL(srx_merge_kernel, dim3((unsigned)((int64_t)nq * groups)), dim3(THREADS), 0, stream, cur.doc, cur.score,
+                           cur.count, nq, lists, k, fan, groups, 0, lay, cur.row_stride, cur.cnt_stride, (int64_t)0, lvl.doc,
+                           lvl.score, lvl.count, lvl.row_stride, lvl.cnt_stride, gate, 0, 0);
         HIP_TRY(hipGetLastError());
         lay = 0;
-        row_stride = k;
-        cnt_stride = 1;
-        cur_doc = od;
-        cur_score = os;
-        cur_count = oc;
+        cur = lvl;
         lists = groups;
         ++level;
     }
-    return srx_launch_final_merge(cur_doc, cur_score, cur_count, nq, lists, k, lay, row_stride, cnt_stride, (int64_t)0, out_doc,
-                                  out_score, out_count, ors, ocs, gate, 0, skip_marked, false, stream);
+    return srx_launch_final_merge(cur, nq, lists, k, lay, (int64_t)0, out, gate, 0, skip_marked, false, stream);
 }
 
 SRX_API int srx_merge_topk(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count,
                            int32_t nq, int32_t n_lists, int32_t k, int32_t gathered, int32_t *out_doc, float *out_score,
                            int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v) {
-    return srx_merge_impl(device, in_doc, in_score, in_count, nq, n_lists, k, gathered ? 1 : 0, (int64_t)k, (int64_t)1, out_doc,
-                      out_score, out_count, (int64_t)k, (int64_t)1, workspace, workspace_bytes, stream_v, nullptr);
+    return srx_merge_impl(device, srx_plain_rows(in_doc, in_score, in_count, k), nq, n_lists, k, gathered ? 1 : 0,
+                          srx_plain_rows(out_doc, out_score, out_count, k), workspace, workspace_bytes, stream_v);
 }
 
 SRX_API int srx_merge_topk_packed(int32_t device, const int32_t *packed, int32_t nq, int32_t n_lists, int32_t k,
                                   int32_t *out_doc, float *out_score, int32_t *out_count, void *workspace,
                                   int64_t workspace_bytes, void *stream_v) {
     if (!packed || k <= 0) return fail(SRX_ERR_INVALID, "srx_merge_topk_packed: bad argument%s");
-    const int64_t row = 2 * (int64_t)k + 1;  // [k doc ids][k score bit patterns][count]
-    return srx_merge_impl(device, packed, reinterpret_cast<const float *>(packed + k), packed + 2 * k, nq, n_lists, k, 1, row, row,
-                      out_doc, out_score, out_count, (int64_t)k, (int64_t)1, workspace, workspace_bytes, stream_v, nullptr);
+    return srx_merge_impl(device, srx_packed_rows<const float>(packed, k), nq, n_lists, k, 1, srx_plain_rows(out_doc, out_score, out_count, k),
+                          workspace, workspace_bytes, stream_v);
 }
 
 SRX_API int srx_merge_topk_packed_out(int32_t device, const int32_t *packed, int32_t nq, int32_t n_lists, int32_t k,
                                       int32_t *out_packed, void *workspace, int64_t workspace_bytes, void *stream_v) {
     if (!packed || !out_packed || k <= 0) return fail(SRX_ERR_INVALID, "srx_merge_topk_packed_out: bad argument%s");
-    const int64_t row = 2 * (int64_t)k + 1;
-    return srx_merge_impl(device, packed, reinterpret_cast<const float *>(packed + k), packed + 2 * k, nq, n_lists, k, 1, row, row,
-                      out_packed, reinterpret_cast<float *>(out_packed + k), out_packed + 2 * k, row, row, workspace,
-                      workspace_bytes, stream_v, nullptr);
+    return srx_merge_impl(device, srx_packed_rows<const float>(packed, k), nq, n_lists, k, 1, srx_packed_rows<float>(out_packed, k), workspace,
+                          workspace_bytes, stream_v);
 }

@@ -209,14 +209,13 @@ SRX_API int64_t srx_search_workspace_bytes(const srx_index *ix, int32_t nq, int3
 
 namespace {
 int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
-                int32_t k, int32_t *out_doc, float *out_score, int32_t *out_count, int64_t ors, int64_t ocs,
-                void *workspace, int64_t workspace_bytes, void *stream_v, const int32_t *after_doc = nullptr,
-                const float *after_score = nullptr) {
+                int32_t k, const srx_rows &out, void *workspace, int64_t workspace_bytes, void *stream_v,
+                const int32_t *after_doc = nullptr, const float *after_score = nullptr) {
     if (!ix) return fail(SRX_ERR_INVALID, "srx_search: null index%s");
     if ((after_doc == nullptr) != (after_score == nullptr)) return fail(SRX_ERR_INVALID, "srx_search_after: after_doc and after_score go together%s");
     if (nq < 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_search: need nq >= 0 and 1 <= k <= 1024%s");
     if (nq == 0) return SRX_OK;
-    if (!q_ptr || !out_doc || !out_score || !out_count) return fail(SRX_ERR_INVALID, "srx_search: null query / output pointer%s");
+    if (!q_ptr || !out.doc || !out.score || !out.count) return fail(SRX_ERR_INVALID, "srx_search: null query / output pointer%s");
     const Plan p = make_plan(ix, nq, k);
     const SearchWs w = search_ws(workspace, p, nq, k);
     if (!workspace || workspace_bytes < w.bytes) return fail(SRX_ERR_NOMEM, "srx_search: workspace too small%s");
@@ -265,8 +264,8 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
         wl.dbg = dbg | (p.tpu != ix->d.unit_tiles ? 8 : 0);  // another unit than the padded one: everything to tier 2
         wl.ovf = w.ovf; wl.ovf_words = p.ovf_words; wl.lists_per_q = p.lists_per_q; wl.work = w.work; wl.done = w.done;
         wl.cand_doc = w.cand_doc; wl.cand_score = w.cand_score; wl.cand_count = w.cand_count;
-        wl.doc_base = ix->d.doc_base; wl.out_doc = out_doc; wl.out_score = out_score; wl.out_count = out_count;
-        wl.out_row_stride = ors; wl.out_cnt_stride = ocs;
+        wl.doc_base = ix->d.doc_base; wl.out_doc = out.doc; wl.out_score = out.score; wl.out_count = out.count;
+        wl.out_row_stride = out.row_stride; wl.out_cnt_stride = out.cnt_stride;
         const int rc = srx_launch_wave_kernel(wl, ix->d.val_type, blocks, stream);
         if (rc != SRX_OK) return rc;
     }
@@ -289,8 +288,8 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
         sl.ovf = w.ovf; sl.ovf_words = p.ovf_words; sl.lists_per_q = p.lists_per_q; sl.work = w.work;
         sl.cand_doc = w.cand_doc; sl.cand_score = w.cand_score; sl.cand_count = w.cand_count;
         sl.after_doc = after_doc; sl.after_score = after_score;
-        sl.doc_base = ix->d.doc_base; sl.out_doc = out_doc; sl.out_score = out_score; sl.out_count = out_count;
-        sl.out_row_stride = ors; sl.out_cnt_stride = ocs; sl.hint = ix->d_hint;
+        sl.doc_base = ix->d.doc_base; sl.out_doc = out.doc; sl.out_score = out.score; sl.out_count = out.count;
+        sl.out_row_stride = out.row_stride; sl.out_cnt_stride = out.cnt_stride; sl.hint = ix->d_hint;
         const int rc = srx_launch_score_kernel(sl, ix->d.val_type, t2_grid, stream);
         if (rc != SRX_OK) return rc;
     }
@@ -298,9 +297,8 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
     // merge (merge.hip): only the SPLIT queries [n_whole, nq) have lists to merge (an unsplit query's final row was written
     // by tier 1 or, when it had work for tier 2, by tier 2); debug bit 256 forces the block kernel
     if (nq > p.n_whole) {
-        const int rc = srx_launch_final_merge(w.cand_doc, w.cand_score, w.cand_count, nq, p.lists_per_q, k, 0, (int64_t)k,
-                                              (int64_t)1, ix->d.doc_base, out_doc, out_score, out_count, ors, ocs, nullptr,
-                                              p.n_whole, 1, (dbg & 256) != 0, stream);
+        const int rc = srx_launch_final_merge(srx_plain_rows(w.cand_doc, w.cand_score, w.cand_count, k), nq, p.lists_per_q, k, 0,
+                                              ix->d.doc_base, out, nullptr, p.n_whole, 1, (dbg & 256) != 0, stream);
         if (rc != SRX_OK) return rc;
     }
     if (prof) {
@@ -315,7 +313,7 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
 SRX_API int srx_search(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
                        int32_t k, int32_t *out_doc, float *out_score, int32_t *out_count, void *workspace,
                        int64_t workspace_bytes, void *stream_v) {
-    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, out_doc, out_score, out_count, (int64_t)k, (int64_t)1, workspace,
+    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_plain_rows(out_doc, out_score, out_count, k), workspace,
                        workspace_bytes, stream_v);
 }
 
@@ -323,16 +321,14 @@ SRX_API int srx_search_packed(srx_index *ix, const int32_t *q_ptr, const int32_t
                               int32_t nq, int32_t k, int32_t *out_packed, void *workspace, int64_t workspace_bytes,
                               void *stream_v) {
     if (!out_packed || k <= 0) return fail(SRX_ERR_INVALID, "srx_search_packed: bad argument%s");
-    const int64_t row = 2 * (int64_t)k + 1;  // [k doc ids][k score bit patterns][count]
-    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, out_packed, reinterpret_cast<float *>(out_packed + k),
-                       out_packed + 2 * k, row, row, workspace, workspace_bytes, stream_v);
+    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_packed_rows<float>(out_packed, k), workspace, workspace_bytes, stream_v);
 }
 
 SRX_API int srx_search_after(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
                              int32_t k, const int32_t *after_doc, const float *after_score, int32_t *out_doc, float *out_score,
                              int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v) {
     if (!after_doc || !after_score) return fail(SRX_ERR_INVALID, "srx_search_after: null bound arrays%s");
-    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, out_doc, out_score, out_count, (int64_t)k, (int64_t)1, workspace,
+    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_plain_rows(out_doc, out_score, out_count, k), workspace,
                        workspace_bytes, stream_v, after_doc, after_score);
 }
 
@@ -340,9 +336,8 @@ SRX_API int srx_search_after_packed(srx_index *ix, const int32_t *q_ptr, const i
                                     int32_t nq, int32_t k, const int32_t *after_doc, const float *after_score,
                                     int32_t *out_packed, void *workspace, int64_t workspace_bytes, void *stream_v) {
     if (!out_packed || k <= 0 || !after_doc || !after_score) return fail(SRX_ERR_INVALID, "srx_search_after_packed: bad argument%s");
-    const int64_t row = 2 * (int64_t)k + 1;
-    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, out_packed, reinterpret_cast<float *>(out_packed + k),
-                       out_packed + 2 * k, row, row, workspace, workspace_bytes, stream_v, after_doc, after_score);
+    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_packed_rows<float>(out_packed, k), workspace, workspace_bytes, stream_v,
+                       after_doc, after_score);
 }
 
 SRX_API int srx_profile_read(srx_index *ix, float *h_ms4) {

@@ -772,6 +772,27 @@ struct MergeShared {
 }  // namespace
 
 // ---- host functions shared between the translation units (hidden visibility: not part of the C ABI) ----
+// Top-k lists as the merge, the search driver and the dense side pass them around: list i has its ids at doc + i * row_stride,
+// its scores at score + i * row_stride, its length at count[i * cnt_stride].  Plain rows: three arrays, k slots per list.
+// Packed rows: one block per list, [k doc ids][k score bit patterns][count].
+template <typename I, typename F>
+struct srx_rows_of {
+    I *doc;
+    F *score;
+    I *count;
+    int64_t row_stride, cnt_stride;
+    operator srx_rows_of<const I, const F>() const { return {doc, score, count, row_stride, cnt_stride}; }
+};
+using srx_rows = srx_rows_of<int32_t, float>;
+using srx_const_rows = srx_rows_of<const int32_t, const float>;  // lists that are only read
+template <typename I, typename F>
+srx_rows_of<I, F> srx_plain_rows(I *doc, F *score, I *count, int k) { return {doc, score, count, k, 1}; }
+template <typename F, typename I>  // F = float or const float, as I is
+srx_rows_of<I, F> srx_packed_rows(I *packed, int k) {
+    const int64_t row = 2 * (int64_t)k + 1;
+    return {packed, reinterpret_cast<F *>(packed + k), packed + 2 * k, row, row};
+}
+
 struct srx_wave_launch {
     IndexView ix;
     const int32_t *q_ptr, *q_term;
@@ -816,14 +837,10 @@ struct srx_score_launch {
 int srx_launch_score_kernel(const srx_score_launch &a, int val_type, unsigned grid, hipStream_t stream);
 // the last merge level (merge.hip): the `lists` lists of every query in [q0, nq) -> its ranked final row; skip_final leaves
 // a query alone whose first list has a negative count; force_block takes the workgroup kernel where one wavefront would do
-int srx_launch_final_merge(const int32_t *in_doc, const float *in_score, const int32_t *in_count, int nq, int lists, int k,
-                           int lay, int64_t row_stride, int64_t cnt_stride, int64_t doc_base, int32_t *out_doc,
-                           float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, const int *gate, int q0,
-                           int skip_final, bool force_block, hipStream_t stream);
+int srx_launch_final_merge(const srx_const_rows &in, int nq, int lists, int k, int lay, int64_t doc_base, const srx_rows &out,
+                           const int *gate, int q0, int skip_final, bool force_block, hipStream_t stream);
 // exact merge of candidate lists (merge.hip), also used by the dense side.  A negative count is an empty list.  skip_marked
 // (plain layout, n_lists * k <= 4096 only): a query whose FIRST list has a negative count is left alone instead -- its output
 // row was written by an earlier pass (the dense side's filtered pass and its fallback share one set of rows).
-int srx_merge_impl(int32_t device, const int32_t *in_doc, const float *in_score, const int32_t *in_count, int32_t nq,
-                   int32_t n_lists, int32_t k, int lay, int64_t row_stride, int64_t cnt_stride, int32_t *out_doc,
-                   float *out_score, int32_t *out_count, int64_t ors, int64_t ocs, void *workspace, int64_t workspace_bytes,
-                   void *stream_v, const int *gate = nullptr, int skip_marked = 0);
+int srx_merge_impl(int32_t device, const srx_const_rows &in, int32_t nq, int32_t n_lists, int32_t k, int lay, const srx_rows &out,
+                   void *workspace, int64_t workspace_bytes, void *stream_v, const int *gate = nullptr, int skip_marked = 0);

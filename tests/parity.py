@@ -232,7 +232,7 @@ def dense_ks_params(dim):
     """Per-instantiation constants of srx_dense_i8_filter_kernel<KS>: doc tiles per wave (DT), survivor list entries per
     wave (DENSE_CB), query tiles in LDS (NBUF), waves per workgroup (NW) and docs per workgroup."""
     ks = dim // 32
-    nw = 4  # DENSE_NW_LONG = 4 too
+    nw = 4  # dense_filter_geom: four waves at every KS
     dt = 2 if ks <= 12 else 1
     cb = 512 if ks <= 12 else (256 if ks <= 24 else 128)
     nbuf = 3 if ks <= 16 else 2

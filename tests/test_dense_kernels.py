@@ -290,6 +290,36 @@ def test_int8_tiny_corpus_k_above_n_docs(lib, n_docs):
                 _assert_rows(ix.search(q, qs, k), _oracle(q, qs, c, cs, k), f"n {n_docs} dim {dim} k {k} packed={packed}")
 
 
+# ---- INT8: a row length without an instantiation is refused, the outputs stay as they were --------------------------------------
+def test_int8_uninstantiated_ks_is_refused(lib):
+    """dim = 160 is a multiple of 32 but KS = 5 is not compiled (DenseInt8Index would pad it to 192; the C ABI does not):
+    -1 and the list of row lengths, and the three output arrays keep their sentinels.  This pins the refusal, not its place in
+    the driver: a library that enqueues the query packing before it refuses never touches the outputs either and passes too."""
+    import torch
+    dim, n_docs, nq, k = 160, 64, 1, 5
+    assert dim not in DENSE_DIMS and dim % 32 == 0
+    dev = torch.device("cuda:0")
+    c = torch.ones(lib.srx_dense_packed_bytes(n_docs, dim), dtype=torch.int8, device=dev)  # n_docs x dim in either order
+    cs = torch.ones(n_docs, dtype=torch.float32, device=dev)
+    q = torch.ones(nq * dim, dtype=torch.int8, device=dev)
+    qs = torch.ones(nq, dtype=torch.float32, device=dev)
+    ws_bytes = lib.srx_dense_workspace_bytes(nq, n_docs, k)
+    assert ws_bytes > 0
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+    for entry in ("srx_dense_search_i8", "srx_dense_search_i8_packed"):
+        od = torch.full((nq * k,), -7, dtype=torch.int32, device=dev)
+        os_ = torch.full((nq * k,), -3.5, dtype=torch.float32, device=dev)
+        oc = torch.full((nq,), -9, dtype=torch.int32, device=dev)
+        rc = getattr(lib, entry)(0, c.data_ptr(), cs.data_ptr(), n_docs, dim, q.data_ptr(), qs.data_ptr(), nq, k, DOC_BASE,
+                                 od.data_ptr(), os_.data_ptr(), oc.data_ptr(), ws.data_ptr(), ws_bytes,
+                                 torch.cuda.current_stream().cuda_stream)
+        msg = lib.srx_last_error().decode()
+        torch.cuda.synchronize()
+        assert rc == -1, entry
+        assert "dim must be 32, 64, 96, 128, 192, 256, 384, 512, 768 or 1024" in msg, (entry, msg)
+        assert (od.cpu().numpy() == -7).all() and (os_.cpu().numpy() == np.float32(-3.5)).all() and (oc.cpu().numpy() == -9).all(), entry
+
+
 # ---- srx_dense_pack_i8 against the layout of include/sparse_rx.h -------------------------------------------------------------
 def test_pack_i8_layout(lib):
     """rows[32 T + (l & 31)][32 s + 16 (l >> 5) ..] at packed + ((T dim / 32 + s) 64 + l) 16, zeros past n_rows."""

@@ -134,7 +134,7 @@ def test_symbol_is_declared_bound_and_listed():
     from sparse_rx import _capi
     assert "srx_score_docs" in _capi.SYMBOLS and "score_docs.hip" in _capi.SOURCES and len(_capi.SYMBOLS) == 35
     assert _capi.lib().srx_version() == 301
-    assert _capi.kernel_sources_sha256() == "72cb4d234173d7c1b2f1f0e12b7f521ccae5fd2436cbd4aa248332adaf8775f8"
+    assert _capi.kernel_sources_sha256() == "d39ee7393407379aac20048be2329e3fb6f908a33e58a0534a264953e80f08f9"
 
 
 # ---------------------------------------------------------------------------------------------------------------
