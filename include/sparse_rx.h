@@ -118,6 +118,19 @@ typedef struct {
 
 typedef struct srx_index srx_index;
 
+/* Debug bits of srx_search_opts.reserved: alternative paths with the same, exact results. */
+typedef enum {
+    SRX_DBG_TIER2_ONLY = 8,            /* every query through the tier-2 (block) kernel */
+    SRX_DBG_NO_TERM_BOUND = 16,        /* ignore term_bound */
+    SRX_DBG_NO_FLAT_TILES = 128,       /* no flat-tile path in tier 2 */
+    SRX_DBG_BLOCK_MERGE = 256,         /* block merge kernel only */
+    SRX_DBG_NO_WAVE_DENSE = 2048,      /* no wave-level dense tiles in tier 2 */
+    SRX_DBG_WAVE_DENSE_MASKED = 4096,  /* their masked form even on one-tile units */
+    SRX_DBG_WAVE_DENSE_GENERAL = 8192, /* their general selection */
+    SRX_DBG_ALL = SRX_DBG_TIER2_ONLY | SRX_DBG_NO_TERM_BOUND | SRX_DBG_NO_FLAT_TILES | SRX_DBG_BLOCK_MERGE | SRX_DBG_NO_WAVE_DENSE |
+                  SRX_DBG_WAVE_DENSE_MASKED | SRX_DBG_WAVE_DENSE_GENERAL
+} srx_debug_bits;
+
 /* Search-time tuning knobs; zero-initialise for defaults. */
 typedef struct {
     int32_t supertile_log2; /* docs per unit = 2^supertile_log2 (>= tile_log2); 0 = the index's unit.  Any unit other than
@@ -126,10 +139,7 @@ typedef struct {
     int32_t profile;        /* N > 0: bracket the kernels of every N-th search with hipEvents (read with srx_profile_read); an
                              * event record between two kernels costs the stream a few microseconds, so sampling keeps the
                              * timed steps close to unprofiled ones */
-    int32_t reserved;       /* debug bits: alternative paths with the same, exact results.  8 = every query through the
-                             * tier-2 (block) kernel, 16 = ignore term_bound, 128 = no flat-tile path in tier 2, 256 = block
-                             * merge kernel only, 2048 = no wave-level dense tiles, 4096 = their masked form even on one-tile
-                             * units, 8192 = their general selection.  Any other bit: SRX_ERR_INVALID. */
+    int32_t reserved;       /* an OR of srx_debug_bits.  Any other bit: SRX_ERR_INVALID. */
     int32_t unit_tiles;     /* docs per unit = unit_tiles * 2^tile_log2 (1..64, need not be a power of two); 0 = the index's.
                                Takes precedence over supertile_log2. */
 } srx_search_opts;

@@ -22,17 +22,76 @@
 
 thread_local char srx_g_err[512] = "";
 
+#define SRX_TRY(expr)                  \
+    do {                               \
+        const int rc_ = (expr);        \
+        if (rc_ != SRX_OK) return rc_; \
+    } while (0)
+
+namespace {
+// The profiler of a handle: the searches it samples are bracketed with PROF_EVENTS events each, kept in a ring of PROF_SLOTS
+// slots; read() averages the steps of the slots filled since the last read.
 constexpr int PROF_SLOTS = 256;
 constexpr int PROF_EVENTS = 4;  // start, after tier 1, after tier 2, after merge
+struct SearchProfile {
+    hipEvent_t *ev;    // PROF_SLOTS x PROF_EVENTS events, created lazily
+    hipEvent_t *cur;   // the slot of the search being issued; null: that search is not sampled
+    int n;             // profiled calls recorded since the last read (<= PROF_SLOTS, then it wraps)
+    int64_t calls;     // profiled calls ever recorded
+    int64_t searches;  // searches issued while profiling was on (every = N samples every N-th of them)
+
+    int begin(int every) {
+        cur = nullptr;
+        if (every <= 0 || (searches++ % every) != 0) return SRX_OK;
+        if (!ev) {
+            ev = new (std::nothrow) hipEvent_t[PROF_EVENTS * PROF_SLOTS];
+            if (!ev) return fail(SRX_ERR_NOMEM, "srx_search: host allocation failed%s");
+            for (int i = 0; i < PROF_EVENTS * PROF_SLOTS; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+        }
+        cur = ev + PROF_EVENTS * (int)(calls % PROF_SLOTS);
+        return SRX_OK;
+    }
+    int mark(int i, hipStream_t stream) {
+        if (cur) HIP_TRY(hipEventRecord(cur[i], stream));
+        return SRX_OK;
+    }
+    void end() {  // the sampled search was issued whole: its slot counts
+        if (!cur) return;
+        ++calls;
+        if (n < PROF_SLOTS) ++n;
+    }
+    int read(float *h_ms4) {
+        if (n == 0 || !ev) return fail(SRX_ERR_INVALID, "srx_profile_read: no profiled srx_search has run%s");
+        static constexpr int FROM[4] = {0, 1, 2, 0}, TO[4] = {1, 2, 3, 3};  // tier 1, tier 2, merge, the whole call
+        double acc[4] = {0, 0, 0, 0};
+        for (int i = 0; i < n; ++i) {
+            const hipEvent_t *e = ev + PROF_EVENTS * (int)((calls - 1 - i) % PROF_SLOTS);
+            HIP_TRY(hipEventSynchronize(e[3]));
+            for (int j = 0; j < 4; ++j) {
+                float ms = 0;
+                HIP_TRY(hipEventElapsedTime(&ms, e[FROM[j]], e[TO[j]]));
+                acc[j] += ms;
+            }
+        }
+        for (int j = 0; j < 4; ++j) h_ms4[j] = (float)(acc[j] / n);
+        const int averaged = n;
+        n = 0;
+        return averaged;
+    }
+    void destroy() {
+        if (!ev) return;
+        for (int i = 0; i < PROF_EVENTS * PROF_SLOTS; ++i) (void)hipEventDestroy(ev[i]);
+        delete[] ev;
+    }
+};
+}  // namespace
+
 struct srx_index {
     srx_index_desc d;
     srx_search_opts opts;
-    hipEvent_t *ev;   // PROF_SLOTS x PROF_EVENTS events, created lazily
-    int ev_n;         // profiled calls recorded since the last srx_profile_read (<= PROF_SLOTS, then it wraps)
-    int64_t ev_calls;
-    int64_t n_calls;  // searches issued (profile = N samples every N-th of them)
-    int *h_hint;      // pinned, device-mapped word: the tier-2 worklist length of a recent search (sizes the next tier-2 grid)
-    int *d_hint;      // its device address
+    SearchProfile prof;
+    int *h_hint;  // pinned, device-mapped word: the tier-2 worklist length of a recent search (sizes the next tier-2 grid)
+    int *d_hint;  // its device address
 };
 
 SRX_API int srx_version(void) { return SRX_VERSION; }
@@ -74,27 +133,19 @@ SRX_API int srx_index_create(const srx_index_desc *d, srx_index **out) {
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (d->device < 0 || d->device >= ndev) return fail(SRX_ERR_NODEVICE, "srx_index_create: device ordinal not visible%s");
-    srx_index *ix = new (std::nothrow) srx_index();
+    srx_index *ix = new (std::nothrow) srx_index();  // value-initialised: default options, no events, no hint
     if (!ix) return fail(SRX_ERR_NOMEM, "srx_index_create: host allocation failed%s");
     ix->d = *d;
-    memset(&ix->opts, 0, sizeof(ix->opts));
-    ix->ev = nullptr;
-    ix->ev_n = 0;
-    ix->ev_calls = 0;
-    ix->n_calls = 0;
     // 64 bytes of pinned host memory, created once with the handle (srx_search itself allocates nothing).  Not fatal when
     // it cannot be had: the tier-2 grid then always has its full size.
-    ix->h_hint = nullptr;
-    ix->d_hint = nullptr;
-    if (hipSetDevice(d->device) == hipSuccess && hipHostMalloc((void **)&ix->h_hint, 64, hipHostMallocMapped) == hipSuccess) {
-        ix->h_hint[0] = -1;  // unknown
-        if (hipHostGetDevicePointer((void **)&ix->d_hint, ix->h_hint, 0) != hipSuccess) {
-            (void)hipHostFree(ix->h_hint);
-            ix->h_hint = nullptr;
-            ix->d_hint = nullptr;
-        }
+    int *h = nullptr, *dev = nullptr;
+    const bool pinned = hipSetDevice(d->device) == hipSuccess && hipHostMalloc((void **)&h, 64, hipHostMallocMapped) == hipSuccess;
+    if (pinned && hipHostGetDevicePointer((void **)&dev, h, 0) == hipSuccess) {
+        h[0] = -1;  // unknown
+        ix->h_hint = h;
+        ix->d_hint = dev;
     } else {
-        ix->h_hint = nullptr;
+        if (pinned) (void)hipHostFree(h);
         (void)hipGetLastError();
     }
     *out = ix;
@@ -103,10 +154,7 @@ SRX_API int srx_index_create(const srx_index_desc *d, srx_index **out) {
 
 SRX_API void srx_index_destroy(srx_index *ix) {
     if (!ix) return;
-    if (ix->ev) {
-        for (int i = 0; i < PROF_EVENTS * PROF_SLOTS; ++i) (void)hipEventDestroy(ix->ev[i]);
-        delete[] ix->ev;
-    }
+    ix->prof.destroy();
     if (ix->h_hint) (void)hipHostFree(ix->h_hint);
     delete ix;
 }
@@ -117,7 +165,7 @@ SRX_API int srx_index_set_opts(srx_index *ix, const srx_search_opts *o) {
         return fail(SRX_ERR_INVALID, "srx_index_set_opts: supertile_log2 must be in [tile_log2, tile_log2+6]%s");
     if (o->unit_tiles < 0 || o->unit_tiles > MAX_TPS) return fail(SRX_ERR_INVALID, "srx_index_set_opts: unit_tiles must be in [0, 64]%s");
     if (o->target_blocks < 0) return fail(SRX_ERR_INVALID, "srx_index_set_opts: target_blocks < 0%s");
-    if (o->reserved & ~(8 | 16 | 128 | 256 | 2048 | 4096 | 8192))
+    if (o->reserved & ~SRX_DBG_ALL)
         return fail(SRX_ERR_INVALID, "srx_index_set_opts: reserved takes only the bits 8, 16, 128, 256, 2048, 4096, 8192%s");
     ix->opts = *o;
     return SRX_OK;
@@ -208,6 +256,17 @@ SRX_API int64_t srx_search_workspace_bytes(const srx_index *ix, int32_t nq, int3
 }
 
 namespace {
+// The index as the kernels see it; without the score bounds for a search-after (they assume an unrestricted top-k) or on request.
+IndexView index_view(const srx_index *ix, bool after) {
+    const srx_index_desc &d = ix->d;
+    IndexView v;
+    v.term_ptr = d.term_ptr; v.post = d.post; v.post16 = d.post16; v.tile_skip = d.tile_skip; v.idf = d.idf;
+    v.term_bound = ((ix->opts.reserved & SRX_DBG_NO_TERM_BOUND) || after) ? nullptr : d.term_bound;
+    v.n_docs = d.n_docs; v.vocab = d.vocab; v.zero_block = d.n_blocks;
+    v.tile_log2 = d.tile_log2; v.n_tiles = d.n_tiles; v.unit_tiles = d.unit_tiles;
+    return v;
+}
+
 int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
                 int32_t k, const srx_rows &out, void *workspace, int64_t workspace_bytes, void *stream_v,
                 const int32_t *after_doc = nullptr, const float *after_score = nullptr) {
@@ -217,95 +276,53 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
     if (nq == 0) return SRX_OK;
     if (!q_ptr || !out.doc || !out.score || !out.count) return fail(SRX_ERR_INVALID, "srx_search: null query / output pointer%s");
     const Plan p = make_plan(ix, nq, k);
-    const SearchWs w = search_ws(workspace, p, nq, k);
+    const SearchWs w = search_ws(workspace, p, nq, k);  // w.items work items: one per unsplit query, n_splits per split query
     if (!workspace || workspace_bytes < w.bytes) return fail(SRX_ERR_NOMEM, "srx_search: workspace too small%s");
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(ix->d.device));
     if (ix->d.post == nullptr && p.tpu != ix->d.unit_tiles)
         return fail(SRX_ERR_INVALID, "srx_search: this index keeps no canonical blocks: a unit other than the one it was built for cannot be served%s");
-    const int64_t blocks = w.items;  // work items: one per unsplit query, n_splits per split query
     if (w.lists > 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "srx_search: nq * splits overflows the grid%s");
 
-    IndexView v;
-    v.term_ptr = ix->d.term_ptr;
-    v.post = ix->d.post;
-    v.post16 = ix->d.post16;
-    v.zero_block = ix->d.n_blocks;
-    v.unit_tiles = ix->d.unit_tiles;
-    v.tile_skip = ix->d.tile_skip;
-    v.idf = ix->d.idf;
-    v.term_bound = ((ix->opts.reserved & 16) || after_score) ? nullptr : ix->d.term_bound;  // debug bit 16: ignore the score bounds
-    v.n_docs = ix->d.n_docs;
-    v.vocab = ix->d.vocab;
-    v.tile_log2 = ix->d.tile_log2;
-    v.n_tiles = ix->d.n_tiles;
-    const int dbg = ix->opts.reserved | (after_score ? 8 : 0);  // search-after: the tier-2 kernel applies the bound, it takes every query
+    // Everything goes to tier 2: by request, for a search-after (the tier-2 kernel applies the bound), and with another unit
+    // than the padded one (tier 1 needs the padded runs).
+    const bool tier2_only = (ix->opts.reserved & SRX_DBG_TIER2_ONLY) != 0 || after_score != nullptr || p.tpu != ix->d.unit_tiles;
+    srx_score_launch sl;  // one descriptor of the search: tier 1 takes sl.w, tier 2 all of it
+    srx_wave_launch &a = sl.w;
+    a.ix = index_view(ix, after_score != nullptr);
+    a.q_ptr = q_ptr; a.q_term = q_term; a.q_weight = q_weight;
+    a.nq = nq; a.k = k; a.n_splits = p.n_splits; a.n_whole = p.n_whole; a.n_super = p.n_super;
+    a.dbg = ix->opts.reserved | (tier2_only ? SRX_DBG_TIER2_ONLY : 0);
+    a.ovf = w.ovf; a.ovf_words = p.ovf_words; a.lists_per_q = p.lists_per_q; a.work = w.work; a.done = w.done;
+    a.cand_doc = w.cand_doc; a.cand_score = w.cand_score; a.cand_count = w.cand_count;
+    a.doc_base = ix->d.doc_base; a.out_doc = out.doc; a.out_score = out.score; a.out_count = out.count;
+    a.out_row_stride = out.row_stride; a.out_cnt_stride = out.cnt_stride;
+    sl.tpu = p.tpu; sl.after_doc = after_doc; sl.after_score = after_score; sl.hint = ix->d_hint;
 
-    const bool prof = ix->opts.profile > 0 && (ix->n_calls++ % ix->opts.profile) == 0;  // profile = N: every N-th call is bracketed
-    hipEvent_t *ev = nullptr;
-    if (prof) {
-        if (!ix->ev) {
-            ix->ev = new (std::nothrow) hipEvent_t[PROF_EVENTS * PROF_SLOTS];
-            if (!ix->ev) return fail(SRX_ERR_NOMEM, "srx_search: host allocation failed%s");
-            for (int i = 0; i < PROF_EVENTS * PROF_SLOTS; ++i) HIP_TRY(hipEventCreate(&ix->ev[i]));
-        }
-        ev = ix->ev + PROF_EVENTS * (int)(ix->ev_calls % PROF_SLOTS);
-    }
+    SRX_TRY(ix->prof.begin(ix->opts.profile));  // profile = N: every N-th call is bracketed
     // one small memset: the worklist length and the split queries' arrival counters (a few KB: one fill launch); every other
     // slot of the workspace is initialised by the tier-1 work item that owns it
     HIP_TRY(hipMemsetAsync(w.done, 0, (size_t)(1 + (nq - p.n_whole)) * 4, stream));
-    if (prof) HIP_TRY(hipEventRecord(ev[0], stream));
+    SRX_TRY(ix->prof.mark(0, stream));
     // tier 1: one wavefront per (query, split) (wave_kernel.hip)
-    {
-        srx_wave_launch wl;
-        wl.ix = v;
-        wl.q_ptr = q_ptr; wl.q_term = q_term; wl.q_weight = q_weight;
-        wl.nq = nq; wl.k = k; wl.n_splits = p.n_splits; wl.n_whole = p.n_whole; wl.n_super = p.n_super;
-        wl.dbg = dbg | (p.tpu != ix->d.unit_tiles ? 8 : 0);  // another unit than the padded one: everything to tier 2
-        wl.ovf = w.ovf; wl.ovf_words = p.ovf_words; wl.lists_per_q = p.lists_per_q; wl.work = w.work; wl.done = w.done;
-        wl.cand_doc = w.cand_doc; wl.cand_score = w.cand_score; wl.cand_count = w.cand_count;
-        wl.doc_base = ix->d.doc_base; wl.out_doc = out.doc; wl.out_score = out.score; wl.out_count = out.count;
-        wl.out_row_stride = out.row_stride; wl.out_cnt_stride = out.cnt_stride;
-        const int rc = srx_launch_wave_kernel(wl, ix->d.val_type, blocks, stream);
-        if (rc != SRX_OK) return rc;
-    }
-    if (prof) HIP_TRY(hipEventRecord(ev[1], stream));
+    SRX_TRY(srx_launch_wave_kernel(sl.w, ix->d.val_type, w.items, stream));
+    SRX_TRY(ix->prof.mark(1, stream));
     // tier 2 (tier2_kernel.hip): flagged units, long queries, k > 112 -- a persistent grid drains the worklist tier 1 filled.
     // Any grid size is correct; when a recent search of this index left the worklist empty (the hint word the kernel writes to
     // pinned host memory, read here without synchronisation) a small grid spares an otherwise idle launch most of its dispatch
-    // time.
-    {
-        const int dbg2 = dbg | (p.tpu != ix->d.unit_tiles ? 8 : 0);
-        const bool t2_everything = (dbg2 & 8) != 0 || k > W1_KMAX || ix->d.post16 == nullptr;  // tier 1 serves nothing: full grid
-        const int hint = ix->h_hint ? *(volatile int *)ix->h_hint : -1;
-        const int64_t t2_full = blocks < 1024 ? blocks : 1024;
-        const unsigned t2_grid = (unsigned)((hint == 0 && !t2_everything && t2_full > 128) ? 128 : t2_full);
-        srx_score_launch sl;
-        sl.ix = v;
-        sl.q_ptr = q_ptr; sl.q_term = q_term; sl.q_weight = q_weight;
-        sl.nq = nq; sl.k = k; sl.n_splits = p.n_splits; sl.n_whole = p.n_whole; sl.tpu = p.tpu; sl.n_super = p.n_super;
-        sl.dbg = dbg2;
-        sl.ovf = w.ovf; sl.ovf_words = p.ovf_words; sl.lists_per_q = p.lists_per_q; sl.work = w.work;
-        sl.cand_doc = w.cand_doc; sl.cand_score = w.cand_score; sl.cand_count = w.cand_count;
-        sl.after_doc = after_doc; sl.after_score = after_score;
-        sl.doc_base = ix->d.doc_base; sl.out_doc = out.doc; sl.out_score = out.score; sl.out_count = out.count;
-        sl.out_row_stride = out.row_stride; sl.out_cnt_stride = out.cnt_stride; sl.hint = ix->d_hint;
-        const int rc = srx_launch_score_kernel(sl, ix->d.val_type, t2_grid, stream);
-        if (rc != SRX_OK) return rc;
-    }
-    if (prof) HIP_TRY(hipEventRecord(ev[2], stream));
+    // time -- unless tier 1 serves nothing: full grid.
+    const int hint = ix->h_hint ? *(volatile int *)ix->h_hint : -1;
+    const int64_t t2_full = w.items < 1024 ? w.items : 1024;
+    const bool t2_small = hint == 0 && t2_full > 128 && !tier1_serves_nothing(a.ix, k, p.tpu, a.dbg);
+    SRX_TRY(srx_launch_score_kernel(sl, ix->d.val_type, (unsigned)(t2_small ? 128 : t2_full), stream));
+    SRX_TRY(ix->prof.mark(2, stream));
     // merge (merge.hip): only the SPLIT queries [n_whole, nq) have lists to merge (an unsplit query's final row was written
-    // by tier 1 or, when it had work for tier 2, by tier 2); debug bit 256 forces the block kernel
-    if (nq > p.n_whole) {
-        const int rc = srx_launch_final_merge(srx_plain_rows(w.cand_doc, w.cand_score, w.cand_count, k), nq, p.lists_per_q, k, 0,
-                                              ix->d.doc_base, out, nullptr, p.n_whole, 1, (dbg & 256) != 0, stream);
-        if (rc != SRX_OK) return rc;
-    }
-    if (prof) {
-        HIP_TRY(hipEventRecord(ev[3], stream));
-        ++ix->ev_calls;
-        if (ix->ev_n < PROF_SLOTS) ++ix->ev_n;
-    }
+    // by tier 1 or, when it had work for tier 2, by tier 2)
+    if (nq > p.n_whole)
+        SRX_TRY(srx_launch_final_merge(srx_plain_rows(w.cand_doc, w.cand_score, w.cand_count, k), nq, p.lists_per_q, k, 0, ix->d.doc_base,
+                                       out, nullptr, p.n_whole, 1, (a.dbg & SRX_DBG_BLOCK_MERGE) != 0, stream));
+    SRX_TRY(ix->prof.mark(3, stream));
+    ix->prof.end();
     return SRX_OK;
 }
 }  // namespace
@@ -342,26 +359,7 @@ SRX_API int srx_search_after_packed(srx_index *ix, const int32_t *q_ptr, const i
 
 SRX_API int srx_profile_read(srx_index *ix, float *h_ms4) {
     if (!ix || !h_ms4) return fail(SRX_ERR_INVALID, "srx_profile_read: null argument%s");
-    if (ix->ev_n == 0 || !ix->ev) return fail(SRX_ERR_INVALID, "srx_profile_read: no profiled srx_search has run%s");
-    double acc[4] = {0, 0, 0, 0};
-    for (int i = 0; i < ix->ev_n; ++i) {
-        const int slot = (int)((ix->ev_calls - 1 - i) % PROF_SLOTS);
-        hipEvent_t *ev = ix->ev + PROF_EVENTS * slot;
-        float a = 0, b = 0, c = 0, d = 0;
-        HIP_TRY(hipEventSynchronize(ev[3]));
-        HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
-        HIP_TRY(hipEventElapsedTime(&c, ev[2], ev[3]));
-        HIP_TRY(hipEventElapsedTime(&d, ev[0], ev[3]));
-        acc[0] += a;
-        acc[1] += b;
-        acc[2] += c;
-        acc[3] += d;
-    }
-    for (int j = 0; j < 4; ++j) h_ms4[j] = (float)(acc[j] / ix->ev_n);
-    const int n = ix->ev_n;
-    ix->ev_n = 0;
-    return n;
+    return ix->prof.read(h_ms4);
 }
 
 SRX_API int srx_memcpy_async(void *dst, const void *src, int64_t bytes, void *stream_v) {

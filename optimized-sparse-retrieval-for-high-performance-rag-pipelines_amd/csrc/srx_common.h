@@ -483,10 +483,13 @@ __device__ __forceinline__ void load_block(const int32_t *blk, __half, int (&d)[
 
 // The one rule both tiers apply: tier 1 (wave_kernel.hip) serves a query of nt > 0 terms iff this is false; tier 2
 // (tier2_kernel.hip) then takes the whole query instead of the flagged units only.
-__device__ __forceinline__ bool tier1_cannot_serve(const IndexView &ix, int nt, int k, int tpu, int dbg) {
-    return nt > W_MAXT || k > W1_KMAX || (tpu << ix.tile_log2) > W_UNIT_MAX_DOCS || ix.post16 == nullptr || (dbg & 8) != 0 ||
+__host__ __device__ __forceinline__ bool tier1_cannot_serve(const IndexView &ix, int nt, int k, int tpu, int dbg) {
+    return nt > W_MAXT || k > W1_KMAX || (tpu << ix.tile_log2) > W_UNIT_MAX_DOCS || ix.post16 == nullptr || (dbg & SRX_DBG_TIER2_ONLY) != 0 ||
            ix.vocab * (int64_t)(ix.n_tiles + 1) >= (1ll << 30);  // tier 1 addresses the skip table with 32-bit byte offsets
 }
+// The rule without its one clause about the query (nt = 0 passes it): true when tier 1 serves no query of the search at all.
+// The driver sizes the tier-2 grid by it.
+__host__ __forceinline__ bool tier1_serves_nothing(const IndexView &ix, int k, int tpu, int dbg) { return tier1_cannot_serve(ix, 0, k, tpu, dbg); }
 
 // one block of the compact copy: 4 unit-local docs + 4 values
 __device__ __forceinline__ void load_block16(const int32_t *blk, float, int (&d)[4], float (&v)[4]) {
@@ -813,26 +816,14 @@ struct srx_wave_launch {
 };
 // tier 1 (wave_kernel.hip): one wavefront per (query, split); `blocks` work items
 int srx_launch_wave_kernel(const srx_wave_launch &a, int val_type, int64_t blocks, hipStream_t stream);
-// tier 2 (tier2_kernel.hip): the parameters of srx_score_kernel; `grid` persistent workgroups drain the worklist `work`
+// tier 2 (tier2_kernel.hip): tier 1's descriptor of the same search (out_*: the final rows of the queries that are one work
+// item) plus what only srx_score_kernel takes; `grid` persistent workgroups drain the worklist `w.work`
 struct srx_score_launch {
-    IndexView ix;
-    const int32_t *q_ptr, *q_term;
-    const float *q_weight;
-    int nq, k, n_splits, n_whole, tpu, n_super, dbg;
-    const unsigned *ovf;
-    int ovf_words, lists_per_q;
-    const int *work;
-    int32_t *cand_doc;
-    float *cand_score;
-    int32_t *cand_count;
+    srx_wave_launch w;
+    int tpu;                   // tiles per unit of this search (tier 1 only ever runs on the index's own)
     const int32_t *after_doc;  // srx_search_after's bounds (both null: a plain search)
     const float *after_score;
-    int64_t doc_base;
-    int32_t *out_doc;    // final rows of the queries that are one work item
-    float *out_score;
-    int32_t *out_count;
-    int64_t out_row_stride, out_cnt_stride;
-    int *hint;           // device address of the pinned word that receives the worklist length (may be null)
+    int *hint;                 // device address of the pinned word that receives the worklist length (may be null)
 };
 int srx_launch_score_kernel(const srx_score_launch &a, int val_type, unsigned grid, hipStream_t stream);
 // the last merge level (merge.hip): the `lists` lists of every query in [q0, nq) -> its ranked final row; skip_final leaves

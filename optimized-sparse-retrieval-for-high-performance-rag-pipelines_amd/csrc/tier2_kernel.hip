@@ -928,7 +928,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
             S.m_qw[tid] = q_weight[t0 + tid];
         }
         // wave-level dense path (tiles of <= 4096 docs, <= 64 terms): lane i of EVERY wave carries term i
-        const bool wave_dense = (4 << ix.tile_log2) <= TBL_WORDS && nt <= 64 && !(dbg & 2048);
+        const bool wave_dense = (4 << ix.tile_log2) <= TBL_WORDS && nt <= 64 && !(dbg & SRX_DBG_NO_WAVE_DENSE);
         int64_t wbase = 0;
         const int32_t *wskip = ix.tile_skip;
         float w_idf = 0.f, w_qw = 0.f;
@@ -940,7 +940,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
             w_qw = q_weight[t0 + (tid & 63)];
         }
         // one-tile units + finite weights: the unmasked form (see wave_dense_accumulate)
-        const bool wd_aligned = ix.unit_tiles == 1 && !nonfinite && !(dbg & 4096);
+        const bool wd_aligned = ix.unit_tiles == 1 && !nonfinite && !(dbg & SRX_DBG_WAVE_DENSE_MASKED);
         auto dense_quads = [&](int ja, int jb) {  // tiles [ja, jb): four at a time, one per wave, no block barriers inside
             // my term's run boundaries of the NEXT group's tile are loaded while this group is accumulated (a dependent
             // load at the top of every group exposed one memory round trip per four tiles); clamped index, no branch
@@ -959,7 +959,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                     wave_dense_accumulate<VT, false, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + a, b - a, w_idf, w_qw);
                 const int n_old = (int)S.tk.count;  // stable here: nothing appends before the barrier
                 __syncthreads();
-                dense_tile_select<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES, (dbg & 8192) ? -1 : n_old, OVF_CAP);
+                dense_tile_select<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES, (dbg & SRX_DBG_WAVE_DENSE_GENERAL) ? -1 : n_old, OVF_CAP);
             }
             if (S.tk.count > (unsigned)KMAX)  // uniform (stable since the last barrier): the overflow area goes back to its owners
                 list_compact_select(S, k, S.tk.count, reinterpret_cast<unsigned *>(S.m_start), reinterpret_cast<int *>(S.m_start) + OVF_CAP);
@@ -981,7 +981,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
             const int my_len = hi - lo;
             const unsigned P = block_sum((unsigned)my_len, S.tk.red);
             // many-term queries on a one-tile unit: all terms at once (flat_tile) instead of term by term
-            const bool flat_ok = tps == 1 && nt >= FLAT_MIN_TERMS && P > 0 && P <= (unsigned)FLAT_CAP && !(dbg & 128);
+            const bool flat_ok = tps == 1 && nt >= FLAT_MIN_TERMS && P > 0 && P <= (unsigned)FLAT_CAP && !(dbg & SRX_DBG_NO_FLAT_TILES);
             bool served = false;
             if (flat_ok) {
                 if (tid < nt) {
@@ -1057,7 +1057,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                     } else {  // one dense tile (gb == ga + 1 by construction)
                         const int tile_base = ga << ix.tile_log2;
                         dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, true, (su * tps) << ix.tile_log2);
-                        dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & 8192) ? -1 : n_old, 0);  // m_start / m_len are live: no overflow area
+                        dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & SRX_DBG_WAVE_DENSE_GENERAL) ? -1 : n_old, 0);  // m_start / m_len are live: no overflow area
                         for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;  // back to hash mode
                         __syncthreads();
                     }
@@ -1087,7 +1087,7 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
                 __syncthreads();
                 dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, pass == 0, ((j / ix.unit_tiles) * ix.unit_tiles) << ix.tile_log2);
             }
-            dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & 8192) ? -1 : n_old, 0);
+            dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & SRX_DBG_WAVE_DENSE_GENERAL) ? -1 : n_old, 0);
         }
     }
 
@@ -1158,14 +1158,15 @@ __global__ __launch_bounds__(THREADS, 2) void srx_score_kernel(IndexView ix, con
 // instances are first named in decides which helpers the compiler inlines, so it is part of the generated code.
 int srx_launch_score_kernel(const srx_score_launch &a, int val_type, unsigned grid, hipStream_t stream) {
     Tier2Final fin;
-    fin.out_doc = a.out_doc; fin.out_score = a.out_score; fin.out_count = a.out_count;
-    fin.ors = a.out_row_stride; fin.ocs = a.out_cnt_stride; fin.hint = a.hint;
-#define SRX_LAUNCH_T2(VT, AFTER, CP)                                                                                             \
-    hipLaunchKernelGGL((srx_score_kernel<VT, AFTER, CP>), dim3(grid), dim3(THREADS), 0, stream, a.ix, a.q_ptr, a.q_term,         \
-                       a.q_weight, a.nq, a.k, a.n_splits, a.n_whole, a.tpu, a.n_super, a.dbg, a.ovf, a.ovf_words, a.lists_per_q, \
-                       a.work, a.cand_doc, a.cand_score, a.cand_count, a.after_doc, a.after_score, a.doc_base, fin)
+    fin.out_doc = a.w.out_doc; fin.out_score = a.w.out_score; fin.out_count = a.w.out_count;
+    fin.ors = a.w.out_row_stride; fin.ocs = a.w.out_cnt_stride; fin.hint = a.hint;
+#define SRX_LAUNCH_T2(VT, AFTER, CP)                                                                                                \
+    hipLaunchKernelGGL((srx_score_kernel<VT, AFTER, CP>), dim3(grid), dim3(THREADS), 0, stream, a.w.ix, a.w.q_ptr, a.w.q_term,      \
+                       a.w.q_weight, a.w.nq, a.w.k, a.w.n_splits, a.w.n_whole, a.tpu, a.w.n_super, a.w.dbg, a.w.ovf, a.w.ovf_words, \
+                       a.w.lists_per_q, a.w.work, a.w.cand_doc, a.w.cand_score, a.w.cand_count, a.after_doc, a.after_score,         \
+                       a.w.doc_base, fin)
     const bool after = a.after_score != nullptr;
-    const bool cp = a.ix.post == nullptr;  // no canonical blocks: tier 2 reads the compact copy too
+    const bool cp = a.w.ix.post == nullptr;  // no canonical blocks: tier 2 reads the compact copy too
     if (val_type == SRX_VAL_F32) {
         if (after) { if (cp) SRX_LAUNCH_T2(float, true, true); else SRX_LAUNCH_T2(float, true, false); }
         else { if (cp) SRX_LAUNCH_T2(float, false, true); else SRX_LAUNCH_T2(float, false, false); }
