@@ -316,9 +316,43 @@ __device__ unsigned radix_kth(const unsigned (&key)[N], unsigned k, unsigned mx,
 }
 
 // ------------------------------------------------------------------------------------------------
+// The selection cut: the k best of a set of (score bits, doc) entries in the total order "larger score first, then
+// smaller doc".  T = the k-th largest score key; when more entries tie at T than are still needed, T2 = the need-th
+// largest tie key (0x7FFFFFFF - doc: smaller docs first) among them, otherwise 0 (every tie is kept).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned tie_key(int doc) { return 0x7FFFFFFFu - (unsigned)doc; }
+// The keys of the two selections, from an entry's (score bits, doc); key 0 = not a candidate.
+struct ScoreKeys {
+    static constexpr bool SCORE = true;
+    __device__ __forceinline__ unsigned operator()(unsigned x, int) const { return x; }
+};
+struct TieKeys {
+    static constexpr bool SCORE = false;
+    unsigned T;
+    __device__ __forceinline__ unsigned operator()(unsigned x, int doc) const { return x == T ? tie_key(doc) : 0u; }
+};
+struct TopkCut {
+    unsigned T, T2;
+    __device__ __forceinline__ bool keeps(unsigned x, int doc) const {
+        return x != 0u && (x > T || (x == T && tie_key(doc) >= T2));
+    }
+};
+// kth(keys, k, n_cand, &n_gt, &n_eq) = the exact k-th largest of keys(score bits, doc) over the caller's entries, of which
+// n_cand are candidates (tier 2: block_radix_kth_lds over keys that stay in LDS).  topk_fold and tier 1's wave_list_select
+// spell the same rule out in place.
+// Requires 1 <= k <= n_cand.  ScoreKeys::SCORE tells a caller that already knows the score keys' max / min to skip that pass.
+template <typename Kth>
+__device__ __forceinline__ TopkCut topk_cut(unsigned k, unsigned n_cand, Kth kth) {
+    unsigned n_gt, n_eq, g2, e2;
+    TopkCut cut = {kth(ScoreKeys(), k, n_cand, &n_gt, &n_eq), 0u};
+    const unsigned need = k - n_gt;  // ties to accept, 1 <= need <= n_eq
+    if (n_eq > need) cut.T2 = kth(TieKeys{cut.T}, need, n_eq, &g2, &e2);  // uniform
+    return cut;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Running top-k list of a workgroup, kept in LDS (unordered).  `tau` = key of the k-th best once a
 // selection has run (0 before): a later candidate with key < tau cannot enter.
-// Total order: larger score first, then smaller doc ("key2" = 0x7FFFFFFF - doc, larger first).
 // ------------------------------------------------------------------------------------------------
 struct TopkShared {
     unsigned bits[KMAX];
@@ -327,6 +361,12 @@ struct TopkShared {
     unsigned tau;
     unsigned red[16];
 };
+// one entry more (the caller knows there is room)
+__device__ __forceinline__ void list_push(TopkShared &tk, unsigned bits, int doc) {
+    const unsigned p = atomicAdd(&tk.count, 1u);
+    tk.bits[p] = bits;
+    tk.doc[p] = doc;
+}
 
 // Fold the candidates of one unit (register arrays ubits/udoc, ubits == 0 -> none) into the list.
 // Candidates must already satisfy ubits >= tau.  hist = RADIX_BINS words of free LDS.
@@ -377,6 +417,8 @@ __device__ void topk_fold(unsigned (&ubits)[N], const int (&udoc)[N], int k, Top
     const SumMaxMin r = block_sum_max_min(0u, lmx, lmn, tk.red);  // also orders the list reads above
     unsigned n_gt, n_eq;
     const unsigned T = radix_kth<N + KPT>(key, (unsigned)k, r.mx, r.mn, n_old + n_new, hist, tk.red, &n_gt, &n_eq);
+    // The rule of topk_cut / TopkCut::keeps, spelled out: routed through them, the five kernels that inline this function
+    // (merge, dense, fuse, term bounds) compile to different code.
     const unsigned need = (unsigned)k - n_gt;  // ties to accept, 1 <= need <= n_eq
     unsigned T2 = 0;                            // accept ties with key2 >= T2
     if (n_eq > need) {
@@ -384,7 +426,7 @@ __device__ void topk_fold(unsigned (&ubits)[N], const int (&udoc)[N], int k, Top
         unsigned mx2 = 0, mn2 = 0xFFFFFFFFu;
 #pragma unroll
         for (int n = 0; n < N + KPT; ++n) {
-            key2[n] = (key[n] == T) ? (0x7FFFFFFFu - (unsigned)doc[n]) : 0u;
+            key2[n] = (key[n] == T) ? tie_key(doc[n]) : 0u;
             if (key2[n] != 0) {
                 mx2 = max(mx2, key2[n]);
                 mn2 = min(mn2, key2[n]);
@@ -402,7 +444,7 @@ __device__ void topk_fold(unsigned (&ubits)[N], const int (&udoc)[N], int k, Top
 #pragma unroll
     for (int n = 0; n < N + KPT; ++n) {
         const unsigned x = key[n];
-        const bool take = (x > T) || (x == T && (0x7FFFFFFFu - (unsigned)doc[n]) >= T2);
+        const bool take = (x > T) || (x == T && tie_key(doc[n]) >= T2);
         if (x != 0 && take) {
             const unsigned p = atomicAdd(&tk.count, 1u);
             tk.bits[p] = x;
@@ -654,7 +696,7 @@ __device__ __noinline__ unsigned wave_list_select(SH &S, unsigned count, int k) 
     unsigned n_gt, n_eq;
     const unsigned T = wave_radix_kth([&](unsigned i) -> unsigned { return S.lbits[i]; }, count, (unsigned)k, mx, mn, count,
                                       S.hist, &n_gt, &n_eq);
-    const unsigned need = (unsigned)k - n_gt;
+    const unsigned need = (unsigned)k - n_gt;  // the rule of topk_cut / TopkCut::keeps, spelled out (tier 1's code stays as it compiles today)
     unsigned T2 = 0;
     if (n_eq > need) {  // uniform: more entries tie at T than fit -> the `need` smallest doc ids among them
         auto key2 = [&](unsigned i) -> unsigned { return S.lbits[i] == T ? 0x7FFFFFFFu - (unsigned)S.ldoc[i] : 0u; };

@@ -8,14 +8,19 @@
 // Per block: block-level LDS hash units of up to 4096 postings, a greedy tile packer, and dense fp32 accumulators acc[G]
 // in LDS for tiles whose postings exceed that (a barrier between terms keeps the summation order).  No MFMA (sparse
 // gather/reduce, HBM-bound), no float atomics (LDS ds_add_f32 serialises at ~192 cycles per wave-instruction on gfx950,
-// and sums must be deterministic).  DESIGN.md 4.2.
+// and sums must be deterministic).  The kernel takes srx_score_launch by value; score_block is the dispatch (open_item,
+// one path per unit, emit_item); its own selections are srx_common.h's topk_cut; LDS that serves two purposes has a named
+// accessor or a struct with its size assert (ScoreShared, FlatScratch).  DESIGN.md 4.2.
+
+#include <stddef.h>
 
 #include "srx_common.h"
 
 namespace {
 
-// Scoring kernel: one workgroup per (query, split of the doc range).
-// ------------------------------------------------------------------------------------------------
+// LDS of one workgroup = one (query, split of the doc range) at a time
+constexpr int RADIX8_BINS = 256;  // block_radix_kth_lds: 8-bit digits, one bin per thread
+constexpr int OVF_CAP = 384;  // entries of the append scan's overflow area ((sizeof m_start + sizeof m_len) / 8)
 struct ScoreShared {
     unsigned tbl[TBL_WORDS];  // hash keys [0,SLOTS) + vals [SLOTS,2*SLOTS)  |  dense acc[G]  |  radix hist
     TopkShared tk;
@@ -30,7 +35,20 @@ struct ScoreShared {
     int n_grp;
     unsigned ub_bits;  // srx_search_after: only candidates ranked strictly AFTER (ub_bits, ub_doc) in (score desc, doc asc)
     int ub_doc;        // order are collected; ub_bits = 0xFFFFFFFF: no bound (every score's bit pattern is below it)
+
+    // ---- areas that borrow a table while its owner is idle ----
+    // overflow area of the append scan: OVF_CAP (score bits, doc) entries on m_start / m_len (the wave-level dense path's runs travel in registers)
+    __device__ __forceinline__ unsigned *ovf_bits() { return reinterpret_cast<unsigned *>(m_start); }
+    __device__ __forceinline__ int *ovf_doc() { return reinterpret_cast<int *>(m_start) + OVF_CAP; }
+    // histogram of block_radix_kth_lds (one bin per thread) on the hash path's step table, idle during a dense selection
+    __device__ __forceinline__ unsigned *hist256() { return reinterpret_cast<unsigned *>(st_off); }
+    static_assert(MAX_STEPS >= RADIX8_BINS && RADIX8_BINS == THREADS, "radix histogram on st_off, one bin per thread");
+    // the private word a lane's masked postings are added to in the dense accumulation loops, on the same idle table
+    __device__ __forceinline__ float *dummy_word(int lane) { return reinterpret_cast<float *>(st_off) + lane; }
+    static_assert(MAX_STEPS >= 64, "dummy words on st_off: one per lane");
 };
+static_assert(offsetof(ScoreShared, m_len) == offsetof(ScoreShared, m_start) + sizeof(int64_t[MAXT]) &&
+              sizeof(int64_t[MAXT]) + sizeof(int[MAXT]) >= OVF_CAP * 2 * sizeof(unsigned), "overflow area: m_len follows m_start, both hold it");
 
 // srx_search_after's exclusive upper bound on (score bits, shard-local doc): true when the candidate ranks after it
 // AFTER = false is the instance plain searches run: the test (two LDS reads + compares wherever a candidate is formed)
@@ -40,16 +58,6 @@ __device__ __forceinline__ bool after_bound(const ScoreShared &S, unsigned b, in
     if constexpr (!AFTER) return true;
     return b < S.ub_bits || (b == S.ub_bits && doc > S.ub_doc);
 }
-
-// Where the tier-2 kernel writes FINAL rows (queries that are one work item: nothing is left for the merge kernel) and the
-// worklist length it reports back to the host (pinned word, read without synchronisation by the next call: a hint only).
-struct Tier2Final {
-    int32_t *out_doc;
-    float *out_score;
-    int32_t *out_count;
-    int64_t ors, ocs;
-    int *hint;
-};
 
 // Hash-accumulate the unit described by m_start/m_len (P <= HASH_CAP postings) and fold its positive
 // scores into the running top-k.  nt = terms in this pass.
@@ -200,7 +208,7 @@ __device__ void dense_tile_accumulate(ScoreShared &S, const IndexView &ix, int n
         // serialises NB LDS round trips per batch -- the dense tiles' main stall before).
         // Branch-free: a masked posting (doc < 0) reads and writes a private dummy word instead of an accumulator (as
         // per-posting branches the compiler emitted one exec-masked block and one LDS wait per posting).
-        float *const dummy = reinterpret_cast<float *>(S.st_off) + (tid & 63);  // the hash path's step table is idle here
+        float *const dummy = S.dummy_word(tid & 63);
         float *slot[NB];
         float acc_r[NB];
 #pragma unroll
@@ -266,19 +274,28 @@ constexpr int FLAT_SLOTS = 2048;               // doc hash slots of the grouping
 constexpr int FLAT_MPT = FLAT_MCAP / THREADS;  // 8
 constexpr int FLAT_MIN_TERMS = 12;             // below this the term-by-term paths are at least as good
 
+constexpr int FLAT_HDR = TBL_WORDS - 4 * FLAT_MCAP - 3 * FLAT_SLOTS;  // flat_tile's scratch, laid over the 64 KiB table: words before mk_key
+struct FlatScratch {
+    unsigned bm1[MAX_G / 32], bm2[MAX_G / 32];  // doc seen / doc seen twice: one bit per doc of the tile
+    int pre[MAXT + 1];                          // exclusive prefix of m_len: flat posting index -> term
+    unsigned mcount;                            // multi-term postings collected
+    unsigned pad_[FLAT_HDR - (2 * (MAX_G / 32) + MAXT + 2)];  // the header takes what the arrays below leave of the table
+    int mk_key[FLAT_MCAP];                      // the multi-term postings: (doc << 8 | term, contribution) ...
+    float mk_c[FLAT_MCAP];
+    int so_key[FLAT_MCAP];                      // ... and the same grouped by doc
+    float so_c[FLAT_MCAP];
+    int hk[FLAT_SLOTS], hcnt[FLAT_SLOTS], hoff[FLAT_SLOTS];  // doc hash of the grouping step: key, postings, first position
+};
+static_assert(sizeof(FlatScratch) == sizeof(unsigned[TBL_WORDS]) && offsetof(FlatScratch, mk_key) == FLAT_HDR * 4, "flat_tile scratch fills the table exactly");
+static_assert(2 * (MAX_G / 32) == 4 * THREADS && MAXT <= 256, "one uint4 per thread zeroes both bitmaps; mk_key / so_key pack the term into 8 bits");
+
 template <typename VT, bool AFTER, bool CP>
 __device__ bool flat_tile(ScoreShared &S, const IndexView &ix, int nt, int my_len, int tile_base, int k) {  // one-tile units: the tile IS the unit
     const int tid = threadIdx.x;
-    unsigned *bm1 = S.tbl, *bm2 = S.tbl + 512;
-    int *pre = reinterpret_cast<int *>(S.tbl + 1024);  // [nt + 1] exclusive prefix of m_len: flat posting index -> term
-    unsigned *mcount = S.tbl + 1024 + MAXT + 1;        // multi-term postings collected
-    int *mk_key = reinterpret_cast<int *>(S.tbl + 2048);
-    float *mk_c = reinterpret_cast<float *>(S.tbl + 4096);
-    int *so_key = reinterpret_cast<int *>(S.tbl + 6144);
-    float *so_c = reinterpret_cast<float *>(S.tbl + 8192);
-    int *hk = reinterpret_cast<int *>(S.tbl + 10240);
-    int *hcnt = reinterpret_cast<int *>(S.tbl + 12288);
-    int *hoff = reinterpret_cast<int *>(S.tbl + 14336);
+    FlatScratch &F = *reinterpret_cast<FlatScratch *>(S.tbl);
+    unsigned *bm1 = F.bm1, *bm2 = F.bm2, *mcount = &F.mcount;
+    int *pre = F.pre, *mk_key = F.mk_key, *so_key = F.so_key, *hk = F.hk, *hcnt = F.hcnt, *hoff = F.hoff;
+    float *mk_c = F.mk_c, *so_c = F.so_c;
     const int32_t *post = CP ? ix.post16 : ix.post;
 
     unsigned P;
@@ -288,7 +305,7 @@ __device__ bool flat_tile(ScoreShared &S, const IndexView &ix, int nt, int my_le
         pre[nt] = (int)P;
         *mcount = 0;
     }
-    reinterpret_cast<uint4 *>(S.tbl)[tid] = make_uint4(0u, 0u, 0u, 0u);  // both bitmaps: 1024 words
+    reinterpret_cast<uint4 *>(F.bm1)[tid] = make_uint4(0u, 0u, 0u, 0u);  // both bitmaps
     for (int i = tid; i < FLAT_SLOTS; i += THREADS) {
         hk[i] = EMPTY_KEY;
         hcnt[i] = 0;
@@ -509,7 +526,7 @@ __device__ void wave_dense_accumulate(ScoreShared &S, const IndexView &ix, int n
         if (valid) ++istep;
     };
     // branch-free: a masked posting / sentinel (doc < 0) goes to a private dummy word; one term's docs are distinct
-    float *const dummy = reinterpret_cast<float *>(S.st_off) + lane;
+    float *const dummy = S.dummy_word(lane);
     float *const acc0 = acc - (int)tile_base;
     auto add = [&](const Blk &b) {
         float *slot[4];
@@ -603,150 +620,136 @@ __device__ unsigned block_radix_kth_lds(KeyFn keyfn, unsigned n_items, unsigned 
 }
 
 // Running list + overflow area -> the k best, tau = the k-th best.  n_total = entries appended so far: positions
-// [0, KMAX) live in tk.bits / tk.doc, [KMAX, KMAX + OVF_CAP) in ovf_bits / ovf_doc.  Requires k <= n_total <=
-// KMAX + OVF_CAP and k <= KMAX.  Every entry is a real candidate (key >= 1).  Same tie rule as everywhere: the smaller
-// doc id wins.  Touches ~1.4 k entries instead of the tile's 16 k accumulators (dense_tile_select's general path).
-constexpr int OVF_CAP = 384;  // (sizeof m_start + sizeof m_len) / 8: those tables are idle on the wave-level dense path
-__device__ void list_compact_select(ScoreShared &S, int k, unsigned n_total, unsigned *ovf_bits, int *ovf_doc) {
+// [0, KMAX) live in tk.bits / tk.doc, [KMAX, KMAX + OVF_CAP) in the overflow area.  Requires k <= n_total <=
+// KMAX + OVF_CAP and k <= KMAX.  Every entry is a real candidate (key >= 1).  Touches ~1.4 k entries instead of the
+// tile's 16 k accumulators (dense_tile_general).
+__device__ void list_compact_select(ScoreShared &S, int k, unsigned n_total) {
     const int tid = threadIdx.x;
-    unsigned *hist = reinterpret_cast<unsigned *>(S.st_off);
-    auto key1 = [&](unsigned i) -> unsigned { return i < (unsigned)KMAX ? S.tk.bits[i] : ovf_bits[i - KMAX]; };
-    auto doc_of = [&](unsigned i) -> int { return i < (unsigned)KMAX ? S.tk.doc[i] : ovf_doc[i - KMAX]; };
+    auto key1 = [&](unsigned i) -> unsigned { return i < (unsigned)KMAX ? S.tk.bits[i] : S.ovf_bits()[i - KMAX]; };
+    auto doc_of = [&](unsigned i) -> int { return i < (unsigned)KMAX ? S.tk.doc[i] : S.ovf_doc()[i - KMAX]; };
     constexpr int IPT = (KMAX + OVF_CAP + THREADS - 1) / THREADS;  // entries per thread
     unsigned ek[IPT];
     int ed[IPT];
-    unsigned mx = 0, mn = 0xFFFFFFFFu;
 #pragma unroll
     for (int j = 0; j < IPT; ++j) {
         const unsigned i = tid + j * THREADS;
         ek[j] = i < n_total ? key1(i) : 0u;
         ed[j] = i < n_total ? doc_of(i) : 0;
-        if (ek[j] != 0u) {
-            mx = max(mx, ek[j]);
-            mn = min(mn, ek[j]);
-        }
     }
-    const SumMaxMin r1 = block_sum_max_min(0u, mx, mn, S.tk.red);
-    unsigned n_gt, n_eq;
-    const unsigned T = block_radix_kth_lds(key1, n_total, (unsigned)k, r1.mx, r1.mn, n_total, hist, S.tk.red, &n_gt, &n_eq);
-    const unsigned need = (unsigned)k - n_gt;  // ties to accept, 1 <= need <= n_eq
-    unsigned T2 = 0;                            // accept ties with 0x7FFFFFFF - doc >= T2 (smaller docs first)
-    if (n_eq > need) {
-        auto key2 = [&](unsigned i) -> unsigned { return key1(i) == T ? 0x7FFFFFFFu - (unsigned)doc_of(i) : 0u; };
-        unsigned mx2 = 0, mn2 = 0xFFFFFFFFu;
+    const TopkCut cut = topk_cut((unsigned)k, n_total, [&](auto keys, unsigned kk, unsigned n_cand, unsigned *n_gt, unsigned *n_eq) {
+        unsigned mx = 0, mn = 0xFFFFFFFFu;
 #pragma unroll
-        for (int j = 0; j < IPT; ++j)
-            if (ek[j] == T && ek[j] != 0u) {
-                const unsigned x = 0x7FFFFFFFu - (unsigned)ed[j];
-                mx2 = max(mx2, x);
-                mn2 = min(mn2, x);
+        for (int j = 0; j < IPT; ++j) {
+            const unsigned x = keys(ek[j], ed[j]);
+            if (x != 0u) {
+                mx = max(mx, x);
+                mn = min(mn, x);
             }
-        const SumMaxMin r2 = block_sum_max_min(0u, mx2, mn2, S.tk.red);
-        unsigned g2, e2;
-        T2 = block_radix_kth_lds(key2, n_total, need, r2.mx, r2.mn, n_eq, hist, S.tk.red, &g2, &e2);
-    }
+        }
+        const SumMaxMin r = block_sum_max_min(0u, mx, mn, S.tk.red);
+        return block_radix_kth_lds([&](unsigned i) -> unsigned { return keys(key1(i), doc_of(i)); }, n_total, kk, r.mx, r.mn, n_cand,
+                                   S.hist256(), S.tk.red, n_gt, n_eq);
+    });
     __syncthreads();  // every read of the old entries is done (the registers hold them)
     if (tid == 0) {
         S.tk.count = 0;
-        S.tk.tau = T;
+        S.tk.tau = cut.T;
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < IPT; ++j)
-        if (ek[j] != 0u && (ek[j] > T || (ek[j] == T && (0x7FFFFFFFu - (unsigned)ed[j]) >= T2))) {
-            const unsigned p = atomicAdd(&S.tk.count, 1u);
-            S.tk.bits[p] = ek[j];
-            S.tk.doc[p] = ed[j];
-        }
+        if (cut.keeps(ek[j], ed[j])) list_push(S.tk, ek[j], ed[j]);
     __syncthreads();
 }
 
-// Fold the positive accumulators of a dense tile into the block's running top-k.  The accumulators stay in LDS: a
-// counting pass, then either an append pass (the common case: the lazy list has room) or an exact selection over
-// (list U tile candidates) whose keys are re-read from LDS.
-// n_old_in >= 0 (the wave-level dense path; the caller read tk.count BEFORE its last barrier, and m_start / m_len are idle):
-// one scan appends the candidates to the list and, past its capacity, to an overflow area; a selection then only touches
-// those ~1.4 k entries (list_compact_select), and only when the area is full.  The caller shrinks the list back into
-// tk (dense_list_flush) before anything else reads it.
+// The append scan of a dense tile: one pass over the accumulators (G = span_tiles << tile_log2 of them, in LDS) appends
+// every candidate to the lazy list and, past its capacity KMAX, to the first ovf_cap entries of the overflow area (0 where
+// m_start / m_len are live).  n_old = tk.count as the caller read it BEFORE its last barrier.  Returns true when the tile is
+// served: no selection ran; the caller shrinks a list that reaches into the overflow area back into tk (list_compact_select)
+// before anything else reads it.  When the appends do not fit they are dropped, what was there before is shrunk to its k
+// best (tau rises) and the scan runs once more.  Still too many (a query's first tiles), or nothing to shrink: false, the
+// list is what it was (or its k best) and dense_tile_general has to serve the tile.
 template <bool AFTER>
-__device__ void dense_tile_select(ScoreShared &S, const IndexView &ix, int tile_base, int k, int span_tiles = 1, int n_old_in = -1,
-                                  int ovf_cap = 0) {
+__device__ bool dense_tile_append(ScoreShared &S, const IndexView &ix, int tile_base, int k, int span_tiles, unsigned n_old, int ovf_cap) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float *acc = reinterpret_cast<const float *>(S.tbl);
+    const int G = span_tiles << ix.tile_log2;
+    unsigned *ovf_bits = S.ovf_bits();
+    int *ovf_doc = S.ovf_doc();
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const unsigned tau_now = S.tk.tau;
+        // accumulators of docs past n_docs were zeroed and never touched: no bound check.  G / 4 is a multiple of
+        // THREADS (whole waves run every iteration); four float4 per thread are read before anything is tested
+        auto append4 = [&](int i, const float4 a4) {  // whole waves only
+            const float a[4] = {a4.x, a4.y, a4.z, a4.w};
+            bool ok[4];
+            unsigned long long m[4];
+            unsigned tot = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                ok[c] = a[c] > 0.0f && __float_as_uint(a[c]) >= tau_now && after_bound<AFTER>(S, __float_as_uint(a[c]), tile_base + 4 * i + c);
+                m[c] = __ballot(ok[c]);
+                tot += (unsigned)__popcll(m[c]);
+            }
+            if (tot == 0u) return;  // uniform
+            unsigned base = 0;      // one atomic per wave; a candidate's slot = its rank among the wave's candidates
+            if (lane == 0) base = atomicAdd(&S.tk.count, tot);
+            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (ok[c]) {
+                    const unsigned p = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m[c] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[c], 0u));
+                    if (p < (unsigned)KMAX) {
+                        S.tk.bits[p] = __float_as_uint(a[c]);
+                        S.tk.doc[p] = tile_base + 4 * i + c;
+                    } else if (p < (unsigned)(KMAX + ovf_cap)) {
+                        ovf_bits[p - KMAX] = __float_as_uint(a[c]);
+                        ovf_doc[p - KMAX] = tile_base + 4 * i + c;
+                    }
+                }
+                base += (unsigned)__popcll(m[c]);
+            }
+        };
+        // signed-int order of the bit patterns = float order for x > 0, negatives sort below: a conservative screen
+        const int tau_i = (int)max(tau_now, 1u);
+        const float4 *acc4 = reinterpret_cast<const float4 *>(acc);
+        auto imax4 = [](const float4 r) {
+            return max(max(__float_as_int(r.x), __float_as_int(r.y)), max(__float_as_int(r.z), __float_as_int(r.w)));
+        };
+        const int n4 = G / 4, n4r = (n4 + 63) & ~63;  // whole waves run every iteration (tiny tiles: n4 < 64)
+        const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        int i = tid;
+        for (; i + 3 * THREADS < n4; i += 4 * THREADS) {
+            const float4 r0 = acc4[i], r1 = acc4[i + THREADS], r2 = acc4[i + 2 * THREADS], r3 = acc4[i + 3 * THREADS];
+            const int mm = max(max(imax4(r0), imax4(r1)), max(imax4(r2), imax4(r3)));
+            // no accumulator of these 16 x 64 can enter: the common case once tau has risen
+            if (__ballot(mm >= tau_i) == 0ull) continue;
+            append4(i, r0);
+            append4(i + THREADS, r1);
+            append4(i + 2 * THREADS, r2);
+            append4(i + 3 * THREADS, r3);
+        }
+        for (; i < n4r; i += THREADS) append4(i, i < n4 ? acc4[i] : zero4);
+        __syncthreads();
+        const unsigned n_total = S.tk.count;
+        if (n_total <= (unsigned)(KMAX + ovf_cap)) return true;  // uniform.  The list stays lazy: no selection until it is full
+        __syncthreads();
+        if (tid == 0) S.tk.count = n_old;
+        __syncthreads();
+        if (n_old <= (unsigned)k) break;
+        list_compact_select(S, k, n_old);
+        n_old = (unsigned)k;
+    }
+    return false;
+}
+
+// The general selection of a dense tile: a counting pass over the accumulators, then either an append pass (the lazy list
+// has room) or the exact cut over (list U tile candidates), whose keys are re-read from LDS in every radix pass.
+template <bool AFTER>
+__device__ void dense_tile_general(ScoreShared &S, const IndexView &ix, int tile_base, int k, int span_tiles) {
     const int tid = threadIdx.x;
     const float *acc = reinterpret_cast<const float *>(S.tbl);
     const int G = span_tiles << ix.tile_log2;  // accumulators in LDS: span_tiles consecutive tiles
-    if (n_old_in >= 0) {
-        unsigned *ovf_bits = reinterpret_cast<unsigned *>(S.m_start);
-        int *ovf_doc = reinterpret_cast<int *>(ovf_bits + OVF_CAP);
-        static_assert(sizeof(S.m_start) + sizeof(S.m_len) >= OVF_CAP * 8, "overflow area");
-        const int lane = tid & 63;
-        unsigned n_old = (unsigned)n_old_in;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            const unsigned tau_now = S.tk.tau;
-            // accumulators of docs past n_docs were zeroed and never touched: no bound check.  G / 4 is a multiple of
-            // THREADS (whole waves run every iteration); four float4 per thread are read before anything is tested
-            auto append4 = [&](int i, const float4 a4) {  // whole waves only
-                const float a[4] = {a4.x, a4.y, a4.z, a4.w};
-                bool ok[4];
-                unsigned long long m[4];
-                unsigned tot = 0;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    ok[c] = a[c] > 0.0f && __float_as_uint(a[c]) >= tau_now && after_bound<AFTER>(S, __float_as_uint(a[c]), tile_base + 4 * i + c);
-                    m[c] = __ballot(ok[c]);
-                    tot += (unsigned)__popcll(m[c]);
-                }
-                if (tot == 0u) return;  // uniform
-                unsigned base = 0;      // one atomic per wave; a candidate's slot = its rank among the wave's candidates
-                if (lane == 0) base = atomicAdd(&S.tk.count, tot);
-                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (ok[c]) {
-                        const unsigned p = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m[c] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[c], 0u));
-                        if (p < (unsigned)KMAX) {
-                            S.tk.bits[p] = __float_as_uint(a[c]);
-                            S.tk.doc[p] = tile_base + 4 * i + c;
-                        } else if (p < (unsigned)(KMAX + ovf_cap)) {
-                            ovf_bits[p - KMAX] = __float_as_uint(a[c]);
-                            ovf_doc[p - KMAX] = tile_base + 4 * i + c;
-                        }
-                    }
-                    base += (unsigned)__popcll(m[c]);
-                }
-            };
-            // signed-int order of the bit patterns = float order for x > 0, negatives sort below: a conservative screen
-            const int tau_i = (int)max(tau_now, 1u);
-            const float4 *acc4 = reinterpret_cast<const float4 *>(acc);
-            auto imax4 = [](const float4 r) {
-                return max(max(__float_as_int(r.x), __float_as_int(r.y)), max(__float_as_int(r.z), __float_as_int(r.w)));
-            };
-            const int n4 = G / 4, n4r = (n4 + 63) & ~63;  // whole waves run every iteration (tiny tiles: n4 < 64)
-            const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            int i = tid;
-            for (; i + 3 * THREADS < n4; i += 4 * THREADS) {
-                const float4 r0 = acc4[i], r1 = acc4[i + THREADS], r2 = acc4[i + 2 * THREADS], r3 = acc4[i + 3 * THREADS];
-                const int mm = max(max(imax4(r0), imax4(r1)), max(imax4(r2), imax4(r3)));
-                // no accumulator of these 16 x 64 can enter: the common case once tau has risen
-                if (__ballot(mm >= tau_i) == 0ull) continue;
-                append4(i, r0);
-                append4(i + THREADS, r1);
-                append4(i + 2 * THREADS, r2);
-                append4(i + 3 * THREADS, r3);
-            }
-            for (; i < n4r; i += THREADS) append4(i, i < n4 ? acc4[i] : zero4);
-            __syncthreads();
-            const unsigned n_total = S.tk.count;
-            if (n_total <= (unsigned)(KMAX + ovf_cap)) return;  // uniform.  The list stays lazy: no selection until it is full
-            // The area is full: drop this scan's appends, shrink what was there before to the k best (tau rises) and scan
-            // again.  Still too many (a query's first tiles), or nothing to shrink: the general path below.
-            __syncthreads();
-            if (tid == 0) S.tk.count = n_old;
-            __syncthreads();
-            if (n_old <= (unsigned)k) break;
-            list_compact_select(S, k, n_old, ovf_bits, ovf_doc);
-            n_old = (unsigned)k;
-        }
-    }
     const unsigned tau = S.tk.tau;
     const unsigned n_old = S.tk.count;  // read BEFORE the barriers below
     const int n_valid = (int)min((int64_t)G, ix.n_docs - (int64_t)tile_base);  // docs of this tile that exist
@@ -770,44 +773,37 @@ __device__ void dense_tile_select(ScoreShared &S, const IndexView &ix, int tile_
     if (n_old + n_new <= (unsigned)KMAX) {  // room in the lazy list: append
         for (int o = tid; o < n_valid; o += THREADS) {
             const unsigned x = cand_key(o);
-            if (x != 0u) {
-                const unsigned p = atomicAdd(&S.tk.count, 1u);
-                S.tk.bits[p] = x;
-                S.tk.doc[p] = tile_base + o;
-            }
+            if (x != 0u) list_push(S.tk, x, tile_base + o);
         }
         __syncthreads();
         return;
     }
-    // ---- selection over (list U candidates) ----
-    unsigned *hist = reinterpret_cast<unsigned *>(S.st_off);  // 256 words: the hash path's step table is idle here
+    // ---- the cut over (list U candidates) ----
     unsigned omx = 0, omn = 0xFFFFFFFFu;
     for (unsigned i = tid; i < n_old; i += THREADS) {
         omx = max(omx, S.tk.bits[i]);
         omn = min(omn, S.tk.bits[i]);
     }
-    const SumMaxMin r1 = block_sum_max_min(0u, max(omx, r.mx), min(omn, r.mn), S.tk.red);
     const unsigned n_items = n_old + (unsigned)n_valid;
     auto key1 = [&](unsigned i) -> unsigned { return i < n_old ? S.tk.bits[i] : cand_key((int)(i - n_old)); };
     auto doc_of = [&](unsigned i) -> int { return i < n_old ? S.tk.doc[i] : tile_base + (int)(i - n_old); };
-    unsigned n_gt, n_eq;
-    const unsigned T = block_radix_kth_lds(key1, n_items, (unsigned)k, r1.mx, r1.mn, n_old + n_new, hist, S.tk.red, &n_gt, &n_eq);
-    const unsigned need = (unsigned)k - n_gt;  // ties to accept, 1 <= need <= n_eq
-    unsigned T2 = 0;                            // accept ties with 0x7FFFFFFF - doc >= T2 (smaller docs first)
-    if (n_eq > need) {
-        auto key2 = [&](unsigned i) -> unsigned { return key1(i) == T ? 0x7FFFFFFFu - (unsigned)doc_of(i) : 0u; };
-        unsigned mx2 = 0, mn2 = 0xFFFFFFFFu;
-        for (unsigned i = tid; i < n_items; i += THREADS) {
-            const unsigned x = key2(i);
-            if (x != 0u) {
-                mx2 = max(mx2, x);
-                mn2 = min(mn2, x);
+    const TopkCut cut = topk_cut((unsigned)k, n_old + n_new, [&](auto keys, unsigned kk, unsigned n_cand, unsigned *n_gt, unsigned *n_eq) {
+        auto key = [&](unsigned i) -> unsigned { return keys(key1(i), doc_of(i)); };
+        unsigned mx = max(omx, r.mx), mn = min(omn, r.mn);  // the score keys: the list's range and the counting pass's
+        if constexpr (!decltype(keys)::SCORE) {
+            mx = 0;
+            mn = 0xFFFFFFFFu;
+            for (unsigned i = tid; i < n_items; i += THREADS) {
+                const unsigned x = key(i);
+                if (x != 0u) {
+                    mx = max(mx, x);
+                    mn = min(mn, x);
+                }
             }
         }
-        const SumMaxMin r2 = block_sum_max_min(0u, mx2, mn2, S.tk.red);
-        unsigned g2, e2;
-        T2 = block_radix_kth_lds(key2, n_items, need, r2.mx, r2.mn, n_eq, hist, S.tk.red, &g2, &e2);
-    }
+        const SumMaxMin rr = block_sum_max_min(0u, mx, mn, S.tk.red);
+        return block_radix_kth_lds(key, n_items, kk, rr.mx, rr.mn, n_cand, S.hist256(), S.tk.red, n_gt, n_eq);
+    });
     // rebuild the list: the old entries first go to registers (KPT per thread), then everything that survives is appended
     unsigned okey[KPT];
     int odoc[KPT];
@@ -820,285 +816,176 @@ __device__ void dense_tile_select(ScoreShared &S, const IndexView &ix, int tile_
     __syncthreads();
     if (tid == 0) {
         S.tk.count = 0;
-        S.tk.tau = T;
+        S.tk.tau = cut.T;
     }
     __syncthreads();
-    auto keep = [&](unsigned x, int d) { return x != 0u && (x > T || (x == T && (0x7FFFFFFFu - (unsigned)d) >= T2)); };
 #pragma unroll
     for (int j = 0; j < KPT; ++j)
-        if (keep(okey[j], odoc[j])) {
-            const unsigned p = atomicAdd(&S.tk.count, 1u);
-            S.tk.bits[p] = okey[j];
-            S.tk.doc[p] = odoc[j];
-        }
+        if (cut.keeps(okey[j], odoc[j])) list_push(S.tk, okey[j], odoc[j]);
     // candidates below the OLD tau were already excluded by cand_key (tau captured above); T >= that tau
     for (int o = tid; o < n_valid; o += THREADS) {
         const unsigned x = cand_key(o);
-        if (keep(x, tile_base + o)) {
-            const unsigned p = atomicAdd(&S.tk.count, 1u);
-            S.tk.bits[p] = x;
-            S.tk.doc[p] = tile_base + o;
-        }
+        if (cut.keeps(x, tile_base + o)) list_push(S.tk, x, tile_base + o);
     }
     __syncthreads();
 }
 
 constexpr int DENSE_MIN = HASH_CAP;  // a tile with more postings than this is accumulated densely
 
-template <typename VT, bool AFTER, bool CP>
-__device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const int32_t *__restrict__ q_ptr,
-                            const int32_t *__restrict__ q_term, const float *__restrict__ q_weight, int nq, int k,
-                            int n_splits, int n_whole, int tpu, int n_super, int dbg, const unsigned *__restrict__ ovf,
-                            int ovf_words, int lists_per_q, int32_t *__restrict__ cand_doc,
-                            float *__restrict__ cand_score, int32_t *__restrict__ cand_count,
-                            const int32_t *__restrict__ after_doc, const float *__restrict__ after_score, int64_t doc_base,
-                            const Tier2Final &fin) {
-    const int tid = threadIdx.x;
-    int q, split, nsq;
-    decode_item(bid, n_whole, n_splits, q, split, nsq);
-    if (q >= nq) return;
-    const int64_t list = (int64_t)q * lists_per_q + n_splits + split;  // tier-2 lists follow the tier-1 lists
-    const int t0 = q_ptr[q];
-    const int nt_all = q_ptr[q + 1] - t0;
-    // this split's supertiles [su_lo, su_hi)
-    const int su_lo = (int)(((int64_t)n_super * split) / nsq);
-    const int su_hi = (int)(((int64_t)n_super * (split + 1)) / nsq);
-    // Tier 2 takes the whole query when tier 1 cannot serve it, otherwise only the units tier 1 flagged.
-    const bool all_units = tier1_cannot_serve(ix, nt_all, k, tpu, dbg);
-    const unsigned *my_ovf = ovf + (int64_t)bid * ovf_words;  // the flags tier 1's item of the same (query, split) left
-    bool any = all_units && nt_all > 0;
-    if (!all_units && nt_all > 0)
-        for (int wd = su_lo >> 5; wd <= (su_hi - 1) >> 5 && su_lo < su_hi; ++wd) any = any || (my_ovf[wd] != 0u);
-    if (!any) {  // uniform
-        if (tid == 0) cand_count[list] = 0;
-        return;
+// thread i < nt: term i's run in the unit that hash_unit / flat_tile / dense_tile_accumulate read after the caller's barrier
+__device__ __forceinline__ void set_runs(ScoreShared &S, int nt, int64_t start, int len) {
+    if ((int)threadIdx.x < nt) {
+        S.m_start[threadIdx.x] = start;
+        S.m_len[threadIdx.x] = len;
     }
-    const int tps = tpu;  // tiles per unit
-    const int row = ix.n_tiles + 1;
-    int *keys = reinterpret_cast<int *>(S.tbl);
+}
 
-    // initial threshold from the index's per-term score bounds (see srx_wave_kernel): exact lower bound on the
-    // k-th best score when every query idf is >= 0
-    unsigned tau0 = 0;
-    bool nonfinite = false;
-    {
-        const int col = bound_column(k);
-        unsigned t0b = 0, negf = 0;
-        for (int i = tid; i < nt_all; i += THREADS) {
-            const int term = q_term[t0 + i];
-            const float idf = ix.idf[term], qw = q_weight[t0 + i];
-            if (!(fabsf(idf) <= 3.0e38f) || !(fabsf(qw) <= 3.0e38f)) negf |= 0x10000u;  // inf / nan weight
-            if (idf < 0.0f || qw < 0.0f) {
-                negf |= 1u;
-            } else if (ix.term_bound != nullptr && col >= 0 && idf > 0.0f && qw > 0.0f) {
-                const float b = 0.0f + (ix.term_bound[(int64_t)term * 4 + col] * idf) * qw;
-                t0b = max(t0b, __float_as_uint(b > 0.0f ? b : 0.0f));
-            }
+// Back to hash mode: the key half of the table reads as empty (dense accumulators or flat_tile's scratch were there).
+__device__ __forceinline__ void hash_mode(ScoreShared &S) {
+    int *keys = reinterpret_cast<int *>(S.tbl);
+    for (int i = threadIdx.x; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;
+    __syncthreads();
+}
+
+// Opens a work item: empty list, the search-after bound, the table in hash mode, and the initial threshold from the
+// index's per-term score bounds (see srx_wave_kernel): an exact lower bound on the k-th best score when every query idf is
+// >= 0.  Returns true when a weight of the query is inf / nan.
+__device__ bool open_item(ScoreShared &S, const srx_score_launch &a, int q, int t0, int nt_all) {
+    const int tid = threadIdx.x;
+    const IndexView &ix = a.w.ix;
+    const int col = bound_column(a.w.k);
+    unsigned t0b = 0, negf = 0;
+    for (int i = tid; i < nt_all; i += THREADS) {
+        const int term = a.w.q_term[t0 + i];
+        const float idf = ix.idf[term], qw = a.w.q_weight[t0 + i];
+        if (!(fabsf(idf) <= 3.0e38f) || !(fabsf(qw) <= 3.0e38f)) negf |= 0x10000u;  // inf / nan weight
+        if (idf < 0.0f || qw < 0.0f) {
+            negf |= 1u;
+        } else if (ix.term_bound != nullptr && col >= 0 && idf > 0.0f && qw > 0.0f) {
+            const float b = 0.0f + (ix.term_bound[(int64_t)term * 4 + col] * idf) * qw;
+            t0b = max(t0b, __float_as_uint(b > 0.0f ? b : 0.0f));
         }
-        const SumMaxMin r = block_sum_max_min(negf, t0b, 0u, S.tk.red);  // sum: low half = #negative, high half = #non-finite
-        tau0 = (r.sum || after_score != nullptr) ? 0u : r.mx;  // the bounds speak of the k best of ALL docs, not of those after a row
-        nonfinite = r.sum >= 0x10000u;
     }
+    const SumMaxMin r = block_sum_max_min(negf, t0b, 0u, S.tk.red);  // sum: low half = #negative, high half = #non-finite
     if (tid == 0) {
         S.tk.count = 0;
-        S.tk.tau = tau0;
+        S.tk.tau = (r.sum || a.after_score != nullptr) ? 0u : r.mx;  // the bounds speak of the k best of ALL docs, not of those after a row
         S.ub_bits = 0xFFFFFFFFu;
         S.ub_doc = 0;
-        if (after_score != nullptr) {  // rows come back as GLOBAL ids: the bound is compared in shard-local ids
-            const int64_t d = (int64_t)after_doc[q] - doc_base;
-            S.ub_bits = __float_as_uint(fmaxf(after_score[q], 0.0f));
+        if (a.after_score != nullptr) {  // rows come back as GLOBAL ids: the bound is compared in shard-local ids
+            const int64_t d = (int64_t)a.after_doc[q] - a.w.doc_base;
+            S.ub_bits = __float_as_uint(fmaxf(a.after_score[q], 0.0f));
             S.ub_doc = d < -1 ? -1 : d > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)d;
         }
     }
-    for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;
+    hash_mode(S);
+    return r.sum >= 0x10000u;
+}
+
+// Overflow packer (a unit of several tiles with more than DENSE_MIN postings, on an index whose tiles are too large for the
+// wave-level dense path): the unit's tiles [ja, jb) are packed greedily into groups of <= DENSE_MIN postings, each a hash
+// unit; a single tile above that is accumulated densely.  Thread i < nt owns term i (base / skip_row).
+template <typename VT, bool AFTER, bool CP>
+__device__ void packed_unit(ScoreShared &S, const IndexView &ix, int nt, int k, int64_t base, const int32_t *skip_row, int ja, int jb,
+                            bool append_scan) {
+    const int tid = threadIdx.x;
+    const int nt_tiles = jb - ja;
+    for (int j = tid; j <= nt_tiles; j += THREADS) S.ptile[j] = 0;
     __syncthreads();
-
-    const int n_pass = (nt_all + MAXT - 1) / MAXT;  // 1 unless the query has > 256 distinct terms
-
-    if (n_pass == 1) {
-        // ---- thread i owns term i ----
-        const int nt = nt_all;
-        int64_t base = 0;
-        const int32_t *skip_row = ix.tile_skip;
-        if (tid < nt) {
-            const int term = q_term[t0 + tid];
-            base = ix.term_ptr[term];
-            skip_row = ix.tile_skip + (int64_t)term * row;
-            S.m_idf[tid] = ix.idf[term];
-            S.m_qw[tid] = q_weight[t0 + tid];
-        }
-        // wave-level dense path (tiles of <= 4096 docs, <= 64 terms): lane i of EVERY wave carries term i
-        const bool wave_dense = (4 << ix.tile_log2) <= TBL_WORDS && nt <= 64 && !(dbg & SRX_DBG_NO_WAVE_DENSE);
-        int64_t wbase = 0;
-        const int32_t *wskip = ix.tile_skip;
-        float w_idf = 0.f, w_qw = 0.f;
-        if (wave_dense && (tid & 63) < nt) {
-            const int term = q_term[t0 + (tid & 63)];
-            wbase = ix.term_ptr[term];
-            wskip = ix.tile_skip + (int64_t)term * row;
-            w_idf = ix.idf[term];
-            w_qw = q_weight[t0 + (tid & 63)];
-        }
-        // one-tile units + finite weights: the unmasked form (see wave_dense_accumulate)
-        const bool wd_aligned = ix.unit_tiles == 1 && !nonfinite && !(dbg & SRX_DBG_WAVE_DENSE_MASKED);
-        auto dense_quads = [&](int ja, int jb) {  // tiles [ja, jb): four at a time, one per wave, no block barriers inside
-            // my term's run boundaries of the NEXT group's tile are loaded while this group is accumulated (a dependent
-            // load at the top of every group exposed one memory round trip per four tiles); clamped index, no branch
-            const int jlast = ix.n_tiles - 1;
-            int a_n = gload_i32(wskip + min(ja + (tid >> 6), jlast)), b_n = gload_i32(wskip + min(ja + (tid >> 6), jlast) + 1);
-            for (int j0 = ja; j0 < jb; j0 += WAVES) {
-                const int j = j0 + (tid >> 6);
-                const bool has_tile = j < jb;
-                const bool mine = has_tile && (tid & 63) < nt;
-                const int a = mine ? a_n : 0, b = mine ? b_n : 0;
-                a_n = gload_i32(wskip + min(j + WAVES, jlast));
-                b_n = gload_i32(wskip + min(j + WAVES, jlast) + 1);
-                if (wd_aligned)
-                    wave_dense_accumulate<VT, true, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + a, b - a, w_idf, w_qw);
-                else
-                    wave_dense_accumulate<VT, false, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + a, b - a, w_idf, w_qw);
-                const int n_old = (int)S.tk.count;  // stable here: nothing appends before the barrier
-                __syncthreads();
-                dense_tile_select<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES, (dbg & SRX_DBG_WAVE_DENSE_GENERAL) ? -1 : n_old, OVF_CAP);
-            }
-            if (S.tk.count > (unsigned)KMAX)  // uniform (stable since the last barrier): the overflow area goes back to its owners
-                list_compact_select(S, k, S.tk.count, reinterpret_cast<unsigned *>(S.m_start), reinterpret_cast<int *>(S.m_start) + OVF_CAP);
-            for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;  // back to hash mode
-            __syncthreads();
-        };
-        if (all_units && wave_dense) {
-            // tier 2 has the whole query (k or the term count rules tier 1 out): units mean nothing here, the split's tile
-            // range goes through the wave-level dense path in full groups of four tiles
-            dense_quads(su_lo * tps, min(su_hi * tps, ix.n_tiles));
-        } else
-        for (int su = su_lo; su < su_hi; ++su) {
-            if (!all_units && !((my_ovf[su >> 5] >> (su & 31)) & 1u)) continue;  // uniform
-            int lo = 0, hi = 0;
-            if (tid < nt) {
-                lo = gload_i32(skip_row + min(su * tps, ix.n_tiles));
-                hi = gload_i32(skip_row + min((su + 1) * tps, ix.n_tiles));
-            }
-            const int my_len = hi - lo;
-            const unsigned P = block_sum((unsigned)my_len, S.tk.red);
-            // many-term queries on a one-tile unit: all terms at once (flat_tile) instead of term by term
-            const bool flat_ok = tps == 1 && nt >= FLAT_MIN_TERMS && P > 0 && P <= (unsigned)FLAT_CAP && !(dbg & SRX_DBG_NO_FLAT_TILES);
-            bool served = false;
-            if (flat_ok) {
-                if (tid < nt) {
-                    S.m_start[tid] = base + lo;
-                    S.m_len[tid] = my_len;
-                }
-                __syncthreads();
-                served = flat_tile<VT, AFTER, CP>(S, ix, nt, my_len, su << ix.tile_log2, k);
-                for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;  // back to hash mode
-                __syncthreads();
-            }
-            if (served) {
-            } else if (P > 0 && P <= (unsigned)DENSE_MIN) {
-                if (tid < nt) {
-                    S.m_start[tid] = base + lo;
-                    S.m_len[tid] = my_len;
-                }
-                __syncthreads();
-                hash_unit<VT, AFTER, CP>(S, ix, nt, my_len, k, (su * tps) << ix.tile_log2);
-            } else if (P > 0 && wave_dense) {
-                dense_quads(su * tps, min(su * tps + tps, ix.n_tiles));
-            } else if (P > 0) {
-                // ---- overflow: pack this supertile's tiles greedily into units of <= HASH_CAP postings;
-                //      a single tile above that is accumulated densely ----
-                const int ja = su * tps;
-                const int jb = min(ja + tps, ix.n_tiles);
-                const int nt_tiles = jb - ja;
-                for (int j = tid; j <= nt_tiles; j += THREADS) S.ptile[j] = 0;
-                __syncthreads();
-                if (tid < nt) {
-                    int prev = skip_row[ja];
-                    for (int j = 0; j < nt_tiles; ++j) {
-                        const int cur = skip_row[ja + j + 1];
-                        if (cur != prev) atomicAdd(&S.ptile[j], cur - prev);
-                        prev = cur;
-                    }
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    int ng = 0, acc_p = 0;
-                    S.grp[0] = 0;
-                    for (int j = 0; j < nt_tiles; ++j) {
-                        const int pj = S.ptile[j];
-                        if (acc_p > 0 && acc_p + pj > DENSE_MIN) {
-                            S.grp[++ng] = j;
-                            acc_p = 0;
-                        }
-                        acc_p += pj;
-                    }
-                    S.grp[++ng] = nt_tiles;
-                    S.n_grp = ng;
-                }
-                __syncthreads();
-                const int ng = S.n_grp;
-                for (int g = 0; g < ng; ++g) {
-                    const int ga = ja + S.grp[g], gb = ja + S.grp[g + 1];
-                    int glo = 0, ghi = 0;
-                    if (tid < nt) {
-                        glo = skip_row[ga];
-                        ghi = skip_row[gb];
-                    }
-                    const int glen = ghi - glo;
-                    const unsigned GP = block_sum((unsigned)glen, S.tk.red);
-                    if (GP == 0) continue;
-                    if (tid < nt) {
-                        S.m_start[tid] = base + glo;
-                        S.m_len[tid] = glen;
-                    }
-                    const int n_old = (int)S.tk.count;  // stable here: nothing appends before the barrier
-                    __syncthreads();
-                    if (GP <= (unsigned)DENSE_MIN) {
-                        hash_unit<VT, AFTER, CP>(S, ix, nt, glen, k, (su * tps) << ix.tile_log2);
-                    } else {  // one dense tile (gb == ga + 1 by construction)
-                        const int tile_base = ga << ix.tile_log2;
-                        dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, true, (su * tps) << ix.tile_log2);
-                        dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & SRX_DBG_WAVE_DENSE_GENERAL) ? -1 : n_old, 0);  // m_start / m_len are live: no overflow area
-                        for (int i = tid; i < SLOTS; i += THREADS) keys[i] = EMPTY_KEY;  // back to hash mode
-                        __syncthreads();
-                    }
-                }
-            }
-        }
-    } else {
-        // ---- general path (> MAXT query terms): tile by tile, dense accumulators, term passes in
-        //      ascending order so the per-doc summation order is unchanged ----
-        const int ja = su_lo * tps;
-        const int jb = min(su_hi * tps, ix.n_tiles);
-        for (int j = ja; j < jb; ++j) {
-            const int tile_base = j << ix.tile_log2;
-            const int n_old = (int)S.tk.count;  // stable: the barrier that opens every pass comes before any append
-            for (int pass = 0; pass < n_pass; ++pass) {
-                const int nt = min(MAXT, nt_all - pass * MAXT);
-                __syncthreads();
-                if (tid < nt) {
-                    const int term = q_term[t0 + pass * MAXT + tid];
-                    const int32_t *skip_row = ix.tile_skip + (int64_t)term * row;
-                    const int a = skip_row[j], b = skip_row[j + 1];
-                    S.m_start[tid] = ix.term_ptr[term] + a;
-                    S.m_len[tid] = b - a;
-                    S.m_idf[tid] = ix.idf[term];
-                    S.m_qw[tid] = q_weight[t0 + pass * MAXT + tid];
-                }
-                __syncthreads();
-                dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, pass == 0, ((j / ix.unit_tiles) * ix.unit_tiles) << ix.tile_log2);
-            }
-            dense_tile_select<AFTER>(S, ix, tile_base, k, 1, (dbg & SRX_DBG_WAVE_DENSE_GENERAL) ? -1 : n_old, 0);
+    if (tid < nt) {
+        int prev = skip_row[ja];
+        for (int j = 0; j < nt_tiles; ++j) {
+            const int cur = skip_row[ja + j + 1];
+            if (cur != prev) atomicAdd(&S.ptile[j], cur - prev);
+            prev = cur;
         }
     }
+    __syncthreads();
+    if (tid == 0) {
+        int ng = 0, acc_p = 0;
+        S.grp[0] = 0;
+        for (int j = 0; j < nt_tiles; ++j) {
+            const int pj = S.ptile[j];
+            if (acc_p > 0 && acc_p + pj > DENSE_MIN) {
+                S.grp[++ng] = j;
+                acc_p = 0;
+            }
+            acc_p += pj;
+        }
+        S.grp[++ng] = nt_tiles;
+        S.n_grp = ng;
+    }
+    __syncthreads();
+    const int ng = S.n_grp;
+    for (int g = 0; g < ng; ++g) {
+        const int ga = ja + S.grp[g], gb = ja + S.grp[g + 1];
+        int glo = 0, ghi = 0;
+        if (tid < nt) {
+            glo = skip_row[ga];
+            ghi = skip_row[gb];
+        }
+        const int glen = ghi - glo;
+        const unsigned GP = block_sum((unsigned)glen, S.tk.red);
+        if (GP == 0) continue;
+        set_runs(S, nt, base + glo, glen);
+        const unsigned n_old = S.tk.count;  // stable here: nothing appends before the barrier
+        __syncthreads();
+        if (GP <= (unsigned)DENSE_MIN) {
+            hash_unit<VT, AFTER, CP>(S, ix, nt, glen, k, ja << ix.tile_log2);
+        } else {  // one dense tile (gb == ga + 1 by construction)
+            const int tile_base = ga << ix.tile_log2;
+            dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, true, ja << ix.tile_log2);
+            // m_start / m_len are live: the append scan has no overflow area
+            if (!(append_scan && dense_tile_append<AFTER>(S, ix, tile_base, k, 1, n_old, 0))) dense_tile_general<AFTER>(S, ix, tile_base, k, 1);
+            hash_mode(S);
+        }
+    }
+}
 
-    // ---- emit this split's list (unordered; the merge kernel ranks) ----
+// Queries of more than MAXT terms: tile by tile over [ja, jb), dense accumulators, term passes in ascending order so the
+// per-doc summation order is unchanged.
+template <typename VT, bool AFTER, bool CP>
+__device__ void many_term_tiles(ScoreShared &S, const srx_score_launch &a, int t0, int nt_all, int ja, int jb, bool append_scan) {
+    const int tid = threadIdx.x;
+    const IndexView &ix = a.w.ix;
+    const int row = ix.n_tiles + 1;
+    const int n_pass = (nt_all + MAXT - 1) / MAXT;
+    for (int j = ja; j < jb; ++j) {
+        const int tile_base = j << ix.tile_log2;
+        const unsigned n_old = S.tk.count;  // stable: the barrier that opens every pass comes before any append
+        for (int pass = 0; pass < n_pass; ++pass) {
+            const int nt = min(MAXT, nt_all - pass * MAXT);
+            __syncthreads();
+            if (tid < nt) {
+                const int term = a.w.q_term[t0 + pass * MAXT + tid];
+                const int32_t *skip_row = ix.tile_skip + (int64_t)term * row;
+                const int lo = skip_row[j], hi = skip_row[j + 1];
+                set_runs(S, nt, ix.term_ptr[term] + lo, hi - lo);
+                S.m_idf[tid] = ix.idf[term];
+                S.m_qw[tid] = a.w.q_weight[t0 + pass * MAXT + tid];
+            }
+            __syncthreads();
+            dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, pass == 0, ((j / ix.unit_tiles) * ix.unit_tiles) << ix.tile_log2);
+        }
+        // m_start / m_len are live: the append scan has no overflow area
+        if (!(append_scan && dense_tile_append<AFTER>(S, ix, tile_base, a.w.k, 1, n_old, 0))) dense_tile_general<AFTER>(S, ix, tile_base, a.w.k, 1);
+    }
+}
+
+// Closes a work item: the list shrinks to its k best and goes to the split's candidate list (unordered; the merge kernel
+// ranks) -- or, for an unsplit query, straight to the final row.
+__device__ void emit_item(ScoreShared &S, const srx_score_launch &a, int q, int nsq, int64_t list) {
+    const int tid = threadIdx.x;
+    const int k = a.w.k;
+    int32_t *__restrict__ cand_doc = a.w.cand_doc, *__restrict__ cand_count = a.w.cand_count;
+    float *__restrict__ cand_score = a.w.cand_score;
     __syncthreads();
     topk_shrink(k, S.tk, S.tbl);
-    if (nsq == 1 && fin.out_doc != nullptr) {
+    if (nsq == 1 && a.w.out_doc != nullptr) {
         // An unsplit query is ONE work item: this block holds everything tier 1 did not score.  Fold tier 1's list of the
         // same query in (it was complete before this kernel started; its docs come from other units), rank, and write the
         // final row here -- the merge kernel only ever sees split queries.
-        const int64_t l1 = (int64_t)q * lists_per_q;
+        const int64_t l1 = (int64_t)q * a.w.lists_per_q;
         const int c1 = min(max(cand_count[l1], 0), k);
         const unsigned tau = S.tk.tau;  // k entries >= tau are in the list once a selection has run: nothing below can enter
         unsigned ub[KPT];
@@ -1113,8 +1000,8 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
         __syncthreads();
         topk_fold<KPT, false>(ub, ud, k, S.tk, S.tbl);
         __syncthreads();
-        block_rank_emit(S.tk, reinterpret_cast<unsigned long long *>(S.tbl), k, doc_base, fin.out_doc + (int64_t)q * fin.ors,
-                        fin.out_score + (int64_t)q * fin.ors, fin.out_count + (int64_t)q * fin.ocs);
+        block_rank_emit(S.tk, reinterpret_cast<unsigned long long *>(S.tbl), k, a.w.doc_base, a.w.out_doc + (int64_t)q * a.w.out_row_stride,
+                        a.w.out_score + (int64_t)q * a.w.out_row_stride, a.w.out_count + (int64_t)q * a.w.out_cnt_stride);
         if (tid == 0) cand_count[l1] = -1;  // final (as when tier 1 finishes a query on its own)
         return;
     }
@@ -1127,54 +1014,166 @@ __device__ void score_block(ScoreShared &S, int bid, const IndexView &ix, const 
     if (tid == 0) cand_count[list] = (int)cnt;
 }
 
-// Tier-2 kernel: a fixed grid of workgroups drains the worklist of (query, split) blocks that tier 1 could not
-// finish (flagged units, > 64 terms, k > 128).  work[0] = number of entries, work[1..] = block ids.
+// One work item = one (query, split of the doc range): which of the paths above serves which of its units.
 template <typename VT, bool AFTER, bool CP>
-__global__ __launch_bounds__(THREADS, 2) void srx_score_kernel(IndexView ix, const int32_t *__restrict__ q_ptr,
-                                                               const int32_t *__restrict__ q_term,
-                                                               const float *__restrict__ q_weight, int nq, int k,
-                                                               int n_splits, int n_whole, int tpu, int n_super, int dbg,
-                                                               const unsigned *__restrict__ ovf, int ovf_words,
-                                                               int lists_per_q, const int *__restrict__ work,
-                                                               int32_t *__restrict__ cand_doc,
-                                                               float *__restrict__ cand_score,
-                                                               int32_t *__restrict__ cand_count,
-                                                               const int32_t *__restrict__ after_doc,
-                                                               const float *__restrict__ after_score, int64_t doc_base,
-                                                               const Tier2Final fin) {
+__device__ void score_block(ScoreShared &S, int bid, const srx_score_launch &a) {
+    const int tid = threadIdx.x;
+    const IndexView &ix = a.w.ix;
+    const int32_t *__restrict__ q_term = a.w.q_term;
+    const float *__restrict__ q_weight = a.w.q_weight;
+    const int k = a.w.k, tps = a.tpu, dbg = a.w.dbg;  // tps: tiles per unit
+    int q, split, nsq;
+    decode_item(bid, a.w.n_whole, a.w.n_splits, q, split, nsq);
+    if (q >= a.w.nq) return;
+    const int64_t list = (int64_t)q * a.w.lists_per_q + a.w.n_splits + split;  // tier-2 lists follow the tier-1 lists
+    const int t0 = a.w.q_ptr[q];
+    const int nt_all = a.w.q_ptr[q + 1] - t0;
+    // this split's supertiles [su_lo, su_hi)
+    const int su_lo = (int)(((int64_t)a.w.n_super * split) / nsq);
+    const int su_hi = (int)(((int64_t)a.w.n_super * (split + 1)) / nsq);
+    // Tier 2 takes the whole query when tier 1 cannot serve it, otherwise only the units tier 1 flagged.
+    const bool all_units = tier1_cannot_serve(ix, nt_all, k, tps, dbg);
+    const unsigned *__restrict__ my_ovf = a.w.ovf + (int64_t)bid * a.w.ovf_words;  // the flags tier 1's item of the same (query, split) left
+    bool any = all_units && nt_all > 0;
+    if (!all_units && nt_all > 0)
+        for (int wd = su_lo >> 5; wd <= (su_hi - 1) >> 5 && su_lo < su_hi; ++wd) any = any || (my_ovf[wd] != 0u);
+    if (!any) {  // uniform
+        if (tid == 0) a.w.cand_count[list] = 0;
+        return;
+    }
+    const bool nonfinite = open_item(S, a, q, t0, nt_all);
+    const bool append_scan = !(dbg & SRX_DBG_WAVE_DENSE_GENERAL);  // dense tiles try the append scan before the general selection
+
+    if (nt_all > MAXT) {
+        many_term_tiles<VT, AFTER, CP>(S, a, t0, nt_all, su_lo * tps, min(su_hi * tps, ix.n_tiles), append_scan);
+        emit_item(S, a, q, nsq, list);
+        return;
+    }
+    // ---- thread i owns term i ----
+    const int nt = nt_all;
+    const int row = ix.n_tiles + 1;
+    int64_t base = 0;
+    const int32_t *skip_row = ix.tile_skip;
+    if (tid < nt) {
+        const int term = q_term[t0 + tid];
+        base = ix.term_ptr[term];
+        skip_row = ix.tile_skip + (int64_t)term * row;
+        S.m_idf[tid] = ix.idf[term];
+        S.m_qw[tid] = q_weight[t0 + tid];
+    }
+    // wave-level dense path (tiles of <= 4096 docs, <= 64 terms): lane i of EVERY wave carries term i
+    const bool wave_dense = (4 << ix.tile_log2) <= TBL_WORDS && nt <= 64 && !(dbg & SRX_DBG_NO_WAVE_DENSE);
+    int64_t wbase = 0;
+    const int32_t *wskip = ix.tile_skip;
+    float w_idf = 0.f, w_qw = 0.f;
+    if (wave_dense && (tid & 63) < nt) {
+        const int term = q_term[t0 + (tid & 63)];
+        wbase = ix.term_ptr[term];
+        wskip = ix.tile_skip + (int64_t)term * row;
+        w_idf = ix.idf[term];
+        w_qw = q_weight[t0 + (tid & 63)];
+    }
+    // one-tile units + finite weights: the unmasked form (see wave_dense_accumulate)
+    const bool wd_aligned = ix.unit_tiles == 1 && !nonfinite && !(dbg & SRX_DBG_WAVE_DENSE_MASKED);
+    auto dense_quads = [&](int ja, int jb) {  // tiles [ja, jb): four at a time, one per wave, no block barriers inside
+        // my term's run boundaries of the NEXT group's tile are loaded while this group is accumulated (a dependent
+        // load at the top of every group exposed one memory round trip per four tiles); clamped index, no branch
+        const int jlast = ix.n_tiles - 1;
+        int a_n = gload_i32(wskip + min(ja + (tid >> 6), jlast)), b_n = gload_i32(wskip + min(ja + (tid >> 6), jlast) + 1);
+        for (int j0 = ja; j0 < jb; j0 += WAVES) {
+            const int j = j0 + (tid >> 6);
+            const bool has_tile = j < jb;
+            const bool mine = has_tile && (tid & 63) < nt;
+            const int lo = mine ? a_n : 0, hi = mine ? b_n : 0;
+            a_n = gload_i32(wskip + min(j + WAVES, jlast));
+            b_n = gload_i32(wskip + min(j + WAVES, jlast) + 1);
+            if (wd_aligned)
+                wave_dense_accumulate<VT, true, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + lo, hi - lo, w_idf, w_qw);
+            else
+                wave_dense_accumulate<VT, false, CP>(S, ix, nt, (int64_t)j << ix.tile_log2, has_tile, wbase + lo, hi - lo, w_idf, w_qw);
+            const unsigned n_old = S.tk.count;  // stable here: nothing appends before the barrier
+            __syncthreads();
+            // m_start / m_len are idle on this path: the append scan has the whole overflow area
+            if (!(append_scan && dense_tile_append<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES, n_old, OVF_CAP)))
+                dense_tile_general<AFTER>(S, ix, j0 << ix.tile_log2, k, WAVES);
+        }
+        if (S.tk.count > (unsigned)KMAX) list_compact_select(S, k, S.tk.count);  // uniform (stable since the last barrier): the overflow area goes back to its owners
+        hash_mode(S);
+    };
+    if (all_units && wave_dense) {
+        // tier 2 has the whole query (k or the term count rules tier 1 out): units mean nothing here, the split's tile
+        // range goes through the wave-level dense path in full groups of four tiles
+        dense_quads(su_lo * tps, min(su_hi * tps, ix.n_tiles));
+    } else
+    for (int su = su_lo; su < su_hi; ++su) {
+        if (!all_units && !((my_ovf[su >> 5] >> (su & 31)) & 1u)) continue;  // uniform
+        const int ja = su * tps, jb = min(ja + tps, ix.n_tiles);  // the unit's tiles
+        int lo = 0, hi = 0;
+        if (tid < nt) {
+            lo = gload_i32(skip_row + min(ja, ix.n_tiles));
+            hi = gload_i32(skip_row + min(ja + tps, ix.n_tiles));
+        }
+        const int my_len = hi - lo;
+        const unsigned P = block_sum((unsigned)my_len, S.tk.red);
+        if (P == 0) continue;  // uniform
+        // many-term queries on a one-tile unit: all terms at once (flat_tile) instead of term by term
+        const bool flat_ok = tps == 1 && nt >= FLAT_MIN_TERMS && P <= (unsigned)FLAT_CAP && !(dbg & SRX_DBG_NO_FLAT_TILES);
+        bool served = false;
+        if (flat_ok) {
+            set_runs(S, nt, base + lo, my_len);
+            __syncthreads();
+            served = flat_tile<VT, AFTER, CP>(S, ix, nt, my_len, su << ix.tile_log2, k);
+            hash_mode(S);
+        }
+        if (served) continue;
+        if (P <= (unsigned)DENSE_MIN) {
+            set_runs(S, nt, base + lo, my_len);
+            __syncthreads();
+            hash_unit<VT, AFTER, CP>(S, ix, nt, my_len, k, ja << ix.tile_log2);
+        } else if (wave_dense) {
+            dense_quads(ja, jb);
+        } else {
+            packed_unit<VT, AFTER, CP>(S, ix, nt, k, base, skip_row, ja, jb, append_scan);
+        }
+    }
+    emit_item(S, a, q, nsq, list);
+}
+
+// Tier-2 kernel: a fixed grid of workgroups drains the worklist of (query, split) blocks that tier 1 could not
+// finish (flagged units, > 64 terms, k > 112).  work[0] = number of entries, work[1..] = block ids.
+template <typename VT, bool AFTER, bool CP>
+__global__ __launch_bounds__(THREADS, 2) void srx_score_kernel(const srx_score_launch a) {
     __shared__ ScoreShared S;
+    static_assert(2 * sizeof(ScoreShared) <= 160 * 1024, "the launch bounds: two workgroups share a CU's 160 KiB of LDS");
+    const int *__restrict__ work = a.w.work;
     const int n_work = work[0];
-    if (fin.hint != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *fin.hint = n_work;
+    if (a.hint != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *a.hint = n_work;
     for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
         __syncthreads();  // the previous block's LDS state is dead
-        score_block<VT, AFTER, CP>(S, work[1 + w], ix, q_ptr, q_term, q_weight, nq, k, n_splits, n_whole, tpu, n_super, dbg, ovf,
-                        ovf_words, lists_per_q, cand_doc, cand_score, cand_count, after_doc, after_score, doc_base, fin);
+        score_block<VT, AFTER, CP>(S, work[1 + w], a);
     }
+}
+
+template <typename VT, bool AFTER, bool CP>
+void launch_instance(const srx_score_launch &a, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL((srx_score_kernel<VT, AFTER, CP>), dim3(grid), dim3(THREADS), 0, stream, a);
+}
+template <typename VT, bool AFTER>
+void launch_copy(const srx_score_launch &a, unsigned grid, hipStream_t stream) {  // no canonical blocks: tier 2 reads the compact copy too
+    a.w.ix.post == nullptr ? launch_instance<VT, AFTER, true>(a, grid, stream) : launch_instance<VT, AFTER, false>(a, grid, stream);
+}
+template <typename VT>
+void launch_after(const srx_score_launch &a, unsigned grid, hipStream_t stream) {  // srx_search_after: every candidate is tested against the bound
+    a.after_score != nullptr ? launch_copy<VT, true>(a, grid, stream) : launch_copy<VT, false>(a, grid, stream);
 }
 
 }  // namespace
 
-// The eight instances in a fixed order (float before __half, AFTER before plain, CP before canonical): the order the
-// instances are first named in decides which helpers the compiler inlines, so it is part of the generated code.
+// The launcher names the three choices once each -- value type, search-after, compact copy -- and with them the eight
+// instances in a fixed order (float before __half, AFTER before plain, CP before canonical): the order the instances are
+// first named in decides which helpers the compiler inlines, so it is part of the generated code.
 int srx_launch_score_kernel(const srx_score_launch &a, int val_type, unsigned grid, hipStream_t stream) {
-    Tier2Final fin;
-    fin.out_doc = a.w.out_doc; fin.out_score = a.w.out_score; fin.out_count = a.w.out_count;
-    fin.ors = a.w.out_row_stride; fin.ocs = a.w.out_cnt_stride; fin.hint = a.hint;
-#define SRX_LAUNCH_T2(VT, AFTER, CP)                                                                                                \
-    hipLaunchKernelGGL((srx_score_kernel<VT, AFTER, CP>), dim3(grid), dim3(THREADS), 0, stream, a.w.ix, a.w.q_ptr, a.w.q_term,      \
-                       a.w.q_weight, a.w.nq, a.w.k, a.w.n_splits, a.w.n_whole, a.tpu, a.w.n_super, a.w.dbg, a.w.ovf, a.w.ovf_words, \
-                       a.w.lists_per_q, a.w.work, a.w.cand_doc, a.w.cand_score, a.w.cand_count, a.after_doc, a.after_score,         \
-                       a.w.doc_base, fin)
-    const bool after = a.after_score != nullptr;
-    const bool cp = a.w.ix.post == nullptr;  // no canonical blocks: tier 2 reads the compact copy too
-    if (val_type == SRX_VAL_F32) {
-        if (after) { if (cp) SRX_LAUNCH_T2(float, true, true); else SRX_LAUNCH_T2(float, true, false); }
-        else { if (cp) SRX_LAUNCH_T2(float, false, true); else SRX_LAUNCH_T2(float, false, false); }
-    } else {
-        if (after) { if (cp) SRX_LAUNCH_T2(__half, true, true); else SRX_LAUNCH_T2(__half, true, false); }
-        else { if (cp) SRX_LAUNCH_T2(__half, false, true); else SRX_LAUNCH_T2(__half, false, false); }
-    }
-#undef SRX_LAUNCH_T2
+    val_type == SRX_VAL_F32 ? launch_after<float>(a, grid, stream) : launch_after<__half>(a, grid, stream);
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }

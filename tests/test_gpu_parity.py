@@ -241,6 +241,53 @@ def test_zipf_dense_and_overflow_paths(rx):
         ix.close()
 
 
+def _tie_group_corpus(n=20_000):
+    """Dot mode, every stored value 1.0: terms 0 and 1 in every doc, term 2 in the docs with d % 64 == 5 -> those 313 docs
+    score 3.0 above ONE tie group of 19 687 docs scoring 2.0.  Returns (indptr, indices, data, doc_lengths, query)."""
+    top = np.arange(n) % 64 == 5
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum(2 + top)
+    indices = np.empty(indptr[-1], dtype=np.int32)
+    indices[indptr[:-1]], indices[indptr[:-1] + 1], indices[indptr[:-1][top] + 2] = 0, 1, 2
+    query = (np.array([0, 3], np.int32), np.array([0, 1, 2], np.int32), np.ones(3, np.float32))
+    return indptr, indices, np.ones(len(indices), np.float32), (2 + top).astype(np.float32), query
+
+
+def _tie_group_expected(n, k):
+    """The contract stated directly: the first min(k, 313) ids are the d % 64 == 5 docs ascending, the rest the smallest
+    remaining ids ascending."""
+    d = np.arange(n)
+    ids = np.concatenate([d[d % 64 == 5], d[d % 64 != 5]])[:k]
+    return ids.astype(np.int32), np.where(ids % 64 == 5, np.float32(3.0), np.float32(2.0))
+
+
+def test_tier2_selection_sites_cut_a_giant_tie_group(rx):
+    """Tier 2's own selection sites each have to cut INSIDE one tie group of 19 687 docs by doc id: the append scan +
+    list_compact_select of the wave-level dense tiles (tile_log2 = 12 unmasked / masked, and 10), the block-level dense tiles
+    (debug 2048 at tile_log2 = 12), the general selection (8192), and the hash path's topk_fold (debug 2048 at tile_log2 = 10:
+    without the wave-level path every 1 024-doc unit has 2 064 postings <= HASH_CAP and goes through hash_unit, whose second
+    unit already overflows the lazy list with far more ties than needed).  k = 2500 runs search-after pages inside the group
+    (the AFTER instances)."""
+    n = 20_000
+    indptr, indices, data, dl, q = _tie_group_corpus(n)
+    ones = np.ones(3, np.float32)
+    ks = (1, 313, 314, 1000, 1024, 2500)
+    exp = {k: oracle.search_batch(indptr, indices, data, dl, ones, *q, k, avgdl=1.0, mode=oracle.MODE_TFIDF_F32) for k in ks}
+    for k in ks:  # the oracle alone produces the stated contract
+        ids, sc = _tie_group_expected(n, k)
+        assert exp[k][2][0] == k and np.array_equal(exp[k][0][0], ids) and np.array_equal(exp[k][1][0], sc), f"oracle k={k}"
+    for tl, ut, dbgs in ((12, 1, (0, 2048, 8192)), (12, 2, (0, 2048, 8192)), (10, 1, (0, 2048))):
+        ix = rx.DeviceIndex.from_csr(indptr, indices, data, ones, mode="dot", tile_log2=tl, unit_tiles=ut)
+        for dbg in dbgs:
+            ix.set_opts(debug=dbg | 8)  # 8: everything through the tier-2 kernel
+            for k in ks:
+                got = ix.search(*q, k)
+                _assert_exact(got, exp[k], f"tie group tile={tl} ut={ut} debug={dbg | 8} k={k}")
+                ids, sc = _tie_group_expected(n, k)
+                assert got[2][0] == k and np.array_equal(got[0][0], ids) and np.array_equal(got[1][0], sc), f"tile={tl} ut={ut} debug={dbg | 8} k={k}"
+        ix.close()
+
+
 def test_splade_dot_f16_k1000(rx):
     """C4-shaped, scaled down: learned-sparse weights in fp16, 50 terms / query, k = 1000, dot mode."""
     from sparse_rx import synth

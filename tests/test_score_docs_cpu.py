@@ -134,7 +134,7 @@ def test_symbol_is_declared_bound_and_listed():
     from sparse_rx import _capi
     assert "srx_score_docs" in _capi.SYMBOLS and "score_docs.hip" in _capi.SOURCES and len(_capi.SYMBOLS) == 35
     assert _capi.lib().srx_version() == 301
-    assert _capi.kernel_sources_sha256() == "faba1764bf3395e4eb6b4d78f1e9056ea1633cdf1d5ff599c510918253937517"
+    assert _capi.kernel_sources_sha256() == "2eb63ec607c9e32df0c6ef89bb47c4cbb7595a20202a96c5ebffed881c45ca2b"
 
 
 # ---------------------------------------------------------------------------------------------------------------
