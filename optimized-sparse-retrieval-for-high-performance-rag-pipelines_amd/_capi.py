@@ -1,4 +1,4 @@
-"""ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h).
+"""ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h and include/sparse_rx_rescore.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -16,7 +16,7 @@ _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
-           "score_docs.hip"]                                    # one translation unit each, compiled in parallel
+           "score_docs.hip", "dense_score.hip"]                 # one translation unit each, compiled in parallel
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
@@ -90,6 +90,16 @@ SYMBOLS = {
     "srx_profile_read": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_float)]),
 }
 
+# every symbol include/sparse_rx_rescore.h declares (the second header of the same library)
+_F32 = ctypes.c_float
+RESCORE_SYMBOLS = {
+    "srx_dense_score_docs_f32": (ctypes.c_int, [_I32, _VP, _I64, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _VP]),
+    "srx_dense_score_docs_u8": (ctypes.c_int, [_I32, _VP, _VP, _I64, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _VP]),
+    "srx_dense_score_docs_i8": (ctypes.c_int, [_I32, _VP, _I32, _VP, _I64, _I32, _VP, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _VP]),
+    "srx_fuse_topk_scored": (ctypes.c_int, [_I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _F32, _F32,
+                                            _VP, _VP, _VP, _VP]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -107,7 +117,8 @@ def kernel_sources_sha256() -> str:
 
 def _deps():
     return [os.path.join(CSRC_DIR, f) for f in SOURCES] + [os.path.join(CSRC_DIR, "srx_common.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_rescore.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -120,7 +131,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         raise SparseRxUnavailable("hipcc not found: cannot build libsparse_rx.so")
     objdir = os.path.join(CSRC_DIR, "build")
     os.makedirs(objdir, exist_ok=True)
-    newest_hdr = max(os.path.getmtime(os.path.join(CSRC_DIR, "srx_common.h")), os.path.getmtime(os.path.join(INCLUDE_DIR, "sparse_rx.h")))
+    newest_hdr = max(os.path.getmtime(p) for p in _deps()[len(SOURCES):])
     procs, objs = [], []
     for f in SOURCES:
         src, obj = os.path.join(CSRC_DIR, f), os.path.join(objdir, f.replace(".hip", ".o"))
@@ -154,7 +165,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

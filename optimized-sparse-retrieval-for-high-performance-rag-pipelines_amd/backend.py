@@ -192,39 +192,86 @@ class SparseBackend:
         {qid: {doc_id: exact score}} with every listed candidate in the caller's order (0.0 where no query term matches,
         and for a blank or all-OOV query); a qid without candidates gives {}; an unknown doc id raises ValueError.  One
         batch: ragged lists are padded with -1 and passed with their lengths (``cand_count``)."""
-        ids = self.host.doc_ids
-        if getattr(self, "_row_of_ids", None) is not ids:
-            self._row_of, self._row_of_ids = {d: i for i, d in enumerate(ids)}, ids
-        results = {qid: {} for qid in queries}
-        live, rows = [], []
-        for qid, text in queries.items():
-            cands = list(candidates.get(qid, ()) or ())
-            if not cands:
-                continue
-            try:
-                rows.append([self._row_of[d] for d in cands])
-            except KeyError as e:
-                raise ValueError(f"unknown doc id {e.args[0]!r} among the candidates of {qid!r}") from None
-            live.append((qid, text or "", cands))
+        results, live, cand_doc, cand_count = self.candidate_block(queries, candidates)
         if not live:
             return results
-        m = max(len(r) for r in rows)
-        cand_doc = np.full((len(rows), m), -1, dtype=np.int32)
-        cand_count = np.zeros(len(rows), dtype=np.int32)
-        for i, r in enumerate(rows):
-            cand_doc[i, : len(r)] = r
-            cand_count[i] = len(r)
         q_ptr, q_term, q_weight = encode_queries([text for _, text, _ in live], self.host.vocabulary, order=order)
         scores = self.score_arrays(q_ptr, q_term, q_weight, cand_doc, cand_count)
-        for i, (qid, _, cands) in enumerate(live):
-            results[qid] = {d: float(scores[i, c]) for c, d in enumerate(cands)}
-        return results
+        return scores_to_dicts(results, live, scores)
+
+    def candidate_block(self, queries, candidates):
+        """:func:`candidate_block` over this index's doc ids (their row numbers are kept between calls)"""
+        if getattr(self, "_rows", None) is None or self._rows.ids is not self.host.doc_ids:
+            self._rows = RowOfIds(self.host.doc_ids)
+        return self._rows.candidate_block(queries, candidates)
 
     def close(self) -> None:
         if self.dev is not None:
             self.dev.close()
             self.dev = None
         self.searcher = None
+
+
+class RowOfIds:
+    """doc id -> row of one list of doc ids, built once and kept by whoever scores named docs (``ids`` is the list it was
+    built from: a holder rebuilds it when its list is another object)."""
+
+    def __init__(self, ids):
+        self.ids = ids
+        self.row_of = {d: i for i, d in enumerate(ids)}
+
+    @classmethod
+    def numbered(cls, n: int) -> "RowOfIds":
+        """Docs named by their row number as a string: no table"""
+        r = cls(())
+        r.row_of = _NumberedRows(n)
+        return r
+
+    def candidate_block(self, queries, candidates):
+        return candidate_block(self.row_of, queries, candidates)
+
+
+class _NumberedRows:
+    def __init__(self, n: int):
+        self.n = n
+
+    def __getitem__(self, d):
+        i = int(d) if isinstance(d, str) and d.isdigit() else -1
+        if not (0 <= i < self.n and str(i) == d):
+            raise KeyError(d)
+        return i
+
+
+def candidate_block(row_of, queries, candidates):
+    """``candidates`` {qid: sequence of doc ids} for the qids of ``queries`` as one padded block; ``row_of`` maps a doc id
+    to its row.  Returns (results = {qid: {}} for every qid, live = [(qid, queries[qid], or "" for None, its candidates)]
+    for the qids that have any, cand_doc i32[len(live), m] padded with -1, cand_count i32[len(live)]).  An unknown doc id
+    raises ValueError."""
+    results = {qid: {} for qid in queries}
+    live, rows = [], []
+    for qid, text in queries.items():
+        cands = list(candidates.get(qid, ()) or ())
+        if not cands:
+            continue
+        try:
+            rows.append([row_of[d] for d in cands])
+        except KeyError as e:
+            raise ValueError(f"unknown doc id {e.args[0]!r} among the candidates of {qid!r}") from None
+        live.append((qid, "" if text is None else text, cands))
+    m = max((len(r) for r in rows), default=1)
+    cand_doc = np.full((len(rows), m), -1, dtype=np.int32)
+    cand_count = np.zeros(len(rows), dtype=np.int32)
+    for i, r in enumerate(rows):
+        cand_doc[i, : len(r)] = r
+        cand_count[i] = len(r)
+    return results, live, cand_doc, cand_count
+
+
+def scores_to_dicts(results, live, scores):
+    """f32[len(live), m] scores of a :func:`candidate_block` into ``results``: every candidate in the caller's order"""
+    for i, (qid, _, cands) in enumerate(live):
+        results[qid] = {d: float(scores[i, c]) for c, d in enumerate(cands)}
+    return results
 
 
 class SparseIndexViews:

@@ -258,6 +258,165 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_block_kernel(FuseArgs a) {
     block_rank_emit(S.tk, S.sortkey, k, (int64_t)0, a.out_doc + (int64_t)q * k, a.out_score + (int64_t)q * k, a.out_count + q);
 }
 
+// ---- fusion of two COMPLETED lists (srx_fuse_topk_scored, include/sparse_rx_rescore.h) -----------------------------------
+// Every entry carries the other side's score of its doc (`*_other`), so no contribution crosses between the lists: the
+// table only finds the entries of list B whose doc list A holds as well, and those are dropped.  The same two forms, the
+// same table, selection and ranking as above.
+struct FuseScoredArgs {
+    FuseArgs f;  // mode = SRX_FUSE_WEIGHTED
+    const float *a_other, *b_other;
+};
+// The heads of the two lists and what an entry fuses to
+struct FuseScoredSides {
+    float wa, wb, ma, mb;  // m = 0: the side has no normaliser and contributes nothing anywhere
+    // a score on side A / B: its contribution, or +0 (adding +0 changes no bit of a value >= 0)
+    __device__ __forceinline__ float from_a(float s) const { return (ma > 0.0f && s > 0.0f) ? wa * (s / ma) : 0.0f; }
+    __device__ __forceinline__ float from_b(float s) const { return (mb > 0.0f && s > 0.0f) ? wb * (s / mb) : 0.0f; }
+};
+// Candidate c of query q (c < ka: list A's entry c, else list B's entry c - ka): its doc, or -1 when the entry is not used,
+// and its fused score (two operands: the order of the sum does not matter)
+__device__ __forceinline__ void fuse_scored_load(const FuseScoredArgs &s, const FuseScoredSides &w, int c, int ca, int cb, int64_t a0,
+                                                 int64_t b0, int &doc, float &fused) {
+    const FuseArgs &a = s.f;
+    float sa = 0.0f, sb = 0.0f, own = 0.0f;
+    doc = -1;
+    if (c < a.ka) {
+        if (c < ca) {
+            own = sa = a.a_score[a0 + c];
+            sb = s.a_other[a0 + c];
+            doc = a.a_doc[a0 + c];
+        }
+    } else if (c - a.ka < cb) {
+        own = sb = a.b_score[b0 + (c - a.ka)];
+        sa = s.b_other[b0 + (c - a.ka)];
+        doc = a.b_doc[b0 + (c - a.ka)];
+    }
+    if (!(own > 0.0f)) doc = -1;
+    fused = doc >= 0 ? w.from_a(sa) + w.from_b(sb) : 0.0f;
+}
+
+__global__ __launch_bounds__(THREADS) void srx_fuse_scored_wave_kernel(FuseScoredArgs s) {
+    __shared__ FuseWaveShared FW[WAVES];
+    const FuseArgs &a = s.f;
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (q >= a.nq) return;  // whole waves leave; nothing below is a block barrier
+    FuseWaveShared &S = FW[threadIdx.x >> 6];
+    const int ka = a.ka, kb = a.kb, k = a.k;
+    const int64_t a0 = (int64_t)q * ka, b0 = (int64_t)q * kb;
+    const int ca = max(0, min(a.a_count[q], ka)), cb = max(0, min(a.b_count[q], kb));
+    const FuseScoredSides w = {a.wa, a.wb, fuse_head(a.a_doc, a.a_score, ca, a0), fuse_head(a.b_doc, a.b_score, cb, b0)};
+    float sc[FW_NPL];  // fused score
+    int dd[FW_NPL];    // doc; -1 = entry not used
+#pragma unroll
+    for (int j = 0; j < FW_NPL; ++j) fuse_scored_load(s, w, j * 64 + lane, ca, cb, a0, b0, dd[j], sc[j]);
+#pragma unroll
+    for (int j = 0; j < F_SLOTS / 256; ++j) reinterpret_cast<uint4 *>(S.tbl)[j * 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
+    wsync();
+    // list A: the entries that rank (fused score > 0) are compacted into the list and entered; the used entries that do
+    // not rank are parked behind them, docs only, and entered too: a duplicate in B is dropped whatever A's entry fuses to
+    unsigned count = 0;  // wave-uniform
+#pragma unroll
+    for (int j = 0; j < FW_NPL; ++j) {
+        if (j * 64 >= ka) break;
+        const bool ok = j * 64 + lane < ka && sc[j] > 0.0f;
+        const unsigned long long m = __ballot(ok);
+        if (ok) {
+            const unsigned p = count + lane_rank(m);
+            S.lbits[p] = __float_as_uint(sc[j]);
+            S.ldoc[p] = dd[j];
+            fuse_insert(S.tbl, dd[j], p);  // claims a slot only: keys are compared by the probes, after the wsync below
+        }
+        count += (unsigned)__popcll(m);
+    }
+    unsigned parked = count;
+#pragma unroll
+    for (int j = 0; j < FW_NPL; ++j) {
+        if (j * 64 >= ka) break;
+        const bool ok = j * 64 + lane < ka && dd[j] >= 0 && !(sc[j] > 0.0f);
+        const unsigned long long m = __ballot(ok);
+        if (ok) {
+            const unsigned p = parked + lane_rank(m);
+            S.ldoc[p] = dd[j];
+            fuse_insert(S.tbl, dd[j], p);
+        }
+        parked += (unsigned)__popcll(m);
+    }
+    wsync();
+    // list B: every probe first (the parked docs are still in place), then the misses are appended over the parked docs
+#pragma unroll
+    for (int j = 0; j < FW_NPL; ++j) {
+        if ((j + 1) * 64 <= ka) continue;
+        const bool isb = j * 64 + lane >= ka && sc[j] > 0.0f;
+        if (isb && parked > 0 && fuse_find(S.tbl, dd[j], [&](unsigned p) -> int { return S.ldoc[p]; }) >= 0) sc[j] = 0.0f;
+    }
+    wsync();
+#pragma unroll
+    for (int j = 0; j < FW_NPL; ++j) {
+        if ((j + 1) * 64 <= ka) continue;
+        const bool app = j * 64 + lane >= ka && sc[j] > 0.0f;
+        const unsigned long long m = __ballot(app);
+        if (app) {
+            const unsigned p = count + lane_rank(m);
+            S.lbits[p] = __float_as_uint(sc[j]);
+            S.ldoc[p] = dd[j];
+        }
+        count += (unsigned)__popcll(m);
+    }
+    wsync();
+    if (count > (unsigned)k) {
+        wave_list_select(S, count, k);
+        count = (unsigned)k;
+    }
+    wave_rank_emit(S, S.sortkey, count, k, (int64_t)0, a.out_doc + (int64_t)q * k, a.out_score + (int64_t)q * k);
+    if (lane == 0) a.out_count[q] = (int)count;
+}
+
+__global__ __launch_bounds__(THREADS) void srx_fuse_scored_block_kernel(FuseScoredArgs s) {
+    __shared__ FuseBlockShared S;
+    const FuseArgs &a = s.f;
+    int *const adoc = reinterpret_cast<int *>(S.sortkey);  // list A by rank: the table's keys
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x;
+    const int ka = a.ka, kb = a.kb, k = a.k;
+    const int64_t a0 = (int64_t)q * ka, b0 = (int64_t)q * kb;
+    const int ca = max(0, min(a.a_count[q], ka)), cb = max(0, min(a.b_count[q], kb));
+    const FuseScoredSides w = {a.wa, a.wb, fuse_head(a.a_doc, a.a_score, ca, a0), fuse_head(a.b_doc, a.b_score, cb, b0)};
+    float sc[FB_NPT];
+    int dd[FB_NPT];
+#pragma unroll
+    for (int n = 0; n < FB_NPT; ++n) fuse_scored_load(s, w, n * THREADS + tid, ca, cb, a0, b0, dd[n], sc[n]);
+    for (int i = tid; i < F_SLOTS; i += THREADS) S.hist[i] = 0u;
+    if (tid == 0) {
+        S.tk.count = 0;
+        S.tk.tau = 0;
+    }
+#pragma unroll
+    for (int n = 0; n < FB_NPT; ++n) {
+        const int c = n * THREADS + tid;
+        if (c < ka && dd[n] >= 0) adoc[c] = dd[n];  // every used entry of A, whatever it fuses to
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < FB_NPT; ++n) {
+        const int c = n * THREADS + tid;
+        if (c < ka && dd[n] >= 0) fuse_insert(S.hist, dd[n], (unsigned)c);
+    }
+    __syncthreads();
+    unsigned ubits[FB_NPT];
+    int udoc[FB_NPT];
+#pragma unroll
+    for (int n = 0; n < FB_NPT; ++n) {
+        const int c = n * THREADS + tid;
+        if (c >= ka && sc[n] > 0.0f && fuse_find(S.hist, dd[n], [&](unsigned p) -> int { return adoc[p]; }) >= 0) sc[n] = 0.0f;
+        ubits[n] = sc[n] > 0.0f ? __float_as_uint(sc[n]) : 0u;
+        udoc[n] = dd[n];
+    }
+    __syncthreads();  // the table and list A's docs are dead: their words become the selection histogram and the sort keys
+    topk_fold<FB_NPT, false>(ubits, udoc, k, S.tk, S.hist);
+    block_rank_emit(S.tk, S.sortkey, k, (int64_t)0, a.out_doc + (int64_t)q * k, a.out_score + (int64_t)q * k, a.out_count + q);
+}
+
 }  // namespace
 
 SRX_API int srx_fuse_topk(int32_t device, const int32_t *a_doc, const float *a_score, const int32_t *a_count, int32_t ka,
@@ -286,6 +445,34 @@ SRX_API int srx_fuse_topk(int32_t device, const int32_t *a_doc, const float *a_s
         return SRX_OK;
     }
     hipLaunchKernelGGL(srx_fuse_block_kernel, dim3((unsigned)nq), dim3(THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return SRX_OK;
+}
+
+#include "sparse_rx_rescore.h"
+
+SRX_API int srx_fuse_topk_scored(int32_t device, const int32_t *a_doc, const float *a_score, const float *a_other,
+                                 const int32_t *a_count, int32_t ka, const int32_t *b_doc, const float *b_score,
+                                 const float *b_other, const int32_t *b_count, int32_t kb, int32_t nq, int32_t k, float weight_a,
+                                 float weight_b, int32_t *out_doc, float *out_score, int32_t *out_count, void *stream_v) {
+    if (nq < 0) return fail(SRX_ERR_INVALID, "srx_fuse_topk_scored: nq < 0%s");
+    if (ka < 1 || ka > KMAX || kb < 1 || kb > KMAX) return fail(SRX_ERR_INVALID, "srx_fuse_topk_scored: ka / kb must be in 1..1024%s");
+    if (k < 1 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_fuse_topk_scored: k must be in 1..1024%s");
+    if (!isfinite(weight_a) || !isfinite(weight_b) || weight_a < 0.0f || weight_b < 0.0f)
+        return fail(SRX_ERR_INVALID, "srx_fuse_topk_scored: weights must be finite and >= 0%s");
+    if (weight_a == 0.0f && weight_b == 0.0f) return fail(SRX_ERR_INVALID, "srx_fuse_topk_scored: both weights are 0%s");
+    if (nq == 0) return SRX_OK;
+    if (!a_doc || !a_score || !a_other || !a_count || !b_doc || !b_score || !b_other || !b_count || !out_doc || !out_score || !out_count)
+        return fail(SRX_ERR_INVALID, "srx_fuse_topk_scored: null pointer%s");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const FuseScoredArgs s = {{a_doc, b_doc, a_score, b_score, a_count, b_count, out_doc, out_score, out_count, nq, ka, kb, k,
+                               SRX_FUSE_WEIGHTED, weight_a, weight_b, 0.0f},
+                              a_other, b_other};
+    if (ka + kb <= FW_CAP && k <= W_KMAX)  // the dispatch rule of srx_fuse_topk
+        hipLaunchKernelGGL(srx_fuse_scored_wave_kernel, dim3((unsigned)((nq + WAVES - 1) / WAVES)), dim3(THREADS), 0, stream, s);
+    else
+        hipLaunchKernelGGL(srx_fuse_scored_block_kernel, dim3((unsigned)nq), dim3(THREADS), 0, stream, s);
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }

@@ -10,7 +10,8 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from .index import _check_k, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, rows_to_dict
+from .index import (_candidate_block, _check_k, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, rows_to_dict,
+                    validate_candidates)
 
 DIMS = (32, 64, 96, 128, 192, 256, 384, 512, 768, 1024)  # row lengths the kernel is instantiated for
 
@@ -93,14 +94,42 @@ class _DenseIndex:
         nq = int(queries.shape[0])
         L = _capi.lib()
         with torch.cuda.device(self.device):
-            q = torch.zeros((nq, self.dim_pad), dtype=dtype, device=self.device)
-            q[:, : self.dim] = queries
+            q = self._padded(torch, queries, dtype)
             out = _empty_topk(torch, nq, k, self.device)
             if nq == 0:
                 return out
             ws = _grow_ws(torch, self, _capi.check(getattr(L, self._workspace_fn)(nq, self.n_docs, k), self._workspace_fn))
             _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), self._entry)
         return out
+
+    def _padded(self, torch, queries, dtype):
+        q = torch.zeros((int(queries.shape[0]), self.dim_pad), dtype=dtype, device=self.device)
+        q[:, : self.dim] = queries
+        return q
+
+    def _score_docs_device(self, queries, dtype, cand_doc, cand_count, out, *extra):
+        """The candidate block checked (as ``DeviceIndex.score_docs_device`` checks it), the query block zero-padded to
+        ``dim_pad``, then the class's ``_launch_score(L, q, nq, cand_doc, cand_count, m, out, stream, *extra)`` -> the entry
+        point's return code.  Asynchronous on the current stream; an empty batch launches nothing.  Returns f32[nq, m]."""
+        torch = _torch()
+        nq = int(queries.shape[0])
+        L = _capi.lib()
+        with torch.cuda.device(self.device):
+            cand_doc, cand_count, m, out = _candidate_block(torch, nq, cand_doc, cand_count, out, self.device)
+            if nq > 0:
+                rc = self._launch_score(L, self._padded(torch, queries, dtype), nq, cand_doc, cand_count, m, out,
+                                        _stream_ptr(torch, self.device), *extra)
+                _capi.check(rc, self._score_entry)
+        return out
+
+    def _score_docs(self, cand_doc, cand_count, nq: int, score_fn) -> np.ndarray:
+        """Host candidates (:func:`validate_candidates`) through ``score_fn(cand_doc, cand_count)`` on device tensors: one
+        launch, one synchronisation, one copy.  Returns f32[nq, m]."""
+        torch = _torch()
+        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
+        cd = torch.as_tensor(cand_doc, device=self.device)
+        cc = None if cand_count is None else torch.as_tensor(cand_count, device=self.device)
+        return self._host((score_fn(cd, cc),))[0]
 
     def _host(self, out):
         return _to_host(_torch(), self.device, out)
@@ -112,7 +141,7 @@ class DenseInt8Index(_DenseIndex):
     (retriever_registry.py:389-392).  By default the matrix is kept in MFMA-fragment order only (``srx_dense_pack_i8``:
     same bytes; a wave's B-fragment loads are contiguous); ``packed=False`` keeps the row-major matrix and searches that."""
 
-    _workspace_fn, _entry = "srx_dense_workspace_bytes", "srx_dense_search_i8"
+    _workspace_fn, _entry, _score_entry = "srx_dense_workspace_bytes", "srx_dense_search_i8", "srx_dense_score_docs_i8"
 
     def __init__(self, corpus_int8, corpus_scales, device="cuda:0", doc_base: int = 0, packed: bool = True):
         torch = self._open(device)
@@ -151,9 +180,30 @@ class DenseInt8Index(_DenseIndex):
 
     def search(self, queries_int8: np.ndarray, query_scales: np.ndarray, k: int):
         """Host arrays in, host arrays out."""
+        return self._host(self.search_device(*self._queries_to_device(queries_int8, query_scales), k))
+
+    def _queries_to_device(self, queries_int8, query_scales):
         torch = _torch()
-        return self._host(self.search_device(torch.as_tensor(np.ascontiguousarray(queries_int8, dtype=np.int8), device=self.device),
-                                             torch.as_tensor(np.ascontiguousarray(query_scales, dtype=np.float32), device=self.device), k))
+        return (torch.as_tensor(np.ascontiguousarray(queries_int8, dtype=np.int8), device=self.device),
+                torch.as_tensor(np.ascontiguousarray(query_scales, dtype=np.float32), device=self.device))
+
+    def score_docs_device(self, queries_int8, query_scales, cand_doc, cand_count=None, out=None):
+        """``srx_dense_score_docs_i8`` (include/sparse_rx_rescore.h): the score of every (query, candidate) pair with the
+        arithmetic of :meth:`search_device` -- a row it returned scores to its own bits.  cand_doc i32[nq, m] GLOBAL ids,
+        cand_count i32[nq] or None: the triple of any search can be passed as it is.  Returns f32[nq, m] (``out`` when
+        given): ``+0`` for padding and ids outside the index, no ``score > 0`` filter.  Asynchronous on the current stream."""
+        return self._score_docs_device(queries_int8, _torch().int8, cand_doc, cand_count, out, query_scales)
+
+    def _launch_score(self, L, q, nq, cand_doc, cand_count, m, out, stream, query_scales):
+        qs = query_scales.to(device=self.device, dtype=_torch().float32).contiguous()
+        return L.srx_dense_score_docs_i8(self.device.index or 0, _ptr(self.corpus), int(self.packed), _ptr(self.scales), self.n_docs,
+                                         self.dim_pad, _ptr(q), _ptr(qs), nq, self.doc_base, _ptr(cand_doc), _ptr(cand_count), m,
+                                         _ptr(out), stream)
+
+    def score_docs(self, queries_int8: np.ndarray, query_scales: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
+        """Host arrays in (the candidates validated by :func:`validate_candidates`), f32[nq, m] out."""
+        q, qs = self._queries_to_device(queries_int8, query_scales)
+        return self._score_docs(cand_doc, cand_count, int(q.shape[0]), lambda cd, cc: self.score_docs_device(q, qs, cd, cc))
 
 
 class DenseUint8Index(_DenseIndex):
@@ -162,7 +212,7 @@ class DenseUint8Index(_DenseIndex):
     ``_numpy_quantized_similarity`` (:550-559) + the top-k for a batch of de-quantized query vectors
     (``srx_dense_search_u8``, which indexes the table the way the reference's reader does)."""
 
-    _entry = "srx_dense_search_u8"
+    _entry, _score_entry = "srx_dense_search_u8", "srx_dense_score_docs_u8"
 
     def __init__(self, corpus_uint8, corpus_scales, device="cuda:0", doc_base: int = 0):
         torch = self._open(device)
@@ -188,9 +238,25 @@ class DenseUint8Index(_DenseIndex):
 
     def search(self, queries_uint8: np.ndarray, query_scales: np.ndarray, k: int):
         """queries u8[nq, dim] + f32[nq, 2] (scale, min) as the reference's search builds them (:486-491); host arrays out."""
-        torch = _torch()
+        return self._host(self.search_device(self._queries_to_device(queries_uint8, query_scales), k))
+
+    def _queries_to_device(self, queries_uint8, query_scales):
+        """The de-quantized f32 query block on the device"""
         qf = np.stack([dequantize_query_asymmetric(q, s) for q, s in zip(np.asarray(queries_uint8), np.asarray(query_scales))])
-        return self._host(self.search_device(torch.as_tensor(np.ascontiguousarray(qf, dtype=np.float32), device=self.device), k))
+        return _torch().as_tensor(np.ascontiguousarray(qf, dtype=np.float32), device=self.device)
+
+    def score_docs_device(self, queries_f32, cand_doc, cand_count=None, out=None):
+        """``srx_dense_score_docs_u8`` for de-quantized queries f32[nq, dim]: as ``DenseInt8Index.score_docs_device``."""
+        return self._score_docs_device(queries_f32, _torch().float32, cand_doc, cand_count, out)
+
+    def _launch_score(self, L, q, nq, cand_doc, cand_count, m, out, stream):
+        return L.srx_dense_score_docs_u8(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad, _ptr(q),
+                                         nq, self.doc_base, _ptr(cand_doc), _ptr(cand_count), m, _ptr(out), stream)
+
+    def score_docs(self, queries_uint8: np.ndarray, query_scales: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
+        """queries as in :meth:`search`, host candidates (:func:`validate_candidates`); f32[nq, m] out."""
+        q = self._queries_to_device(queries_uint8, query_scales)
+        return self._score_docs(cand_doc, cand_count, int(q.shape[0]), lambda cd, cc: self.score_docs_device(q, cd, cc))
 
 
 class QuantizedEmbeddingIndex:
@@ -227,7 +293,7 @@ class DenseF32Index(_DenseIndex):
     ``search`` replaces ``np.dot(self.embedding_index, query_vector)`` + top-k of ``search_by_vector`` (:411-423) for a
     batch of query vectors (``srx_dense_search_f32``)."""
 
-    _entry = "srx_dense_search_f32"
+    _entry, _score_entry = "srx_dense_search_f32", "srx_dense_score_docs_f32"
 
     def __init__(self, embeddings, device="cuda:0", doc_base: int = 0):
         torch = self._open(device)
@@ -273,8 +339,24 @@ class DenseF32Index(_DenseIndex):
                                       _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream, float(score_offset))
 
     def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0):
-        torch = _torch()
+        return self._host(self.search_device(self._queries_to_device(queries), k, score_offset))
+
+    def _queries_to_device(self, queries):
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
-        return self._host(self.search_device(torch.as_tensor(q, device=self.device), k, score_offset))
+        return _torch().as_tensor(q, device=self.device)
+
+    def score_docs_device(self, queries, cand_doc, cand_count=None, out=None):
+        """``srx_dense_score_docs_f32``: as ``DenseInt8Index.score_docs_device``; the bits are those of :meth:`search_device`
+        with ``score_offset = 0``."""
+        return self._score_docs_device(queries, _torch().float32, cand_doc, cand_count, out)
+
+    def _launch_score(self, L, q, nq, cand_doc, cand_count, m, out, stream):
+        return L.srx_dense_score_docs_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, self.doc_base,
+                                          _ptr(cand_doc), _ptr(cand_count), m, _ptr(out), stream)
+
+    def score_docs(self, queries: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
+        """Host arrays in (the candidates validated by :func:`validate_candidates`), f32[nq, m] out."""
+        q = self._queries_to_device(queries)
+        return self._score_docs(cand_doc, cand_count, int(q.shape[0]), lambda cd, cc: self.score_docs_device(q, cd, cc))

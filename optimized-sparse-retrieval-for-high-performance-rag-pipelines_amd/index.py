@@ -263,6 +263,24 @@ def search_host_batch(search_fn, q_ptr, q_term, q_weight, k: int, vocab: int, de
     return _to_host(torch, device, out, wait)
 
 
+def _candidate_block(torch, nq: int, cand_doc, cand_count, out, device):
+    """The candidate block of every ``score_docs_device`` (sparse and dense) checked and made contiguous, and its output:
+    cand_doc int32[nq, m] with m >= 1, cand_count int32[nq] or None, ``out`` a contiguous float32[nq, m] (allocated on
+    ``device`` when None).  Returns (cand_doc, cand_count, m, out).  Raises ValueError."""
+    if cand_doc.dim() != 2 or int(cand_doc.shape[0]) != nq or cand_doc.dtype != torch.int32:
+        raise ValueError("score_docs_device: cand_doc must be an int32 tensor [nq, m]")
+    m = int(cand_doc.shape[1])
+    if m < 1:
+        raise ValueError("score_docs_device: cand_doc needs m >= 1 columns")
+    if cand_count is not None and (cand_count.dtype != torch.int32 or cand_count.numel() != nq):
+        raise ValueError("score_docs_device: cand_count must be an int32 tensor [nq]")
+    if out is None:
+        out = torch.empty((nq, m), dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (nq, m) or not out.is_contiguous():
+        raise ValueError("score_docs_device: out must be a contiguous float32 tensor [nq, m]")
+    return cand_doc.contiguous(), None if cand_count is None else cand_count.contiguous(), m, out
+
+
 def score_host_batch(score_fn, q_ptr, q_term, q_weight, cand_doc, cand_count, vocab: int, device) -> np.ndarray:
     """A host CSR batch and a host candidate block through any ``score_fn(q_ptr, q_term, q_weight, cand_doc, cand_count)``
     on device tensors: validate both, upload, one launch, one synchronisation, one copy.  Returns f32[nq, m]."""
@@ -650,20 +668,8 @@ class DeviceIndex:
         non-decreasing, 0 <= q_term < vocab, no term twice inside a query -- :meth:`score_docs` checks host batches."""
         torch = _torch()
         nq = q_ptr.numel() - 1
-        if cand_doc.dim() != 2 or int(cand_doc.shape[0]) != nq or cand_doc.dtype != torch.int32:
-            raise ValueError("score_docs_device: cand_doc must be an int32 tensor [nq, m]")
-        m = int(cand_doc.shape[1])
-        if m < 1:
-            raise ValueError("score_docs_device: cand_doc needs m >= 1 columns")
-        if cand_count is not None and (cand_count.dtype != torch.int32 or cand_count.numel() != nq):
-            raise ValueError("score_docs_device: cand_count must be an int32 tensor [nq]")
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((nq, m), dtype=torch.float32, device=self.device)
-            if out.dtype != torch.float32 or tuple(out.shape) != (nq, m) or not out.is_contiguous():
-                raise ValueError("score_docs_device: out must be a contiguous float32 tensor [nq, m]")
-            cand_doc = cand_doc.contiguous()
-            cand_count = None if cand_count is None else cand_count.contiguous()
+            cand_doc, cand_count, m, out = _candidate_block(torch, nq, cand_doc, cand_count, out, self.device)
             rc = _capi.lib().srx_score_docs(ctypes.byref(self._desc), _ptr(q_ptr), _ptr(q_term), _ptr(q_weight), nq, _ptr(cand_doc),
                                             _ptr(cand_count), m, _ptr(out), _stream_ptr(torch, self.device))
             _capi.check(rc, "srx_score_docs")
@@ -901,6 +907,32 @@ def check_fuse_args(mode, weights, rrf_c) -> Tuple[int, float, float, float]:
     return FUSE_MODES[mode], wa, wb, rrf_c
 
 
+def _fuse_lists(torch, who: str, a, b, k: int, others=()):
+    """The two list triples of a fusion checked: [nq, kx] doc / score tensors of one shape per list, the same queries on
+    both sides, widths and k in [1, max_k], int32 / float32, all on one HIP device; ``others`` = further f32 tensors as
+    (tensor, the doc tensor whose shape it must have).  Returns (nq, ka, kb, device).  Raises ValueError."""
+    max_k = _capi.SRX_MAX_K
+    (a_doc, a_score, a_count), (b_doc, b_score, b_count) = a, b
+    if a_doc.dim() != 2 or b_doc.dim() != 2 or a_doc.shape != a_score.shape or b_doc.shape != b_score.shape:
+        raise ValueError(f"{who}: doc / score must be [nq, k] tensors of one shape per list")
+    nq, ka, kb = int(a_doc.shape[0]), int(a_doc.shape[1]), int(b_doc.shape[1])
+    if int(b_doc.shape[0]) != nq or a_count.numel() != nq or b_count.numel() != nq:
+        raise ValueError(f"{who}: the two lists must cover the same queries")
+    if not (1 <= ka <= max_k and 1 <= kb <= max_k and 1 <= int(k) <= max_k):
+        raise ValueError(f"{who}: list widths and k must be in [1, {max_k}], got {ka}, {kb}, {k}")
+    dev = a_doc.device
+    for t, doc in others:
+        if t.shape != doc.shape:
+            raise ValueError(f"{who}: the other side's scores must have the shape of the list they complete")
+    for t, dt in ((a_doc, torch.int32), (a_score, torch.float32), (a_count, torch.int32), (b_doc, torch.int32),
+                  (b_score, torch.float32), (b_count, torch.int32), *((t, torch.float32) for t, _ in others)):
+        if t.dtype != dt or t.device != dev:
+            raise ValueError(f"{who}: doc / count must be int32, score float32, all on one device")
+    if dev.type != "cuda":
+        raise ValueError(f"{who}: the lists must be device tensors")
+    return nq, ka, kb, dev
+
+
 def fuse_topk_device(a, b, k: int, mode: str = "weighted", weights=(0.3, 0.7), rrf_c: float = 60.0):
     """``srx_fuse_topk`` on device tensors: one fused ranking per query from two ranked lists over the same doc ids.
     ``a`` (sparse side) and ``b`` (dense side) are ``(doc i32[nq, kx], score f32[nq, kx], count i32[nq])`` as the
@@ -910,27 +942,11 @@ def fuse_topk_device(a, b, k: int, mode: str = "weighted", weights=(0.3, 0.7), r
     tensors' device."""
     torch = _torch()
     code, wa, wb, rrf_c = check_fuse_args(mode, weights, rrf_c)
-    max_k = _capi.SRX_MAX_K
-    (a_doc, a_score, a_count), (b_doc, b_score, b_count) = a, b
-    if a_doc.dim() != 2 or b_doc.dim() != 2 or a_doc.shape != a_score.shape or b_doc.shape != b_score.shape:
-        raise ValueError("fuse_topk_device: doc / score must be [nq, k] tensors of one shape per list")
-    nq, ka, kb = int(a_doc.shape[0]), int(a_doc.shape[1]), int(b_doc.shape[1])
-    if int(b_doc.shape[0]) != nq or a_count.numel() != nq or b_count.numel() != nq:
-        raise ValueError("fuse_topk_device: the two lists must cover the same queries")
-    if not (1 <= ka <= max_k and 1 <= kb <= max_k and 1 <= int(k) <= max_k):
-        raise ValueError(f"fuse_topk_device: list widths and k must be in [1, {max_k}], got {ka}, {kb}, {k}")
-    dev = a_doc.device
-    for t, dt in ((a_doc, torch.int32), (a_score, torch.float32), (a_count, torch.int32), (b_doc, torch.int32),
-                  (b_score, torch.float32), (b_count, torch.int32)):
-        if t.dtype != dt or t.device != dev:
-            raise ValueError("fuse_topk_device: doc / count must be int32, score float32, all on one device")
-    if dev.type != "cuda":
-        raise ValueError("fuse_topk_device: the lists must be device tensors")
+    nq, ka, kb, dev = _fuse_lists(torch, "fuse_topk_device", a, b, k)
     L = _capi.lib()
     with torch.cuda.device(dev):
         out = _empty_topk(torch, nq, k, dev)
-        a_doc, a_score, a_count = a_doc.contiguous(), a_score.contiguous(), a_count.contiguous()
-        b_doc, b_score, b_count = b_doc.contiguous(), b_score.contiguous(), b_count.contiguous()
+        (a_doc, a_score, a_count), (b_doc, b_score, b_count) = (tuple(t.contiguous() for t in side) for side in (a, b))
         rc = L.srx_fuse_topk(dev.index or 0, _ptr(a_doc), _ptr(a_score), _ptr(a_count), ka, _ptr(b_doc), _ptr(b_score),
                              _ptr(b_count), kb, nq, int(k), code, wa, wb, rrf_c, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                              _stream_ptr(torch, dev))
@@ -938,15 +954,58 @@ def fuse_topk_device(a, b, k: int, mode: str = "weighted", weights=(0.3, 0.7), r
     return out
 
 
+def fuse_scored_device(a, a_other, b, b_other, k: int, weights=(0.3, 0.7)):
+    """``srx_fuse_topk_scored`` (include/sparse_rx_rescore.h) on device tensors: the weighted fusion of two COMPLETED
+    lists.  ``a`` / ``b`` as in :func:`fuse_topk_device`; ``a_other`` f32[nq, ka] = side B's score of the doc in A's slot,
+    ``b_other`` f32[nq, kb] = side A's score of the doc in B's slot (the ``score_docs_device`` of the opposite engine over
+    the list's own triple).  Every used entry fuses both of its scores, each divided by its side's best listed score; a
+    doc in both lists is taken once, from ``a``.  The result is the (doc, score, count) triple with ``k`` columns.
+    Asynchronous on the current stream of the tensors' device."""
+    torch = _torch()
+    _, wa, wb, _ = check_fuse_args("weighted", weights, 60.0)
+    nq, ka, kb, dev = _fuse_lists(torch, "fuse_scored_device", a, b, k, others=((a_other, a[0]), (b_other, b[0])))
+    L = _capi.lib()
+    with torch.cuda.device(dev):
+        out = _empty_topk(torch, nq, k, dev)
+        (a_doc, a_score, a_count), (b_doc, b_score, b_count) = (tuple(t.contiguous() for t in side) for side in (a, b))
+        a_other, b_other = a_other.contiguous(), b_other.contiguous()
+        rc = L.srx_fuse_topk_scored(dev.index or 0, _ptr(a_doc), _ptr(a_score), _ptr(a_other), _ptr(a_count), ka, _ptr(b_doc),
+                                    _ptr(b_score), _ptr(b_other), _ptr(b_count), kb, nq, int(k), wa, wb, _ptr(out[0]), _ptr(out[1]),
+                                    _ptr(out[2]), _stream_ptr(torch, dev))
+        _capi.check(rc, "srx_fuse_topk_scored")
+    return out
+
+
+def check_rescore_args(mode, rescore) -> bool:
+    """``rescore`` as a bool, or ``ValueError``: only the weighted fusion can be rescored (a rank beyond the fetched depth
+    is unknown, so reciprocal-rank fusion has nothing to complete a list with)."""
+    rescore = bool(rescore)
+    if rescore and mode != "weighted":
+        raise ValueError(f"rescore=True needs fusion='weighted', got {mode!r}: ranks beyond the fetched depth are unknown")
+    return rescore
+
+
 def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, ka: int, kb: int, k: int, mode: str, weights,
-                  rrf_c: float):
+                  rrf_c: float, rescore: bool = False, dense_score=None):
     """The hybrid pipeline of the API mirrors: sparse search of a host CSR batch on ``index`` (``ka`` rows per query),
     ``dense_search(kb)`` -> the dense side's device triple for the same queries, ``fuse_topk_device``; the three steps
-    stay on the device, then one synchronisation and the copy back (:func:`search_host_batch`).  Returns host (doc, score, count)."""
+    stay on the device, then one synchronisation and the copy back (:func:`search_host_batch`).  Returns host (doc, score, count).
+
+    ``rescore=True`` (weighted fusion only) completes both lists before they are fused, five steps on the device: the two
+    searches, ``index.score_docs_device`` over the dense list's rows, ``dense_score(cand_doc, cand_count)`` -> the dense
+    side's f32[nq, ka] scores of the sparse list's rows, ``fuse_scored_device``.  The fused score of a returned doc then
+    does not depend on ``ka`` / ``kb``."""
     check_fuse_args(mode, weights, rrf_c)
+    if check_rescore_args(mode, rescore) and dense_score is None:
+        raise ValueError("hybrid_search: rescore=True needs dense_score")
 
     def fused(qp, qt, qw, kk):
-        return fuse_topk_device(index.search_device(qp, qt, qw, ka), dense_search(kb), kk, mode=mode, weights=weights, rrf_c=rrf_c)
+        a, b = index.search_device(qp, qt, qw, ka), dense_search(kb)
+        if not rescore:
+            return fuse_topk_device(a, b, kk, mode=mode, weights=weights, rrf_c=rrf_c)
+        b_other = index.score_docs_device(qp, qt, qw, b[0], b[2])
+        a_other = dense_score(a[0], a[2])
+        return fuse_scored_device(a, a_other, b, b_other, kk, weights)
 
     return search_host_batch(fused, q_ptr, q_term, q_weight, k, index.vocab, index.device)
 

@@ -22,7 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from .backend import SparseBackend, SparseIndexViews
-from .index import HostIndex, check_fuse_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
+from .index import HostIndex, check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
 
 _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
 
@@ -222,6 +222,31 @@ class QuantizedEmbeddingRetriever:
             results[qid] = rows_to_dict(self.doc_ids, d, s, n, i)  # score > 0 only (:515-519)
         return results
 
+    def score(self, query_embeddings: Dict[str, np.ndarray], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
+        """The score of caller-named documents for caller-given query embeddings ``{qid: f32[embedding_dim]}``:
+        ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in the caller's order, quantized and scored with
+        the arithmetic of :meth:`search` (``srx_dense_score_docs_i8`` / ``_u8`` / ``_f32``).  No ``score > 0`` filter;
+        ``{}`` for a qid without candidates; ``ValueError`` for an unknown doc id.  One batch, no cache."""
+        from .backend import RowOfIds, scores_to_dicts
+        from .dense import quantize_query_asymmetric, quantize_query_symmetric
+        if self._index is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        if getattr(self, "_rows", None) is None or self._rows.ids is not self.doc_ids:
+            self._rows = RowOfIds(self.doc_ids)  # kept between calls, like the sparse side's
+        results, live, cand_doc, cand_count = self._rows.candidate_block(query_embeddings, candidates)
+        if not live:
+            return results
+        embs = [np.asarray(e, dtype=np.float32) for _, e, _ in live]
+        if self.use_quantization and self.quantization_method == "symmetric":
+            qq = [quantize_query_symmetric(e) for e in embs]
+            scores = self._index.score_docs(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), cand_doc, cand_count)
+        elif self.use_quantization:
+            qq = [quantize_query_asymmetric(e) for e in embs]
+            scores = self._index.score_docs(np.stack([a for a, _ in qq]), np.stack([b for _, b in qq]), cand_doc, cand_count)
+        else:
+            scores = self._index.score_docs(np.stack(embs), cand_doc, cand_count)
+        return scores_to_dicts(results, live, scores)
+
 
 class HybridRetriever:
     """The ``hybrid`` retriever type the reference configures (configs/ms_marco_paper_results.yaml:108-120: ``model:
@@ -231,7 +256,11 @@ class HybridRetriever:
 
     ``fusion``: "weighted" (each side's scores divided by its best score, then the weighted sum) or "rrf" (weighted
     reciprocal rank fusion with constant ``rrf_c``).  ``candidates``: rows fetched from each side (default ``top_k``; each
-    side is capped at ``min(candidates, n_docs, 1024)``).  A doc only one side retrieved scores with that side alone.
+    side is capped at ``min(candidates, n_docs, 1024)``).  A doc only one side retrieved scores with that side alone,
+    unless ``rescore=True`` ("weighted" only; ``ValueError`` with "rrf"; also read from the registry block's ``params``):
+    then each list is completed with the other side's exact score of its docs before the fusion (``srx_score_docs``,
+    ``srx_dense_score_docs_i8``, ``srx_fuse_topk_scored``; include/sparse_rx_rescore.h) and the fused score of a returned
+    doc no longer depends on ``candidates``.
     With one weight 0 the result is the other side's SET, but equal normalised scores rank by doc id, so the order can
     differ from that side's own.  ``top_k`` > 1024 raises ``ValueError``: fused rankings deeper than the engine's lists
     are not paged, and a silently shorter list would be worse than an error.  The dense side is the symmetric INT8 engine
@@ -239,12 +268,13 @@ class HybridRetriever:
 
     def __init__(self, model=None, sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted",
                  rrf_c: float = 60.0, candidates: Optional[int] = None, embedding_dim: int = 768, device: Optional[str] = None,
-                 k1: float = 1.2, b: float = 0.75, tile_log2: int = 14, **kwargs):
+                 k1: float = 1.2, b: float = 0.75, tile_log2: int = 14, rescore: bool = False, **kwargs):
         model = model or {}
         if not isinstance(model, dict):
             raise ValueError("hybrid retriever: model must be a dict {sparse: ..., dense: ...}")
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
+        self.rescore = check_rescore_args(fusion, rescore)
         if candidates is not None and int(candidates) < 1:
             raise ValueError(f"candidates must be >= 1, got {candidates}")
         self.method = "hybrid"
@@ -297,6 +327,7 @@ class HybridRetriever:
         mirror's simulated query vectors (seeded by ``hash(text)``: they differ between processes, like the reference's)."""
         from .dense import quantize_query_symmetric
         self._refuse_sharded()
+        rescore = check_rescore_args(self.fusion, self.rescore)  # both are plain attributes
         if self.sparse.host is None or self.dense._index is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
@@ -325,8 +356,13 @@ class HybridRetriever:
             return self.dense._index.search_device(torch.as_tensor(np.ascontiguousarray(q_i8, dtype=np.int8), device=self.device),
                                                    torch.as_tensor(q_scale, device=self.device), kb)
 
+        def dense_score(cand_doc, cand_count):
+            import torch
+            return self.dense._index.score_docs_device(torch.as_tensor(np.ascontiguousarray(q_i8, dtype=np.int8), device=self.device),
+                                                       torch.as_tensor(q_scale, device=self.device), cand_doc, cand_count)
+
         doc, score, count = hybrid_search(self.sparse.dev, q_ptr, q_term, q_w, dense_search, cand, cand, k, self.fusion,
-                                          (self.sparse_weight, self.dense_weight), self.rrf_c)
+                                          (self.sparse_weight, self.dense_weight), self.rrf_c, rescore, dense_score)
         for i, (qid, _) in enumerate(live):
             results[qid] = rows_to_dict(self.doc_ids, doc, score, count, i)
         return results

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .backend import SparseBackend, SparseIndexViews
-from .index import check_fuse_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
+from .index import check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
 
 logger = logging.getLogger(__name__)
 
@@ -182,13 +182,17 @@ class RetrievalService(SparseIndexViews):
 
     def search_hybrid(self, queries: Dict[str, str], query_vectors: Dict[str, np.ndarray], top_k: int = 10, *,
                       sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted", rrf_c: float = 60.0,
-                      candidates: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+                      candidates: Optional[int] = None, rescore: bool = False) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
         arithmetic).  ``fusion`` "weighted": each side's scores divided by its best score, then
         ``sparse_weight * s + dense_weight * d``; "rrf": ``weight / (rrf_c + rank)`` per side.  A doc only one side
-        retrieved scores with that side alone; a query without in-vocabulary terms is the dense list re-scored.
+        retrieved scores with that side alone -- unless ``rescore=True`` ("weighted" only; with "rrf" it raises
+        ``ValueError``): then each list is completed with the other side's exact score of its docs before the fusion
+        (``srx_score_docs``, ``srx_dense_score_docs_f32``, ``srx_fuse_topk_scored``; include/sparse_rx_rescore.h), and the
+        fused score of a returned doc no longer depends on ``candidates``.  A query without in-vocabulary terms is the
+        dense list re-scored.
         ``candidates``: rows fetched from each side (default ``top_k``, capped at ``min(candidates, n_docs, 1024)``).
         All queries of the call run as one batch: sparse search, dense search and fusion stay on the device, followed by
         one synchronisation and the copy back.  Returns ``{qid: {doc_id: fused score}}`` in rank order, ``{}`` for a blank
@@ -198,6 +202,7 @@ class RetrievalService(SparseIndexViews):
         Needs the whole index on one GPU."""
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
+        rescore = check_rescore_args(fusion, rescore)
         k, cand = hybrid_depths(top_k, candidates, self._be.n_docs_total)
         if self._be.sharded():
             raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
@@ -224,11 +229,35 @@ class RetrievalService(SparseIndexViews):
             import torch
             return self._dense.search_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), kb)
 
+        def dense_score(cand_doc, cand_count):
+            import torch
+            return self._dense.score_docs_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), cand_doc, cand_count)
+
         doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
-                                          (sparse_weight, dense_weight), rrf_c)
+                                          (sparse_weight, dense_weight), rrf_c, rescore, dense_score)
         for i, (qid, _) in enumerate(live):
             results[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return results
+
+    def score_by_vector(self, query_vectors: Dict[str, np.ndarray], candidates: Dict[str, Sequence[str]]) -> Dict[str, Dict[str, float]]:
+        """The dense twin of :meth:`score_bm25`: ``{qid: {doc_id: score}}`` with the ``embedding_index`` score of every doc
+        of ``candidates[qid]`` for ``query_vectors[qid]``, in the caller's order, with the arithmetic of the dense search
+        (``srx_dense_score_docs_f32``: a row :meth:`search_hybrid`'s dense side returned scores to the same float).  No
+        ``score > 0`` filter; a qid without candidates gives ``{}``; an unknown doc id raises ``ValueError``.  One batch
+        (ragged lists padded with -1, passed with their lengths); no cache."""
+        from .backend import RowOfIds, scores_to_dicts
+        self._ensure_dense()
+        if self.host is not None:
+            results, live, cand_doc, cand_count = self._be.candidate_block(query_vectors, candidates)  # its doc id -> row map is kept
+        else:  # embeddings without a BM25 index: docs are named by their row number, as search_by_vector names them
+            results, live, cand_doc, cand_count = RowOfIds.numbered(self._dense.n_docs).candidate_block(query_vectors, candidates)
+        if not live:
+            return results
+        vecs = [np.asarray(v, dtype=np.float32) for _, v, _ in live]
+        for (qid, _, _), v in zip(live, vecs):
+            if v.shape != (self._dense.dim,):
+                raise ValueError(f"query vector of {qid!r} has shape {v.shape}, expected ({self._dense.dim},)")
+        return scores_to_dicts(results, live, self._dense.score_docs(np.stack(vecs), cand_doc, cand_count))
 
     def clear_cache(self) -> None:
         with self.cache_lock:
