@@ -6,7 +6,8 @@ from .index import DeviceIndex, HostBatchPipeline, HostIndex, build_host_index, 
 from .service import RetrievalService
 from .registry import HybridRetriever, OptimizedBM25Retriever, OptimizedRetriever, QuantizedEmbeddingRetriever, RetrieverRegistry, load_index_npz, save_index_npz
 from .dense import (DenseF32Index, DenseInt8Index, DenseUint8Index, QuantizedEmbeddingIndex, quantize_asymmetric,
-                    quantize_query_asymmetric, quantize_query_symmetric, quantize_symmetric)
+                    quantize_asymmetric_device, quantize_queries_asymmetric_device, quantize_queries_symmetric_device,
+                    quantize_query_asymmetric, quantize_query_symmetric, quantize_symmetric, quantize_symmetric_device)
 from .distributed import (ShardedSearcher, shard_range, global_df, global_avgdl, global_term_bounds, bm25_idf_from_df,
                           build_sharded_host_index)
 from .backend import SparseBackend
@@ -16,4 +17,5 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "global_df", "global_avgdl", "global_term_bounds", "bm25_idf_from_df", "build_sharded_host_index", "SparseBackend", "OptimizedBM25Retriever", "OptimizedRetriever", "QuantizedEmbeddingRetriever", "RetrieverRegistry",
            "load_index_npz", "save_index_npz", "DenseF32Index", "DenseInt8Index", "DenseUint8Index", "QuantizedEmbeddingIndex", "quantize_symmetric",
            "quantize_asymmetric", "quantize_query_asymmetric",
-           "quantize_query_symmetric"]
+           "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
+           "quantize_queries_asymmetric_device"]

@@ -1,4 +1,5 @@
-"""ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h and include/sparse_rx_rescore.h).
+"""ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h and
+include/sparse_rx_quant.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -16,7 +17,7 @@ _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
-           "score_docs.hip", "dense_score.hip"]                 # one translation unit each, compiled in parallel
+           "score_docs.hip", "dense_score.hip", "dense_quant.hip"]  # one translation unit each, compiled in parallel
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
@@ -100,6 +101,15 @@ RESCORE_SYMBOLS = {
                                             _VP, _VP, _VP, _VP]),
 }
 
+# every symbol include/sparse_rx_quant.h declares (the third header of the same library)
+QUANT_SYMBOLS = {
+    "srx_dense_quantize_i8": (ctypes.c_int, [_I32, _VP, _I64, _I64, _I32, _I32, _I64, _I64, _I32, _VP, _VP, _VP, _VP]),
+    "srx_dense_quantize_u8": (ctypes.c_int, [_I32, _VP, _I64, _I64, _I32, _I32, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "srx_dense_quantize_queries_i8": (ctypes.c_int, [_I32, _VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "srx_dense_quantize_queries_u8": (ctypes.c_int, [_I32, _VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+}
+SRX_QUANT_NONFINITE, SRX_QUANT_DEGENERATE = 1, 2  # bits of the quantisers' flag word
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -118,7 +128,8 @@ def kernel_sources_sha256() -> str:
 def _deps():
     return [os.path.join(CSRC_DIR, f) for f in SOURCES] + [os.path.join(CSRC_DIR, "srx_common.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_rescore.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_rescore.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_quant.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -165,7 +176,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

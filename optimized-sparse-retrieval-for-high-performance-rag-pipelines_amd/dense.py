@@ -56,6 +56,150 @@ def dequantize_query_asymmetric(query_uint8: np.ndarray, query_scales: np.ndarra
     return query_uint8.astype(np.float32) * query_scale + query_min
 
 
+def check_quantize_arg(quantize) -> str:
+    """``quantize=`` of the API mirrors: "host" (the NumPy quantisers above) or "device" (``include/sparse_rx_quant.h``)."""
+    q = str(quantize).lower()
+    if q not in ("host", "device"):
+        raise ValueError(f"quantize must be 'host' or 'device', got {quantize!r}")
+    return q
+
+
+def _require_f32(x, what: str) -> None:
+    """The device quantisers take float32 only: no silent cast, because the host functions compute in the dtype they are given."""
+    dtype = getattr(x, "dtype", None)
+    if dtype is None or str(dtype).split(".")[-1] != "float32":
+        raise ValueError(f"{what} must be float32, got {dtype} (the device quantisers do not cast)")
+    if len(x.shape) != 2:
+        raise ValueError(f"{what} must be 2-D [rows, dim], got shape {tuple(x.shape)}")
+
+
+def _f32_rows(torch, x, what: str):
+    """A 2-D float32 device tensor as the quantisers read it -> (tensor with unit column stride, row stride in elements)."""
+    _require_f32(x, what)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError(f"{what} must be a device tensor")
+    n, dim = int(x.shape[0]), int(x.shape[1])
+    if dim > 0 and (x.stride(1) != 1 or (n > 1 and x.stride(0) < dim)):
+        x = x.contiguous()
+    return x, (int(x.stride(0)) if n > 1 else dim)
+
+
+def _quantize_device(entry: str, x, dim_pad: int, outs, flag=None, row0: int = 0, n_total=None, packed=None):
+    """One launch of a quantiser of include/sparse_rx_quant.h on the current stream of ``x``'s device.  ``outs``: the
+    entry point's output tensors in its order (None = NULL).  Returns the flag tensor i32[1] (made and zeroed when not given)."""
+    torch = _torch()
+    x, ld = _f32_rows(torch, x, "embeddings")
+    dev = x.device
+    n, dim = int(x.shape[0]), int(x.shape[1])
+    with torch.cuda.device(dev):
+        if flag is None:
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        args = [dev.index or 0, _ptr(x), ld, n, dim, dim_pad]
+        if n_total is not None:  # a corpus call: a chunk of the whole
+            args += [row0, n_total] + ([int(packed)] if packed is not None else [])
+        args += [_ptr(t) for t in outs] + [_ptr(flag), _stream_ptr(torch, dev)]
+        _capi.check(getattr(_capi.lib(), entry)(*args), entry)
+    return flag
+
+
+def _pad64(dim: int, engine: str) -> int:
+    dim_pad = (dim + 63) // 64 * 64
+    if dim_pad > 1024:
+        raise ValueError(f"embedding dim {dim} > 1024 is not supported by the {engine} engine")
+    return dim_pad
+
+
+def quantize_symmetric_device(emb):
+    """:func:`quantize_symmetric` on the device (``srx_dense_quantize_i8``): f32[n, dim] device tensor -> (i8[n, dim] -- a view
+    of the zero-padded i8[n, dim_pad] the INT8 engine takes --, f32[n] scales, flag i32[1]), bit for bit the host function's.
+    Asynchronous on the current stream.  Flag bit 0: a row holds a non-finite value (codes 0, scale 1e-8)."""
+    torch = _torch()
+    _require_f32(emb, "embeddings")
+    n, dim = int(emb.shape[0]), int(emb.shape[1])
+    dim_pad = _pad_dim(dim)
+    codes = torch.empty((n, dim_pad), dtype=torch.int8, device=emb.device)
+    scales = torch.empty((n,), dtype=torch.float32, device=emb.device)
+    flag = _quantize_device("srx_dense_quantize_i8", emb, dim_pad, (codes, scales), n_total=n, packed=0)
+    return codes[:, :dim], scales, flag
+
+
+def quantize_asymmetric_device(emb):
+    """:func:`quantize_asymmetric` on the device (``srx_dense_quantize_u8``): -> (u8[n, dim] view of u8[n, dim_pad], the
+    f32[2 n] table -- all scales, then all minima --, flag i32[1])."""
+    torch = _torch()
+    _require_f32(emb, "embeddings")
+    n, dim = int(emb.shape[0]), int(emb.shape[1])
+    dim_pad = _pad64(dim, "uint8")
+    codes = torch.empty((n, dim_pad), dtype=torch.uint8, device=emb.device)
+    scales = torch.empty((2 * n,), dtype=torch.float32, device=emb.device)
+    flag = _quantize_device("srx_dense_quantize_u8", emb, dim_pad, (codes, scales), n_total=n)
+    return codes[:, :dim], scales, flag
+
+
+def quantize_queries_symmetric_device(q):
+    """:func:`quantize_query_symmetric` for a batch (``srx_dense_quantize_queries_i8``): f32[nq, dim] device tensor ->
+    (i8[nq, dim] view of i8[nq, dim_pad], f32[nq] query scales, flag i32[1]).  Flag bit 0: a non-finite query, bit 1: an
+    all-zero one; both get codes 0 and scale 0, so every score of theirs is 0 (the host function divides by zero there)."""
+    torch = _torch()
+    _require_f32(q, "queries")
+    nq, dim = int(q.shape[0]), int(q.shape[1])
+    dim_pad = _pad_dim(dim)
+    codes = torch.empty((nq, dim_pad), dtype=torch.int8, device=q.device)
+    scales = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    flag = _quantize_device("srx_dense_quantize_queries_i8", q, dim_pad, (codes, scales))
+    return codes[:, :dim], scales, flag
+
+
+def quantize_queries_asymmetric_device(q, codes: bool = True):
+    """:func:`quantize_query_asymmetric` + :func:`dequantize_query_asymmetric` for a batch
+    (``srx_dense_quantize_queries_u8``): -> (u8[nq, dim], f32[nq, 2] = (scale, min), de-quantised f32[nq, dim], flag i32[1]);
+    the three are views of dim_pad-wide zero-padded tensors.  ``codes=False``: only the de-quantised block is written (the
+    first two are None).  Flag bit 0: a non-finite query (block 0), bit 1: a constant one (the block is the query itself)."""
+    torch = _torch()
+    _require_f32(q, "queries")
+    nq, dim = int(q.shape[0]), int(q.shape[1])
+    dim_pad = _pad64(dim, "uint8")
+    u8 = torch.empty((nq, dim_pad), dtype=torch.uint8, device=q.device) if codes else None
+    scales = torch.empty((nq, 2), dtype=torch.float32, device=q.device) if codes else None
+    deq = torch.empty((nq, dim_pad), dtype=torch.float32, device=q.device)
+    flag = _quantize_device("srx_dense_quantize_queries_u8", q, dim_pad, (u8, scales, deq))
+    return (u8[:, :dim] if codes else None), scales, deq[:, :dim], flag
+
+
+def unpack_i8_host(packed: np.ndarray, n_docs: int, dim_pad: int) -> np.ndarray:
+    """The row-major i8[n_docs, dim_pad] of a corpus in the fragment order ``srx_dense_pack_i8`` documents (host arrays)."""
+    ks = dim_pad // 32
+    t = np.asarray(packed).view(np.int8).reshape(-1, ks, 2, 32, 16)  # [tile][k-step][half][row][16 bytes]
+    return np.ascontiguousarray(t.transpose(0, 3, 1, 2, 4)).reshape(-1, dim_pad)[:n_docs]
+
+
+def _default_chunk_rows(dim: int) -> int:
+    return max(32, ((64 << 20) // (4 * max(1, dim))) // 32 * 32)  # <= 64 MB of f32 rows, a multiple of the 32-row tile
+
+
+def _quantize_corpus(index, torch, emb, chunk_rows, entry: str, outs, packed=None):
+    """``from_embeddings``' loop: a device tensor is quantised in one launch; a host array (possibly a read-only memory map) is
+    copied through ONE staging tensor of ``chunk_rows`` rows, so the device holds the finished corpus plus one chunk.  Ends
+    with the build's one synchronisation, the read of the flag word."""
+    _require_f32(emb, "embeddings")
+    n = index.n_docs
+    flag = torch.zeros(1, dtype=torch.int32, device=index.device)
+    if isinstance(emb, torch.Tensor):
+        _quantize_device(entry, emb.to(index.device), index.dim_pad, outs, flag, 0, n, packed)
+    else:
+        rows = _default_chunk_rows(index.dim) if chunk_rows is None else int(chunk_rows)
+        if rows < 32 or rows % 32 != 0:
+            raise ValueError(f"chunk_rows must be a positive multiple of 32, got {chunk_rows}")
+        stage = torch.empty((min(rows, n), index.dim), dtype=torch.float32, device=index.device)
+        for lo in range(0, n, rows):
+            chunk = torch.from_numpy(np.array(emb[lo: lo + rows], dtype=np.float32))  # np.array copies the chunk only
+            m = int(chunk.shape[0])
+            stage[:m].copy_(chunk)  # stream-ordered behind the previous chunk's kernel
+            _quantize_device(entry, stage[:m], index.dim_pad, outs, flag, lo, n, packed)
+    if int(flag.item()) & _capi.SRX_QUANT_NONFINITE:
+        raise ValueError("embeddings hold a non-finite value (NaN / inf, or a row whose max - min overflows)")
+
+
 def _pad_dim(dim: int) -> int:
     for d in DIMS:
         if d >= dim:
@@ -81,10 +225,7 @@ class _DenseIndex:
 
     def _pad64(self, engine: str) -> int:
         """Row length rounded up to the 64 columns the f32 / uint8 kernels step by."""
-        dim_pad = (self.dim + 63) // 64 * 64
-        if dim_pad > 1024:
-            raise ValueError(f"embedding dim {self.dim} > 1024 is not supported by the {engine} engine")
-        return dim_pad
+        return _pad64(self.dim, engine)
 
     def _search_device(self, queries, dtype, k: int, *extra):
         """k check, the query block zero-padded to ``dim_pad``, the output triple and the workspace, then the class's
@@ -168,6 +309,50 @@ class DenseInt8Index(_DenseIndex):
         assert self.scales.numel() == self.n_docs
         self.doc_base = int(doc_base)
 
+    @classmethod
+    def from_embeddings(cls, emb, device="cuda:0", doc_base: int = 0, packed: bool = True, chunk_rows=None):
+        """The index of f32[n_docs, dim] embeddings quantised ON THE DEVICE (``srx_dense_quantize_i8``): the corpus and scale
+        tensors are bit for bit those of ``DenseInt8Index(*quantize_symmetric(emb))``; with ``packed`` the kernel writes the
+        fragment order directly (no row-major intermediate).  ``emb``: a float32 device tensor (one launch) or host array
+        (uploaded ``chunk_rows`` rows at a time, a multiple of 32; default: 64 MB of rows).  ``ValueError`` for a non-finite
+        value, raised after the one synchronisation the build needs."""
+        _require_f32(emb, "embeddings")
+        self = cls.__new__(cls)
+        torch = self._open(device)
+        self.n_docs, self.dim = int(emb.shape[0]), int(emb.shape[1])
+        if self.n_docs == 0:
+            raise ValueError("Empty corpus provided")
+        self.dim_pad = _pad_dim(self.dim)
+        self.packed, self.doc_base = bool(packed), int(doc_base)
+        with torch.cuda.device(self.device):
+            if self.packed:
+                nbytes = _capi.check(_capi.lib().srx_dense_packed_bytes(self.n_docs, self.dim_pad), "srx_dense_packed_bytes")
+                self.corpus = torch.empty(nbytes, dtype=torch.int8, device=self.device)
+            else:
+                self.corpus = torch.empty((self.n_docs, self.dim_pad), dtype=torch.int8, device=self.device)
+            self.scales = torch.empty((self.n_docs,), dtype=torch.float32, device=self.device)
+            _quantize_corpus(self, torch, emb, chunk_rows, "srx_dense_quantize_i8", (self.corpus, self.scales), int(self.packed))
+        return self
+
+    def corpus_to_host(self):
+        """(i8[n_docs, dim], f32[n_docs]) host copies of the resident corpus: what ``quantize_symmetric`` returned for it."""
+        torch = _torch()
+        torch.cuda.synchronize(self.device)
+        c = self.corpus.cpu().numpy()
+        rows = unpack_i8_host(c, self.n_docs, self.dim_pad) if self.packed else c
+        return np.ascontiguousarray(rows[:, : self.dim]), self.scales.cpu().numpy()
+
+    def search_f32_device(self, queries_f32, k: int):
+        """f32[nq, dim] query vectors on the device: quantised there (:func:`quantize_queries_symmetric_device`), then
+        :meth:`search_device`.  Asynchronous; a non-finite or all-zero query returns an empty row."""
+        q, qs, _ = quantize_queries_symmetric_device(queries_f32.to(self.device))
+        return self.search_device(q, qs, k)
+
+    def score_docs_f32_device(self, queries_f32, cand_doc, cand_count=None, out=None):
+        """:meth:`score_docs_device` for f32[nq, dim] query vectors on the device, quantised there."""
+        q, qs, _ = quantize_queries_symmetric_device(queries_f32.to(self.device))
+        return self.score_docs_device(q, qs, cand_doc, cand_count, out)
+
     def search_device(self, queries_int8, query_scales, k: int):
         """queries i8[nq, dim] + f32[nq] on the device -> (doc i32[nq,k], score f32[nq,k], count i32[nq]); asynchronous."""
         return self._search_device(queries_int8, _torch().int8, k, query_scales)
@@ -229,6 +414,38 @@ class DenseUint8Index(_DenseIndex):
             self.scales = torch.as_tensor(s).to(self.device)
         self.doc_base = int(doc_base)
 
+    @classmethod
+    def from_embeddings(cls, emb, device="cuda:0", doc_base: int = 0, chunk_rows=None):
+        """As ``DenseInt8Index.from_embeddings`` for the asymmetric scheme (``srx_dense_quantize_u8``): the tensors of
+        ``DenseUint8Index(*quantize_asymmetric(emb))``."""
+        _require_f32(emb, "embeddings")
+        self = cls.__new__(cls)
+        torch = self._open(device)
+        self.n_docs, self.dim = int(emb.shape[0]), int(emb.shape[1])
+        if self.n_docs == 0:
+            raise ValueError("Empty corpus provided")
+        self.dim_pad = self._pad64("uint8")
+        self.doc_base = int(doc_base)
+        with torch.cuda.device(self.device):
+            self.corpus = torch.empty((self.n_docs, self.dim_pad), dtype=torch.uint8, device=self.device)
+            self.scales = torch.empty((2 * self.n_docs,), dtype=torch.float32, device=self.device)
+            _quantize_corpus(self, torch, emb, chunk_rows, "srx_dense_quantize_u8", (self.corpus, self.scales))
+        return self
+
+    def corpus_to_host(self):
+        """(u8[n_docs, dim], f32[2 n_docs]) host copies of the resident corpus: what ``quantize_asymmetric`` returned for it."""
+        _torch().cuda.synchronize(self.device)
+        return np.ascontiguousarray(self.corpus.cpu().numpy()[:, : self.dim]), self.scales.cpu().numpy()
+
+    def search_raw_device(self, queries_f32, k: int):
+        """RAW f32[nq, dim] query vectors on the device: quantised and de-quantised there as the reference's search does
+        (``srx_dense_quantize_queries_u8``'s out_deq), then :meth:`search_device`.  Asynchronous."""
+        return self.search_device(quantize_queries_asymmetric_device(queries_f32.to(self.device), codes=False)[2], k)
+
+    def score_docs_raw_device(self, queries_f32, cand_doc, cand_count=None, out=None):
+        """:meth:`score_docs_device` for RAW query vectors, as :meth:`search_raw_device`."""
+        return self.score_docs_device(quantize_queries_asymmetric_device(queries_f32.to(self.device), codes=False)[2], cand_doc, cand_count, out)
+
     def search_device(self, queries_f32, k: int):
         return self._search_device(queries_f32, _torch().float32, k)
 
@@ -259,22 +476,39 @@ class DenseUint8Index(_DenseIndex):
         return self._score_docs(cand_doc, cand_count, int(q.shape[0]), lambda cd, cc: self.score_docs_device(q, cd, cc))
 
 
+def stack_queries_f32(index, embs):
+    """Query vectors for the device quantisers as ONE f32[nq, dim] tensor on ``index.device``: a list of host rows is stacked
+    once and uploaded once, a 2-D host array is uploaded, a device tensor is taken as it is.  float32 only (``ValueError``
+    otherwise: the host quantisers compute in the dtype they are given)."""
+    torch = _torch()
+    if isinstance(embs, torch.Tensor):
+        _require_f32(embs, "query embeddings")
+        return embs.to(index.device)
+    q = np.stack([np.asarray(e) for e in embs]) if isinstance(embs, (list, tuple)) else np.asarray(embs)
+    _require_f32(q, "query embeddings")
+    return torch.as_tensor(np.ascontiguousarray(q), device=index.device)
+
+
 class QuantizedEmbeddingIndex:
     """The search half of the reference's ``QuantizedEmbeddingRetriever`` (symmetric INT8) over given embeddings:
     ``build(doc_ids, embeddings)`` quantizes like :435-447, ``search(query_embeddings, top_k)`` quantizes each query like
     :482-485 and returns ``{doc_id: score}`` ranked, ``score > 0`` only (:515-519), for every query at once."""
 
-    def __init__(self, device="cuda:0"):
+    def __init__(self, device="cuda:0", quantize: str = "host"):
         self.device = device
+        self.quantize = check_quantize_arg(quantize)  # "device": build and search quantise in HIP (float32 embeddings only)
         self.doc_ids: List[str] = []
         self.index = None
 
-    def build(self, doc_ids: Sequence[str], embeddings: np.ndarray) -> None:
+    def build(self, doc_ids: Sequence[str], embeddings) -> None:
         if len(doc_ids) == 0:
             raise ValueError("Empty corpus provided")
-        q, scales = quantize_symmetric(embeddings)
+        if self.quantize == "device":
+            self.index = DenseInt8Index.from_embeddings(embeddings, device=self.device)
+        else:
+            q, scales = quantize_symmetric(embeddings)
+            self.index = DenseInt8Index(q, scales, device=self.device)
         self.doc_ids = list(doc_ids)
-        self.index = DenseInt8Index(q, scales, device=self.device)
 
     def search(self, query_embeddings: Dict[str, np.ndarray], top_k: int = 10) -> Dict[str, Dict[str, float]]:
         if self.index is None:
@@ -282,9 +516,12 @@ class QuantizedEmbeddingIndex:
         qids = list(query_embeddings)
         if not qids:
             return {}
-        qq = [quantize_query_symmetric(query_embeddings[q]) for q in qids]
         k = min(top_k, len(self.doc_ids))
-        d, s, n = self.index.search(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), k)
+        if self.quantize == "device":
+            d, s, n = self.index._host(self.index.search_f32_device(stack_queries_f32(self.index, [query_embeddings[q] for q in qids]), k))
+        else:
+            qq = [quantize_query_symmetric(query_embeddings[q]) for q in qids]
+            d, s, n = self.index.search(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), k)
         return {qid: rows_to_dict(self.doc_ids, d, s, n, i) for i, qid in enumerate(qids)}
 
 

@@ -159,11 +159,80 @@ class QuantizedEmbeddingRetriever:
         self.use_quantization = kwargs.get("use_quantization", True)
         self.quantization_method = kwargs.get("quantization_method", "symmetric")
         self.device = device
-        self.corpus_embeddings_int8: Optional[np.ndarray] = None
-        self.corpus_scales: Optional[np.ndarray] = None
+        from .dense import check_quantize_arg
+        # "host": the NumPy quantisers (the reference's path); "device": the corpus and every query batch are quantised in
+        # HIP (include/sparse_rx_quant.h) -- the same codes and scales bit for bit, no per-query host loop
+        self.quantize = check_quantize_arg(kwargs.get("quantize", "host"))
+        self.corpus_embeddings_int8 = None
+        self.corpus_scales = None
         self.corpus_embeddings_fp32: Optional[np.ndarray] = None
         self.doc_ids: List[str] = []
         self._index = None
+
+    # The reference keeps the quantised corpus as host arrays (:389-392).  With quantize="device" they exist on the device only
+    # and are copied back on first access.
+    @property
+    def corpus_embeddings_int8(self) -> Optional[np.ndarray]:
+        self._fetch_corpus()
+        return self._corpus_codes
+
+    @corpus_embeddings_int8.setter
+    def corpus_embeddings_int8(self, value) -> None:
+        self._corpus_codes = value
+
+    @property
+    def corpus_scales(self) -> Optional[np.ndarray]:
+        self._fetch_corpus()
+        return self._corpus_scales
+
+    @corpus_scales.setter
+    def corpus_scales(self, value) -> None:
+        self._corpus_scales = value
+
+    def _fetch_corpus(self) -> None:
+        if getattr(self, "_corpus_codes", None) is None and self.quantize == "device" and self.use_quantization and self._index is not None:
+            self._corpus_codes, self._corpus_scales = self._index.corpus_to_host()
+
+    def _build_quantized(self, emb) -> None:
+        """The quantised index of ``emb`` by the scheme and the ``quantize`` route this retriever is set to."""
+        from .dense import DenseInt8Index, DenseUint8Index, quantize_asymmetric, quantize_symmetric
+        symmetric = self.quantization_method == "symmetric"  # any other value is the asymmetric scheme, like the reference's else branch (:449)
+        cls = DenseInt8Index if symmetric else DenseUint8Index
+        if self.quantize == "device":
+            self.corpus_embeddings_int8 = self.corpus_scales = None
+            self._index = None
+            self._index = cls.from_embeddings(emb, device=self.device)
+        else:
+            self.corpus_embeddings_int8, self.corpus_scales = (quantize_symmetric if symmetric else quantize_asymmetric)(emb)
+            self._index = cls(self.corpus_embeddings_int8, self.corpus_scales, device=self.device)
+
+    def _search_quantized(self, embs, k):
+        """Host (doc, score, count) of the quantised search for a list of f32 query vectors."""
+        from .dense import quantize_query_asymmetric, quantize_query_symmetric, stack_queries_f32
+        symmetric = self.quantization_method == "symmetric"
+        if self.quantize == "device":
+            q = stack_queries_f32(self._index, embs)
+            return self._index._host(self._index.search_f32_device(q, k) if symmetric else self._index.search_raw_device(q, k))
+        if symmetric:
+            qq = [quantize_query_symmetric(e) for e in embs]
+            return self._index.search(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), k)
+        qq = [quantize_query_asymmetric(e) for e in embs]
+        return self._index.search(np.stack([a for a, _ in qq]), np.stack([b for _, b in qq]), k)
+
+    def _score_quantized(self, embs, cand_doc, cand_count):
+        """Host f32[nq, m] scores of the candidate block for a list of f32 query vectors."""
+        from .dense import quantize_query_asymmetric, quantize_query_symmetric, stack_queries_f32
+        symmetric = self.quantization_method == "symmetric"
+        ix = self._index
+        if self.quantize == "device":
+            q = stack_queries_f32(ix, embs)
+            fn = ix.score_docs_f32_device if symmetric else ix.score_docs_raw_device
+            return ix._score_docs(cand_doc, cand_count, len(embs), lambda cd, cc: fn(q, cd, cc))
+        if symmetric:
+            qq = [quantize_query_symmetric(e) for e in embs]
+            return ix.score_docs(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), cand_doc, cand_count)
+        qq = [quantize_query_asymmetric(e) for e in embs]
+        return ix.score_docs(np.stack([a for a, _ in qq]), np.stack([b for _, b in qq]), cand_doc, cand_count)
 
     def synthetic_embeddings(self, num_docs: int) -> np.ndarray:
         """retriever_registry.py:409-433: cluster centres + 0.1 noise from the legacy NumPy stream seeded with 42, rows
@@ -187,21 +256,16 @@ class QuantizedEmbeddingRetriever:
         return self.query_embedding_from_seed(hash(query_text) % (2 ** 31))  # process-dependent, like the reference's
 
     def build_index_from_corpus(self, corpus: Dict[str, Dict]) -> None:
-        from .dense import DenseF32Index, DenseInt8Index, DenseUint8Index, quantize_asymmetric, quantize_symmetric
+        from .dense import DenseF32Index
         self.doc_ids = list(corpus.keys())
         emb = self.synthetic_embeddings(len(corpus))
-        if self.use_quantization and self.quantization_method == "symmetric":
-            self.corpus_embeddings_int8, self.corpus_scales = quantize_symmetric(emb)
-            self._index = DenseInt8Index(self.corpus_embeddings_int8, self.corpus_scales, device=self.device)
-        elif self.use_quantization:  # any other value is the asymmetric scheme, like the reference's else branch (:449)
-            self.corpus_embeddings_int8, self.corpus_scales = quantize_asymmetric(emb)
-            self._index = DenseUint8Index(self.corpus_embeddings_int8, self.corpus_scales, device=self.device)
+        if self.use_quantization:
+            self._build_quantized(emb)
         else:
             self.corpus_embeddings_fp32 = emb
             self._index = DenseF32Index(emb, device=self.device)
 
     def search(self, queries: Dict[str, str], top_k: int = 10) -> Dict[str, Dict[str, float]]:
-        from .dense import quantize_query_asymmetric, quantize_query_symmetric
         if self._index is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
@@ -210,12 +274,8 @@ class QuantizedEmbeddingRetriever:
             return results
         embs = [self._generate_query_embedding(text) for _, text in live]
         k = max(1, min(int(top_k), len(self.doc_ids)))
-        if self.use_quantization and self.quantization_method == "symmetric":
-            qq = [quantize_query_symmetric(e) for e in embs]
-            d, s, n = self._index.search(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), k)
-        elif self.use_quantization:
-            qq = [quantize_query_asymmetric(e) for e in embs]
-            d, s, n = self._index.search(np.stack([a for a, _ in qq]), np.stack([b for _, b in qq]), k)
+        if self.use_quantization:
+            d, s, n = self._search_quantized(embs, k)
         else:
             d, s, n = self._index.search(np.stack(embs), k)
         for i, (qid, _) in enumerate(live):
@@ -228,7 +288,6 @@ class QuantizedEmbeddingRetriever:
         the arithmetic of :meth:`search` (``srx_dense_score_docs_i8`` / ``_u8`` / ``_f32``).  No ``score > 0`` filter;
         ``{}`` for a qid without candidates; ``ValueError`` for an unknown doc id.  One batch, no cache."""
         from .backend import RowOfIds, scores_to_dicts
-        from .dense import quantize_query_asymmetric, quantize_query_symmetric
         if self._index is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         if getattr(self, "_rows", None) is None or self._rows.ids is not self.doc_ids:
@@ -237,12 +296,8 @@ class QuantizedEmbeddingRetriever:
         if not live:
             return results
         embs = [np.asarray(e, dtype=np.float32) for _, e, _ in live]
-        if self.use_quantization and self.quantization_method == "symmetric":
-            qq = [quantize_query_symmetric(e) for e in embs]
-            scores = self._index.score_docs(np.stack([a for a, _ in qq]), np.array([b for _, b in qq], dtype=np.float32), cand_doc, cand_count)
-        elif self.use_quantization:
-            qq = [quantize_query_asymmetric(e) for e in embs]
-            scores = self._index.score_docs(np.stack([a for a, _ in qq]), np.stack([b for _, b in qq]), cand_doc, cand_count)
+        if self.use_quantization:
+            scores = self._score_quantized(embs, cand_doc, cand_count)
         else:
             scores = self._index.score_docs(np.stack(embs), cand_doc, cand_count)
         return scores_to_dicts(results, live, scores)
@@ -268,7 +323,7 @@ class HybridRetriever:
 
     def __init__(self, model=None, sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted",
                  rrf_c: float = 60.0, candidates: Optional[int] = None, embedding_dim: int = 768, device: Optional[str] = None,
-                 k1: float = 1.2, b: float = 0.75, tile_log2: int = 14, rescore: bool = False, **kwargs):
+                 k1: float = 1.2, b: float = 0.75, tile_log2: int = 14, rescore: bool = False, quantize: str = "host", **kwargs):
         model = model or {}
         if not isinstance(model, dict):
             raise ValueError("hybrid retriever: model must be a dict {sparse: ..., dense: ...}")
@@ -290,7 +345,7 @@ class HybridRetriever:
             self.sparse = OptimizedBM25Retriever(method=sparse if sparse.lower() in _BM25_TYPES else "bm25", model=sparse, k1=k1, b=b,
                                                  device=device, tile_log2=tile_log2, cache_queries=False, **group)
         self.dense = QuantizedEmbeddingRetriever(method=dense if dense.lower() in ("dpr", "contriever", "splade") else "dpr",
-                                                 model=dense, embedding_dim=embedding_dim, device=self.sparse.device)
+                                                 model=dense, embedding_dim=embedding_dim, device=self.sparse.device, quantize=quantize)
         self.device = self.sparse.device
 
     @property
@@ -303,8 +358,8 @@ class HybridRetriever:
 
     def build_index_from_corpus(self, corpus: Dict[str, Dict], embeddings=None) -> None:
         """``embeddings``: f32[n_docs, dim], row i = the i-th corpus key; ``None`` = the dense mirror's simulated
-        vectors (what the reference's dense types index).  Either way the rows are quantised into one INT8 index."""
-        from .dense import DenseInt8Index, quantize_symmetric
+        vectors (what the reference's dense types index).  Either way the rows are quantised into one INT8 index -- on the
+        host, or with ``quantize="device"`` by ``DenseInt8Index.from_embeddings``."""
         self._refuse_sharded()
         if not corpus:
             raise ValueError("Empty corpus provided")
@@ -319,13 +374,40 @@ class HybridRetriever:
         d.embedding_dim = int(emb.shape[1])
         d.doc_ids = list(corpus.keys())
         d.use_quantization, d.quantization_method = True, "symmetric"
-        d.corpus_embeddings_int8, d.corpus_scales = quantize_symmetric(emb)
-        d._index = DenseInt8Index(d.corpus_embeddings_int8, d.corpus_scales, device=self.device)
+        d.device = self.device
+        d._build_quantized(emb)
+
+    def _live_query_vectors(self, queries, live, query_embeddings):
+        """The f32 vectors of the ``live`` (qid, text) pairs: a list of host rows -- or, for a 2-D block with
+        ``quantize="device"``, the block's live rows as they are (a device tensor stays on the device)."""
+        d = self.dense
+        if query_embeddings is None:
+            return [d._generate_query_embedding(text) for _, text in live]
+        if not isinstance(query_embeddings, dict):  # a 2-D block: row i belongs to the i-th key of ``queries``
+            block = query_embeddings
+            if tuple(block.shape) != (len(queries), d.embedding_dim):
+                raise ValueError(f"query_embeddings has shape {tuple(block.shape)}, expected ({len(queries)}, {d.embedding_dim})")
+            rows = [i for i, text in enumerate(queries.values()) if text]
+            if d.quantize == "device":
+                return block[rows]
+            block = block.cpu().numpy() if hasattr(block, "cpu") else np.asarray(block)  # the host quantisers take NumPy rows
+            return [np.asarray(block[i], dtype=np.float32) for i in rows]
+        embs = []
+        for qid, _ in live:
+            if qid not in query_embeddings:
+                raise ValueError(f"no query embedding for {qid!r}")
+            e = np.asarray(query_embeddings[qid], dtype=np.float32)
+            if e.shape != (d.embedding_dim,):
+                raise ValueError(f"query embedding of {qid!r} has shape {e.shape}, expected ({d.embedding_dim},)")
+            embs.append(e)
+        return embs
 
     def search(self, queries: Dict[str, str], top_k: int = 10, query_embeddings=None) -> Dict[str, Dict[str, float]]:
-        """``{qid: {doc_id: fused score}}`` in rank order.  ``query_embeddings``: ``{qid: f32[dim]}``; ``None`` = the dense
-        mirror's simulated query vectors (seeded by ``hash(text)``: they differ between processes, like the reference's)."""
-        from .dense import quantize_query_symmetric
+        """``{qid: {doc_id: fused score}}`` in rank order.  ``query_embeddings``: ``{qid: f32[dim]}``, or a 2-D tensor /
+        array whose row i belongs to the i-th key of ``queries`` (a float32 device tensor stays on the device with
+        ``quantize="device"``); ``None`` = the dense mirror's simulated query vectors (seeded by ``hash(text)``: they differ
+        between processes, like the reference's)."""
+        from .dense import quantize_queries_symmetric_device, quantize_query_symmetric, stack_queries_f32
         self._refuse_sharded()
         rescore = check_rescore_args(self.fusion, self.rescore)  # both are plain attributes
         if self.sparse.host is None or self.dense._index is None:
@@ -336,30 +418,21 @@ class HybridRetriever:
         live = [(qid, text) for qid, text in queries.items() if text]
         if k <= 0 or not live:
             return results
-        embs = []
-        for qid, text in live:
-            if query_embeddings is None:
-                e = self.dense._generate_query_embedding(text)
-            else:
-                if qid not in query_embeddings:
-                    raise ValueError(f"no query embedding for {qid!r}")
-                e = np.asarray(query_embeddings[qid], dtype=np.float32)
-                if e.shape != (self.dense.embedding_dim,):
-                    raise ValueError(f"query embedding of {qid!r} has shape {e.shape}, expected ({self.dense.embedding_dim},)")
-            embs.append(e)
-        qq = [quantize_query_symmetric(e) for e in embs]
-        q_i8, q_scale = np.stack([a for a, _ in qq]), np.array([s for _, s in qq], dtype=np.float32)
+        import torch
+        vecs = self._live_query_vectors(queries, live, query_embeddings)
+        if self.dense.quantize == "device":  # one stack, one upload (none for a device tensor), one quantisation launch
+            q_dev = quantize_queries_symmetric_device(stack_queries_f32(self.dense._index, vecs))[:2]
+        else:
+            qq = [quantize_query_symmetric(e) for e in vecs]
+            q_i8, q_scale = np.stack([a for a, _ in qq]), np.array([s for _, s in qq], dtype=np.float32)
+            q_dev = (torch.as_tensor(np.ascontiguousarray(q_i8, dtype=np.int8), device=self.device), torch.as_tensor(q_scale, device=self.device))
         q_ptr, q_term, q_w = encode_queries([text for _, text in live], self.sparse.host.vocabulary)
 
         def dense_search(kb):
-            import torch
-            return self.dense._index.search_device(torch.as_tensor(np.ascontiguousarray(q_i8, dtype=np.int8), device=self.device),
-                                                   torch.as_tensor(q_scale, device=self.device), kb)
+            return self.dense._index.search_device(*q_dev, kb)
 
         def dense_score(cand_doc, cand_count):
-            import torch
-            return self.dense._index.score_docs_device(torch.as_tensor(np.ascontiguousarray(q_i8, dtype=np.int8), device=self.device),
-                                                       torch.as_tensor(q_scale, device=self.device), cand_doc, cand_count)
+            return self.dense._index.score_docs_device(*q_dev, cand_doc, cand_count)
 
         doc, score, count = hybrid_search(self.sparse.dev, q_ptr, q_term, q_w, dense_search, cand, cand, k, self.fusion,
                                           (self.sparse_weight, self.dense_weight), self.rrf_c, rescore, dense_score)
