@@ -534,7 +534,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W_WAVES_PER_
         // release fence compiles to NOTHING here (a workgroup of one wave is its own scope), which let the last split read
         // lists that were still in flight (caught by bench.py's multi-stream parity check on C2).
         // This hand-off is outside the HIP memory model; it rests on three properties of gfx950, and
-        // tests/test_search_plans.py (split queries on several streams at once) is its regression guard:
+        // tests/test_search_plans.py (split queries on several streams at once) is its regression guard
+        // (tests/test_tier1_routes_gpu.py pins which units this kernel serves and which it flags for tier 2, with split plans):
         //   * global stores are counted in vmcnt, so vmcnt(0) means this wave's list stores have been acknowledged;
         //   * agent-scope relaxed stores write through the XCD's L2 to memory: an acknowledged store is visible device-wide;
         //   * agent-scope relaxed loads are coherent across the XCD L2s: the merging wave, on any XCD, reads memory, not a

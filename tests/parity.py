@@ -354,3 +354,171 @@ def dense_topk_rows(similarities, k):
         out_s[i, : len(c)] = s[i, c]
         out_n[i] = len(c)
     return out_d, out_s, out_n
+
+
+# ---- tier 1's hand-over rules, restated (csrc/wave_kernel.hip, csrc/sparse_rx.hip: search_ws) -----------------------------
+# After a search the caller's workspace still holds what tier 1 decided: ovf[items][ovf_words], one bit per (work item,
+# global unit index) that tier 1 left to tier 2, and the worklist work[0] (its length), work[1 ..] (the items on it).  The
+# route tests (test_tier1_routes_gpu.py) read both and compare them with tier1_routes below.
+W_MAXT = 64  # query terms tier 1 serves
+W_R = 12  # postings per lane per unit: a term's run of more than 3 LPT blocks does not fit the registers
+W_DUPCAP = 48  # multi-term resolution visits per unit (the 49th rolls the unit back)
+W_UNIT_MAX_DOCS = 49152
+BOUND_KS = (1, 10, 100, 1000)  # the ranks of the term_bound columns
+
+
+def search_ws(p, nq, k):
+    """search_ws of sparse_rx.hip: byte offsets of the regions of a search's workspace for plan `p`, and `end` (the first
+    byte behind the worklist; end + 256 = srx_search_workspace_bytes)."""
+    lists = nq * p["lists_per_q"]
+    items = p["items"]
+    w, off = {}, 0
+    for name, nbytes in (("cand_doc", lists * k * 4), ("cand_score", lists * k * 4), ("cand_count", lists * 4),
+                         ("ovf", items * p["ovf_words"] * 4), ("done", (nq - p["n_whole"]) * 4), ("work", (1 + items) * 4)):
+        w[name] = off
+        off += nbytes
+    w["end"] = off
+    return w
+
+
+def item_of(p, q, split):
+    """decode_item inverted: the work item of (query, split).  The first n_whole queries are one item each."""
+    if q < p["n_whole"]:
+        assert split == 0
+        return q
+    return p["n_whole"] + (q - p["n_whole"]) * p["n_splits"] + split
+
+
+def item_queries(p, nq):
+    """decode_item for every work item: (q i64[items], split i64[items], nsq i64[items])."""
+    it = np.arange(p["items"], dtype=np.int64)
+    j = np.maximum(it - p["n_whole"], 0)
+    whole = it < p["n_whole"]
+    q = np.where(whole, it, p["n_whole"] + j // p["n_splits"])
+    split = np.where(whole, 0, j % p["n_splits"])
+    nsq = np.where(whole, 1, p["n_splits"])
+    assert np.all(q < nq)
+    return q, split, nsq
+
+
+def bound_column_of(k):
+    """bound_column of srx_common.h: the column of term_bound valid for top-k k (-1: none)."""
+    return 0 if k <= 1 else 1 if k <= 10 else 2 if k <= 100 else 3 if k <= 1000 else -1
+
+
+def stored_values(indptr, data, doc_lengths, mode="bm25", val_dtype="f32", k1=1.2, b=0.75, avgdl=1.0):
+    """The value the index stores for every CSR entry: the oracle's fp32 impact (bm25) or the entry itself, through fp16
+    when the index keeps fp16 values (dot mode only)."""
+    data = np.asarray(data, np.float32)
+    if mode == "bm25":
+        from oracle import np_oracle
+        rows = np.repeat(np.arange(len(indptr) - 1), np.diff(np.asarray(indptr)))
+        return np_oracle.impacts_f32(data, rows, doc_lengths, k1, b, avgdl).astype(np.float32)
+    return data.astype(np.float16).astype(np.float32) if val_dtype == "f16" else data
+
+
+def tier1_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_tiles, k, p, term_bound=True, mode="bm25",
+                 val_dtype="f32", k1=1.2, b=0.75, avgdl=1.0):
+    """Tier 1's hand-over rules for every (work item, unit) of one search: which units it MUST flag for tier 2, which it
+    MUST serve itself, and which MAY go either way.  q = (q_ptr, q_term, q_weight) with the terms in the order the kernel
+    accumulates them; p = plan().  Returns a dict of
+      nt[items], all_t2[items]  -- nt > 64 or k > 112 (or a unit too large for 16-bit local ids): the item is on the
+                                   worklist when nt > 0 and its flag words stay 0;
+      in_range[items, n_super]  -- the unit belongs to the item's [su_lo, su_hi);
+      must_flag, must_serve, may [items, n_super] -- a partition of in_range for the items tier 1 serves (nt > 0):
+        must_flag : some term has ceil(cnt / 4) > 3 LPT blocks in the unit (LPT = 64 >> ceil(log2 nt)), or the unit needs
+                    sum over docs of (m_d - 1) >= 49 resolution visits (m_d = query terms with a non-zero stored value);
+        must_serve: not must_flag and k + E <= 256, E = docs of the unit with exact fp32 score > 0 and >= tau0 (the list
+                    takes at most one entry per such doc and tau never falls below tau0, the kernel's initial threshold);
+        may       : the rest -- whether the list has room depends on its state.
+      tau0[nq] (fp32)."""
+    from scipy.sparse import csr_matrix
+    import oracle
+    f = np.float32
+    indptr = np.asarray(indptr, np.int64)
+    indices = np.asarray(indices, np.int32)
+    data = np.asarray(data, np.float32)
+    idf = np.asarray(idf, np.float32)
+    q_ptr, q_term, q_w = (np.asarray(x) for x in q)
+    q_w = q_w.astype(np.float32)
+    nq = len(q_ptr) - 1
+    n_docs, V = len(indptr) - 1, len(idf)
+    unit_docs = unit_tiles << tile_log2
+    n_super = p["n_super"]
+    n_tiles = (n_docs + (1 << tile_log2) - 1) >> tile_log2
+    assert n_super == (n_tiles + unit_tiles - 1) // unit_tiles, "the plan is of another index"
+    sv = stored_values(indptr, data, doc_lengths, mode, val_dtype, k1, b, avgdl)
+    csc = csr_matrix((sv, indices, indptr), shape=(n_docs, V)).tocsc()  # explicit zeros stay: they are postings
+    csc.sort_indices()
+    bounds_on = bool(term_bound) and bound_column_of(k) >= 0 and not np.any(sv < 0)
+    K = BOUND_KS[bound_column_of(k)] if bounds_on else 0
+    sdata = sv if mode == "dot" else data  # the oracle computes the impact itself; in dot mode it gets the stored (fp16-exact) values
+
+    q_of, split_of, nsq_of = item_queries(p, nq)
+    items = p["items"]
+    nt_q = np.diff(q_ptr).astype(np.int64)
+    out = {"nt": nt_q[q_of], "in_range": np.zeros((items, n_super), bool), "tau0": np.zeros(nq, f)}
+    out["all_t2"] = (out["nt"] > W_MAXT) | (k > W1_KMAX) | (unit_docs > W_UNIT_MAX_DOCS)
+    per_q = {}
+    for qi in range(nq):
+        nt = int(nt_q[qi])
+        if nt == 0 or nt > W_MAXT or k > W1_KMAX or unit_docs > W_UNIT_MAX_DOCS:
+            continue
+        terms = q_term[q_ptr[qi]:q_ptr[qi + 1]]
+        w = q_w[q_ptr[qi]:q_ptr[qi + 1]]
+        lg = 0
+        while (1 << lg) < nt:
+            lg += 1
+        lpt = 64 >> lg
+        long_run = np.zeros(n_super, bool)
+        m = np.zeros(n_docs, np.int64)
+        tau0, neg = f(0.0), False
+        for t, wt in zip(terms, w):
+            docs = csc.indices[csc.indptr[t]:csc.indptr[t + 1]]
+            vals = csc.data[csc.indptr[t]:csc.indptr[t + 1]]
+            cnt = np.bincount(docs // unit_docs, minlength=n_super)
+            long_run |= (cnt + 3) // 4 > (W_R // 4) * lpt
+            np.add.at(m, docs[vals != 0], 1)
+            neg = neg or idf[t] < 0 or wt < 0
+            if bounds_on and idf[t] > 0 and wt > 0:
+                pos = np.sort(vals[vals > 0])[::-1]
+                bnd = pos[K - 1] if len(pos) >= K else f(0.0)
+                tau0 = max(tau0, f(0.0) + (f(bnd) * idf[t]) * f(wt))
+        tau0 = f(0.0) if neg else f(tau0)
+        out["tau0"][qi] = tau0
+        unit_of = np.arange(n_docs) // unit_docs
+        visits = np.bincount(unit_of, weights=np.maximum(m - 1, 0), minlength=n_super).astype(np.int64)
+        matched = np.bincount(unit_of, weights=(m > 0), minlength=n_super).astype(np.int64)
+        flag = long_run | (visits > W_DUPCAP)
+        E = matched.copy()
+        if np.any(~flag & (k + matched > W1_LCAP)):  # only then does the exact count matter: E <= matched
+            s = oracle.scores_given_order(indptr, indices, sdata, doc_lengths, idf, terms.astype(np.int32), w, k1, b, avgdl, tfidf=(mode == "dot"))
+            E = np.bincount(unit_of, weights=((s > 0) & (s >= tau0)), minlength=n_super).astype(np.int64)
+        per_q[qi] = (flag, ~flag & (k + E <= W1_LCAP))
+    must_flag = np.zeros((items, n_super), bool)
+    must_serve = np.zeros((items, n_super), bool)
+    for it in range(items):
+        lo = n_super * int(split_of[it]) // int(nsq_of[it])
+        hi = n_super * (int(split_of[it]) + 1) // int(nsq_of[it])
+        out["in_range"][it, lo:hi] = True
+        if int(q_of[it]) in per_q:
+            fl, srv = per_q[int(q_of[it])]
+            must_flag[it, lo:hi] = fl[lo:hi]
+            must_serve[it, lo:hi] = srv[lo:hi]
+    served_item = (~out["all_t2"] & (out["nt"] > 0))[:, None]
+    out["must_flag"], out["must_serve"] = must_flag, must_serve
+    out["may"] = out["in_range"] & served_item & ~must_flag & ~must_serve
+    return out
+
+
+def decode_routes(ws_bytes, p, nq, k):
+    """The flags and the worklist out of a workspace (a uint8 array) after a search: (ovf bool[items, 32 ovf_words] -- bit su
+    of item i --, the items on tier 2's worklist in list order, the list's length work[0])."""
+    w = search_ws(p, nq, k)
+    words = np.frombuffer(ws_bytes.tobytes(), dtype=np.uint32)
+    ovf = words[w["ovf"] // 4: w["ovf"] // 4 + p["items"] * p["ovf_words"]].reshape(p["items"], p["ovf_words"])
+    bits = ((ovf[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & 1).astype(bool).reshape(p["items"], -1)
+    work = words[w["work"] // 4: w["work"] // 4 + 1 + p["items"]].view(np.int32)
+    n = int(work[0])
+    assert 0 <= n <= p["items"], f"work[0] = {n} with {p['items']} items"
+    return bits, work[1:1 + n].tolist(), n
