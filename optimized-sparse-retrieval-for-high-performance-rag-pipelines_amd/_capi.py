@@ -1,5 +1,5 @@
-"""ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h and
-include/sparse_rx_quant.h).
+"""ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
+include/sparse_rx_quant.h and include/sparse_rx_filter.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -17,7 +17,8 @@ _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
-           "score_docs.hip", "dense_score.hip", "dense_quant.hip"]  # one translation unit each, compiled in parallel
+           "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip"]  # one translation unit each, compiled in parallel
+INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
@@ -110,6 +111,26 @@ QUANT_SYMBOLS = {
 }
 SRX_QUANT_NONFINITE, SRX_QUANT_DEGENERATE = 1, 2  # bits of the quantisers' flag word
 
+
+class DocFilterDesc(ctypes.Structure):
+    """``srx_doc_filter`` (include/sparse_rx_filter.h): a host struct of device pointers"""
+    _fields_ = [("bits", ctypes.c_void_p), ("n_filters", ctypes.c_int32), ("q_filter", ctypes.c_void_p)]
+
+
+# every symbol include/sparse_rx_filter.h declares (the fourth header of the same library)
+_FP = ctypes.POINTER(DocFilterDesc)
+FILTER_SYMBOLS = {
+    "srx_filter_words": (_I64, [_I64]),
+    "srx_filter_fill": (ctypes.c_int, [_I32, _VP, _I32, _I64, _I32, _VP]),
+    "srx_filter_set_docs": (ctypes.c_int, [_I32, _VP, _I64, _I64, _VP, _I64, _I32, _VP]),
+    "srx_filter_count": (ctypes.c_int, [_I32, _VP, _I32, _I64, _VP, _VP]),
+    "srx_search_filtered": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _FP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "srx_search_filtered_packed": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _FP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "srx_dense_search_f32_filtered": (ctypes.c_int, [_I32, _VP, _I64, _I32, _VP, _I32, _I32, _I64, _FP, _VP, _VP, _VP, _VP, _I64, _VP,
+                                                     ctypes.c_float]),
+    "srx_dense_search_u8_filtered": (ctypes.c_int, [_I32, _VP, _VP, _I64, _I32, _VP, _I32, _I32, _I64, _FP, _VP, _VP, _VP, _VP, _I64, _VP]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -126,10 +147,11 @@ def kernel_sources_sha256() -> str:
 
 
 def _deps():
-    return [os.path.join(CSRC_DIR, f) for f in SOURCES] + [os.path.join(CSRC_DIR, "srx_common.h"),
+    return [os.path.join(CSRC_DIR, f) for f in SOURCES] + [os.path.join(CSRC_DIR, "srx_common.h"), os.path.join(CSRC_DIR, "filter_common.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_rescore.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_quant.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_quant.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_filter.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -147,7 +169,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     for f in SOURCES:
         src, obj = os.path.join(CSRC_DIR, f), os.path.join(objdir, f.replace(".hip", ".o"))
         objs.append(obj)
-        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_hdr):
+        newest_src = max(os.path.getmtime(os.path.join(CSRC_DIR, x)) for x in [f, *INCLUDED_SOURCES.get(f, [])])
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(newest_src, newest_hdr):
             continue
         cmd = [hipcc, *HIPCC_FLAGS, f"-I{INCLUDE_DIR}", f"-I{CSRC_DIR}", "-c", "-o", obj, src]
         if verbose:
@@ -176,7 +199,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

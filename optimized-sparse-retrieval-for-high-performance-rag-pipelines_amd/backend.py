@@ -129,8 +129,18 @@ class SparseBackend:
         ids = self.host.doc_ids
         return {ids[int(i)]: float(s) for i, s in zip(idx, sc) if s > 0}
 
+    def doc_filter_spec(self, queries, allowed_docs, excluded_docs):
+        """:func:`doc_filter_spec` over this index's doc ids (None when both keywords are None); a sharded index refuses."""
+        if allowed_docs is None and excluded_docs is None:
+            return None
+        if self.sharded():
+            raise ValueError("allowed_docs / excluded_docs need the whole index on one GPU (a sharded search takes no doc filter)")
+        if getattr(self, "_rows", None) is None or self._rows.ids is not self.host.doc_ids:
+            self._rows = RowOfIds(self.host.doc_ids)
+        return doc_filter_spec(self._rows.row_of, queries, allowed_docs, excluded_docs)
+
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
-                     blank: str = "empty"):
+                     blank: str = "empty", filter: Optional["DocFilterSpec"] = None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
         in the caller's order, one batched search for all texts the cache does not hold (equal texts share one row).  What
         the call sites of the reference do differently is named here:
@@ -146,12 +156,19 @@ class SparseBackend:
 
         A row without in-vocabulary terms gives ``{}`` and is not cached (retrieval.py:237-238, :251-252).  ``top_k`` beyond
         the corpus asks for ``n_docs`` rows; ``top_k <= 0`` keeps nothing (the reference's ``argpartition(...)[:0]``), cache
-        hits aside."""
+        hits aside.
+
+        ``filter`` (:meth:`doc_filter_spec`): the search is restricted to each query's allowed docs (``srx_search_filtered``).
+        A filtered call neither reads nor writes the cache -- its key is the query text --, and equal texts share a row only
+        under the same filter row."""
+        if filter is not None:
+            cache = None
         k_eff = min(int(top_k), self.n_docs_total)  # any depth: search_arrays pages past the engine's 1024-row lists
         results: Dict[str, Dict[str, float]] = {}
         pending: Dict[str, List[str]] = {}  # cache key -> the qids waiting for it
         texts: List[str] = []
         keys: List[str] = []
+        frows: List[int] = []  # filtered: the filter row of every searched text
         for qid, text in queries.items():
             if not text or (blank == "whitespace" and not text.strip()):
                 results[qid] = {}
@@ -165,14 +182,22 @@ class SparseBackend:
                 results[qid] = self.to_dict(*hit)
                 continue
             results[qid] = {}  # keeps the caller's qid order; filled below
+            if filter is not None:
+                key = (key, filter.row_of_qid[qid])
             if key not in pending:
                 pending[key] = []
                 texts.append(text)
                 keys.append(key)
+                if filter is not None:
+                    frows.append(filter.row_of_qid[qid])
             pending[key].append(qid)
         if texts and k_eff > 0:
             q_ptr, q_term, q_weight = encode_queries(texts, self.host.vocabulary, order=order)
-            docs, scores, counts = self.search_arrays(q_ptr, q_term, q_weight, k_eff)
+            if filter is None:
+                docs, scores, counts = self.search_arrays(q_ptr, q_term, q_weight, k_eff)
+            else:
+                docs, scores, counts = self.dev.search(q_ptr, q_term, q_weight, k_eff, filter=filter.on_device(self.dev),
+                                                       q_filter=np.asarray(frows, dtype=np.int32))
             for i, key in enumerate(keys):
                 if q_ptr[i + 1] == q_ptr[i]:
                     continue
@@ -265,6 +290,55 @@ def candidate_block(row_of, queries, candidates):
         cand_doc[i, : len(r)] = r
         cand_count[i] = len(r)
     return results, live, cand_doc, cand_count
+
+
+class DocFilterSpec:
+    """The ``allowed_docs`` / ``excluded_docs`` keywords of one API call, resolved on the host: ``lists`` = one array of doc
+    rows per filter row, ``allow`` = the listed rows are the allowed ones (else the excluded ones), ``row_of_qid`` = every
+    qid's filter row (-1: not filtered)."""
+
+    def __init__(self, allow: bool, lists, row_of_qid):
+        self.allow, self.lists, self.row_of_qid = allow, lists, row_of_qid
+
+    def on_device(self, index):
+        """The :class:`~.filter.DocFilter` over ``index``'s rows (a DeviceIndex or a dense index of the same corpus)"""
+        from .filter import DocFilter
+        build = DocFilter.allow if self.allow else DocFilter.deny
+        base = int(index.doc_base)
+        return build([r + base for r in self.lists], index.n_docs, device=index.device, doc_base=base)
+
+
+def doc_filter_spec(row_of, queries, allowed_docs, excluded_docs) -> Optional[DocFilterSpec]:
+    """The two filter keywords of the API mirrors -> a :class:`DocFilterSpec`, or None when both are None.  Each keyword is a
+    sequence of doc ids (one filter for every query of the call) or a dict ``qid -> sequence`` (a qid missing from it is not
+    filtered).  Giving both, a bare string, or an unknown doc id raises ValueError (``row_of`` maps a doc id to its row)."""
+    if allowed_docs is None and excluded_docs is None:
+        return None
+    if allowed_docs is not None and excluded_docs is not None:
+        raise ValueError("give allowed_docs or excluded_docs, not both")
+    allow = allowed_docs is not None
+    what, given = ("allowed_docs", allowed_docs) if allow else ("excluded_docs", excluded_docs)
+    if isinstance(given, (str, bytes)):
+        raise ValueError(f"{what} must be a sequence of doc ids or a dict qid -> sequence, not one string")
+
+    def rows(ids, whose):
+        if isinstance(ids, (str, bytes)):
+            raise ValueError(f"{what}{whose} must be a sequence of doc ids, not one string")
+        try:
+            return np.asarray([row_of[d] for d in ids], dtype=np.int64)
+        except KeyError as e:
+            raise ValueError(f"unknown doc id {e.args[0]!r} in {what}{whose}") from None
+
+    if not isinstance(given, dict):
+        return DocFilterSpec(allow, [rows(given, "")], {qid: 0 for qid in queries})
+    lists, row_of_qid = [], {}
+    for qid in queries:
+        if qid in given:
+            row_of_qid[qid] = len(lists)
+            lists.append(rows(given[qid], f"[{qid!r}]"))
+        else:
+            row_of_qid[qid] = -1
+    return DocFilterSpec(allow, lists or [np.zeros(0, np.int64)], row_of_qid)
 
 
 def scores_to_dicts(results, live, scores):

@@ -3,6 +3,7 @@
 // merge.hip).
 
 #include "srx_common.h"
+#include "filter_common.h"
 
 // The integer dot products are one MFMA GEMM (v_mfma_i32_32x32x32_i8, exact); the two scalings are done in fp64 like
 // the reference's NumPy scalars (int32 * float32 -> float64), so the stored fp32 score is the reference's bit for bit.
@@ -756,7 +757,8 @@ namespace {
 // rows: f32 embeddings (u8_scale_min == nullptr) or uint8 rows de-quantized with u8_scale_min
 int dense_rows_search(const char *who, int32_t device, const void *rows, const float *u8_scale_min, int64_t n_docs, int32_t dim,
                       const float *queries, int32_t nq, int32_t k, int64_t doc_base, int32_t *out_doc, float *out_score,
-                      int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v, float score_offset) {
+                      int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v, float score_offset,
+                      const srx_doc_filter *filter = nullptr) {
     const float *emb = (const float *)rows;
     if (nq < 0 || n_docs <= 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "%s: need n_docs > 0, 1 <= k <= 1024", who);
     if (dim <= 0 || dim % 64 != 0 || dim > 64 * F32_MAXS)
@@ -779,7 +781,15 @@ int dense_rows_search(const char *who, int32_t device, const void *rows, const f
             hipLaunchKernelGGL(srx_dense_u8_scores_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, (const uint8_t *)rows,
                                u8_scale_min, n_docs, (int)dim, queries + (int64_t)q0 * dim, qb, w.rank.scores, w.rank.ld);
         w.rank.nq = qb;
-        const int rc = dense_rank_merge(device, stream_v, w.rank, srx_plain_rows(out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k, out_count + q0, k));
+        const srx_rows out = srx_plain_rows(out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k, out_count + q0, k);
+        int rc;
+        if (filter == nullptr) {
+            rc = dense_rank_merge(device, stream_v, w.rank, out);
+        } else {  // the same lists from the filtered rank kernel (filter.hip); the pass's queries are q0 .. of the call's
+            const DenseTopkJob &j = w.rank;
+            rc = srx_launch_filtered_topk(j.scores, j.ld, j.n_docs, j.nq, j.k, j.n_splits, j.doc_base, *filter, q0, j.cand, stream);
+            if (rc == SRX_OK) rc = srx_merge_impl(device, j.cand, j.nq, j.n_splits, j.k, 0, out, nullptr, 0, stream_v);
+        }
         if (rc != SRX_OK) return rc;
     }
     return SRX_OK;
@@ -799,4 +809,24 @@ SRX_API int srx_dense_search_u8(int32_t device, const uint8_t *corpus, const flo
     if (!corpus_scales) return fail(SRX_ERR_INVALID, "srx_dense_search_u8: null pointer%s");
     return dense_rows_search("srx_dense_search_u8", device, corpus, corpus_scales, n_docs, dim, queries, nq, k, doc_base, out_doc,
                              out_score, out_count, workspace, workspace_bytes, stream_v, 0.0f);
+}
+
+SRX_API int srx_dense_search_f32_filtered(int32_t device, const float *emb, int64_t n_docs, int32_t dim, const float *queries, int32_t nq,
+                                          int32_t k, int64_t doc_base, const srx_doc_filter *filter, int32_t *out_doc, float *out_score,
+                                          int32_t *out_count, void *workspace, int64_t workspace_bytes, void *stream_v, float score_offset) {
+    const int rc = srx_check_filter("srx_dense_search_f32_filtered", filter);
+    if (rc != SRX_OK) return rc;
+    return dense_rows_search("srx_dense_search_f32_filtered", device, emb, nullptr, n_docs, dim, queries, nq, k, doc_base, out_doc,
+                             out_score, out_count, workspace, workspace_bytes, stream_v, score_offset, filter);
+}
+
+SRX_API int srx_dense_search_u8_filtered(int32_t device, const uint8_t *corpus, const float *corpus_scales, int64_t n_docs, int32_t dim,
+                                         const float *queries, int32_t nq, int32_t k, int64_t doc_base, const srx_doc_filter *filter,
+                                         int32_t *out_doc, float *out_score, int32_t *out_count, void *workspace, int64_t workspace_bytes,
+                                         void *stream_v) {
+    const int rc = srx_check_filter("srx_dense_search_u8_filtered", filter);
+    if (rc != SRX_OK) return rc;
+    if (!corpus_scales) return fail(SRX_ERR_INVALID, "srx_dense_search_u8_filtered: null pointer%s");
+    return dense_rows_search("srx_dense_search_u8_filtered", device, corpus, corpus_scales, n_docs, dim, queries, nq, k, doc_base, out_doc,
+                             out_score, out_count, workspace, workspace_bytes, stream_v, 0.0f, filter);
 }

@@ -19,6 +19,7 @@
 //           (score desc, doc asc).  Queries that tier 1 or tier 2 finished on their own are skipped.
 
 #include "srx_common.h"
+#include "filter_common.h"
 
 thread_local char srx_g_err[512] = "";
 
@@ -256,12 +257,13 @@ SRX_API int64_t srx_search_workspace_bytes(const srx_index *ix, int32_t nq, int3
 }
 
 namespace {
-// The index as the kernels see it; without the score bounds for a search-after (they assume an unrestricted top-k) or on request.
-IndexView index_view(const srx_index *ix, bool after) {
+// The index as the kernels see it; without the score bounds for a restricted search -- a search-after, a filtered search -- (they
+// assume an unrestricted top-k: a threshold derived from a doc the search may not return would cut docs it may) or on request.
+IndexView index_view(const srx_index *ix, bool restricted) {
     const srx_index_desc &d = ix->d;
     IndexView v;
     v.term_ptr = d.term_ptr; v.post = d.post; v.post16 = d.post16; v.tile_skip = d.tile_skip; v.idf = d.idf;
-    v.term_bound = ((ix->opts.reserved & SRX_DBG_NO_TERM_BOUND) || after) ? nullptr : d.term_bound;
+    v.term_bound = ((ix->opts.reserved & SRX_DBG_NO_TERM_BOUND) || restricted) ? nullptr : d.term_bound;
     v.n_docs = d.n_docs; v.vocab = d.vocab; v.zero_block = d.n_blocks;
     v.tile_log2 = d.tile_log2; v.n_tiles = d.n_tiles; v.unit_tiles = d.unit_tiles;
     return v;
@@ -269,7 +271,7 @@ IndexView index_view(const srx_index *ix, bool after) {
 
 int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
                 int32_t k, const srx_rows &out, void *workspace, int64_t workspace_bytes, void *stream_v,
-                const int32_t *after_doc = nullptr, const float *after_score = nullptr) {
+                const int32_t *after_doc = nullptr, const float *after_score = nullptr, const srx_doc_filter *filter = nullptr) {
     if (!ix) return fail(SRX_ERR_INVALID, "srx_search: null index%s");
     if ((after_doc == nullptr) != (after_score == nullptr)) return fail(SRX_ERR_INVALID, "srx_search_after: after_doc and after_score go together%s");
     if (nq < 0 || k <= 0 || k > KMAX) return fail(SRX_ERR_INVALID, "srx_search: need nq >= 0 and 1 <= k <= 1024%s");
@@ -284,12 +286,13 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
         return fail(SRX_ERR_INVALID, "srx_search: this index keeps no canonical blocks: a unit other than the one it was built for cannot be served%s");
     if (w.lists > 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "srx_search: nq * splits overflows the grid%s");
 
-    // Everything goes to tier 2: by request, for a search-after (the tier-2 kernel applies the bound), and with another unit
-    // than the padded one (tier 1 needs the padded runs).
-    const bool tier2_only = (ix->opts.reserved & SRX_DBG_TIER2_ONLY) != 0 || after_score != nullptr || p.tpu != ix->d.unit_tiles;
+    // Everything goes to tier 2: by request, for a search-after or a filtered search (the tier-2 kernel applies the bound and
+    // the filter), and with another unit than the padded one (tier 1 needs the padded runs).
+    const bool restricted = after_score != nullptr || filter != nullptr;
+    const bool tier2_only = (ix->opts.reserved & SRX_DBG_TIER2_ONLY) != 0 || restricted || p.tpu != ix->d.unit_tiles;
     srx_score_launch sl;  // one descriptor of the search: tier 1 takes sl.w, tier 2 all of it
     srx_wave_launch &a = sl.w;
-    a.ix = index_view(ix, after_score != nullptr);
+    a.ix = index_view(ix, restricted);
     a.q_ptr = q_ptr; a.q_term = q_term; a.q_weight = q_weight;
     a.nq = nq; a.k = k; a.n_splits = p.n_splits; a.n_whole = p.n_whole; a.n_super = p.n_super;
     a.dbg = ix->opts.reserved | (tier2_only ? SRX_DBG_TIER2_ONLY : 0);
@@ -314,7 +317,11 @@ int search_impl(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, cons
     const int hint = ix->h_hint ? *(volatile int *)ix->h_hint : -1;
     const int64_t t2_full = w.items < 1024 ? w.items : 1024;
     const bool t2_small = hint == 0 && t2_full > 128 && !tier1_serves_nothing(a.ix, k, p.tpu, a.dbg);
-    SRX_TRY(srx_launch_score_kernel(sl, ix->d.val_type, (unsigned)(t2_small ? 128 : t2_full), stream));
+    const unsigned t2_grid = (unsigned)(t2_small ? 128 : t2_full);
+    if (filter == nullptr)
+        SRX_TRY(srx_launch_score_kernel(sl, ix->d.val_type, t2_grid, stream));
+    else  // the filtered instances (tier2_filter.hip): the same descriptor plus the rows
+        SRX_TRY(srx_launch_filtered_score_kernel(sl, {filter->bits, filter->q_filter, srx_filter_row_words(ix->d.n_docs)}, ix->d.val_type, t2_grid, stream));
     SRX_TRY(ix->prof.mark(2, stream));
     // merge (merge.hip): only the SPLIT queries [n_whole, nq) have lists to merge (an unsplit query's final row was written
     // by tier 1 or, when it had work for tier 2, by tier 2)
@@ -355,6 +362,25 @@ SRX_API int srx_search_after_packed(srx_index *ix, const int32_t *q_ptr, const i
     if (!out_packed || k <= 0 || !after_doc || !after_score) return fail(SRX_ERR_INVALID, "srx_search_after_packed: bad argument%s");
     return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_packed_rows<float>(out_packed, k), workspace, workspace_bytes, stream_v,
                        after_doc, after_score);
+}
+
+SRX_API int srx_search_filtered(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight, int32_t nq,
+                                int32_t k, const srx_doc_filter *filter, const int32_t *after_doc, const float *after_score,
+                                int32_t *out_doc, float *out_score, int32_t *out_count, void *workspace, int64_t workspace_bytes,
+                                void *stream_v) {
+    SRX_TRY(srx_check_filter("srx_search_filtered", filter));
+    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_plain_rows(out_doc, out_score, out_count, k), workspace,
+                       workspace_bytes, stream_v, after_doc, after_score, filter);
+}
+
+SRX_API int srx_search_filtered_packed(srx_index *ix, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight,
+                                       int32_t nq, int32_t k, const srx_doc_filter *filter, const int32_t *after_doc,
+                                       const float *after_score, int32_t *out_packed, void *workspace, int64_t workspace_bytes,
+                                       void *stream_v) {
+    SRX_TRY(srx_check_filter("srx_search_filtered_packed", filter));
+    if (!out_packed || k <= 0) return fail(SRX_ERR_INVALID, "srx_search_filtered_packed: bad argument%s");
+    return search_impl(ix, q_ptr, q_term, q_weight, nq, k, srx_packed_rows<float>(out_packed, k), workspace, workspace_bytes, stream_v,
+                       after_doc, after_score, filter);
 }
 
 SRX_API int srx_profile_read(srx_index *ix, float *h_ms4) {

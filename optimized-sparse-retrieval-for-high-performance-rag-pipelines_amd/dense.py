@@ -10,6 +10,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _capi
+from .filter import q_filter_to_device, resolve_filter
 from .index import (_candidate_block, _check_k, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, rows_to_dict,
                     validate_candidates)
 
@@ -227,9 +228,11 @@ class _DenseIndex:
         """Row length rounded up to the 64 columns the f32 / uint8 kernels step by."""
         return _pad64(self.dim, engine)
 
-    def _search_device(self, queries, dtype, k: int, *extra):
+    def _search_device(self, queries, dtype, k: int, *extra, filter=None, q_filter=None):
         """k check, the query block zero-padded to ``dim_pad``, the output triple and the workspace, then the class's
-        ``_launch(L, q, nq, k, out, ws, stream, *extra)`` -> the entry point's return code.  An empty batch launches nothing."""
+        ``_launch(L, q, nq, k, out, ws, stream, *extra)`` -> the entry point's return code.  An empty batch launches nothing.
+        With a ``filter`` (a :class:`~.filter.DocFilter` over this index's rows; ``q_filter`` int32 device tensor [nq] or None)
+        the class's ``_launch_filtered(L, q, nq, k, out, ws, stream, fdesc, *extra)`` (include/sparse_rx_filter.h)."""
         torch = _torch()
         _check_k(k)
         nq = int(queries.shape[0])
@@ -240,8 +243,23 @@ class _DenseIndex:
             if nq == 0:
                 return out
             ws = _grow_ws(torch, self, _capi.check(getattr(L, self._workspace_fn)(nq, self.n_docs, k), self._workspace_fn))
-            _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), self._entry)
+            fdesc, keep = resolve_filter(self, filter, q_filter, nq)  # keep: alive until the call has been issued
+            if fdesc is None:
+                _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), self._entry)
+            else:
+                _capi.check(self._launch_filtered(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), fdesc, *extra), self._entry + "_filtered")
         return out
+
+    def _launch_filtered(self, *args):
+        raise ValueError(f"{type(self).__name__} has no filtered search")
+
+    def _host_q_filter(self, filter, q_filter, nq: int):
+        """The host-array doors: ``q_filter`` validated and uploaded (None without a filter)"""
+        if filter is None:
+            if q_filter is not None:
+                raise ValueError("q_filter picks rows of a filter: it needs filter=")
+            return None
+        return q_filter_to_device(filter.for_index(self), q_filter, nq)
 
     def _padded(self, torch, queries, dtype):
         q = torch.zeros((int(queries.shape[0]), self.dim_pad), dtype=dtype, device=self.device)
@@ -353,8 +371,13 @@ class DenseInt8Index(_DenseIndex):
         q, qs, _ = quantize_queries_symmetric_device(queries_f32.to(self.device))
         return self.score_docs_device(q, qs, cand_doc, cand_count, out)
 
-    def search_device(self, queries_int8, query_scales, k: int):
-        """queries i8[nq, dim] + f32[nq] on the device -> (doc i32[nq,k], score f32[nq,k], count i32[nq]); asynchronous."""
+    def search_device(self, queries_int8, query_scales, k: int, filter=None, q_filter=None):
+        """queries i8[nq, dim] + f32[nq] on the device -> (doc i32[nq,k], score f32[nq,k], count i32[nq]); asynchronous.
+        A ``filter`` raises ValueError: the fused screen of this search takes its thresholds from a sample of ALL docs, so a
+        doc filter is not a test that can be added to it (filter the f32 or the uint8 index)."""
+        if filter is not None or q_filter is not None:
+            raise ValueError("the INT8 dense search takes no doc filter (its screen thresholds come from a sample of all docs): "
+                             "use DenseF32Index or DenseUint8Index")
         return self._search_device(queries_int8, _torch().int8, k, query_scales)
 
     def _launch(self, L, q, nq, k, out, ws, stream, query_scales):
@@ -446,16 +469,25 @@ class DenseUint8Index(_DenseIndex):
         """:meth:`score_docs_device` for RAW query vectors, as :meth:`search_raw_device`."""
         return self.score_docs_device(quantize_queries_asymmetric_device(queries_f32.to(self.device), codes=False)[2], cand_doc, cand_count, out)
 
-    def search_device(self, queries_f32, k: int):
-        return self._search_device(queries_f32, _torch().float32, k)
+    def search_device(self, queries_f32, k: int, filter=None, q_filter=None):
+        """De-quantized queries f32[nq, dim] on the device; ``filter`` / ``q_filter`` as ``DeviceIndex.search_device``
+        (``srx_dense_search_u8_filtered``)."""
+        return self._search_device(queries_f32, _torch().float32, k, filter=filter, q_filter=q_filter)
+
+    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc):
+        return L.srx_dense_search_u8_filtered(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad,
+                                              _ptr(q), nq, k, self.doc_base, fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws),
+                                              ws.numel(), stream)
 
     def _launch(self, L, q, nq, k, out, ws, stream):
         return L.srx_dense_search_u8(self.device.index or 0, _ptr(self.corpus), _ptr(self.scales), self.n_docs, self.dim_pad, _ptr(q),
                                      nq, k, self.doc_base, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream)
 
-    def search(self, queries_uint8: np.ndarray, query_scales: np.ndarray, k: int):
-        """queries u8[nq, dim] + f32[nq, 2] (scale, min) as the reference's search builds them (:486-491); host arrays out."""
-        return self._host(self.search_device(self._queries_to_device(queries_uint8, query_scales), k))
+    def search(self, queries_uint8: np.ndarray, query_scales: np.ndarray, k: int, filter=None, q_filter=None):
+        """queries u8[nq, dim] + f32[nq, 2] (scale, min) as the reference's search builds them (:486-491); host arrays out.
+        ``q_filter``: a host sequence of row numbers, validated here."""
+        q = self._queries_to_device(queries_uint8, query_scales)
+        return self._host(self.search_device(q, k, filter=filter, q_filter=self._host_q_filter(filter, q_filter, int(q.shape[0]))))
 
     def _queries_to_device(self, queries_uint8, query_scales):
         """The de-quantized f32 query block on the device"""
@@ -567,16 +599,23 @@ class DenseF32Index(_DenseIndex):
             self._max_norm = best ** 0.5
         return self._max_norm
 
-    def search_device(self, queries, k: int, score_offset: float = 0.0):
-        """Top-k of (score + score_offset) > 0 per query (include/sparse_rx.h); the returned scores carry the offset."""
-        return self._search_device(queries, _torch().float32, k, score_offset)
+    def search_device(self, queries, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+        """Top-k of (score + score_offset) > 0 per query (include/sparse_rx.h); the returned scores carry the offset.
+        ``filter`` / ``q_filter`` as ``DeviceIndex.search_device`` (``srx_dense_search_f32_filtered``)."""
+        return self._search_device(queries, _torch().float32, k, score_offset, filter=filter, q_filter=q_filter)
+
+    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc, score_offset):
+        return L.srx_dense_search_f32_filtered(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k,
+                                               self.doc_base, fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream,
+                                               float(score_offset))
 
     def _launch(self, L, q, nq, k, out, ws, stream, score_offset):
         return L.srx_dense_search_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k, self.doc_base,
                                       _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream, float(score_offset))
 
-    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0):
-        return self._host(self.search_device(self._queries_to_device(queries), k, score_offset))
+    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+        q = self._queries_to_device(queries)
+        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=self._host_q_filter(filter, q_filter, int(q.shape[0]))))
 
     def _queries_to_device(self, queries):
         q = np.ascontiguousarray(queries, dtype=np.float32)

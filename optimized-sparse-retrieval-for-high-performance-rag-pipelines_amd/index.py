@@ -13,6 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
+from .filter import DocFilter, q_filter_to_device, resolve_filter
 
 BLOCK_PAD = 256  # SRX_BLOCK_PAD in include/sparse_rx.h: all-sentinel blocks behind the last run
 _TOKEN_RE = re.compile(r"\b\w+\b")
@@ -604,26 +605,31 @@ class DeviceIndex:
     def workspace_bytes(self, nq: int, k: int) -> int:
         return _capi.check(_capi.lib().srx_search_workspace_bytes(self._h, nq, k), "srx_search_workspace_bytes")
 
-    def search_device(self, q_ptr, q_term, q_weight, k: int, out=None, after=None):
+    def search_device(self, q_ptr, q_term, q_weight, k: int, out=None, after=None, filter=None, q_filter=None):
         """Batched search on device tensors (q_ptr i32[nq+1], q_term i32, q_weight f32).
         Returns (doc i32[nq,k], score f32[nq,k], count i32[nq]) device tensors; asynchronous on the current stream.
         Precondition (NOT checked here, the tensors never leave the device): q_ptr starts at 0 and is non-decreasing,
         0 <= q_term < vocab, no term twice inside a query -- ``validate_queries`` / ``search`` check host batches.
         ``after`` = (doc i32[nq] GLOBAL ids, score f32[nq]) device tensors: ``srx_search_after`` -- only docs ranked
-        strictly after that row in (score desc, doc asc) order (the next page of a ranking deeper than max_k)."""
-        return self._search(False, q_ptr, q_term, q_weight, k, out, after, None, None)
+        strictly after that row in (score desc, doc asc) order (the next page of a ranking deeper than max_k).
+        ``filter`` = a :class:`~.filter.DocFilter` over this index's rows, ``q_filter`` = None or an int32 device tensor [nq]
+        (the filter row of every query; -1: not filtered; values outside [-1, n_filters) are a precondition violation):
+        ``srx_search_filtered`` -- the ranking of the allowed docs alone, exact, ``after`` included."""
+        return self._search(False, q_ptr, q_term, q_weight, k, out, after, None, None, filter, q_filter)
 
-    def search_packed_device(self, q_ptr, q_term, q_weight, k: int, out=None, stream=None, workspace=None, after=None):
+    def search_packed_device(self, q_ptr, q_term, q_weight, k: int, out=None, stream=None, workspace=None, after=None, filter=None,
+                             q_filter=None):
         """``srx_search_packed``: the same search, each query's result written as one row
         [k doc ids][k score bit patterns][count] of ``out`` (i32[nq, 2k+1], contiguous) -- the exchange format of the
         sharded search, so no packing kernel runs.  Returns ``out``.  ``stream`` (a torch stream, default: the current
         one) and ``workspace`` (a uint8 tensor of ``workspace_bytes`` bytes, default: the index's own) let several
         searches of one index be in flight on different streams."""
-        return self._search(True, q_ptr, q_term, q_weight, k, out, after, stream, workspace)
+        return self._search(True, q_ptr, q_term, q_weight, k, out, after, stream, workspace, filter, q_filter)
 
-    def _search(self, packed: bool, q_ptr, q_term, q_weight, k: int, out, after, stream, workspace):
+    def _search(self, packed: bool, q_ptr, q_term, q_weight, k: int, out, after, stream, workspace, filter=None, q_filter=None):
         """The one body of :meth:`search_device` and :meth:`search_packed_device`: k check, output, workspace, stream, then
-        ``srx_search[_after][_packed]`` -- the four entry points differ in the bound row and in the output pointers."""
+        ``srx_search[_after][_packed]`` -- the four entry points differ in the bound row and in the output pointers -- or,
+        with a filter, ``srx_search_filtered[_packed]`` (the filter, then the bound row or two nulls)."""
         torch = _torch()
         nq = q_ptr.numel() - 1
         _check_k(k)
@@ -639,7 +645,11 @@ class DeviceIndex:
                 workspace = _grow_ws(torch, self, self.workspace_bytes(nq, k), 1 << 20)
             sp = stream.cuda_stream if stream is not None else _stream_ptr(torch, self.device)
             name = "srx_search_packed" if packed else "srx_search"
-            if after is None:
+            fdesc, keep = resolve_filter(self, filter, q_filter, nq)  # keep: alive until the call below has been issued
+            if fdesc is not None:
+                name = name.replace("srx_search", "srx_search_filtered")
+                fn, bound = getattr(_capi.lib(), name), (fdesc, *(_after_ptrs(torch, after, nq) if after is not None else (None, None)))
+            elif after is None:
                 fn, bound = getattr(_capi.lib(), name), ()
             else:
                 fn, bound = getattr(_capi.lib(), name.replace("srx_search", "srx_search_after")), _after_ptrs(torch, after, nq)
@@ -651,11 +661,20 @@ class DeviceIndex:
     def validate_queries(self, q_ptr: np.ndarray, q_term: np.ndarray, q_weight: np.ndarray) -> None:
         validate_query_batch(q_ptr, q_term, q_weight, self.vocab)
 
-    def search(self, q_ptr: np.ndarray, q_term: np.ndarray, q_weight: np.ndarray, k: int):
+    def search(self, q_ptr: np.ndarray, q_term: np.ndarray, q_weight: np.ndarray, k: int, filter=None, q_filter=None):
         """Host arrays in, host arrays out (doc, score, count).  The batch is validated first (``validate_queries``);
         ``search_device`` trusts its device tensors.  Any k >= 1: a ranking deeper than the engine's list capacity
-        (``max_k`` = 1024) is paged with ``srx_search_after`` (:func:`deep_search`)."""
-        return search_host_batch(self.search_device, q_ptr, q_term, q_weight, k, self.vocab, self.device)
+        (``max_k`` = 1024) is paged with ``srx_search_after`` (:func:`deep_search`).  ``filter`` / ``q_filter`` (a host
+        sequence of nq row numbers, validated here) as in :meth:`search_device`; the paging carries them."""
+        if filter is None and q_filter is None:
+            return search_host_batch(self.search_device, q_ptr, q_term, q_weight, k, self.vocab, self.device)
+        if not isinstance(filter, DocFilter):
+            raise ValueError("filter must be a DocFilter (q_filter picks its rows)")
+        qf = q_filter_to_device(filter.for_index(self), q_filter, len(q_ptr) - 1)
+
+        def filtered(qp, qt, qw, kk, after=None):
+            return self.search_device(qp, qt, qw, kk, after=after, filter=filter, q_filter=qf)
+        return search_host_batch(filtered, q_ptr, q_term, q_weight, k, self.vocab, self.device)
 
     # -- scores of given docs ------------------------------------------------------------------------------
     def score_docs_device(self, q_ptr, q_term, q_weight, cand_doc, cand_count=None, out=None):
@@ -986,7 +1005,7 @@ def check_rescore_args(mode, rescore) -> bool:
 
 
 def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, ka: int, kb: int, k: int, mode: str, weights,
-                  rrf_c: float, rescore: bool = False, dense_score=None):
+                  rrf_c: float, rescore: bool = False, dense_score=None, filter=None, q_filter=None):
     """The hybrid pipeline of the API mirrors: sparse search of a host CSR batch on ``index`` (``ka`` rows per query),
     ``dense_search(kb)`` -> the dense side's device triple for the same queries, ``fuse_topk_device``; the three steps
     stay on the device, then one synchronisation and the copy back (:func:`search_host_batch`).  Returns host (doc, score, count).
@@ -994,13 +1013,16 @@ def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, k
     ``rescore=True`` (weighted fusion only) completes both lists before they are fused, five steps on the device: the two
     searches, ``index.score_docs_device`` over the dense list's rows, ``dense_score(cand_doc, cand_count)`` -> the dense
     side's f32[nq, ka] scores of the sparse list's rows, ``fuse_scored_device``.  The fused score of a returned doc then
-    does not depend on ``ka`` / ``kb``."""
+    does not depend on ``ka`` / ``kb``.
+
+    ``filter`` / ``q_filter`` (device tensor) restrict the sparse search as in ``DeviceIndex.search_device``; the caller's
+    ``dense_search`` carries the same filter itself, so the fused list is that of the two filtered lists."""
     check_fuse_args(mode, weights, rrf_c)
     if check_rescore_args(mode, rescore) and dense_score is None:
         raise ValueError("hybrid_search: rescore=True needs dense_score")
 
     def fused(qp, qt, qw, kk):
-        a, b = index.search_device(qp, qt, qw, ka), dense_search(kb)
+        a, b = index.search_device(qp, qt, qw, ka, filter=filter, q_filter=q_filter), dense_search(kb)
         if not rescore:
             return fuse_topk_device(a, b, kk, mode=mode, weights=weights, rrf_c=rrf_c)
         b_other = index.score_docs_device(qp, qt, qw, b[0], b[2])

@@ -46,9 +46,14 @@ class _SparseRetrieverBase(SparseIndexViews):
     def _upload(self):
         self._be.upload(self.mode, self.k1, self.b)
 
-    def search(self, queries: Dict[str, str], top_k: int = 10) -> Dict[str, Dict[str, float]]:
+    def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None) -> Dict[str, Dict[str, float]]:
+        """``allowed_docs`` / ``excluded_docs`` (no reference counterpart): as ``RetrievalService.search_bm25`` -- the top
+        ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call."""
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
+        if spec is not None:
+            return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec)
         # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional
         return self._be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock,
                                      strip_key=self.strip_cache_key, blank="empty")
@@ -402,12 +407,18 @@ class HybridRetriever:
             embs.append(e)
         return embs
 
-    def search(self, queries: Dict[str, str], top_k: int = 10, query_embeddings=None) -> Dict[str, Dict[str, float]]:
-        """``{qid: {doc_id: fused score}}`` in rank order.  ``query_embeddings``: ``{qid: f32[dim]}``, or a 2-D tensor /
+    def search(self, queries: Dict[str, str], top_k: int = 10, query_embeddings=None, *, allowed_docs=None,
+               excluded_docs=None) -> Dict[str, Dict[str, float]]:
+        """``{qid: {doc_id: fused score}}`` in rank order.  ``allowed_docs`` / ``excluded_docs`` raise ``ValueError``: this
+        retriever's dense side is the INT8 engine, whose search takes no doc filter (``RetrievalService.search_hybrid``
+        filters both sides of an f32 hybrid).  ``query_embeddings``: ``{qid: f32[dim]}``, or a 2-D tensor /
         array whose row i belongs to the i-th key of ``queries`` (a float32 device tensor stays on the device with
         ``quantize="device"``); ``None`` = the dense mirror's simulated query vectors (seeded by ``hash(text)``: they differ
         between processes, like the reference's)."""
         from .dense import quantize_queries_symmetric_device, quantize_query_symmetric, stack_queries_f32
+        if allowed_docs is not None or excluded_docs is not None:
+            raise ValueError("HybridRetriever takes no doc filter: its dense side is the INT8 engine, whose screen thresholds come "
+                             "from a sample of all docs (use RetrievalService.search_hybrid)")
         self._refuse_sharded()
         rescore = check_rescore_args(self.fusion, self.rescore)  # both are plain attributes
         if self.sparse.host is None or self.dense._index is None:

@@ -96,15 +96,25 @@ class RetrievalService(SparseIndexViews):
             self.query_cache.clear()
 
     # -- search -----------------------------------------------------------------------------------------
-    def search_bm25(self, queries: Dict[str, str], top_k: int = 10) -> Dict[str, Dict[str, float]]:
-        """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries."""
+    def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None,
+                    excluded_docs=None) -> Dict[str, Dict[str, float]]:
+        """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
+
+        ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
+        out of it, the named docs -- a sequence of doc ids for every query of the call, or a dict ``qid -> sequence`` (a qid
+        missing from it is not filtered).  The result is the top ``top_k`` OF THE ALLOWED DOCS, exact
+        (``srx_search_filtered``), not a filtered top list.  Giving both, or an unknown doc id, raises ``ValueError``; a
+        filtered call neither reads nor writes the query cache; a sharded index refuses."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
+        spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
             self._upload()  # k1 / b are plain attributes on the reference (:116-117): impacts depend on them
         # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on
+        if spec is not None:
+            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec)
         return self._be.search_dicts(queries, top_k, order="term", cache=self.query_cache, lock=self.cache_lock, strip_key=True,
                                      blank="whitespace")
 
@@ -135,7 +145,8 @@ class RetrievalService(SparseIndexViews):
         self.embedding_index = e
         self._dense = DenseF32Index(e, device=self.device)  # streams a memory map to the device in <= 64 MB chunks
 
-    def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0) -> List[Dict]:
+    def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
+                         excluded_docs=None) -> List[Dict]:
         """retrieval.py:402-436: ``np.dot(embedding_index, query_vector)`` + top-k on the GPU (``srx_dense_search_f32``),
         the ``min_score`` cut and the ``[{"doc_id", "score"}]`` result as in the reference.
 
@@ -145,11 +156,16 @@ class RetrievalService(SparseIndexViews):
         thresholds admit negative scores, :425-427) a second pass shifts the scores by a bound on the largest |score| so
         that every doc is rankable; its k rows are re-scored on the host with ``np.dot`` (fp32, the reference's own
         expression) and re-ranked, so the shift never shows in the result.  The shift coarsens that pass's ranking to
-        ulp(offset): docs whose true scores differ by less can swap places at the k-th boundary (scores <= 0 only)."""
+        ulp(offset): docs whose true scores differ by less can swap places at the k-th boundary (scores <= 0 only).
+
+        ``allowed_docs`` / ``excluded_docs``: a sequence of doc ids, as in :meth:`search_bm25`; both passes rank the allowed
+        docs alone (``srx_dense_search_f32_filtered``)."""
         self._ensure_dense()
         q = np.asarray(query_vector, dtype=np.float32)
         kk = max(1, min(int(k), self._dense.n_docs))
-        d, s, n = self._dense.search(q, kk)
+        flt = self._dense_filter({"q": None}, allowed_docs, excluded_docs)
+        flt = {} if flt is None else {"filter": flt[0]}
+        d, s, n = self._dense.search(q, kk, **flt)
         if min_score > 0 or int(n[0]) == kk:
             idx, sc = d[0, : int(n[0])].astype(np.int64), s[0, : int(n[0])]
         else:
@@ -157,7 +173,7 @@ class RetrievalService(SparseIndexViews):
             # the most fp32 resolution for the ranking (the shifted scores are only used to pick the k rows)
             bound = float(np.linalg.norm(q.astype(np.float64))) * self._dense.max_row_norm()
             offset = bound * 1.001 + 1e-30
-            d, s, n = self._dense.search(q, kk, score_offset=offset)
+            d, s, n = self._dense.search(q, kk, score_offset=offset, **flt)
             idx = d[0, : int(n[0])].astype(np.int64)
             sc = np.dot(self.embedding_index[idx], q).astype(np.float32)  # the reference's fp32 expression on the k rows
             order = np.argsort(-sc, kind="stable")
@@ -172,6 +188,17 @@ class RetrievalService(SparseIndexViews):
                 results.append({"doc_id": str(int(i)), "score": float(score)})
         return results
 
+    def _dense_filter(self, queries, allowed_docs, excluded_docs):
+        """The two filter keywords as (DocFilter over the embedding rows, spec), or None when both are None"""
+        if allowed_docs is None and excluded_docs is None:
+            return None
+        if self.host is not None:
+            spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
+        else:  # embeddings without a BM25 index: docs are named by their row number
+            from .backend import RowOfIds, doc_filter_spec
+            spec = doc_filter_spec(RowOfIds.numbered(self._dense.n_docs).row_of, queries, allowed_docs, excluded_docs)
+        return spec.on_device(self._dense), spec
+
     def _ensure_dense(self) -> None:
         if getattr(self, "_dense", None) is None and self.embedding_path and os.path.exists(str(self.embedding_path)) and self.doc_ids:
             n = len(self.doc_ids)
@@ -182,7 +209,8 @@ class RetrievalService(SparseIndexViews):
 
     def search_hybrid(self, queries: Dict[str, str], query_vectors: Dict[str, np.ndarray], top_k: int = 10, *,
                       sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted", rrf_c: float = 60.0,
-                      candidates: Optional[int] = None, rescore: bool = False) -> Dict[str, Dict[str, float]]:
+                      candidates: Optional[int] = None, rescore: bool = False, allowed_docs=None,
+                      excluded_docs=None) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -199,7 +227,9 @@ class RetrievalService(SparseIndexViews):
         query; ``top_k <= 0`` gives ``{}`` per query.  ``top_k`` > 1024 raises ``ValueError``: a fused ranking deeper
         than the engine's lists is not paged, and a silently shorter list would be worse than an error.  With one weight
         0 the result is the other side's set, but equal normalised scores rank by doc id.  The query cache is not used.
-        Needs the whole index on one GPU."""
+        Needs the whole index on one GPU.
+        ``allowed_docs`` / ``excluded_docs`` as in :meth:`search_bm25`: the filter goes to both sides, so the fused list is
+        the fusion of the two FILTERED top lists (``rescore=True`` included: every doc of either list is an allowed one)."""
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
         rescore = check_rescore_args(fusion, rescore)
@@ -224,17 +254,23 @@ class RetrievalService(SparseIndexViews):
         if (self.k1, self.b) != self._built_k1b:
             self._upload()
         q_ptr, q_term, q_weight = encode_queries([text for _, text in live], self.host.vocabulary)
+        flt = {}
+        fs = self._dense_filter(queries, allowed_docs, excluded_docs)  # one DocFilter serves both sides: same rows, same device
+        if fs is not None:
+            import torch
+            q_rows = np.asarray([fs[1].row_of_qid[qid] for qid, _ in live], dtype=np.int32)
+            flt = {"filter": fs[0], "q_filter": torch.as_tensor(q_rows, device=self._dense.device)}
 
         def dense_search(kb):
             import torch
-            return self._dense.search_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), kb)
+            return self._dense.search_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), kb, **flt)
 
         def dense_score(cand_doc, cand_count):
             import torch
             return self._dense.score_docs_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), cand_doc, cand_count)
 
         doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
-                                          (sparse_weight, dense_weight), rrf_c, rescore, dense_score)
+                                          (sparse_weight, dense_weight), rrf_c, rescore, dense_score, **flt)
         for i, (qid, _) in enumerate(live):
             results[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return results
