@@ -5,7 +5,7 @@ from ._capi import SparseRxError, SparseRxUnavailable, build_library
 from .index import DeviceIndex, HostBatchPipeline, HostIndex, build_host_index, encode_queries, fuse_scored_device, fuse_topk_device, merge_topk_device, tokenize, validate_candidates
 from .service import RetrievalService
 from .registry import HybridRetriever, OptimizedBM25Retriever, OptimizedRetriever, QuantizedEmbeddingRetriever, RetrieverRegistry, load_index_npz, save_index_npz
-from .dense import (DenseF32Index, DenseInt8Index, DenseUint8Index, QuantizedEmbeddingIndex, quantize_asymmetric,
+from .dense import (DenseF32Index, DenseHalfIndex, DenseInt8Index, DenseUint8Index, QuantizedEmbeddingIndex, quantize_asymmetric,
                     quantize_asymmetric_device, quantize_queries_asymmetric_device, quantize_queries_symmetric_device,
                     quantize_query_asymmetric, quantize_query_symmetric, quantize_symmetric, quantize_symmetric_device)
 from .distributed import (ShardedSearcher, shard_range, global_df, global_avgdl, global_term_bounds, bm25_idf_from_df,
@@ -16,7 +16,7 @@ from .filter import DocFilter
 __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", "build_host_index", "encode_queries", "merge_topk_device", "fuse_topk_device", "fuse_scored_device", "validate_candidates", "HybridRetriever",
            "tokenize", "build_library", "SparseRxError", "SparseRxUnavailable", "_capi", "ShardedSearcher", "shard_range",
            "global_df", "global_avgdl", "global_term_bounds", "bm25_idf_from_df", "build_sharded_host_index", "SparseBackend", "DocFilter", "OptimizedBM25Retriever", "OptimizedRetriever", "QuantizedEmbeddingRetriever", "RetrieverRegistry",
-           "load_index_npz", "save_index_npz", "DenseF32Index", "DenseInt8Index", "DenseUint8Index", "QuantizedEmbeddingIndex", "quantize_symmetric",
+           "load_index_npz", "save_index_npz", "DenseF32Index", "DenseHalfIndex", "DenseInt8Index", "DenseUint8Index", "QuantizedEmbeddingIndex", "quantize_symmetric",
            "quantize_asymmetric", "quantize_query_asymmetric",
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
            "quantize_queries_asymmetric_device"]

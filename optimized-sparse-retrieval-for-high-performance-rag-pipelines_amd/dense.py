@@ -174,19 +174,32 @@ def unpack_i8_host(packed: np.ndarray, n_docs: int, dim_pad: int) -> np.ndarray:
     return np.ascontiguousarray(t.transpose(0, 3, 1, 2, 4)).reshape(-1, dim_pad)[:n_docs]
 
 
+def unpack_half_host(packed: np.ndarray, n_docs: int, dim_pad: int) -> np.ndarray:
+    """The row-major u16[n_docs, dim_pad] codes of a corpus in the fragment order include/sparse_rx_half.h documents (host
+    arrays): view them as ``np.float16``, or shift them left by 16 into ``float32`` bits for bf16."""
+    ks = dim_pad // 16
+    t = np.asarray(packed).view(np.uint16).reshape(-1, ks, 2, 32, 8)  # [tile][k-step][half][row][8 elements]
+    return np.ascontiguousarray(t.transpose(0, 3, 1, 2, 4)).reshape(-1, dim_pad)[:n_docs]
+
+
 def _default_chunk_rows(dim: int) -> int:
     return max(32, ((64 << 20) // (4 * max(1, dim))) // 32 * 32)  # <= 64 MB of f32 rows, a multiple of the 32-row tile
 
 
-def _quantize_corpus(index, torch, emb, chunk_rows, entry: str, outs, packed=None):
+def _quantize_corpus(index, torch, emb, chunk_rows, entry: str, outs, packed=None, convert=None,
+                     refusal="embeddings hold a non-finite value (NaN / inf, or a row whose max - min overflows)"):
     """``from_embeddings``' loop: a device tensor is quantised in one launch; a host array (possibly a read-only memory map) is
     copied through ONE staging tensor of ``chunk_rows`` rows, so the device holds the finished corpus plus one chunk.  Ends
-    with the build's one synchronisation, the read of the flag word."""
+    with the build's one synchronisation, the read of the flag word.  ``convert(chunk, row0, flag)``: the per-chunk launch of
+    an index whose entry point is not a quantiser of include/sparse_rx_quant.h (``entry`` and ``outs`` are then unused)."""
     _require_f32(emb, "embeddings")
     n = index.n_docs
     flag = torch.zeros(1, dtype=torch.int32, device=index.device)
+    if convert is None:
+        def convert(chunk, row0, flag):
+            _quantize_device(entry, chunk, index.dim_pad, outs, flag, row0, n, packed)
     if isinstance(emb, torch.Tensor):
-        _quantize_device(entry, emb.to(index.device), index.dim_pad, outs, flag, 0, n, packed)
+        convert(emb.to(index.device), 0, flag)
     else:
         rows = _default_chunk_rows(index.dim) if chunk_rows is None else int(chunk_rows)
         if rows < 32 or rows % 32 != 0:
@@ -196,9 +209,9 @@ def _quantize_corpus(index, torch, emb, chunk_rows, entry: str, outs, packed=Non
             chunk = torch.from_numpy(np.array(emb[lo: lo + rows], dtype=np.float32))  # np.array copies the chunk only
             m = int(chunk.shape[0])
             stage[:m].copy_(chunk)  # stream-ordered behind the previous chunk's kernel
-            _quantize_device(entry, stage[:m], index.dim_pad, outs, flag, lo, n, packed)
+            convert(stage[:m], lo, flag)
     if int(flag.item()) & _capi.SRX_QUANT_NONFINITE:
-        raise ValueError("embeddings hold a non-finite value (NaN / inf, or a row whose max - min overflows)")
+        raise ValueError(refusal)
 
 
 def _pad_dim(dim: int) -> int:
@@ -213,6 +226,7 @@ class _DenseIndex:
 
     _workspace_fn = "srx_dense_f32_workspace_bytes"
     _entry = None  # the search entry point ``_launch`` calls, as ``_capi.check`` names it
+    _filtered_entry = None  # the one ``_launch_filtered`` calls, when it is not ``_entry + "_filtered"``
 
     def _open(self, device):
         """The no-GPU refusal, the library and the device: first step of every constructor."""
@@ -247,7 +261,8 @@ class _DenseIndex:
             if fdesc is None:
                 _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), self._entry)
             else:
-                _capi.check(self._launch_filtered(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), fdesc, *extra), self._entry + "_filtered")
+                _capi.check(self._launch_filtered(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), fdesc, *extra),
+                            self._filtered_entry or self._entry + "_filtered")
         return out
 
     def _launch_filtered(self, *args):
@@ -631,6 +646,120 @@ class DenseF32Index(_DenseIndex):
     def _launch_score(self, L, q, nq, cand_doc, cand_count, m, out, stream):
         return L.srx_dense_score_docs_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, self.doc_base,
                                           _ptr(cand_doc), _ptr(cand_count), m, _ptr(out), stream)
+
+    def score_docs(self, queries: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
+        """Host arrays in (the candidates validated by :func:`validate_candidates`), f32[nq, m] out."""
+        q = self._queries_to_device(queries)
+        return self._score_docs(cand_doc, cand_count, int(q.shape[0]), lambda cd, cc: self.score_docs_device(q, cd, cc))
+
+
+HALF_TYPES = {"f16": _capi.SRX_HALF_F16, "bf16": _capi.SRX_HALF_BF16}
+
+
+def check_half_dtype(dtype) -> str:
+    d = str(dtype).lower()
+    if d not in HALF_TYPES:
+        raise ValueError(f"dtype must be 'f16' or 'bf16', got {dtype!r}")
+    return d
+
+
+class DenseHalfIndex(_DenseIndex):
+    """Half-precision embedding matrix resident in HBM (include/sparse_rx_half.h): the rows rounded to f16 or bf16 (nearest
+    even) and kept ONLY in the MFMA-fragment order the search reads.  A whole query batch is one GEMM
+    (``srx_dense_search_half``); filters, ``score_offset`` and the scorer of given docs are those of :class:`DenseF32Index`.
+    Scores are the dot products of the ROUNDED rows and the rounded queries, accumulated in fp32 by the MFMA instruction."""
+
+    _workspace_fn, _entry, _score_entry = "srx_dense_half_workspace_bytes", "srx_dense_search_half", "srx_dense_score_docs_half"
+    _filtered_entry = "srx_dense_search_half"  # one entry point, the filter optional
+
+    def __init__(self, embeddings, dtype="f16", device="cuda:0", doc_base: int = 0, chunk_rows=None):
+        """``embeddings``: f32[n_docs, dim], a device tensor (one launch) or a host array, possibly a read-only memory map
+        (uploaded ``chunk_rows`` rows at a time through one staging tensor, a multiple of 32; default: 64 MB of rows).
+        ``ValueError`` for a row with a non-finite value or one that does not round to a finite value (|x| >= 65520 for
+        f16), raised after the one synchronisation the build needs."""
+        self.dtype = check_half_dtype(dtype)
+        _require_f32(embeddings, "embeddings")
+        torch = self._open(device)
+        self.n_docs, self.dim = int(embeddings.shape[0]), int(embeddings.shape[1])
+        if self.n_docs == 0:
+            raise ValueError("Empty corpus provided")
+        self.dim_pad = self._pad64(self.dtype)
+        self.doc_base = int(doc_base)
+        self._max_norm = None
+        L = _capi.lib()
+        with torch.cuda.device(self.device):
+            nbytes = _capi.check(L.srx_dense_half_bytes(self.n_docs, self.dim_pad), "srx_dense_half_bytes")
+            self.corpus = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _quantize_corpus(self, torch, embeddings, chunk_rows, None, (), convert=lambda x, row0, flag: self._convert(torch, L, x, row0, flag),
+                             refusal=f"embeddings hold a value that is not finite as {self.dtype} (NaN / inf, or too large for the type)")
+
+    def _convert(self, torch, L, x, row0: int, flag) -> None:
+        x, ld = _f32_rows(torch, x, "embeddings")
+        _capi.check(L.srx_dense_convert_half(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(x), ld, int(x.shape[0]), self.dim, self.dim_pad,
+                                             row0, self.n_docs, _ptr(self.corpus), _ptr(flag), _stream_ptr(torch, self.device)),
+                    "srx_dense_convert_half")
+
+    @classmethod
+    def from_embeddings(cls, emb, dtype="f16", device="cuda:0", doc_base: int = 0, chunk_rows=None):
+        """The constructor under the name the quantised indexes give theirs."""
+        return cls(emb, dtype=dtype, device=device, doc_base=doc_base, chunk_rows=chunk_rows)
+
+    def device_bytes(self) -> int:
+        """Bytes of the resident corpus (``srx_dense_half_bytes``)."""
+        return int(self.corpus.numel())
+
+    def corpus_to_host(self) -> np.ndarray:
+        """u16[n_docs, dim]: the 16-bit codes of the rounded rows, row-major (f16: ``.view(np.float16)``; bf16: the upper
+        halves of the float32 bit patterns)."""
+        _torch().cuda.synchronize(self.device)
+        return np.ascontiguousarray(unpack_half_host(self.corpus.cpu().numpy(), self.n_docs, self.dim_pad)[:, : self.dim])
+
+    def max_row_norm(self) -> float:
+        """Largest Euclidean norm of the ROUNDED rows (fp64 accumulation), computed once from a host copy in row chunks."""
+        if self._max_norm is None:
+            c = self.corpus_to_host()
+            rows = max(1, (64 << 20) // (8 * self.dim))
+            best = 0.0
+            for lo in range(0, self.n_docs, rows):
+                x = c[lo: lo + rows]
+                x = (x.view(np.float16) if self.dtype == "f16" else (x.astype(np.uint32) << 16).view(np.float32)).astype(np.float64)
+                best = max(best, float((x * x).sum(axis=1).max()))
+            self._max_norm = best ** 0.5
+        return self._max_norm
+
+    def search_device(self, queries_f32, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+        """f32[nq, dim] queries on the device (rounded to the index's type by the search) -> (doc i32[nq,k], score f32[nq,k],
+        count i32[nq]); asynchronous.  Top-k of (score + score_offset) > 0, the returned scores carry the offset; ``filter`` /
+        ``q_filter`` as ``DeviceIndex.search_device``."""
+        return self._search_device(queries_f32, _torch().float32, k, score_offset, filter=filter, q_filter=q_filter)
+
+    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc, score_offset):
+        return L.srx_dense_search_half(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(self.corpus), self.n_docs, self.dim_pad, _ptr(q), nq, k,
+                                       self.doc_base, fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream,
+                                       float(score_offset))
+
+    def _launch(self, L, q, nq, k, out, ws, stream, score_offset):
+        return self._launch_filtered(L, q, nq, k, out, ws, stream, None, score_offset)
+
+    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+        """Host arrays in, host arrays out; ``q_filter``: a host sequence of row numbers, validated here."""
+        q = self._queries_to_device(queries)
+        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=self._host_q_filter(filter, q_filter, int(q.shape[0]))))
+
+    def _queries_to_device(self, queries):
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        return _torch().as_tensor(q, device=self.device)
+
+    def score_docs_device(self, queries_f32, cand_doc, cand_count=None, out=None):
+        """``srx_dense_score_docs_half``: as ``DenseF32Index.score_docs_device``; the bits are those of :meth:`search_device`
+        with ``score_offset = 0``."""
+        return self._score_docs_device(queries_f32, _torch().float32, cand_doc, cand_count, out)
+
+    def _launch_score(self, L, q, nq, cand_doc, cand_count, m, out, stream):
+        return L.srx_dense_score_docs_half(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(self.corpus), self.n_docs, self.dim_pad, _ptr(q),
+                                           nq, self.doc_base, _ptr(cand_doc), _ptr(cand_count), m, _ptr(out), stream)
 
     def score_docs(self, queries: np.ndarray, cand_doc, cand_count=None) -> np.ndarray:
         """Host arrays in (the candidates validated by :func:`validate_candidates`), f32[nq, m] out."""

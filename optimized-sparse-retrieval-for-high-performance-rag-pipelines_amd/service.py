@@ -133,17 +133,28 @@ class RetrievalService(SparseIndexViews):
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
-    def set_embeddings(self, embeddings) -> None:
+    def set_embeddings(self, embeddings, storage: str = "f32") -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
-        :meth:`search_by_vector`, from ``embedding_path`` once ``build_bm25_index`` has fixed ``doc_ids``."""
-        from .dense import DenseF32Index
+        :meth:`search_by_vector`, from ``embedding_path`` once ``build_bm25_index`` has fixed ``doc_ids``.
+
+        ``storage``: how the GPU keeps the rows.  "f32" (default): as given (``DenseF32Index``, an exact streaming matvec per
+        pass of four queries).  "f16" / "bf16" (no reference counterpart): rounded to half precision and searched a whole
+        query batch at a time by MFMA (``DenseHalfIndex``, include/sparse_rx_half.h); :meth:`search_by_vector`,
+        :meth:`search_hybrid` and :meth:`score_by_vector` then return the scores OF THE ROUNDED ROWS (and rounded query
+        vectors).  Any other value raises ``ValueError``."""
+        from .dense import DenseF32Index, DenseHalfIndex
+        storage = str(storage).lower()
+        if storage not in ("f32", "f16", "bf16"):
+            raise ValueError(f"storage must be 'f32', 'f16' or 'bf16', got {storage!r}")
         e = np.asarray(embeddings, dtype=np.float32)
         if e.ndim != 2 or (self.doc_ids and e.shape[0] != len(self.doc_ids)):
             raise ValueError("embeddings must be [n_docs, dim] with one row per document")
         self.embedding_index = e
-        self._dense = DenseF32Index(e, device=self.device)  # streams a memory map to the device in <= 64 MB chunks
+        # either index streams a memory map to the device in <= 64 MB chunks
+        self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
+        self.embedding_storage = storage
 
     def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
                          excluded_docs=None) -> List[Dict]:
@@ -159,7 +170,11 @@ class RetrievalService(SparseIndexViews):
         ulp(offset): docs whose true scores differ by less can swap places at the k-th boundary (scores <= 0 only).
 
         ``allowed_docs`` / ``excluded_docs``: a sequence of doc ids, as in :meth:`search_bm25`; both passes rank the allowed
-        docs alone (``srx_dense_search_f32_filtered``)."""
+        docs alone (``srx_dense_search_f32_filtered``).
+
+        With half-precision storage (:meth:`set_embeddings`) both passes run on the half index (``srx_dense_search_half``):
+        the first pass returns the scores of the rounded rows; the second pass still re-scores its rows on the host with the
+        f32 rows the service was given."""
         self._ensure_dense()
         q = np.asarray(query_vector, dtype=np.float32)
         kk = max(1, min(int(k), self._dense.n_docs))
@@ -172,7 +187,9 @@ class RetrievalService(SparseIndexViews):
             # |score| <= |q|_2 * max row norm (Cauchy-Schwarz): the smallest shift that makes every doc rankable keeps
             # the most fp32 resolution for the ranking (the shifted scores are only used to pick the k rows)
             bound = float(np.linalg.norm(q.astype(np.float64))) * self._dense.max_row_norm()
-            offset = bound * 1.001 + 1e-30
+            # half storage scores the ROUNDED query: rounding raises a component by up to 2^-9 (bf16) / 2^-12 (f16) of itself,
+            # so its norm can exceed |q|_2 by 0.2 %: the margin covers that (max_row_norm is already that of the rounded rows)
+            offset = bound * (1.001 if getattr(self, "embedding_storage", "f32") == "f32" else 1.01) + 1e-30
             d, s, n = self._dense.search(q, kk, score_offset=offset, **flt)
             idx = d[0, : int(n[0])].astype(np.int64)
             sc = np.dot(self.embedding_index[idx], q).astype(np.float32)  # the reference's fp32 expression on the k rows
@@ -229,7 +246,9 @@ class RetrievalService(SparseIndexViews):
         0 the result is the other side's set, but equal normalised scores rank by doc id.  The query cache is not used.
         Needs the whole index on one GPU.
         ``allowed_docs`` / ``excluded_docs`` as in :meth:`search_bm25`: the filter goes to both sides, so the fused list is
-        the fusion of the two FILTERED top lists (``rescore=True`` included: every doc of either list is an allowed one)."""
+        the fusion of the two FILTERED top lists (``rescore=True`` included: every doc of either list is an allowed one).
+        With half-precision storage (:meth:`set_embeddings`) the dense side is ``srx_dense_search_half`` /
+        ``srx_dense_score_docs_half``: the dense scores are those of the rounded rows, everything else is unchanged."""
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
         rescore = check_rescore_args(fusion, rescore)
@@ -280,7 +299,8 @@ class RetrievalService(SparseIndexViews):
         of ``candidates[qid]`` for ``query_vectors[qid]``, in the caller's order, with the arithmetic of the dense search
         (``srx_dense_score_docs_f32``: a row :meth:`search_hybrid`'s dense side returned scores to the same float).  No
         ``score > 0`` filter; a qid without candidates gives ``{}``; an unknown doc id raises ``ValueError``.  One batch
-        (ragged lists padded with -1, passed with their lengths); no cache."""
+        (ragged lists padded with -1, passed with their lengths); no cache.  With half-precision storage the scores are those
+        of the rounded rows (``srx_dense_score_docs_half``), bit for bit what the half search returns."""
         from .backend import RowOfIds, scores_to_dicts
         self._ensure_dense()
         if self.host is not None:
@@ -314,6 +334,8 @@ class RetrievalService(SparseIndexViews):
                 stats["shard_docs"], stats["shard_doc_base"] = h.n_docs, self._be.doc_base
         if self.dev is not None:
             stats["device_index_mb"] = self.dev.device_bytes() / (1024 * 1024)
+        if getattr(self, "_dense", None) is not None:
+            stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16" or "bf16" (set_embeddings)
         return stats
 
     def __enter__(self):
