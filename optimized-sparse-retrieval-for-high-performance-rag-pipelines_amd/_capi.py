@@ -1,5 +1,5 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
-include/sparse_rx_quant.h, include/sparse_rx_filter.h and include/sparse_rx_half.h).
+include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h and include/sparse_rx_mmr.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -17,7 +17,7 @@ _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
-           "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip"]  # one translation unit each, compiled in parallel
+           "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -141,6 +141,16 @@ HALF_SYMBOLS = {
 }
 SRX_HALF_F16, SRX_HALF_BF16 = 0, 1  # srx_half_type
 
+# every symbol include/sparse_rx_mmr.h declares (the sixth header of the same library)
+_MMR_TAIL = [_I64, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, _F32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]  # doc_base .. stream
+MMR_SYMBOLS = {
+    "srx_mmr_workspace_bytes": (_I64, [_I32, _I32]),
+    "srx_mmr_select_f32": (ctypes.c_int, [_I32, _VP, _I64, _I32, *_MMR_TAIL]),
+    "srx_mmr_select_half": (ctypes.c_int, [_I32, _I32, _VP, _I64, _I32, *_MMR_TAIL]),
+}
+SRX_MMR_DOT, SRX_MMR_COSINE = 0, 1  # srx_mmr_sim
+SRX_MMR_MAX_M = 256                 # candidates per list (pinned to the header by tests/test_mmr_cpu.py)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -159,11 +169,13 @@ def kernel_sources_sha256() -> str:
 def _deps():
     return [os.path.join(CSRC_DIR, f) for f in SOURCES] + [os.path.join(CSRC_DIR, "srx_common.h"), os.path.join(CSRC_DIR, "filter_common.h"),
                                                             os.path.join(CSRC_DIR, "half_common.h"),
+                                                            os.path.join(CSRC_DIR, "mmr_common.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_rescore.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_quant.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_filter.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_half.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_half.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_mmr.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -211,7 +223,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -572,12 +572,106 @@ class QuantizedEmbeddingIndex:
         return {qid: rows_to_dict(self.doc_ids, d, s, n, i) for i, qid in enumerate(qids)}
 
 
-class DenseF32Index(_DenseIndex):
+MMR_SIMILARITIES = {"dot": _capi.SRX_MMR_DOT, "cosine": _capi.SRX_MMR_COSINE}
+MMR_CALL_BYTES = 256 << 20  # the Gram matrices of one ``srx_mmr_select_*`` call: a larger batch is split
+
+
+def check_mmr_args(lambda_, similarity) -> Tuple[int, float, float]:
+    """The argument rules of the MMR selection on the host: (sim_mode, w_rel, w_div) or ``ValueError``.  ``w_rel =
+    float32(lambda_)`` and ``w_div = float32(1.0 - lambda_)``, the difference computed in double."""
+    sim = str(similarity).lower()
+    if sim not in MMR_SIMILARITIES:
+        raise ValueError(f"similarity must be one of {sorted(MMR_SIMILARITIES)}, got {similarity!r}")
+    try:
+        lam = float(lambda_)
+    except (TypeError, ValueError):
+        raise ValueError(f"mmr lambda must be a number in [0, 1], got {lambda_!r}") from None
+    if not (0.0 <= lam <= 1.0):  # false for a NaN
+        raise ValueError(f"mmr lambda must be in [0, 1], got {lambda_!r}")
+    return MMR_SIMILARITIES[sim], float(np.float32(lam)), float(np.float32(1.0 - lam))
+
+
+def check_mmr_shape(m: int, k) -> int:
+    """``k`` as an int for a list of ``m`` candidates, or ``ValueError``: 1 <= m <= 256 (no silent truncation), 1 <= k <= m."""
+    if not (1 <= m <= _capi.SRX_MMR_MAX_M):
+        raise ValueError(f"an MMR pool holds 1 .. {_capi.SRX_MMR_MAX_M} candidates per query, got m={m}")
+    k = int(k)
+    if not (1 <= k <= m):
+        raise ValueError(f"k must be in [1, m={m}] for the MMR selection, got {k}")
+    return k
+
+
+class _MmrSelect:
+    """Diversified top-k over candidate lists (include/sparse_rx_mmr.h) for the indexes that keep rows a similarity can be
+    read from: :class:`DenseF32Index` and :class:`DenseHalfIndex`.  The uint8 / INT8 indexes have no such method."""
+
+    def mmr_device(self, cand_doc, cand_rel, cand_count, k: int, lambda_: float = 0.5, similarity: str = "cosine", return_sim: bool = False):
+        """Maximal Marginal Relevance on the device: ``k`` of the ``m`` candidates of every query, picked greedily, each pick
+        maximising ``lambda_ * relevance - (1 - lambda_) * (largest similarity to a doc already picked)``; ties go to the
+        lowest position.  ``cand_doc`` i32[nq, m] GLOBAL ids, ``cand_rel`` f32[nq, m], ``cand_count`` i32[nq] or None: the
+        (doc, score, count) triple of any search or of the fusion as it is (m <= 256).  A position at or past the count,
+        an id outside the index or a NaN relevance is not a candidate.  ``similarity`` "dot" or "cosine" of this index's
+        rows (the rounded rows of a half index), to the bit the scores ``score_docs_device`` returns for a query that equals
+        a row.  Returns device tensors ``(doc i32[nq, k], rel f32[nq, k], mmr f32[nq, k], count i32[nq])`` -- the docs in
+        SELECTION order with their relevance as given and the value they were picked with, rows padded with -1 / 0 -- plus
+        ``sim`` f32[nq, m, m] (the dot products, 0 for a dead row or column) with ``return_sim``.  Asynchronous on the
+        current stream; a batch whose Gram matrices exceed 256 MiB is split into several calls."""
+        torch = _torch()
+        sim_mode, w_rel, w_div = check_mmr_args(lambda_, similarity)
+        if cand_doc.dim() != 2 or cand_doc.dtype != torch.int32:
+            raise ValueError("mmr_device: cand_doc must be an int32 tensor [nq, m]")
+        nq, m = int(cand_doc.shape[0]), int(cand_doc.shape[1])
+        k = check_mmr_shape(m, k)
+        if cand_rel.dtype != torch.float32 or tuple(cand_rel.shape) != (nq, m):
+            raise ValueError("mmr_device: cand_rel must be a float32 tensor of cand_doc's shape")
+        if cand_count is not None and (cand_count.dtype != torch.int32 or cand_count.numel() != nq):
+            raise ValueError("mmr_device: cand_count must be an int32 tensor [nq]")
+        L = _capi.lib()
+        with torch.cuda.device(self.device):
+            cand_doc, cand_rel = cand_doc.contiguous(), cand_rel.contiguous()
+            cand_count = None if cand_count is None else cand_count.contiguous()
+            doc, rel, count = _empty_topk(torch, nq, k, self.device)
+            mmr = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+            sim = torch.empty((nq, m, m), dtype=torch.float32, device=self.device) if return_sim else None
+            per_call = max(1, MMR_CALL_BYTES // (m * m * 4))
+            stream = _stream_ptr(torch, self.device)
+            for lo in range(0, nq, per_call):
+                n = min(per_call, nq - lo)
+                if return_sim:
+                    ws = sim[lo: lo + n]  # out_sim IS the Gram buffer: it serves as the workspace
+                else:
+                    ws = _grow_ws(torch, self, _capi.check(L.srx_mmr_workspace_bytes(n, m), "srx_mmr_workspace_bytes"))
+                rc = self._launch_mmr(L, _ptr(cand_doc[lo: lo + n]), _ptr(cand_rel[lo: lo + n]), 0 if cand_count is None else _ptr(cand_count[lo: lo + n]),
+                                      n, m, k, sim_mode, w_rel, w_div, _ptr(doc[lo: lo + n]), _ptr(rel[lo: lo + n]), _ptr(mmr[lo: lo + n]),
+                                      _ptr(count[lo: lo + n]), 0 if sim is None else _ptr(ws), _ptr(ws), ws.numel() * ws.element_size(), stream)
+                _capi.check(rc, self._mmr_entry)
+        return (doc, rel, mmr, count, sim) if return_sim else (doc, rel, mmr, count)
+
+    def mmr(self, cand_doc, cand_rel, cand_count, k: int, lambda_: float = 0.5, similarity: str = "cosine", return_sim: bool = False):
+        """Host arrays in (the candidates validated by :func:`validate_candidates`), host arrays out: :meth:`mmr_device`
+        with one synchronisation and one copy back."""
+        torch = _torch()
+        check_mmr_args(lambda_, similarity)
+        d = np.asarray(cand_doc)
+        cand_doc, cand_count = validate_candidates(d, cand_count, int(d.shape[0]) if d.ndim == 2 else 0)
+        check_mmr_shape(int(cand_doc.shape[1]), k)
+        r = np.ascontiguousarray(cand_rel, dtype=np.float32)
+        if r.shape != cand_doc.shape:
+            raise ValueError("cand_rel must have cand_doc's shape")
+        cc = None if cand_count is None else torch.as_tensor(cand_count, device=self.device)
+        return self._host(self.mmr_device(torch.as_tensor(cand_doc, device=self.device), torch.as_tensor(r, device=self.device), cc, k, lambda_,
+                                          similarity, return_sim))
+
+
+class DenseF32Index(_DenseIndex, _MmrSelect):
     """f32 embedding matrix resident in HBM: the ``embedding_index`` of ``RetrievalService`` (retrieval.py:329-335);
     ``search`` replaces ``np.dot(self.embedding_index, query_vector)`` + top-k of ``search_by_vector`` (:411-423) for a
     batch of query vectors (``srx_dense_search_f32``)."""
 
-    _entry, _score_entry = "srx_dense_search_f32", "srx_dense_score_docs_f32"
+    _entry, _score_entry, _mmr_entry = "srx_dense_search_f32", "srx_dense_score_docs_f32", "srx_mmr_select_f32"
+
+    def _launch_mmr(self, L, *tail):
+        return L.srx_mmr_select_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, self.doc_base, *tail)
 
     def __init__(self, embeddings, device="cuda:0", doc_base: int = 0):
         torch = self._open(device)
@@ -663,7 +757,7 @@ def check_half_dtype(dtype) -> str:
     return d
 
 
-class DenseHalfIndex(_DenseIndex):
+class DenseHalfIndex(_DenseIndex, _MmrSelect):
     """Half-precision embedding matrix resident in HBM (include/sparse_rx_half.h): the rows rounded to f16 or bf16 (nearest
     even) and kept ONLY in the MFMA-fragment order the search reads.  A whole query batch is one GEMM
     (``srx_dense_search_half``); filters, ``score_offset`` and the scorer of given docs are those of :class:`DenseF32Index`.
@@ -671,6 +765,10 @@ class DenseHalfIndex(_DenseIndex):
 
     _workspace_fn, _entry, _score_entry = "srx_dense_half_workspace_bytes", "srx_dense_search_half", "srx_dense_score_docs_half"
     _filtered_entry = "srx_dense_search_half"  # one entry point, the filter optional
+    _mmr_entry = "srx_mmr_select_half"
+
+    def _launch_mmr(self, L, *tail):
+        return L.srx_mmr_select_half(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(self.corpus), self.n_docs, self.dim_pad, self.doc_base, *tail)
 
     def __init__(self, embeddings, dtype="f16", device="cuda:0", doc_base: int = 0, chunk_rows=None):
         """``embeddings``: f32[n_docs, dim], a device tensor (one launch) or a host array, possibly a read-only memory map

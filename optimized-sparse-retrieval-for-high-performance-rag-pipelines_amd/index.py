@@ -1005,7 +1005,7 @@ def check_rescore_args(mode, rescore) -> bool:
 
 
 def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, ka: int, kb: int, k: int, mode: str, weights,
-                  rrf_c: float, rescore: bool = False, dense_score=None, filter=None, q_filter=None):
+                  rrf_c: float, rescore: bool = False, dense_score=None, filter=None, q_filter=None, post=None):
     """The hybrid pipeline of the API mirrors: sparse search of a host CSR batch on ``index`` (``ka`` rows per query),
     ``dense_search(kb)`` -> the dense side's device triple for the same queries, ``fuse_topk_device``; the three steps
     stay on the device, then one synchronisation and the copy back (:func:`search_host_batch`).  Returns host (doc, score, count).
@@ -1016,12 +1016,16 @@ def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, k
     does not depend on ``ka`` / ``kb``.
 
     ``filter`` / ``q_filter`` (device tensor) restrict the sparse search as in ``DeviceIndex.search_device``; the caller's
-    ``dense_search`` carries the same filter itself, so the fused list is that of the two filtered lists."""
+    ``dense_search`` carries the same filter itself, so the fused list is that of the two filtered lists.
+
+    ``post(doc, score, count)`` -> a tuple of device tensors: a further step on the fused triple (``k`` deep) that stays on
+    the device, in front of the one synchronisation; its tuple is what comes back as host arrays.  None (the default):
+    nothing is added to the pipeline."""
     check_fuse_args(mode, weights, rrf_c)
     if check_rescore_args(mode, rescore) and dense_score is None:
         raise ValueError("hybrid_search: rescore=True needs dense_score")
 
-    def fused(qp, qt, qw, kk):
+    def fuse(qp, qt, qw, kk):
         a, b = index.search_device(qp, qt, qw, ka, filter=filter, q_filter=q_filter), dense_search(kb)
         if not rescore:
             return fuse_topk_device(a, b, kk, mode=mode, weights=weights, rrf_c=rrf_c)
@@ -1029,6 +1033,7 @@ def hybrid_search(index: "DeviceIndex", q_ptr, q_term, q_weight, dense_search, k
         a_other = dense_score(a[0], a[2])
         return fuse_scored_device(a, a_other, b, b_other, kk, weights)
 
+    fused = fuse if post is None else (lambda qp, qt, qw, kk: post(*fuse(qp, qt, qw, kk)))
     return search_host_batch(fused, q_ptr, q_term, q_weight, k, index.vocab, index.device)
 
 
@@ -1043,6 +1048,19 @@ def hybrid_depths(top_k: int, candidates, n_docs: int) -> Tuple[int, int]:
         raise ValueError(f"candidates must be >= 1, got {candidates}")
     cand = top_k if candidates is None else int(candidates)
     return min(top_k, n_docs), min(cand, n_docs, max_k)
+
+
+def mmr_pool_depth(top_k: int, mmr_pool, n_docs: int) -> int:
+    """Rows of the fused ranking an MMR selection of ``top_k`` picks from, or ``ValueError``: ``mmr_pool`` when given (1 ..
+    256: a deeper pool is refused, not truncated), else ``min(max(4 * top_k, top_k), 256)``; never more than ``n_docs``."""
+    max_m = _capi.SRX_MMR_MAX_M
+    if mmr_pool is None:
+        pool = min(max(4 * int(top_k), int(top_k)), max_m)
+    else:
+        pool = int(mmr_pool)
+        if not (1 <= pool <= max_m):
+            raise ValueError(f"mmr_pool must be in [1, {max_m}], got {mmr_pool}")
+    return max(1, min(pool, n_docs))
 
 
 def combine_term_bounds(fine_tables, world: int = None):

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .backend import SparseBackend, SparseIndexViews
-from .index import check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
+from .index import check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, mmr_pool_depth, rows_to_dict
 
 logger = logging.getLogger(__name__)
 
@@ -227,7 +227,8 @@ class RetrievalService(SparseIndexViews):
     def search_hybrid(self, queries: Dict[str, str], query_vectors: Dict[str, np.ndarray], top_k: int = 10, *,
                       sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted", rrf_c: float = 60.0,
                       candidates: Optional[int] = None, rescore: bool = False, allowed_docs=None,
-                      excluded_docs=None) -> Dict[str, Dict[str, float]]:
+                      excluded_docs=None, mmr_lambda: Optional[float] = None, mmr_pool: Optional[int] = None,
+                      mmr_similarity: str = "cosine") -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -248,11 +249,26 @@ class RetrievalService(SparseIndexViews):
         ``allowed_docs`` / ``excluded_docs`` as in :meth:`search_bm25`: the filter goes to both sides, so the fused list is
         the fusion of the two FILTERED top lists (``rescore=True`` included: every doc of either list is an allowed one).
         With half-precision storage (:meth:`set_embeddings`) the dense side is ``srx_dense_search_half`` /
-        ``srx_dense_score_docs_half``: the dense scores are those of the rounded rows, everything else is unchanged."""
+        ``srx_dense_score_docs_half``: the dense scores are those of the rounded rows, everything else is unchanged.
+        ``mmr_lambda`` (default None: no diversification, every step and result is as described above): a number in [0, 1]
+        makes the call return a DIVERSIFIED ``top_k``.  The fused ranking is then taken ``mmr_pool`` deep (default
+        ``min(max(4 * top_k, top_k), 256, n_docs)``; more than 256 raises ``ValueError``), ``candidates`` defaults to at
+        least the pool, and Maximal Marginal Relevance picks ``top_k`` of the pool on the device (``srx_mmr_select_f32`` /
+        ``_half``, include/sparse_rx_mmr.h; ``mmr_similarity`` "cosine" or "dot" of the embedding rows) -- still one
+        synchronisation and one copy back per call.  The result is what ``diversify(search_hybrid(top_k=mmr_pool, ...),
+        top_k)`` returns: the docs in SELECTION order, each with its fused score, so the values are not descending.  Works
+        with ``rescore=True`` and with the filter keywords (the pool is then the filtered fusion)."""
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
         rescore = check_rescore_args(fusion, rescore)
         k, cand = hybrid_depths(top_k, candidates, self._be.n_docs_total)
+        pool = None
+        if mmr_lambda is not None:
+            from .dense import check_mmr_args
+            check_mmr_args(mmr_lambda, mmr_similarity)
+            pool = mmr_pool_depth(top_k, mmr_pool, self._be.n_docs_total)
+            if candidates is None:
+                cand = hybrid_depths(top_k, max(int(top_k), pool, 1), self._be.n_docs_total)[1]
         if self._be.sharded():
             raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
         if self.host is None:
@@ -288,8 +304,16 @@ class RetrievalService(SparseIndexViews):
             import torch
             return self._dense.score_docs_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), cand_doc, cand_count)
 
-        doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
-                                          (sparse_weight, dense_weight), rrf_c, rescore, dense_score, **flt)
+        if pool is None:
+            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
+                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, **flt)
+        else:
+            def diversified(f_doc, f_score, f_count):  # the fused triple, pool deep, still on the device
+                d, r, _, n = self._dense.mmr_device(f_doc, f_score, f_count, min(k, pool), mmr_lambda, mmr_similarity)
+                return d, r, n
+
+            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, pool, fusion,
+                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=diversified, **flt)
         for i, (qid, _) in enumerate(live):
             results[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return results
@@ -314,6 +338,48 @@ class RetrievalService(SparseIndexViews):
             if v.shape != (self._dense.dim,):
                 raise ValueError(f"query vector of {qid!r} has shape {v.shape}, expected ({self._dense.dim},)")
         return scores_to_dicts(results, live, self._dense.score_docs(np.stack(vecs), cand_doc, cand_count))
+
+    def diversify(self, results: Dict[str, Dict[str, float]], top_k: int = 10, *, mmr_lambda: float = 0.5,
+                  similarity: str = "cosine") -> Dict[str, Dict[str, float]]:
+        """Diversified top-k of ranked lists (no reference counterpart: it cannot diversify): Maximal Marginal Relevance over
+        ``results`` = ``{qid: {doc_id: score}}`` as any search of this service returns it (the dict order is the list order).
+        Each pick maximises ``mmr_lambda * score - (1 - mmr_lambda) * (largest similarity to a doc already picked)``, the
+        similarity ("cosine" or "dot") taken between the ``embedding_index`` rows of the docs -- the rounded rows with
+        half-precision storage -- on the GPU (``srx_mmr_select_f32`` / ``srx_mmr_select_half``, include/sparse_rx_mmr.h has
+        the exact arithmetic; ties go to the doc listed first).  All queries of the call run as one batch.
+
+        Returns the same shape with ``top_k`` docs per query (fewer when the list is shorter) in SELECTION order, each with
+        its ORIGINAL score: the values of a returned dict are therefore NOT descending.  ``mmr_lambda = 1`` keeps the order
+        of the scores.  ``{}`` stays ``{}``, a qid with an empty list keeps it, ``top_k <= 0`` gives ``{}`` per query.
+        ``ValueError``: an unknown doc id, a list longer than 256 docs (no silent truncation), ``mmr_lambda`` outside [0, 1],
+        an unknown ``similarity``, a sharded index (the embedding rows are not sharded)."""
+        from .backend import RowOfIds
+        from .dense import check_mmr_args
+        check_mmr_args(mmr_lambda, similarity)
+        if self._be.sharded():
+            raise ValueError("diversify needs the whole index on one GPU (the dense corpus is not sharded)")
+        if not results:
+            return {}
+        self._ensure_dense()
+        lists = {qid: list(row) for qid, row in results.items()}
+        if self.host is not None:
+            out, live, cand_doc, cand_count = self._be.candidate_block(results, lists)
+            doc_ids = self.host.doc_ids
+        else:  # embeddings without a BM25 index: docs are named by their row number, as search_by_vector names them
+            out, live, cand_doc, cand_count = RowOfIds.numbered(self._dense.n_docs).candidate_block(results, lists)
+            doc_ids = None
+        m = int(cand_doc.shape[1])
+        if m > 256:
+            raise ValueError(f"diversify takes lists of at most 256 docs, got one of {m} (no silent truncation)")
+        if not live or int(top_k) <= 0:
+            return out
+        rel = np.zeros(cand_doc.shape, dtype=np.float32)
+        for i, (qid, _, cands) in enumerate(live):
+            rel[i, : len(cands)] = [results[qid][d] for d in cands]
+        doc, score, _, count = self._dense.mmr(cand_doc, rel, cand_count, min(int(top_k), m), mmr_lambda, similarity)
+        for i, (qid, _, _) in enumerate(live):
+            out[qid] = {(doc_ids[int(doc[i, j])] if doc_ids is not None else str(int(doc[i, j]))): float(score[i, j]) for j in range(int(count[i]))}
+        return out
 
     def clear_cache(self) -> None:
         with self.cache_lock:
