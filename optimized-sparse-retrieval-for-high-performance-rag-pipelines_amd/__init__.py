@@ -2,7 +2,7 @@
 ``RetrievalService.build_bm25_index()`` / ``search_bm25()`` API.  Import as ``sparse_rx``."""
 from . import _capi
 from ._capi import SparseRxError, SparseRxUnavailable, build_library
-from .index import DeviceIndex, HostBatchPipeline, HostIndex, build_host_index, encode_queries, fuse_scored_device, fuse_topk_device, merge_topk_device, mmr_pool_depth, tokenize, validate_candidates
+from .index import DeviceIndex, HostBatchPipeline, HostIndex, build_host_index, encode_queries, fuse_scored_device, fuse_topk_device, merge_topk_device, mmr_pool_depth, parse_operators, tokenize, validate_candidates
 from .service import RetrievalService
 from .registry import HybridRetriever, OptimizedBM25Retriever, OptimizedRetriever, QuantizedEmbeddingRetriever, RetrieverRegistry, load_index_npz, save_index_npz
 from .dense import (DenseF32Index, DenseHalfIndex, DenseInt8Index, DenseUint8Index, QuantizedEmbeddingIndex, check_mmr_args, quantize_asymmetric,
@@ -19,4 +19,4 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "load_index_npz", "save_index_npz", "DenseF32Index", "DenseHalfIndex", "DenseInt8Index", "DenseUint8Index", "QuantizedEmbeddingIndex", "quantize_symmetric",
            "quantize_asymmetric", "quantize_query_asymmetric",
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
-           "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth"]
+           "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators"]

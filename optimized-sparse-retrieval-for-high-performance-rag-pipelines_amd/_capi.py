@@ -1,5 +1,6 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
-include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h and include/sparse_rx_mmr.h).
+include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h and
+include/sparse_rx_terms.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -17,7 +18,8 @@ _ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
-           "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip"]  # one translation unit each, compiled in parallel
+           "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
+           "terms.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -151,6 +153,12 @@ MMR_SYMBOLS = {
 SRX_MMR_DOT, SRX_MMR_COSINE = 0, 1  # srx_mmr_sim
 SRX_MMR_MAX_M = 256                 # candidates per list (pinned to the header by tests/test_mmr_cpu.py)
 
+# every symbol include/sparse_rx_terms.h declares (the seventh header of the same library)
+TERMS_SYMBOLS = {
+    "srx_filter_from_terms_bytes": (_I64, [_I64, _I64]),
+    "srx_filter_from_terms": (ctypes.c_int, [ctypes.POINTER(IndexDesc), _I32, _VP, _VP, _VP, _VP, _VP, _VP, _FP, _VP, _VP]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -175,7 +183,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_quant.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_filter.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_half.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_mmr.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_mmr.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_terms.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -223,7 +232,8 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
+                                   **TERMS_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, score_host_batch, search_host_batch
+from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, parse_operators, score_host_batch, search_host_batch, tokenize
 
 
 class SparseBackend:
@@ -139,6 +139,23 @@ class SparseBackend:
             self._rows = RowOfIds(self.host.doc_ids)
         return doc_filter_spec(self._rows.row_of, queries, allowed_docs, excluded_docs)
 
+    def term_filter_spec(self, queries, must_terms=None, any_terms=None, must_not_terms=None, doc_spec=None):
+        """:func:`term_filter_spec` over this index's vocabulary, bound to its device index and combined with ``doc_spec`` (the
+        :meth:`doc_filter_spec` of the same call, or None) as the base; ``doc_spec`` itself when no term keyword constrains a
+        query.  A sharded index refuses a constrained call."""
+        if must_terms is None and any_terms is None and must_not_terms is None:
+            return doc_spec
+        if self.host is None:
+            raise ValueError("term constraints need the sparse index: build it first")
+        spec = term_filter_spec(self.host.vocabulary, queries, must_terms, any_terms, must_not_terms)
+        if spec is None:  # empty lists, or operators=True on texts without operators
+            return doc_spec
+        if self.sharded():
+            raise ValueError("must_terms / any_terms / must_not_terms need the whole index on one GPU (a sharded search takes no doc filter)")
+        spec = spec.with_base(doc_spec, queries)
+        spec.sparse = lambda: self.dev
+        return spec
+
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
                      blank: str = "empty", filter: Optional["DocFilterSpec"] = None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
@@ -158,7 +175,7 @@ class SparseBackend:
         the corpus asks for ``n_docs`` rows; ``top_k <= 0`` keeps nothing (the reference's ``argpartition(...)[:0]``), cache
         hits aside.
 
-        ``filter`` (:meth:`doc_filter_spec`): the search is restricted to each query's allowed docs (``srx_search_filtered``).
+        ``filter`` (:meth:`doc_filter_spec`, :meth:`term_filter_spec`): the search is restricted to each query's allowed docs (``srx_search_filtered``).
         A filtered call neither reads nor writes the cache -- its key is the query text --, and equal texts share a row only
         under the same filter row."""
         if filter is not None:
@@ -339,6 +356,113 @@ def doc_filter_spec(row_of, queries, allowed_docs, excluded_docs) -> Optional[Do
         else:
             row_of_qid[qid] = -1
     return DocFilterSpec(allow, lists or [np.zeros(0, np.int64)], row_of_qid)
+
+
+class TermFilterSpec:
+    """The ``must_terms`` / ``any_terms`` / ``must_not_terms`` keywords of one API call, resolved on the host: ``rows`` = one
+    (all, any, none) triple of term-id tuples per filter row (-1: an out-of-vocabulary word), ``row_of_qid`` = every qid's row
+    (-1: not filtered).  With a base (:meth:`with_base`): ``base`` = the call's :class:`DocFilterSpec`, ``base_rows`` = its row
+    for every row here (-1: none).  ``sparse`` () -> the DeviceIndex whose postings answer "doc has term" (None: the index
+    :meth:`on_device` is given).  Memory on the device: len(rows) * n_docs / 8 bytes -- 1.25 MB per row at 10 M docs."""
+
+    def __init__(self, rows, row_of_qid, base=None, base_rows=None):
+        self.rows, self.row_of_qid, self.base, self.base_rows, self.sparse = rows, row_of_qid, base, base_rows, None
+
+    def with_base(self, doc_spec, queries) -> "TermFilterSpec":
+        """This spec restricted to the docs ``doc_spec`` allows: one row per distinct (doc row, term row) pair of the call's
+        qids; a qid neither spec filters stays unfiltered."""
+        if doc_spec is None:
+            return self
+        pairs, row_of_qid = {}, {}
+        for qid in queries:
+            pair = (doc_spec.row_of_qid[qid], self.row_of_qid[qid])
+            row_of_qid[qid] = -1 if pair == (-1, -1) else pairs.setdefault(pair, len(pairs))
+        empty = ((), (), ())
+        rows = [self.rows[t] if t >= 0 else empty for _, t in pairs] or [empty]
+        return TermFilterSpec(rows, row_of_qid, doc_spec, [d for d, _ in pairs] or [-1])
+
+    def on_device(self, index):
+        """The :class:`~.filter.DocFilter` of the rows (``srx_filter_from_terms`` on the sparse index), for ``index``: the sparse
+        index itself or a dense index of the same corpus (same n_docs / doc_base / device)"""
+        sparse = index if self.sparse is None else self.sparse()
+        if not hasattr(sparse, "term_filter"):
+            raise ValueError("term constraints need the sparse index of the corpus (its posting lists)")
+        base = None if self.base is None else self.base.on_device(sparse)
+        lists = [[list(r[i]) for r in self.rows] for i in range(3)]
+        return sparse.term_filter(*lists, base=base, q_base=None if base is None else self.base_rows)
+
+
+def term_filter_spec(vocabulary, queries, must_terms=None, any_terms=None, must_not_terms=None) -> Optional[TermFilterSpec]:
+    """The three term keywords of the API mirrors -> a :class:`TermFilterSpec`, or None when no qid of ``queries`` is
+    constrained.  Each keyword is None, a sequence of strings (for every query of the call) or a dict ``qid -> sequence`` (a qid
+    missing from all three is not constrained).  Every string goes through :func:`~.index.tokenize`: all its tokens join the
+    list, an out-of-vocabulary token as -1; a string without tokens, or a bare string where a sequence belongs, raises
+    ValueError.  Equal (must, any, must-not) triples share one row."""
+    per_qid = {qid: [(), (), ()] for qid in queries}
+    for i, (what, given) in enumerate((("must_terms", must_terms), ("any_terms", any_terms), ("must_not_terms", must_not_terms))):
+        if given is None:
+            continue
+        if isinstance(given, (str, bytes)):
+            raise ValueError(f"{what} must be a sequence of strings or a dict qid -> sequence, not one string")
+
+        def ids(words, whose):
+            if isinstance(words, (str, bytes)):
+                raise ValueError(f"{what}{whose} must be a sequence of strings, not one string")
+            out = []
+            for w in words:
+                toks = tokenize(w) if isinstance(w, str) else []
+                if not toks:
+                    raise ValueError(f"{w!r} in {what}{whose} holds no token")
+                out.extend(int(vocabulary.get(t, -1)) for t in toks)
+            return tuple(out)
+
+        if isinstance(given, dict):
+            for qid in queries:
+                if qid in given:
+                    per_qid[qid][i] = ids(given[qid], f"[{qid!r}]")
+        else:
+            shared = ids(given, "")
+            for qid in queries:
+                per_qid[qid][i] = shared
+    rows, row_of, row_of_qid = [], {}, {}
+    for qid in queries:
+        triple = tuple(per_qid[qid])
+        if triple == ((), (), ()):
+            row_of_qid[qid] = -1
+            continue
+        if triple not in row_of:
+            row_of[triple] = len(rows)
+            rows.append(triple)
+        row_of_qid[qid] = row_of[triple]
+    return TermFilterSpec(rows, row_of_qid) if rows else None
+
+
+def apply_operators(queries, must_terms=None, must_not_terms=None):
+    """``operators=True`` of the API mirrors: :func:`~.index.parse_operators` on every query text.  Returns (queries with the
+    scored texts, must_terms, must_not_terms) where the two keywords are dicts ``qid -> list`` that hold the caller's words (a
+    sequence counts for every qid) followed by the query's own ``+`` / ``-`` words."""
+    def per_qid(what, given):
+        if given is None:
+            return {qid: [] for qid in queries}
+        if isinstance(given, (str, bytes)):
+            raise ValueError(f"{what} must be a sequence of strings or a dict qid -> sequence, not one string")
+        if isinstance(given, dict):
+            for qid, words in given.items():
+                if isinstance(words, (str, bytes)):
+                    raise ValueError(f"{what}[{qid!r}] must be a sequence of strings, not one string")
+            return {qid: list(given.get(qid, ())) for qid in queries}
+        return {qid: list(given) for qid in queries}
+
+    must, must_not = per_qid("must_terms", must_terms), per_qid("must_not_terms", must_not_terms)
+    texts = {}
+    for qid, text in queries.items():
+        if not text:
+            texts[qid] = text
+            continue
+        texts[qid], plus, minus = parse_operators(text)
+        must[qid] += plus
+        must_not[qid] += minus
+    return texts, must, must_not
 
 
 def scores_to_dicts(results, live, scores):

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from .filter import DocFilter, q_filter_to_device, resolve_filter
+from .filter import DocFilter, filter_words, q_filter_to_device, resolve_filter
 
 BLOCK_PAD = 256  # SRX_BLOCK_PAD in include/sparse_rx.h: all-sentinel blocks behind the last run
 _TOKEN_RE = re.compile(r"\b\w+\b")
@@ -185,6 +185,49 @@ def validate_candidates(cand_doc, cand_count, nq: int) -> Tuple[np.ndarray, Opti
             raise ValueError("cand_count holds values that are not int32-representable")
         c = np.ascontiguousarray(c, dtype=np.int32)
     return np.ascontiguousarray(d, dtype=np.int32), c
+
+
+def term_lists_csr(lists, vocab: int, what: str = "terms") -> Tuple[np.ndarray, np.ndarray]:
+    """One list of term ids per filter row -> the CSR ``srx_filter_from_terms`` takes (ptr i32[n_rows + 1], term i32), checked on
+    the host: a sequence of sequences of integers in [-1, vocab) (-1: a term no doc has).  Raises ValueError."""
+    if isinstance(lists, (str, bytes)) or not hasattr(lists, "__len__"):
+        raise ValueError(f"{what} must be a list of lists of term ids, one per row")
+    ptr = np.zeros(len(lists) + 1, dtype=np.int32)
+    rows = []
+    for r, ids in enumerate(lists):
+        if isinstance(ids, (str, bytes)) or np.ndim(ids) != 1:
+            raise ValueError(f"{what}[{r}] must be a sequence of term ids")
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"{what}[{r}] must hold integers")
+        a = a.astype(np.int64)
+        if a.size and (int(a.min()) < -1 or int(a.max()) >= vocab):
+            raise ValueError(f"{what}[{r}] holds a term id outside [-1, {vocab})")
+        rows.append(a.astype(np.int32))
+        ptr[r + 1] = ptr[r] + a.size
+    term = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int32)
+    return ptr, np.ascontiguousarray(term, dtype=np.int32)
+
+
+_OPERATOR_RE = re.compile(r"[+-]\w")
+
+
+def parse_operators(text: str) -> Tuple[str, List[str], List[str]]:
+    """The ``+word`` / ``-word`` operators of a query text -> (scored_text, must, must_not).  A white-space separated word
+    that starts with ``+`` or ``-`` followed by a word character is an operator: ``+word`` stays in the scored text (without
+    the sign) and joins ``must``; ``-word`` leaves the text and joins ``must_not``.  Anything else is text: ``a-b``, a lone
+    ``+`` or ``-``, ``+ a``.  The lists hold the words as written (the term constraints tokenise them)."""
+    kept, must, must_not = [], [], []
+    for word in (text or "").split():
+        if _OPERATOR_RE.match(word):
+            if word[0] == "+":
+                must.append(word[1:])
+                kept.append(word[1:])
+            else:
+                must_not.append(word[1:])
+        else:
+            kept.append(word)
+    return " ".join(kept), must, must_not
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -698,6 +741,81 @@ class DeviceIndex:
         """Host arrays in, f32[nq, m] out.  The batch (``validate_queries``) and the candidates
         (:func:`validate_candidates`) are validated first; then one launch, one synchronisation and one copy."""
         return score_host_batch(self.score_docs_device, q_ptr, q_term, q_weight, cand_doc, cand_count, self.vocab, self.device)
+
+    # -- term constraints ---------------------------------------------------------------------------------
+    def term_filter_device(self, all=None, any=None, none=None, base=None, q_base=None, out=None) -> DocFilter:
+        """``srx_filter_from_terms`` (include/sparse_rx_terms.h): filter rows built from this index's posting lists.  Each of
+        ``all`` / ``any`` / ``none`` is None or a ``(ptr, term)`` pair of int32 device tensors, a CSR over the output rows
+        (ptr i32[n_rows + 1], term i32[ptr[-1]]; the given lists agree on n_rows, and at least one is given).  Row r allows the
+        docs that have every term of ``all[r]``, at least one of ``any[r]`` (when that list is not empty) and none of
+        ``none[r]``; term id -1 is "a term no doc has".  ``base``: a :class:`~.filter.DocFilter` over this index the rows are
+        intersected with, ``q_base`` None (base row 0) or an int32 device tensor [n_rows] (the base row of every OUTPUT row; -1:
+        none).  Returns a DocFilter over this index's ``n_docs`` / ``doc_base`` (``out``: its int32 tensor
+        [n_rows, filter_words(n_docs)], every word is written); asynchronous on the current stream.  Precondition (NOT checked
+        here, the tensors never leave the device): ptr starts at 0 and ascends, -1 <= term < vocab, q_base in [-1, n_filters).
+        Memory: n_rows * n_docs / 8 bytes -- 1.25 MB per row at 10 M docs."""
+        torch = _torch()
+        n_rows, ptrs = None, []
+        for name, pair in (("all", all), ("any", any), ("none", none)):
+            if pair is None:
+                ptrs += [None, None]
+                continue
+            ptr, term = pair
+            for t in (ptr, term):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or t.dim() != 1:
+                    raise ValueError(f"{name} must be a (ptr, term) pair of 1-D int32 tensors on {self.device}")
+            if ptr.numel() < 1 or (n_rows is not None and ptr.numel() - 1 != n_rows):
+                raise ValueError("the term lists must have one ptr entry per output row, plus one, and agree on the row count")
+            n_rows = ptr.numel() - 1
+            ptrs += [ptr.contiguous(), term.contiguous() if term.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)]
+        if n_rows is None:
+            raise ValueError("give at least one of all / any / none (an empty list is a ptr of zeros)")
+        if n_rows < 1:
+            raise ValueError("a filter needs at least one row")
+        bdesc, keep = None, None
+        if base is not None:
+            if not isinstance(base, DocFilter):
+                raise ValueError("base must be a DocFilter")
+            bdesc, keep = base.for_index(self).launch_args(q_base, n_rows)
+        elif q_base is not None:
+            raise ValueError("q_base picks rows of a base filter: it needs base=")
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty((n_rows, filter_words(self.n_docs)), dtype=torch.int32, device=self.device)
+            f = DocFilter(out, self.n_docs, self.doc_base)
+            if f.n_filters != n_rows or f.device != self.device:
+                raise ValueError(f"out must be an int32 tensor [{n_rows}, {f.words}] on {self.device}")
+            rc = _capi.lib().srx_filter_from_terms(ctypes.byref(self._desc), n_rows, *[_ptr(t) for t in ptrs], bdesc, _ptr(out),
+                                                   _stream_ptr(torch, self.device))
+            _capi.check(rc, "srx_filter_from_terms")
+        del keep
+        return f
+
+    def term_filter(self, all_terms=None, any_terms=None, none_terms=None, base=None, q_base=None) -> DocFilter:
+        """:meth:`term_filter_device` from host lists: each keyword is None or a list of lists of term ids, one per output row
+        (the given keywords agree on the row count).  Ids are validated against ``vocab`` (-1, "a term no doc has", is legal),
+        ``q_base`` (a host sequence) with :func:`~.filter.validate_q_filter`.  Memory: n_rows * n_docs / 8 bytes."""
+        torch = _torch()
+        pairs, n_rows = [], None
+        for name, lists in (("all_terms", all_terms), ("any_terms", any_terms), ("none_terms", none_terms)):
+            if lists is None:
+                pairs.append(None)
+                continue
+            ptr, term = term_lists_csr(lists, self.vocab, name)
+            if n_rows is not None and len(ptr) - 1 != n_rows:
+                raise ValueError("all_terms / any_terms / none_terms must have one list per output row each")
+            n_rows = len(ptr) - 1
+            pairs.append((torch.as_tensor(ptr, device=self.device), torch.as_tensor(term, device=self.device)))
+        if n_rows is None:
+            raise ValueError("give at least one of all_terms / any_terms / none_terms")
+        qb = None
+        if base is not None:
+            if not isinstance(base, DocFilter):
+                raise ValueError("base must be a DocFilter")
+            qb = q_filter_to_device(base.for_index(self), q_base, n_rows)
+        elif q_base is not None:
+            raise ValueError("q_base picks rows of a base filter: it needs base=")
+        return self.term_filter_device(*pairs, base=base, q_base=qb)
 
     def profile_read(self):
         """Average kernel durations (ms) over the profiled searches since the last read."""

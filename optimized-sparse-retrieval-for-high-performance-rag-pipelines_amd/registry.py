@@ -21,7 +21,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .backend import SparseBackend, SparseIndexViews
+from .backend import SparseBackend, SparseIndexViews, apply_operators
 from .index import HostIndex, check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
 
 _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
@@ -46,12 +46,17 @@ class _SparseRetrieverBase(SparseIndexViews):
     def _upload(self):
         self._be.upload(self.mode, self.k1, self.b)
 
-    def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None) -> Dict[str, Dict[str, float]]:
+    def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
+               must_not_terms=None, operators: bool = False) -> Dict[str, Dict[str, float]]:
         """``allowed_docs`` / ``excluded_docs`` (no reference counterpart): as ``RetrievalService.search_bm25`` -- the top
-        ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call."""
+        ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call.
+        ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators``: term constraints, as ``RetrievalService.search_bm25``
+        (rows built on the GPU from the posting lists, n_docs / 8 bytes per distinct constraint; scores unchanged; no cache)."""
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
+        if operators:
+            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
+        spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, self._be.doc_filter_spec(queries, allowed_docs, excluded_docs))
         if spec is not None:
             return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec)
         # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional

@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .backend import SparseBackend, SparseIndexViews
+from .backend import SparseBackend, SparseIndexViews, apply_operators
 from .index import check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, mmr_pool_depth, rows_to_dict
 
 logger = logging.getLogger(__name__)
@@ -96,18 +96,30 @@ class RetrievalService(SparseIndexViews):
             self.query_cache.clear()
 
     # -- search -----------------------------------------------------------------------------------------
-    def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None,
-                    excluded_docs=None) -> Dict[str, Dict[str, float]]:
+    def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None,
+                    any_terms=None, must_not_terms=None, operators: bool = False) -> Dict[str, Dict[str, float]]:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
 
         ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
         out of it, the named docs -- a sequence of doc ids for every query of the call, or a dict ``qid -> sequence`` (a qid
         missing from it is not filtered).  The result is the top ``top_k`` OF THE ALLOWED DOCS, exact
         (``srx_search_filtered``), not a filtered top list.  Giving both, or an unknown doc id, raises ``ValueError``; a
-        filtered call neither reads nor writes the query cache; a sharded index refuses."""
+        filtered call neither reads nor writes the query cache; a sharded index refuses.
+
+        ``must_terms`` / ``any_terms`` / ``must_not_terms`` (no reference counterpart either): term constraints -- a result must
+        contain every word of ``must_terms``, at least one of ``any_terms`` (when given) and none of ``must_not_terms``; each
+        a sequence of strings for every query, or a dict ``qid -> sequence``.  The words are tokenised like the corpus; a word
+        the vocabulary does not know is contained in no doc.  The rows are built on the GPU from the posting lists
+        (``srx_filter_from_terms``, include/sparse_rx_terms.h: n_docs / 8 bytes per distinct constraint, 1.25 MB at 10 M docs)
+        and restrict the doc set only: scores and the ``score > 0`` rule are unchanged.  They combine with ``allowed_docs`` /
+        ``excluded_docs`` and behave like them otherwise (no cache, a sharded index refuses).  ``operators=True``: the
+        ``+word`` / ``-word`` words of every query text are read as must / must-not constraints
+        (:func:`~.index.parse_operators`) and merged with the keywords."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
-        spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
+        if operators:
+            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
+        spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, self._be.doc_filter_spec(queries, allowed_docs, excluded_docs))
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
@@ -157,7 +169,7 @@ class RetrievalService(SparseIndexViews):
         self.embedding_storage = storage
 
     def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
-                         excluded_docs=None) -> List[Dict]:
+                         excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None) -> List[Dict]:
         """retrieval.py:402-436: ``np.dot(embedding_index, query_vector)`` + top-k on the GPU (``srx_dense_search_f32``),
         the ``min_score`` cut and the ``[{"doc_id", "score"}]`` result as in the reference.
 
@@ -170,16 +182,21 @@ class RetrievalService(SparseIndexViews):
         ulp(offset): docs whose true scores differ by less can swap places at the k-th boundary (scores <= 0 only).
 
         ``allowed_docs`` / ``excluded_docs``: a sequence of doc ids, as in :meth:`search_bm25`; both passes rank the allowed
-        docs alone (``srx_dense_search_f32_filtered``).
+        docs alone (``srx_dense_search_f32_filtered``).  ``must_terms`` / ``any_terms`` / ``must_not_terms``: a sequence of
+        strings each, as in :meth:`search_bm25` -- keyword-constrained vector search: the docs are those whose TEXT satisfies
+        the constraint (the BM25 index's posting lists), so it needs ``build_bm25_index``.
 
         With half-precision storage (:meth:`set_embeddings`) both passes run on the half index (``srx_dense_search_half``):
         the first pass returns the scores of the rounded rows; the second pass still re-scores its rows on the host with the
         f32 rows the service was given."""
+        for what, given in (("must_terms", must_terms), ("any_terms", any_terms), ("must_not_terms", must_not_terms)):
+            if isinstance(given, dict):
+                raise ValueError(f"{what} of search_by_vector must be a sequence of strings (there is one query)")
         self._ensure_dense()
         q = np.asarray(query_vector, dtype=np.float32)
         kk = max(1, min(int(k), self._dense.n_docs))
-        flt = self._dense_filter({"q": None}, allowed_docs, excluded_docs)
-        flt = {} if flt is None else {"filter": flt[0]}
+        flt = self._dense_filter({"q": None}, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms)
+        flt = {} if flt is None else {"filter": flt[0]}  # one query: its row is row 0
         d, s, n = self._dense.search(q, kk, **flt)
         if min_score > 0 or int(n[0]) == kk:
             idx, sc = d[0, : int(n[0])].astype(np.int64), s[0, : int(n[0])]
@@ -205,16 +222,22 @@ class RetrievalService(SparseIndexViews):
                 results.append({"doc_id": str(int(i)), "score": float(score)})
         return results
 
-    def _dense_filter(self, queries, allowed_docs, excluded_docs):
-        """The two filter keywords as (DocFilter over the embedding rows, spec), or None when both are None"""
-        if allowed_docs is None and excluded_docs is None:
+    def _dense_filter(self, queries, allowed_docs, excluded_docs, must_terms=None, any_terms=None, must_not_terms=None):
+        """The filter keywords as (DocFilter over the embedding rows, spec), or None when none constrains a query"""
+        terms = not (must_terms is None and any_terms is None and must_not_terms is None)
+        if allowed_docs is None and excluded_docs is None and not terms:
             return None
         if self.host is not None:
             spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
+            spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, spec)
+        elif terms:
+            raise ValueError("must_terms / any_terms / must_not_terms need the BM25 index (its posting lists): call build_bm25_index() first")
         else:  # embeddings without a BM25 index: docs are named by their row number
             from .backend import RowOfIds, doc_filter_spec
             spec = doc_filter_spec(RowOfIds.numbered(self._dense.n_docs).row_of, queries, allowed_docs, excluded_docs)
-        return spec.on_device(self._dense), spec
+        if spec is None:
+            return None
+        return spec.on_device(self._dense).for_index(self._dense), spec
 
     def _ensure_dense(self) -> None:
         if getattr(self, "_dense", None) is None and self.embedding_path and os.path.exists(str(self.embedding_path)) and self.doc_ids:
@@ -228,7 +251,8 @@ class RetrievalService(SparseIndexViews):
                       sparse_weight: float = 0.3, dense_weight: float = 0.7, fusion: str = "weighted", rrf_c: float = 60.0,
                       candidates: Optional[int] = None, rescore: bool = False, allowed_docs=None,
                       excluded_docs=None, mmr_lambda: Optional[float] = None, mmr_pool: Optional[int] = None,
-                      mmr_similarity: str = "cosine") -> Dict[str, Dict[str, float]]:
+                      mmr_similarity: str = "cosine", must_terms=None, any_terms=None, must_not_terms=None,
+                      operators: bool = False) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -257,7 +281,12 @@ class RetrievalService(SparseIndexViews):
         ``_half``, include/sparse_rx_mmr.h; ``mmr_similarity`` "cosine" or "dot" of the embedding rows) -- still one
         synchronisation and one copy back per call.  The result is what ``diversify(search_hybrid(top_k=mmr_pool, ...),
         top_k)`` returns: the docs in SELECTION order, each with its fused score, so the values are not descending.  Works
-        with ``rescore=True`` and with the filter keywords (the pool is then the filtered fusion)."""
+        with ``rescore=True`` and with the filter keywords (the pool is then the filtered fusion).
+        ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators`` as in :meth:`search_bm25`: the term-built rows go to
+        both sides like a doc filter's (``rescore=True`` and ``mmr_lambda`` included) and combine with ``allowed_docs`` /
+        ``excluded_docs``."""
+        if operators:
+            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
         rescore = check_rescore_args(fusion, rescore)
@@ -290,7 +319,7 @@ class RetrievalService(SparseIndexViews):
             self._upload()
         q_ptr, q_term, q_weight = encode_queries([text for _, text in live], self.host.vocabulary)
         flt = {}
-        fs = self._dense_filter(queries, allowed_docs, excluded_docs)  # one DocFilter serves both sides: same rows, same device
+        fs = self._dense_filter(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms)  # one DocFilter serves both sides: same rows, same device
         if fs is not None:
             import torch
             q_rows = np.asarray([fs[1].row_of_qid[qid] for qid, _ in live], dtype=np.int32)
