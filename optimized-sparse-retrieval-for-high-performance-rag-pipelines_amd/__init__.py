@@ -12,6 +12,7 @@ from .distributed import (ShardedSearcher, shard_range, global_df, global_avgdl,
                           build_sharded_host_index)
 from .backend import SparseBackend
 from .filter import DocFilter
+from .late import TokenIndex, check_late_shape, late_pool_depth
 
 __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", "build_host_index", "encode_queries", "merge_topk_device", "fuse_topk_device", "fuse_scored_device", "validate_candidates", "HybridRetriever",
            "tokenize", "build_library", "SparseRxError", "SparseRxUnavailable", "_capi", "ShardedSearcher", "shard_range",
@@ -19,4 +20,5 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "load_index_npz", "save_index_npz", "DenseF32Index", "DenseHalfIndex", "DenseInt8Index", "DenseUint8Index", "QuantizedEmbeddingIndex", "quantize_symmetric",
            "quantize_asymmetric", "quantize_query_asymmetric",
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
-           "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators"]
+           "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape",
+           "late_pool_depth"]

@@ -1,6 +1,6 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
-include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h and
-include/sparse_rx_terms.h).
+include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
+include/sparse_rx_terms.h and include/sparse_rx_maxsim.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -159,6 +159,15 @@ TERMS_SYMBOLS = {
     "srx_filter_from_terms": (ctypes.c_int, [ctypes.POINTER(IndexDesc), _I32, _VP, _VP, _VP, _VP, _VP, _VP, _FP, _VP, _VP]),
 }
 
+# every symbol include/sparse_rx_maxsim.h declares (the eighth header of the same library)
+_MAXSIM_HEAD = [_I32, _I32, _VP, _I64, _I32, _VP, _I64, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _I32]  # device .. m
+MAXSIM_SYMBOLS = {
+    "srx_maxsim_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "srx_maxsim_score_docs_half": (ctypes.c_int, [*_MAXSIM_HEAD, _VP, _VP, _I64, _VP]),
+    "srx_maxsim_rerank_half": (ctypes.c_int, [*_MAXSIM_HEAD, _I32, _VP, _VP, _VP, _VP, _I64, _VP]),
+}
+SRX_MAXSIM_MAX_QT = 128  # query tokens per query (pinned to the header by tests/test_late_cpu.py)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -184,7 +193,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_filter.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_half.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_mmr.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_terms.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_terms.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_maxsim.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -233,7 +243,7 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
-                                   **TERMS_SYMBOLS}.items():
+                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -252,7 +252,7 @@ class RetrievalService(SparseIndexViews):
                       candidates: Optional[int] = None, rescore: bool = False, allowed_docs=None,
                       excluded_docs=None, mmr_lambda: Optional[float] = None, mmr_pool: Optional[int] = None,
                       mmr_similarity: str = "cosine", must_terms=None, any_terms=None, must_not_terms=None,
-                      operators: bool = False) -> Dict[str, Dict[str, float]]:
+                      operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -284,7 +284,17 @@ class RetrievalService(SparseIndexViews):
         with ``rescore=True`` and with the filter keywords (the pool is then the filtered fusion).
         ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators`` as in :meth:`search_bm25`: the term-built rows go to
         both sides like a doc filter's (``rescore=True`` and ``mmr_lambda`` included) and combine with ``allowed_docs`` /
-        ``excluded_docs``."""
+        ``excluded_docs``.
+        ``late_query_tokens`` (default None: nothing changes): ``{qid: f32[t_q, dim]}`` makes the call return the fused
+        ranking RERANKED by late interaction.  The fused ranking is then taken ``late_pool`` deep (default
+        ``min(max(top_k, 100), 1024, n_docs)``; more than 1024 raises ``ValueError``), ``candidates`` defaults to at least the
+        pool, and the MaxSim scores over the token index of :meth:`set_token_embeddings` pick and order ``top_k`` of the pool
+        on the device (``srx_maxsim_rerank_half``, include/sparse_rx_maxsim.h) -- still one synchronisation and one copy
+        back.  The result is what ``rerank_late(search_hybrid(top_k=late_pool, ...), late_query_tokens, top_k)`` returns: the
+        values are MaxSim scores.  Works with ``rescore=True`` and the filter / term keywords; together with ``mmr_lambda`` it
+        raises ``ValueError`` (chain :meth:`rerank_late` and :meth:`diversify` instead)."""
+        if late_query_tokens is not None and mmr_lambda is not None:
+            raise ValueError("late_query_tokens and mmr_lambda do not combine in one call: chain rerank_late() and diversify()")
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         fusion = str(fusion).lower()
@@ -298,6 +308,12 @@ class RetrievalService(SparseIndexViews):
             pool = mmr_pool_depth(top_k, mmr_pool, self._be.n_docs_total)
             if candidates is None:
                 cand = hybrid_depths(top_k, max(int(top_k), pool, 1), self._be.n_docs_total)[1]
+        late = None
+        if late_query_tokens is not None:
+            from .late import late_pool_depth
+            late = late_pool_depth(top_k, late_pool, self._be.n_docs_total)
+            if candidates is None:
+                cand = hybrid_depths(top_k, max(int(top_k), late, 1), self._be.n_docs_total)[1]
         if self._be.sharded():
             raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
         if self.host is None:
@@ -333,7 +349,19 @@ class RetrievalService(SparseIndexViews):
             import torch
             return self._dense.score_docs_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), cand_doc, cand_count)
 
-        if pool is None:
+        if late is not None:
+            import torch
+            from .late import stack_query_tokens
+            tokens = self._ensure_late()
+            q_tok, q_cnt = stack_query_tokens(late_query_tokens, [qid for qid, _ in live], tokens.dim)
+
+            def reranked(f_doc, f_score, f_count):  # the fused triple, pool deep, still on the device
+                return tokens.rerank_device(torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device),
+                                            f_doc, f_count, min(k, late))
+
+            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, late, fusion,
+                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=reranked, **flt)
+        elif pool is None:
             doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
                                               (sparse_weight, dense_weight), rrf_c, rescore, dense_score, **flt)
         else:
@@ -410,6 +438,78 @@ class RetrievalService(SparseIndexViews):
             out[qid] = {(doc_ids[int(doc[i, j])] if doc_ids is not None else str(int(doc[i, j]))): float(score[i, j]) for j in range(int(count[i]))}
         return out
 
+    # -- late interaction (no reference counterpart) -----------------------------------------------------------
+    def set_token_embeddings(self, token_embeddings, storage: str = "f16") -> None:
+        """Put the TOKEN vectors of the docs on the GPU for :meth:`rerank_late` (:class:`~.late.TokenIndex`; rounded to
+        ``storage`` "f16" or "bf16").  ``token_embeddings``: ``{doc_id: f32[t_d, dim]}`` with every indexed doc present (``t_d``
+        may be 0), or ``(matrix f32[n_tok, dim], counts)`` with the docs' tokens in ``doc_ids`` order.  Needs the BM25 index
+        (it fixes ``doc_ids``) and the whole index on one GPU.  ``ValueError`` otherwise, and for a missing or unknown doc, a
+        shape mismatch, no token at all or a non-finite value."""
+        from .dense import check_half_dtype
+        from .late import TokenIndex
+        storage = check_half_dtype(storage)
+        if self._be.sharded():
+            raise ValueError("late interaction needs the whole index on one GPU (the token store is not sharded)")
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        ids = self.host.doc_ids
+        if isinstance(token_embeddings, dict):
+            known = set(ids)
+            for d in token_embeddings:
+                if d not in known:
+                    raise ValueError(f"unknown doc id {d!r} among the token embeddings")
+            mats = []
+            for d in ids:
+                if d not in token_embeddings:
+                    raise ValueError(f"no token embeddings for doc {d!r} (a doc without tokens needs an empty [0, dim] matrix)")
+                mats.append(np.asarray(token_embeddings[d], dtype=np.float32))
+            dims = {t.shape[1] for t in mats if t.ndim == 2}
+            if any(t.ndim != 2 for t in mats) or len(dims) != 1:
+                raise ValueError("token embeddings must be [t_d, dim] matrices of one dim")
+            matrix, counts = np.concatenate(mats, axis=0), [t.shape[0] for t in mats]
+        else:
+            matrix, counts = token_embeddings
+            matrix = np.asarray(matrix, dtype=np.float32)
+            if matrix.ndim != 2 or len(counts) != len(ids):
+                raise ValueError("token embeddings must be (f32[n_tok, dim], one token count per document)")
+        self._late = TokenIndex.from_token_embeddings(matrix, counts, dtype=storage, device=self.device)
+        self.token_storage = storage
+
+    def _ensure_late(self):
+        if getattr(self, "_late", None) is None:
+            raise ValueError("No token index available. Call set_token_embeddings() first.")
+        return self._late
+
+    def rerank_late(self, results: Dict[str, Dict[str, float]], query_tokens, top_k: int = 10) -> Dict[str, Dict[str, float]]:
+        """Late-interaction rerank of ranked lists (no reference counterpart): ``results`` = ``{qid: {doc_id: score}}`` as any
+        search of this service returns it, ``query_tokens`` = ``{qid: f32[t_q, dim]}``.  Every listed doc is scored
+        ``sum over the query's tokens of the largest similarity to any token of the doc`` over the token index of
+        :meth:`set_token_embeddings`, on the GPU (``srx_maxsim_rerank_half``, include/sparse_rx_maxsim.h has the exact
+        arithmetic).  All queries of the call run as one batch.
+
+        Returns ``{qid: {doc_id: maxsim_score}}`` with the ``top_k`` best docs per query (fewer when the list is shorter) by
+        (score descending, row of the doc ascending); scores may be negative or 0 (a doc without tokens scores 0).  ``{}``
+        stays ``{}``, a qid with an empty list gives ``{}``, ``top_k <= 0`` gives ``{}`` per query.  ``ValueError``: an
+        unknown doc id, a list longer than 1024 docs (no silent truncation), more than 128 query tokens, missing query
+        tokens, no token index, a sharded index."""
+        from .late import LATE_MAX_M, stack_query_tokens
+        if self._be.sharded():
+            raise ValueError("late interaction needs the whole index on one GPU (the token store is not sharded)")
+        if not results:
+            return {}
+        tokens = self._ensure_late()
+        out, live, cand_doc, cand_count = self._be.candidate_block(results, {qid: list(row) for qid, row in results.items()})
+        m = int(cand_doc.shape[1])
+        if m > LATE_MAX_M:
+            raise ValueError(f"rerank_late takes lists of at most {LATE_MAX_M} docs, got one of {m} (no silent truncation)")
+        q_tok, q_cnt = stack_query_tokens(query_tokens, [qid for qid, _, _ in live], tokens.dim)
+        if not live or int(top_k) <= 0:
+            return out
+        doc, score, count = tokens.rerank(q_tok, q_cnt, cand_doc, cand_count, min(int(top_k), m))
+        for i, (qid, _, _) in enumerate(live):
+            out[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
+        return out
+
     def clear_cache(self) -> None:
         with self.cache_lock:
             self.query_cache.clear()
@@ -440,5 +540,8 @@ class RetrievalService(SparseIndexViews):
         self.close()
 
     def close(self) -> None:
+        if getattr(self, "_late", None) is not None:
+            self._late.close()
+            self._late = None
         self._be.close()
         self.clear_cache()
