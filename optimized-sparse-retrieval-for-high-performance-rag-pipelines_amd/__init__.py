@@ -13,6 +13,7 @@ from .distributed import (ShardedSearcher, shard_range, global_df, global_avgdl,
 from .backend import SparseBackend
 from .filter import DocFilter
 from .late import TokenIndex, check_late_shape, late_pool_depth
+from .fields import FieldTable, columns_from_metadata
 
 __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", "build_host_index", "encode_queries", "merge_topk_device", "fuse_topk_device", "fuse_scored_device", "validate_candidates", "HybridRetriever",
            "tokenize", "build_library", "SparseRxError", "SparseRxUnavailable", "_capi", "ShardedSearcher", "shard_range",
@@ -21,4 +22,4 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "quantize_asymmetric", "quantize_query_asymmetric",
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
            "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape",
-           "late_pool_depth"]
+           "late_pool_depth", "FieldTable", "columns_from_metadata"]

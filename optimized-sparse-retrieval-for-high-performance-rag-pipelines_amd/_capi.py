@@ -1,6 +1,6 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
-include/sparse_rx_terms.h and include/sparse_rx_maxsim.h).
+include/sparse_rx_terms.h, include/sparse_rx_maxsim.h and include/sparse_rx_fields.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -168,6 +168,21 @@ MAXSIM_SYMBOLS = {
 }
 SRX_MAXSIM_MAX_QT = 128  # query tokens per query (pinned to the header by tests/test_late_cpu.py)
 
+
+class FieldColDesc(ctypes.Structure):
+    """``srx_field_col`` (include/sparse_rx_fields.h): a host struct of device pointers"""
+    _fields_ = [("data", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("type", ctypes.c_int32)]
+
+
+# every symbol include/sparse_rx_fields.h declares (the ninth header of the same library)
+FIELDS_SYMBOLS = {
+    "srx_filter_from_fields": (ctypes.c_int, [_I32, _I64, ctypes.POINTER(FieldColDesc), _I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                              _FP, _VP, _VP]),
+}
+SRX_FIELD_I32, SRX_FIELD_I64, SRX_FIELD_F32, SRX_FIELD_SET64 = 0, 1, 2, 3         # column types
+SRX_FOP_RANGE, SRX_FOP_IN, SRX_FOP_MASK_ANY, SRX_FOP_MASK_ALL = 0, 1, 2, 3        # clause ops
+SRX_FIELDS_MAX_COLS = 32                                                          # columns one call takes
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -194,7 +209,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_half.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_mmr.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_terms.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_maxsim.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_maxsim.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_fields.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -243,7 +259,7 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
-                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS}.items():
+                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

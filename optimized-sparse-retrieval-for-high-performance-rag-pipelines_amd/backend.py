@@ -47,6 +47,8 @@ class SparseBackend:
         self.doc_base = 0
         self.n_docs_total = 0
         self._doc_lengths_all = None
+        self._fields = None        # set_fields: the docs' metadata columns on the host (fields.HostColumn by name) ...
+        self._field_table = None   # ... and on the device, uploaded by the first call that filters with them
 
     def world(self) -> int:
         try:
@@ -71,6 +73,8 @@ class SparseBackend:
 
     # -- build ------------------------------------------------------------------------------------------
     def build(self, corpus, idf_kind: str = "bm25") -> HostIndex:
+        self._drop_field_table()
+        self._fields = None  # columns are aligned with the docs of one build
         if self.sharded():
             from .distributed import build_sharded_host_index
             self.host, self.doc_base, self.n_docs_total, self._doc_lengths_all = build_sharded_host_index(corpus, idf_kind, self.group)
@@ -82,6 +86,8 @@ class SparseBackend:
         """A complete host index (built here or read from the .npz cache): the one-shard case."""
         if self.sharded():
             raise ValueError("a pre-built whole-corpus index cannot be adopted by a sharded group: build it from the corpus")
+        self._drop_field_table()
+        self._fields = None
         self.host, self.doc_base, self.n_docs_total, self._doc_lengths_all = host, 0, host.n_docs, None
 
     def upload(self, mode: str, k1: float, b: float) -> None:
@@ -154,6 +160,48 @@ class SparseBackend:
             raise ValueError("must_terms / any_terms / must_not_terms need the whole index on one GPU (a sharded search takes no doc filter)")
         spec = spec.with_base(doc_spec, queries)
         spec.sparse = lambda: self.dev
+        return spec
+
+    def set_fields(self, columns) -> None:
+        """The docs' metadata columns (``fields.FieldTable.from_columns`` takes the same dict), row i = the i-th doc of the built
+        index.  Kept on the host; the first ``where=`` call uploads them.  ValueError: no index, a length that is not the index's."""
+        from .fields import host_columns
+        if self.host is None:
+            raise ValueError("the docs' fields are aligned with the index: build it first")
+        cols = host_columns(columns)
+        n = len(next(iter(cols.values())))
+        if n != self.host.n_docs:
+            raise ValueError(f"the columns have {n} entries, the index {self.host.n_docs} docs: one entry per doc, in the order of the corpus")
+        self._drop_field_table()
+        self._fields = cols
+
+    def _drop_field_table(self) -> None:
+        if self._field_table is not None:
+            self._field_table.close()
+            self._field_table = None
+
+    def field_table(self):
+        """The columns of :meth:`set_fields` on this backend's device (uploaded once)"""
+        from .fields import FieldTable
+        if self._field_table is None:
+            self._field_table = FieldTable.from_columns(self._fields, device=self.dev.device if self.dev is not None else self.device, doc_base=self.doc_base)
+        return self._field_table
+
+    def field_filter_spec(self, queries, where, base_spec=None, call: str = "search"):
+        """:func:`field_filter_spec` over the columns of :meth:`set_fields`, with ``base_spec`` (the doc / term spec of the same
+        call, or None) as the base; ``base_spec`` itself when ``where`` is None or constrains no query.  ValueError: no fields
+        (the message names ``call``), a sharded index."""
+        if where is None:
+            return base_spec
+        if self._fields is None:
+            raise ValueError(f"{call}(where=...) needs the docs' fields: call set_doc_fields() first")
+        spec = field_filter_spec(self._fields, queries, where)
+        if spec is None:
+            return base_spec
+        if self.sharded():
+            raise ValueError("where= needs the whole index on one GPU (a sharded search takes no doc filter)")
+        spec = spec.with_base(base_spec, queries)
+        spec.table = self.field_table
         return spec
 
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
@@ -248,6 +296,7 @@ class SparseBackend:
         return self._rows.candidate_block(queries, candidates)
 
     def close(self) -> None:
+        self._drop_field_table()
         if self.dev is not None:
             self.dev.close()
             self.dev = None
@@ -435,6 +484,56 @@ def term_filter_spec(vocabulary, queries, must_terms=None, any_terms=None, must_
             rows.append(triple)
         row_of_qid[qid] = row_of[triple]
     return TermFilterSpec(rows, row_of_qid) if rows else None
+
+
+class FieldFilterSpec:
+    """The ``where`` keyword of one API call, resolved on the host: ``resolver`` = the :class:`~.fields.WhereResolver` that holds
+    the call's clause records, ``rows`` = one (all, any, none) triple of its clause ids per filter row, ``row_of_qid`` = every qid's
+    row (-1: not filtered).  With a base (:meth:`with_base`): ``base`` = the call's :class:`DocFilterSpec` or
+    :class:`TermFilterSpec`, ``base_rows`` = its row for every row here (-1: none).  ``table`` () -> the
+    :class:`~.fields.FieldTable` of the corpus.  Memory on the device: len(rows) * n_docs / 8 bytes."""
+
+    def __init__(self, resolver, rows, row_of_qid, base=None, base_rows=None):
+        self.resolver, self.rows, self.row_of_qid, self.base, self.base_rows, self.table = resolver, rows, row_of_qid, base, base_rows, None
+
+    def with_base(self, base_spec, queries) -> "FieldFilterSpec":
+        """This spec restricted to the docs ``base_spec`` allows: one row per distinct (base row, field row) pair of the call's
+        qids; a qid neither spec filters stays unfiltered."""
+        if base_spec is None:
+            return self
+        pairs, row_of_qid = {}, {}
+        for qid in queries:
+            pair = (base_spec.row_of_qid[qid], self.row_of_qid[qid])
+            row_of_qid[qid] = -1 if pair == (-1, -1) else pairs.setdefault(pair, len(pairs))
+        empty = ((), (), ())
+        rows = [self.rows[f] if f >= 0 else empty for _, f in pairs] or [empty]
+        return FieldFilterSpec(self.resolver, rows, row_of_qid, base_spec, [b for b, _ in pairs] or [-1])
+
+    def on_device(self, index):
+        """The :class:`~.filter.DocFilter` of the rows (``srx_filter_from_fields`` on the field table), for ``index``: any index of
+        the same corpus (same n_docs / doc_base / device)"""
+        if self.table is None:
+            raise ValueError("field predicates need the docs' field table")
+        base = None if self.base is None else self.base.on_device(index)
+        return self.table().filter_resolved(self.resolver, self.rows, base=base, q_base=None if base is None else self.base_rows)
+
+
+def field_filter_spec(schema, queries, where) -> Optional[FieldFilterSpec]:
+    """The ``where`` keyword of the API mirrors -> a :class:`FieldFilterSpec`, or None when no qid of ``queries`` is constrained.
+    ``where`` is one group for every query -- a dict whose keys all lie in {"must", "should", "must_not"}, or a bare list of
+    clauses -- or a dict ``qid -> group`` (a qid missing from it is not constrained).  ``schema``: name ->
+    :class:`~.fields.HostColumn`.  Equal clauses share a record and equal groups a row; a malformed group or clause, an unknown
+    field or a test that does not fit its column raises ValueError."""
+    from .fields import WhereResolver, is_group
+    res = WhereResolver(schema, share_rows=True)
+    if is_group(where):
+        shared = res.add(where)
+        row_of_qid = {qid: shared for qid in queries}
+    elif isinstance(where, dict):
+        row_of_qid = {qid: res.add(where[qid]) if qid in where else -1 for qid in queries}
+    else:
+        raise ValueError("where must be a group (must / should / must_not, or a list of clauses) or a dict qid -> group")
+    return FieldFilterSpec(res, list(res.rows), row_of_qid) if res.rows else None
 
 
 def apply_operators(queries, must_terms=None, must_not_terms=None):

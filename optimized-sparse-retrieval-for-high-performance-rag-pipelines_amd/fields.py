@@ -1,0 +1,604 @@
+"""Field predicates (include/sparse_rx_fields.h): doc metadata as resident columns, and predicates over them as filter rows.
+
+A :class:`FieldTable` keeps typed columns of a corpus on the GPU -- int32 / int64 / float32 values, categories (strings as
+int32 codes, the dictionary stays on the host) and label sets (up to 64 labels as the bits of an int64) -- each with an optional
+validity row for the docs that have no value.  :meth:`FieldTable.filter` turns a ``where`` predicate into the rows of a
+:class:`~.filter.DocFilter` (``srx_filter_from_fields``), which every filtered search takes as it is.  The reference has no
+filters, and nothing reads its ``metadata`` dicts: nothing here mirrors reference code.
+
+The predicate is resolved to clause records ON THE HOST (:class:`WhereResolver`), so that the device's same-type comparison
+equals the comparison in exact arithmetic: a Python bound on a float32 column is rounded towards the inside of its range, a
+non-integral or out-of-range bound on an integer column likewise, and what no value can satisfy becomes clause id -1.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from . import _capi
+from .filter import DocFilter, filter_words, pack_masks, q_filter_to_device
+
+I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
+I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
+GROUP_KEYS = ("must", "should", "must_not")
+_RANGE_KEYS = ("gte", "gt", "lte", "lt")
+_TEST_KEYS = _RANGE_KEYS + ("eq", "in", "any_of", "all_of", "exists")
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class HostColumn:
+    """One column on the host: ``kind`` ("int32", "int64", "float32", "bool", "category", "set"), ``type`` (its SRX_FIELD_*),
+    ``data`` (the array that goes to the device: int32 / int64 / float32; int64 holds a set's bits), ``valid`` (bool[n_docs],
+    or None when every doc has a value) and ``dictionary`` (the sorted distinct strings of a category column -- code = position
+    --, the labels of a set column -- label i = bit i --, else None)."""
+
+    def __init__(self, kind: str, data: np.ndarray, valid: Optional[np.ndarray], dictionary=None):
+        self.kind, self.data, self.valid, self.dictionary = kind, np.ascontiguousarray(data), valid, dictionary
+        self.type = {"int32": _capi.SRX_FIELD_I32, "bool": _capi.SRX_FIELD_I32, "category": _capi.SRX_FIELD_I32, "int64": _capi.SRX_FIELD_I64,
+                     "float32": _capi.SRX_FIELD_F32, "set": _capi.SRX_FIELD_SET64}[kind]
+        self.code_of = {s: i for i, s in enumerate(dictionary)} if dictionary is not None else None
+
+    def __len__(self) -> int:
+        return int(self.data.shape[0])
+
+
+def _array_column(name: str, a: np.ndarray, valid) -> HostColumn:
+    if a.ndim != 1:
+        raise ValueError(f"column {name!r} must have one entry per doc (a 1-D sequence)")
+    if a.dtype == np.float64:
+        raise ValueError(f"column {name!r} is float64: cast it to float32 (the device compares float32 values; a float64 column would "
+                         "change the values a bound is compared with)")
+    if a.dtype == np.bool_:
+        return HostColumn("bool", a.astype(np.int32), valid)
+    if a.dtype in (np.int8, np.int16, np.uint8, np.uint16):
+        a = a.astype(np.int32)
+    elif a.dtype == np.uint32:
+        a = a.astype(np.int64)
+    if a.dtype == np.int32:
+        return HostColumn("int32", a, valid)
+    if a.dtype == np.int64:
+        return HostColumn("int64", a, valid)
+    if a.dtype == np.float32:
+        return HostColumn("float32", a, valid)
+    raise ValueError(f"column {name!r} has dtype {a.dtype}: give int32, int64, float32 or bool values, strings or collections of strings")
+
+
+def host_column(name: str, values) -> HostColumn:
+    """One entry of ``columns`` as a :class:`HostColumn` (the type mapping of :meth:`FieldTable.from_columns`)"""
+    if isinstance(values, np.ma.MaskedArray):
+        mask = np.ma.getmaskarray(values)
+        valid = None if not mask.any() else ~mask
+        data = np.asarray(values.filled(0) if values.dtype != np.bool_ else values.filled(False))
+        return _array_column(name, data, valid)
+    if isinstance(values, np.ndarray) and values.dtype != object:
+        if values.dtype.kind in "US":
+            values = values.tolist()
+        else:
+            return _array_column(name, values, None)
+    if isinstance(values, (str, bytes)) or not hasattr(values, "__len__"):
+        raise ValueError(f"column {name!r} must be a sequence with one entry per doc")
+    seq = list(values)
+    valid = np.asarray([v is not None for v in seq], dtype=bool)
+    some = [v for v in seq if v is not None]
+    if not some:
+        raise ValueError(f"column {name!r} holds no value at all: its type cannot be told")
+    valid_or_none = None if valid.all() else valid
+    if all(isinstance(v, str) for v in some):
+        dictionary = sorted(set(some))
+        code = {s: i for i, s in enumerate(dictionary)}
+        return HostColumn("category", np.asarray([code[v] if v is not None else 0 for v in seq], dtype=np.int32), valid_or_none, dictionary)
+    if all(isinstance(v, (set, frozenset, list, tuple)) for v in some):
+        if not all(isinstance(s, str) for v in some for s in v):
+            raise ValueError(f"column {name!r}: a set column holds collections of strings")
+        labels = sorted({s for v in some for s in v})
+        if len(labels) > 64:
+            raise ValueError(f"column {name!r} holds {len(labels)} distinct labels: a set column takes at most 64")
+        bit = {s: i for i, s in enumerate(labels)}
+        bits = np.asarray([sum(1 << bit[s] for s in set(v)) if v is not None else 0 for v in seq], dtype=np.uint64)
+        return HostColumn("set", bits.view(np.int64), valid_or_none, labels)
+    if all(isinstance(v, (bool, np.bool_)) for v in some):
+        return HostColumn("bool", np.asarray([int(bool(v)) if v is not None else 0 for v in seq], dtype=np.int32), valid_or_none)
+    if all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in some):
+        if any(not (I64_MIN <= int(v) <= I64_MAX) for v in some):
+            raise ValueError(f"column {name!r} holds an integer outside int64")
+        return HostColumn("int64", np.asarray([int(v) if v is not None else 0 for v in seq], dtype=np.int64), valid_or_none)
+    if all(isinstance(v, np.float32) for v in some):
+        return HostColumn("float32", np.asarray([v if v is not None else 0 for v in seq], dtype=np.float32), valid_or_none)
+    if all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) for v in some):
+        raise ValueError(f"column {name!r} holds Python / float64 numbers: cast it to float32 (a float32 array, or a numpy.ma array of "
+                         "float32 where entries are missing)")
+    raise ValueError(f"column {name!r} mixes value types: give numbers, strings or collections of strings (None = no value)")
+
+
+def host_columns(columns) -> Dict[str, HostColumn]:
+    """``columns`` (name -> sequence of n_docs entries) as :class:`HostColumn` objects; the lengths must agree."""
+    if not isinstance(columns, dict) or not columns:
+        raise ValueError("columns must be a non-empty dict name -> sequence of n_docs entries")
+    out = {str(name): host_column(str(name), values) for name, values in columns.items()}
+    if len({len(c) for c in out.values()}) != 1:
+        raise ValueError("the columns must have one entry per doc each: their lengths differ")
+    if len(next(iter(out.values()))) < 1:
+        raise ValueError("the columns are empty")
+    return out
+
+
+def columns_from_metadata(corpus, names: Sequence[str]) -> Dict[str, list]:
+    """The ``metadata`` dicts of a corpus (``{doc_id: {"text": ..., "metadata": {...}}}``) as columns in the corpus's order:
+    ``{name: [corpus[doc_id].get("metadata") or {} ).get(name) for every doc]}``; a missing key is None."""
+    if isinstance(names, (str, bytes)):
+        raise ValueError("names must be a sequence of field names, not one string")
+    metas = [(doc.get("metadata") or {}) if isinstance(doc, dict) else {} for doc in corpus.values()]
+    return {name: [m.get(name) for m in metas] for name in names}
+
+
+# ---- exact bounds -------------------------------------------------------------------------------------------------------------
+def _number(x, what):
+    if isinstance(x, (bool, np.bool_)):
+        return int(x)
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    if isinstance(x, (float, np.floating)):
+        return float(x)
+    raise ValueError(f"{what} must be a number, got {x!r}")
+
+
+def _f32_nearest(b) -> np.float32:
+    try:
+        with np.errstate(over="ignore"):
+            return np.float32(float(b))
+    except OverflowError:  # an int beyond float64
+        return np.float32(np.inf if b > 0 else -np.inf)
+
+
+def f32_at_least(b):
+    """The smallest float32 >= b in exact arithmetic (b an int or a float; NaN: None)"""
+    if isinstance(b, float) and math.isnan(b):
+        return None
+    f = _f32_nearest(b)
+    if float(f) < b:  # Python compares an int with a float exactly
+        with np.errstate(over="ignore"):
+            f = np.nextafter(f, np.float32(np.inf))
+    return f
+
+
+def f32_at_most(b):
+    """The largest float32 <= b in exact arithmetic (NaN: None)"""
+    if isinstance(b, float) and math.isnan(b):
+        return None
+    f = _f32_nearest(b)
+    if float(f) > b:
+        with np.errstate(over="ignore"):
+            f = np.nextafter(f, np.float32(-np.inf))
+    return f
+
+
+def f32_bits(f) -> int:
+    """The bits of a float32 as a non-negative int (the low 32 bits of a clause's lo / hi or of a ``values`` entry)"""
+    return int(np.asarray(f, dtype=np.float32).view(np.uint32))
+
+
+def _int_floor(b):
+    return b if isinstance(b, int) else None if math.isnan(b) else I64_MAX + 1 if b == math.inf else I64_MIN - 1 if b == -math.inf else math.floor(b)
+
+
+def _int_ceil(b):
+    return b if isinstance(b, int) else None if math.isnan(b) else I64_MAX + 1 if b == math.inf else I64_MIN - 1 if b == -math.inf else math.ceil(b)
+
+
+class WhereResolver:
+    """``where`` groups -> clause records, over the columns of one table (``schema``: name -> :class:`HostColumn` or anything with
+    its ``kind`` / ``type`` / ``code_of``).  Equal clauses share a record, and with ``share_rows`` equal groups share a row.
+
+    ``names``    the columns the clauses name, in the order of first use: a clause's ``col`` indexes this list
+    ``clauses``  [(col, op, lo, hi)]; an IN clause holds its value tuple in ``lo`` until :meth:`arrays` lays the lists out
+    ``rows``     [(all, any, none)] tuples of clause ids, -1 = a clause no doc satisfies"""
+
+    def __init__(self, schema, share_rows: bool = False):
+        self.schema, self.share_rows = schema, share_rows
+        self.names: List[str] = []
+        self.clauses: List[tuple] = []
+        self.rows: List[tuple] = []
+        self._clause_of, self._row_of = {}, {}
+
+    # -- one clause ---------------------------------------------------------------------------------------------------------
+    def _record(self, name, op, lo, hi) -> int:
+        key = (name, op, lo, hi)
+        if key not in self._clause_of:
+            if name not in self.names:
+                self.names.append(name)
+            self._clause_of[key] = len(self.clauses)
+            self.clauses.append((self.names.index(name), op, lo, hi))
+        return self._clause_of[key]
+
+    def clause(self, c) -> int:
+        """One clause dict -> its record's id, or -1 when no value can satisfy it.  Raises ValueError for a malformed clause, an
+        unknown field and a test that does not fit the column's type."""
+        if not isinstance(c, dict) or "field" not in c:
+            raise ValueError(f"a clause is a dict with \"field\" and a test, got {c!r}")
+        name = c["field"]
+        if name not in self.schema:
+            raise ValueError(f"unknown field {name!r}")
+        tests = [k for k in c if k != "field"]
+        if not tests or any(k not in _TEST_KEYS for k in tests):
+            raise ValueError(f"the clause on {name!r} needs one of {', '.join(_TEST_KEYS)}; got {sorted(tests)}")
+        if len(tests) > 1 and any(k not in _RANGE_KEYS for k in tests):
+            raise ValueError(f"the clause on {name!r} combines {sorted(tests)}: only gte / gt / lte / lt combine")
+        col = self.schema[name]
+        kind = col.kind
+        if "exists" in c:
+            if c["exists"] is not True:
+                raise ValueError("exists takes True only: put the clause under must_not for the docs without a value")
+            if kind == "set":
+                return self._record(name, _capi.SRX_FOP_MASK_ALL, 0, 0)
+            if kind == "float32":  # the full range: a NaN passes no range, so it counts as missing
+                return self._record(name, _capi.SRX_FOP_RANGE, f32_bits(-np.inf), f32_bits(np.inf))
+            lo, hi = (I64_MIN, I64_MAX) if kind == "int64" else (I32_MIN, I32_MAX)
+            return self._record(name, _capi.SRX_FOP_RANGE, lo, hi)
+        if "any_of" in c or "all_of" in c:
+            key = "any_of" if "any_of" in c else "all_of"
+            if kind != "set":
+                raise ValueError(f"{key} is for set columns; {name!r} is a {kind} column")
+            labels = c[key]
+            if isinstance(labels, (str, bytes)) or not hasattr(labels, "__iter__"):
+                raise ValueError(f"{key} takes a collection of labels, not {labels!r}")
+            labels = list(labels)
+            known = [col.code_of[s] for s in labels if s in col.code_of]
+            mask = sum(1 << b for b in set(known))
+            if key == "all_of":
+                if len(known) != len(labels):
+                    return -1  # a label no doc carries
+                return self._record(name, _capi.SRX_FOP_MASK_ALL, _as_i64(mask), 0)
+            return self._record(name, _capi.SRX_FOP_MASK_ANY, _as_i64(mask), 0) if mask else -1
+        if kind == "set":
+            raise ValueError(f"{name!r} is a set column: it takes any_of / all_of / exists, not {sorted(tests)}")
+        if "eq" in c or "in" in c:
+            if "in" in c and (isinstance(c["in"], (str, bytes)) or not hasattr(c["in"], "__iter__")):
+                raise ValueError(f"in takes a collection of values, not {c['in']!r}")
+            wanted = [c["eq"]] if "eq" in c else list(c["in"])
+            vals = sorted({v for v in (self._exact_value(name, col, x) for x in wanted) if v is not None})
+            if not vals:
+                return -1
+            if len(vals) == 1:  # one value is the range [v, v] (a float's too: IEEE compares, so +0 takes -0 as == does)
+                return self._record(name, _capi.SRX_FOP_RANGE, vals[0], vals[0])
+            return self._record(name, _capi.SRX_FOP_IN, tuple(vals), len(vals))
+        # ---- a range
+        if kind == "category":
+            raise ValueError(f"{name!r} is a category column: it takes eq / in / exists, not a range")
+        bound = {k: _number(c[k], f"{k} on {name!r}") for k in tests}
+        if kind == "float32":
+            lo, hi = np.float32(-np.inf), np.float32(np.inf)
+            for k, b in bound.items():
+                if k in ("gte", "gt"):
+                    f = f32_at_least(b)
+                    if f is not None and k == "gt" and float(f) == b:
+                        f = None if f == np.inf else np.nextafter(f, np.float32(np.inf))
+                    if f is None:
+                        return -1
+                    lo = max(lo, f)
+                else:
+                    f = f32_at_most(b)
+                    if f is not None and k == "lt" and float(f) == b:
+                        f = None if f == -np.inf else np.nextafter(f, np.float32(-np.inf))
+                    if f is None:
+                        return -1
+                    hi = min(hi, f)
+            if lo > hi:
+                return -1
+            return self._record(name, _capi.SRX_FOP_RANGE, f32_bits(lo), f32_bits(hi))
+        tmin, tmax = (I64_MIN, I64_MAX) if kind == "int64" else (I32_MIN, I32_MAX)
+        lo, hi = tmin, tmax
+        for k, b in bound.items():
+            e = _int_ceil(b) if k in ("gte", "lt") else _int_floor(b)
+            if e is None:  # NaN
+                return -1
+            if k == "gte":
+                lo = max(lo, e)
+            elif k == "gt":
+                lo = max(lo, e + 1)
+            elif k == "lte":
+                hi = min(hi, e)
+            else:
+                hi = min(hi, e - 1)
+        if lo > hi:  # also a bound beyond the column's range on the wrong side
+            return -1
+        return self._record(name, _capi.SRX_FOP_RANGE, lo, hi)
+
+    def _exact_value(self, name, col, x):
+        """What ``eq`` / ``in`` compare with, or None when no value of the column equals x"""
+        kind = col.kind
+        if kind == "category":
+            if not isinstance(x, str):
+                raise ValueError(f"{name!r} is a category column: it compares with strings, not {x!r}")
+            return col.code_of.get(x)
+        v = _number(x, f"a value for {name!r}")
+        if kind == "float32":
+            if isinstance(v, float) and math.isnan(v):
+                return None
+            f = _f32_nearest(v)
+            if float(f) != v:
+                return None
+            return f32_bits(np.float32(0.0) if f == 0 else f)  # one spelling of zero: == takes both
+        if isinstance(v, float):
+            if not v.is_integer():
+                return None
+            v = int(v)
+        tmin, tmax = (I64_MIN, I64_MAX) if kind == "int64" else (I32_MIN, I32_MAX)
+        return v if tmin <= v <= tmax else None
+
+    # -- groups -----------------------------------------------------------------------------------------------------------
+    def group(self, g) -> tuple:
+        """One group -> its (all, any, none) triple of clause ids"""
+        g = as_group(g)
+        return tuple(tuple(self.clause(c) for c in g.get(k, ())) for k in GROUP_KEYS)
+
+    def add(self, g) -> int:
+        """One group -> its row (-1 when the group holds no clause and rows are shared: nothing is constrained)"""
+        triple = self.group(g)
+        if not self.share_rows:
+            self.rows.append(triple)
+            return len(self.rows) - 1
+        if triple == ((), (), ()):
+            return -1
+        if triple not in self._row_of:
+            self._row_of[triple] = len(self.rows)
+            self.rows.append(triple)
+        return self._row_of[triple]
+
+    def arrays(self, rows=None):
+        """(clauses int64[n_clauses, 3], values int64[n_values], [(ptr, clause)] * 3) for ``rows`` (default: every row): a record
+        is (col | op << 32, lo, hi), little-endian the 24 bytes of ``srx_field_clause``."""
+        rows = self.rows if rows is None else rows
+        rec = np.zeros((len(self.clauses), 3), dtype=np.int64)
+        values: List[int] = []
+        for i, (col, op, lo, hi) in enumerate(self.clauses):
+            if op == _capi.SRX_FOP_IN:  # lo holds the value tuple
+                first = len(values)
+                values.extend(lo)
+                lo = first
+            rec[i] = (col | (op << 32), lo, hi)
+        lists = []
+        for which in range(3):
+            ptr = np.zeros(len(rows) + 1, dtype=np.int32)
+            ptr[1:] = np.cumsum([len(r[which]) for r in rows])
+            lists.append((ptr, np.asarray([c for r in rows for c in r[which]], dtype=np.int32)))
+        return rec, np.asarray(values, dtype=np.int64), lists
+
+
+def _as_i64(mask: int) -> int:
+    return mask - (1 << 64) if mask >= 1 << 63 else mask
+
+
+def is_group(x) -> bool:
+    """A dict whose keys all lie in {"must", "should", "must_not"} (the empty dict included), or a bare list of clause dicts"""
+    if isinstance(x, dict):
+        return all(k in GROUP_KEYS for k in x)
+    return isinstance(x, (list, tuple)) and all(isinstance(c, dict) and "field" in c for c in x)
+
+
+def as_group(g) -> dict:
+    """A group in its dict form: a bare list of clauses is ``must``, one clause dict a ``must`` of one"""
+    if isinstance(g, dict) and "field" in g:
+        return {"must": [g]}
+    if isinstance(g, dict):
+        bad = [k for k in g if k not in GROUP_KEYS]
+        if bad:
+            raise ValueError(f"a group has the keys must / should / must_not, got {bad}")
+        for k, v in g.items():
+            if isinstance(v, dict) or isinstance(v, (str, bytes)) or not hasattr(v, "__iter__"):
+                raise ValueError(f"{k} takes a list of clauses, got {v!r}")
+        return g
+    if isinstance(g, (list, tuple)):
+        return {"must": list(g)}
+    raise ValueError(f"a group is a dict with must / should / must_not or a list of clauses, got {g!r}")
+
+
+def where_groups(where) -> list:
+    """``where`` of :meth:`FieldTable.filter` as a list of groups, one per output row: one group (a dict, or a bare list of
+    clause dicts) is one row; any other list is a list of groups."""
+    if isinstance(where, dict) or is_group(where):
+        return [where]
+    if isinstance(where, (list, tuple)) and len(where) > 0:
+        return list(where)
+    raise ValueError("where must be a group or a non-empty list of groups")
+
+
+def check_records(types, clauses, n_values: int, lists) -> None:
+    """What the device does not check of host arrays: every ``col`` in [0, len(types)), every op fit for its column's type, every
+    IN range inside ``values``, every clause id in [-1, n_clauses).  Raises ValueError."""
+    rec = np.asarray(clauses)
+    if rec.ndim != 2 or rec.shape[1] != 3 or rec.dtype != np.int64:
+        raise ValueError("clauses must be int64[n_clauses, 3]: (col | op << 32, lo, hi) per record")
+    for i in range(rec.shape[0]):
+        col, op, lo, hi = int(rec[i, 0] & 0xFFFFFFFF), int(rec[i, 0] >> 32), int(rec[i, 1]), int(rec[i, 2])
+        if not (0 <= col < len(types)):
+            raise ValueError(f"clause {i}: col {col} outside [0, {len(types)})")
+        fits = (_capi.SRX_FOP_MASK_ANY, _capi.SRX_FOP_MASK_ALL) if types[col] == _capi.SRX_FIELD_SET64 else (_capi.SRX_FOP_RANGE, _capi.SRX_FOP_IN)
+        if op not in fits:
+            raise ValueError(f"clause {i}: op {op} does not fit a column of type {types[col]}")
+        if op == _capi.SRX_FOP_IN and not (0 <= hi and 0 <= lo and lo + hi <= n_values):
+            raise ValueError(f"clause {i}: its IN range [{lo}, {lo} + {hi}) lies outside the {n_values} values")
+    n_rows = None
+    for pair in lists:
+        if pair is None:
+            continue
+        ptr, ids = np.asarray(pair[0]), np.asarray(pair[1])
+        if ptr.ndim != 1 or len(ptr) < 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or int(ptr[-1]) != len(ids):
+            raise ValueError("a clause list is a CSR: ptr starts at 0, ascends and ends at the number of ids")
+        if n_rows is not None and len(ptr) - 1 != n_rows:
+            raise ValueError("the clause lists must agree on the row count")
+        n_rows = len(ptr) - 1
+        if len(ids) and (int(ids.min()) < -1 or int(ids.max()) >= rec.shape[0]):
+            raise ValueError(f"clause ids must lie in [-1, {rec.shape[0]})")
+    if n_rows is None:
+        raise ValueError("give at least one of the all / any / none lists")
+
+
+class FieldTable:
+    """Typed metadata columns of ``n_docs`` docs, resident on ``device``; row i of every column belongs to the doc with the GLOBAL
+    id ``doc_base + i``.  ``columns`` name -> :class:`HostColumn` (kind, dictionary; its arrays are dropped after the upload)."""
+
+    def __init__(self, columns: Dict[str, HostColumn], tensors, device, doc_base: int = 0):
+        self.columns, self._tensors = columns, tensors
+        self.device, self.doc_base = device, int(doc_base)
+        self.n_docs = len(next(iter(columns.values())))
+
+    @classmethod
+    def from_columns(cls, columns, device="cuda:0", doc_base: int = 0) -> "FieldTable":
+        """``columns``: name -> a sequence of n_docs entries (or an already prepared :class:`HostColumn`).  int32 / int64 /
+        float32 arrays go up as they are (int8 / int16 / uint8 / uint16 widen to int32, uint32 to int64); ``bool`` becomes int32
+        0 / 1; float64 raises ValueError (cast to float32: the device compares float32 values); a sequence of str / None becomes a
+        CATEGORY column (int32 codes in the sorted order of the distinct strings, the dictionary stays here); a sequence of
+        collections of str becomes a SET column (the labels as the bits of an int64; more than 64 distinct labels raise
+        ValueError); None entries, and the masked entries of a ``numpy.ma`` array, become the column's validity row -- such a doc
+        fails every test on the column."""
+        torch = _torch()
+        dev = torch.device(device)
+        host = {str(n): (v if isinstance(v, HostColumn) else host_column(str(n), v)) for n, v in columns.items()} if isinstance(columns, dict) else None
+        if not host:
+            raise ValueError("columns must be a non-empty dict name -> sequence of n_docs entries")
+        n_docs = len(next(iter(host.values())))
+        if any(len(c) != n_docs for c in host.values()):
+            raise ValueError("the columns must have one entry per doc each: their lengths differ")
+        filter_words(n_docs)  # n_docs in [1, 2^31 - 2]
+        tensors = {}
+        for name, c in host.items():
+            data = torch.from_numpy(c.data).to(dev)
+            valid = None if c.valid is None else torch.from_numpy(pack_masks(c.valid).view(np.int32).copy()).to(dev).reshape(-1)
+            tensors[name] = (data, valid)
+        return cls(host, tensors, dev, doc_base)
+
+    def device_bytes(self) -> int:
+        """Bytes the columns and validity rows keep resident"""
+        return sum(d.numel() * d.element_size() + (0 if v is None else v.numel() * 4) for d, v in self._tensors.values())
+
+    def close(self) -> None:
+        self._tensors = {}
+
+    # -- the doors ------------------------------------------------------------------------------------------------------------
+    def _col_descs(self, names):
+        if not (1 <= len(names) <= _capi.SRX_FIELDS_MAX_COLS):
+            raise ValueError(f"one call takes 1 to {_capi.SRX_FIELDS_MAX_COLS} columns, got {len(names)}")
+        arr = (_capi.FieldColDesc * len(names))()
+        for i, name in enumerate(names):
+            if name not in self._tensors:
+                raise ValueError(f"unknown field {name!r}" if name not in self.columns else "the table is closed")
+            data, valid = self._tensors[name]
+            arr[i].data, arr[i].valid, arr[i].type = data.data_ptr(), (None if valid is None else valid.data_ptr()), self.columns[name].type
+        return arr
+
+    def filter_device(self, clauses, values=None, all=None, any=None, none=None, columns=None, base=None, q_base=None, out=None) -> DocFilter:
+        """``srx_filter_from_fields`` on device tensors.  ``clauses``: int64 [n_clauses, 3], one (col | op << 32, lo, hi) record
+        per row (the 24 bytes of ``srx_field_clause``); ``values``: int64 [n_values] or None; each of ``all`` / ``any`` /
+        ``none``: None or a ``(ptr, clause)`` pair of int32 tensors, a CSR over the output rows (at least one is given, and they
+        agree on the row count); ``columns``: the names a record's ``col`` indexes (default: every column of the table, in
+        order; at most 32).  ``base`` / ``q_base`` / ``out`` as in :meth:`~.index.DeviceIndex.term_filter_device`.  Returns a
+        DocFilter over the table's ``n_docs`` / ``doc_base``; asynchronous on the current stream.  Precondition (NOT checked
+        here, the tensors never leave the device): what :func:`check_records` checks of host arrays, and q_base in
+        [-1, n_filters)."""
+        torch = _torch()
+        names = list(self.columns) if columns is None else list(columns)
+        descs = self._col_descs(names)
+
+        def check(t, dtype, what, dim=1):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or t.dim() != dim:
+                raise ValueError(f"{what} must be a {dim}-D {dtype} tensor on {self.device}")
+            return t.contiguous()
+
+        clauses = check(clauses, torch.int64, "clauses", 2)
+        if clauses.shape[1] != 3:
+            raise ValueError("clauses must be int64 [n_clauses, 3]")
+        if values is not None:
+            values = check(values, torch.int64, "values")
+        n_rows, ptrs = None, []
+        for name, pair in (("all", all), ("any", any), ("none", none)):
+            if pair is None:
+                ptrs += [None, None]
+                continue
+            ptr, ids = check(pair[0], torch.int32, name), check(pair[1], torch.int32, name)
+            if ptr.numel() < 1 or (n_rows is not None and ptr.numel() - 1 != n_rows):
+                raise ValueError("the clause lists must have one ptr entry per output row, plus one, and agree on the row count")
+            n_rows = ptr.numel() - 1
+            ptrs += [ptr, ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)]
+        if n_rows is None:
+            raise ValueError("give at least one of all / any / none (an empty list is a ptr of zeros)")
+        if n_rows < 1:
+            raise ValueError("a filter needs at least one row")
+        bdesc, keep = None, None
+        if base is not None:
+            if not isinstance(base, DocFilter):
+                raise ValueError("base must be a DocFilter")
+            bdesc, keep = base.for_index(self).launch_args(q_base, n_rows)
+        elif q_base is not None:
+            raise ValueError("q_base picks rows of a base filter: it needs base=")
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty((n_rows, filter_words(self.n_docs)), dtype=torch.int32, device=self.device)
+            f = DocFilter(out, self.n_docs, self.doc_base)
+            if f.n_filters != n_rows or f.device != self.device:
+                raise ValueError(f"out must be an int32 tensor [{n_rows}, {f.words}] on {self.device}")
+            ptr_of = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = _capi.lib().srx_filter_from_fields(self.device.index or 0, self.n_docs, descs, len(names), ptr_of(clauses), int(clauses.shape[0]),
+                                                    ptr_of(values), n_rows, *[None if t is None else t.data_ptr() for t in ptrs], bdesc,
+                                                    out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_filter_from_fields")
+        del keep
+        return f
+
+    def filter_arrays(self, clauses, values, all=None, any=None, none=None, columns=None, base=None, q_base=None) -> DocFilter:
+        """:meth:`filter_device` from host arrays, validated first (:func:`check_records`: cols, ops against the column types, IN
+        ranges, clause ids; ``q_base`` with :func:`~.filter.validate_q_filter`)."""
+        torch = _torch()
+        names = list(self.columns) if columns is None else list(columns)
+        for name in names:
+            if name not in self.columns:
+                raise ValueError(f"unknown field {name!r}")
+        values = np.zeros(0, np.int64) if values is None else np.ascontiguousarray(values, dtype=np.int64)
+        clauses = np.ascontiguousarray(clauses, dtype=np.int64).reshape(-1, 3)
+        check_records([self.columns[n].type for n in names], clauses, len(values), (all, any, none))
+        n_rows = next(len(p[0]) - 1 for p in (all, any, none) if p is not None)
+        qb = None
+        if base is not None:
+            if not isinstance(base, DocFilter):
+                raise ValueError("base must be a DocFilter")
+            qb = q_filter_to_device(base.for_index(self), q_base, n_rows)
+        elif q_base is not None:
+            raise ValueError("q_base picks rows of a base filter: it needs base=")
+        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)
+        pairs = [None if p is None else (up(p[0], np.int32), up(p[1], np.int32)) for p in (all, any, none)]
+        return self.filter_device(up(clauses, np.int64), up(values, np.int64) if len(values) else None, *pairs, columns=names, base=base, q_base=qb)
+
+    def filter(self, where, base=None, q_base=None) -> DocFilter:
+        """Filter rows from a predicate.  ``where``: one group, or a list of groups -- one per output row.  A group is
+        ``{"must": [...], "should": [...], "must_not": [...]}`` (any of the three absent): a doc passes when EVERY ``must`` clause
+        holds, at least one ``should`` clause (when there are any) and NO ``must_not`` clause; a bare list of clauses is ``must``.
+        A clause is a dict with ``"field"`` and one test:
+
+          * ``gte`` / ``gt`` / ``lte`` / ``lt``  (combinable) on number columns -- compared exactly: a bound that is not a value
+            of the column's type is rounded towards the inside of the range, so ``{"gte": 0.1}`` on a float32 column admits
+            exactly the float32 values >= 0.1;
+          * ``eq``  and ``in``  on number and category columns (a value no entry can equal, an unknown category: no doc);
+          * ``any_of`` / ``all_of``  on set columns: the doc carries one / every listed label (``all_of`` with an unknown label: no doc);
+          * ``exists: True``  the doc has a value.  On a float32 column this is the full range, so a NaN counts as missing.
+
+        A doc WITHOUT a value fails every test, so it passes a clause under ``must_not``.  ``base`` / ``q_base``: a
+        :class:`~.filter.DocFilter` over the same docs the rows are intersected with, and the base row of every output row (a host
+        sequence; None: row 0; -1: none).  A table of more than 32 columns passes the ones the clauses name; a call that names
+        more raises ValueError.  Memory: n_rows * n_docs / 8 bytes."""
+        res = WhereResolver(self.columns)
+        for g in where_groups(where):
+            res.add(g)
+        return self.filter_resolved(res, base=base, q_base=q_base)
+
+    def filter_resolved(self, res: WhereResolver, rows=None, base=None, q_base=None) -> DocFilter:
+        """The rows of a :class:`WhereResolver` over this table's columns (``rows``: other triples of its clause ids)"""
+        rec, values, lists = res.arrays(rows)
+        names = res.names or list(self.columns)[:1]  # no clause: any column serves
+        if len(names) > _capi.SRX_FIELDS_MAX_COLS:
+            raise ValueError(f"the predicate names {len(names)} fields: one call takes at most {_capi.SRX_FIELDS_MAX_COLS}")
+        return self.filter_arrays(rec, values, *lists, columns=names, base=base, q_base=q_base)

@@ -95,9 +95,19 @@ class RetrievalService(SparseIndexViews):
         with self.cache_lock:
             self.query_cache.clear()
 
+    def set_doc_fields(self, columns) -> None:
+        """The docs' metadata as typed columns for the ``where=`` keyword of the searches (no reference counterpart: nothing
+        reads its ``metadata`` dicts).  ``columns``: name -> a sequence with one entry per doc, in the order of the corpus
+        ``build_bm25_index`` was given (:func:`~.fields.columns_from_metadata` makes them from the corpus; the type mapping is
+        :meth:`~.fields.FieldTable.from_columns`'s).  A length that is not the index's raises ``ValueError``.  The columns go to
+        the GPU with the first ``where=`` call and stay there; a rebuilt index drops them."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        self._be.set_fields(columns)
+
     # -- search -----------------------------------------------------------------------------------------
     def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None,
-                    any_terms=None, must_not_terms=None, operators: bool = False) -> Dict[str, Dict[str, float]]:
+                    any_terms=None, must_not_terms=None, operators: bool = False, where=None) -> Dict[str, Dict[str, float]]:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
 
         ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
@@ -114,12 +124,20 @@ class RetrievalService(SparseIndexViews):
         and restrict the doc set only: scores and the ``score > 0`` rule are unchanged.  They combine with ``allowed_docs`` /
         ``excluded_docs`` and behave like them otherwise (no cache, a sharded index refuses).  ``operators=True``: the
         ``+word`` / ``-word`` words of every query text are read as must / must-not constraints
-        (:func:`~.index.parse_operators`) and merged with the keywords."""
+        (:func:`~.index.parse_operators`) and merged with the keywords.
+
+        ``where`` (no reference counterpart): a field predicate over the columns of :meth:`set_doc_fields` -- one group
+        ``{"must": [...], "should": [...], "must_not": [...]}`` (or a bare list of clauses) for every query, or a dict
+        ``qid -> group``; the clauses are :meth:`~.fields.FieldTable.filter`'s.  The rows are built on the GPU
+        (``srx_filter_from_fields``, include/sparse_rx_fields.h) and restrict the doc set only.  It combines with the doc and the
+        term keywords (doc filter, then term rows, then field rows) and behaves like them otherwise: no cache, a sharded index
+        refuses; without :meth:`set_doc_fields` it raises ``ValueError``."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, self._be.doc_filter_spec(queries, allowed_docs, excluded_docs))
+        spec = self._be.field_filter_spec(queries, where, spec, "search_bm25")
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
@@ -169,7 +187,7 @@ class RetrievalService(SparseIndexViews):
         self.embedding_storage = storage
 
     def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
-                         excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None) -> List[Dict]:
+                         excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> List[Dict]:
         """retrieval.py:402-436: ``np.dot(embedding_index, query_vector)`` + top-k on the GPU (``srx_dense_search_f32``),
         the ``min_score`` cut and the ``[{"doc_id", "score"}]`` result as in the reference.
 
@@ -184,7 +202,8 @@ class RetrievalService(SparseIndexViews):
         ``allowed_docs`` / ``excluded_docs``: a sequence of doc ids, as in :meth:`search_bm25`; both passes rank the allowed
         docs alone (``srx_dense_search_f32_filtered``).  ``must_terms`` / ``any_terms`` / ``must_not_terms``: a sequence of
         strings each, as in :meth:`search_bm25` -- keyword-constrained vector search: the docs are those whose TEXT satisfies
-        the constraint (the BM25 index's posting lists), so it needs ``build_bm25_index``.
+        the constraint (the BM25 index's posting lists), so it needs ``build_bm25_index``.  ``where``: one group, as in
+        :meth:`search_bm25` -- vector search under a metadata predicate; it needs :meth:`set_doc_fields`.
 
         With half-precision storage (:meth:`set_embeddings`) both passes run on the half index (``srx_dense_search_half``):
         the first pass returns the scores of the rounded rows; the second pass still re-scores its rows on the host with the
@@ -192,10 +211,14 @@ class RetrievalService(SparseIndexViews):
         for what, given in (("must_terms", must_terms), ("any_terms", any_terms), ("must_not_terms", must_not_terms)):
             if isinstance(given, dict):
                 raise ValueError(f"{what} of search_by_vector must be a sequence of strings (there is one query)")
+        if where is not None:
+            from .fields import is_group
+            if not is_group(where):
+                raise ValueError("where of search_by_vector must be one group (there is one query)")
         self._ensure_dense()
         q = np.asarray(query_vector, dtype=np.float32)
         kk = max(1, min(int(k), self._dense.n_docs))
-        flt = self._dense_filter({"q": None}, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms)
+        flt = self._dense_filter({"q": None}, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_by_vector")
         flt = {} if flt is None else {"filter": flt[0]}  # one query: its row is row 0
         d, s, n = self._dense.search(q, kk, **flt)
         if min_score > 0 or int(n[0]) == kk:
@@ -222,14 +245,18 @@ class RetrievalService(SparseIndexViews):
                 results.append({"doc_id": str(int(i)), "score": float(score)})
         return results
 
-    def _dense_filter(self, queries, allowed_docs, excluded_docs, must_terms=None, any_terms=None, must_not_terms=None):
+    def _dense_filter(self, queries, allowed_docs, excluded_docs, must_terms=None, any_terms=None, must_not_terms=None, where=None,
+                      call: str = "search_hybrid"):
         """The filter keywords as (DocFilter over the embedding rows, spec), or None when none constrains a query"""
         terms = not (must_terms is None and any_terms is None and must_not_terms is None)
-        if allowed_docs is None and excluded_docs is None and not terms:
+        if allowed_docs is None and excluded_docs is None and not terms and where is None:
             return None
         if self.host is not None:
             spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
             spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, spec)
+            spec = self._be.field_filter_spec(queries, where, spec, call)
+        elif where is not None:
+            raise ValueError(f"{call}(where=...) needs the docs' fields: call build_bm25_index() and set_doc_fields() first")
         elif terms:
             raise ValueError("must_terms / any_terms / must_not_terms need the BM25 index (its posting lists): call build_bm25_index() first")
         else:  # embeddings without a BM25 index: docs are named by their row number
@@ -252,7 +279,7 @@ class RetrievalService(SparseIndexViews):
                       candidates: Optional[int] = None, rescore: bool = False, allowed_docs=None,
                       excluded_docs=None, mmr_lambda: Optional[float] = None, mmr_pool: Optional[int] = None,
                       mmr_similarity: str = "cosine", must_terms=None, any_terms=None, must_not_terms=None,
-                      operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+                      operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None, where=None) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -292,7 +319,9 @@ class RetrievalService(SparseIndexViews):
         on the device (``srx_maxsim_rerank_half``, include/sparse_rx_maxsim.h) -- still one synchronisation and one copy
         back.  The result is what ``rerank_late(search_hybrid(top_k=late_pool, ...), late_query_tokens, top_k)`` returns: the
         values are MaxSim scores.  Works with ``rescore=True`` and the filter / term keywords; together with ``mmr_lambda`` it
-        raises ``ValueError`` (chain :meth:`rerank_late` and :meth:`diversify` instead)."""
+        raises ``ValueError`` (chain :meth:`rerank_late` and :meth:`diversify` instead).
+        ``where`` as in :meth:`search_bm25`: the field-built rows go to both sides like a doc filter's (``rescore=True``,
+        ``mmr_lambda`` and ``late_query_tokens`` included) and combine with the doc and the term keywords."""
         if late_query_tokens is not None and mmr_lambda is not None:
             raise ValueError("late_query_tokens and mmr_lambda do not combine in one call: chain rerank_late() and diversify()")
         if operators:
@@ -335,7 +364,7 @@ class RetrievalService(SparseIndexViews):
             self._upload()
         q_ptr, q_term, q_weight = encode_queries([text for _, text in live], self.host.vocabulary)
         flt = {}
-        fs = self._dense_filter(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms)  # one DocFilter serves both sides: same rows, same device
+        fs = self._dense_filter(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where)  # one DocFilter serves both sides: same rows, same device
         if fs is not None:
             import torch
             q_rows = np.asarray([fs[1].row_of_qid[qid] for qid, _ in live], dtype=np.int32)
