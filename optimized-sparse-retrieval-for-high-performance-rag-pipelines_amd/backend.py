@@ -14,6 +14,7 @@ corpus / query dicts (SPMD) and
 """
 from __future__ import annotations
 
+import copy
 import os
 from typing import Dict, List, Optional
 
@@ -49,6 +50,7 @@ class SparseBackend:
         self._doc_lengths_all = None
         self._fields = None        # set_fields: the docs' metadata columns on the host (fields.HostColumn by name) ...
         self._field_table = None   # ... and on the device, uploaded by the first call that filters with them
+        self._rows = None          # _row_table
 
     def world(self) -> int:
         try:
@@ -135,32 +137,44 @@ class SparseBackend:
         ids = self.host.doc_ids
         return {ids[int(i)]: float(s) for i, s in zip(idx, sc) if s > 0}
 
-    def doc_filter_spec(self, queries, allowed_docs, excluded_docs):
-        """:func:`doc_filter_spec` over this index's doc ids (None when both keywords are None); a sharded index refuses."""
-        if allowed_docs is None and excluded_docs is None:
-            return None
-        if self.sharded():
-            raise ValueError("allowed_docs / excluded_docs need the whole index on one GPU (a sharded search takes no doc filter)")
-        if getattr(self, "_rows", None) is None or self._rows.ids is not self.host.doc_ids:
-            self._rows = RowOfIds(self.host.doc_ids)
-        return doc_filter_spec(self._rows.row_of, queries, allowed_docs, excluded_docs)
-
-    def term_filter_spec(self, queries, must_terms=None, any_terms=None, must_not_terms=None, doc_spec=None):
-        """:func:`term_filter_spec` over this index's vocabulary, bound to its device index and combined with ``doc_spec`` (the
-        :meth:`doc_filter_spec` of the same call, or None) as the base; ``doc_spec`` itself when no term keyword constrains a
-        query.  A sharded index refuses a constrained call."""
-        if must_terms is None and any_terms is None and must_not_terms is None:
-            return doc_spec
-        if self.host is None:
-            raise ValueError("term constraints need the sparse index: build it first")
-        spec = term_filter_spec(self.host.vocabulary, queries, must_terms, any_terms, must_not_terms)
-        if spec is None:  # empty lists, or operators=True on texts without operators
-            return doc_spec
-        if self.sharded():
-            raise ValueError("must_terms / any_terms / must_not_terms need the whole index on one GPU (a sharded search takes no doc filter)")
-        spec = spec.with_base(doc_spec, queries)
-        spec.sparse = lambda: self.dev
+    def filter_spec(self, queries, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None,
+                    call: str = "search"):
+        """The filter keywords of one API call as one spec (``.row_of_qid``, ``.on_device(index)``), or None when none of them
+        constrains a query of ``queries``: :func:`doc_filter_spec` over this index's doc ids, then :func:`term_filter_spec` over
+        its vocabulary (bound to its device index), then :func:`field_filter_spec` over the columns of :meth:`set_fields`, each
+        with what came before as its base.  ValueError: a malformed keyword, term keywords without an index, ``where`` without
+        fields (the message names ``call``); a sharded index refuses every kind that constrains a query."""
+        spec = None
+        if allowed_docs is not None or excluded_docs is not None:
+            self._refuse_sharded("allowed_docs / excluded_docs need")
+            spec = doc_filter_spec(self._row_table().row_of, queries, allowed_docs, excluded_docs)
+        if not (must_terms is None and any_terms is None and must_not_terms is None):
+            if self.host is None:
+                raise ValueError("term constraints need the sparse index: build it first")
+            terms = term_filter_spec(self.host.vocabulary, queries, must_terms, any_terms, must_not_terms)
+            if terms is not None:  # else: empty lists, or operators=True on texts without operators
+                self._refuse_sharded("must_terms / any_terms / must_not_terms need")
+                spec = terms.with_base(spec, queries)
+                spec.sparse = lambda: self.dev
+        if where is not None:
+            if self._fields is None:
+                raise ValueError(f"{call}(where=...) needs the docs' fields: call set_doc_fields() first")
+            flds = field_filter_spec(self._fields, queries, where)
+            if flds is not None:
+                self._refuse_sharded("where= needs")
+                spec = flds.with_base(spec, queries)
+                spec.table = self.field_table
         return spec
+
+    def _refuse_sharded(self, what_needs: str) -> None:
+        if self.sharded():
+            raise ValueError(f"{what_needs} the whole index on one GPU (a sharded search takes no doc filter)")
+
+    def _row_table(self) -> "RowOfIds":
+        """doc id -> row of this index's doc ids, kept between calls"""
+        if self._rows is None or self._rows.ids is not self.host.doc_ids:
+            self._rows = RowOfIds(self.host.doc_ids)
+        return self._rows
 
     def set_fields(self, columns) -> None:
         """The docs' metadata columns (``fields.FieldTable.from_columns`` takes the same dict), row i = the i-th doc of the built
@@ -187,23 +201,6 @@ class SparseBackend:
             self._field_table = FieldTable.from_columns(self._fields, device=self.dev.device if self.dev is not None else self.device, doc_base=self.doc_base)
         return self._field_table
 
-    def field_filter_spec(self, queries, where, base_spec=None, call: str = "search"):
-        """:func:`field_filter_spec` over the columns of :meth:`set_fields`, with ``base_spec`` (the doc / term spec of the same
-        call, or None) as the base; ``base_spec`` itself when ``where`` is None or constrains no query.  ValueError: no fields
-        (the message names ``call``), a sharded index."""
-        if where is None:
-            return base_spec
-        if self._fields is None:
-            raise ValueError(f"{call}(where=...) needs the docs' fields: call set_doc_fields() first")
-        spec = field_filter_spec(self._fields, queries, where)
-        if spec is None:
-            return base_spec
-        if self.sharded():
-            raise ValueError("where= needs the whole index on one GPU (a sharded search takes no doc filter)")
-        spec = spec.with_base(base_spec, queries)
-        spec.table = self.field_table
-        return spec
-
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
                      blank: str = "empty", filter: Optional["DocFilterSpec"] = None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
@@ -223,7 +220,7 @@ class SparseBackend:
         the corpus asks for ``n_docs`` rows; ``top_k <= 0`` keeps nothing (the reference's ``argpartition(...)[:0]``), cache
         hits aside.
 
-        ``filter`` (:meth:`doc_filter_spec`, :meth:`term_filter_spec`): the search is restricted to each query's allowed docs (``srx_search_filtered``).
+        ``filter`` (:meth:`filter_spec`): the search is restricted to each query's allowed docs (``srx_search_filtered``).
         A filtered call neither reads nor writes the cache -- its key is the query text --, and equal texts share a row only
         under the same filter row."""
         if filter is not None:
@@ -291,9 +288,7 @@ class SparseBackend:
 
     def candidate_block(self, queries, candidates):
         """:func:`candidate_block` over this index's doc ids (their row numbers are kept between calls)"""
-        if getattr(self, "_rows", None) is None or self._rows.ids is not self.host.doc_ids:
-            self._rows = RowOfIds(self.host.doc_ids)
-        return self._rows.candidate_block(queries, candidates)
+        return self._row_table().candidate_block(queries, candidates)
 
     def close(self) -> None:
         self._drop_field_table()
@@ -407,28 +402,39 @@ def doc_filter_spec(row_of, queries, allowed_docs, excluded_docs) -> Optional[Do
     return DocFilterSpec(allow, lists or [np.zeros(0, np.int64)], row_of_qid)
 
 
-class TermFilterSpec:
-    """The ``must_terms`` / ``any_terms`` / ``must_not_terms`` keywords of one API call, resolved on the host: ``rows`` = one
-    (all, any, none) triple of term-id tuples per filter row (-1: an out-of-vocabulary word), ``row_of_qid`` = every qid's row
-    (-1: not filtered).  With a base (:meth:`with_base`): ``base`` = the call's :class:`DocFilterSpec`, ``base_rows`` = its row
-    for every row here (-1: none).  ``sparse`` () -> the DeviceIndex whose postings answer "doc has term" (None: the index
-    :meth:`on_device` is given).  Memory on the device: len(rows) * n_docs / 8 bytes -- 1.25 MB per row at 10 M docs."""
+class RowFilterSpec:
+    """What the specs of the row builders share: ``rows`` = one (all, any, none) triple of id tuples per filter row,
+    ``row_of_qid`` = every qid's row (-1: not filtered) and, with a base (:meth:`with_base`), ``base`` = the spec the rows are
+    intersected with and ``base_rows`` = its row for every row here (-1: none).  A kind adds what its ids mean and
+    ``on_device(index)``, which builds the rows.  Memory on the device: len(rows) * n_docs / 8 bytes -- 1.25 MB per row at 10 M docs."""
 
     def __init__(self, rows, row_of_qid, base=None, base_rows=None):
-        self.rows, self.row_of_qid, self.base, self.base_rows, self.sparse = rows, row_of_qid, base, base_rows, None
+        self.rows, self.row_of_qid, self.base, self.base_rows = rows, row_of_qid, base, base_rows
 
-    def with_base(self, doc_spec, queries) -> "TermFilterSpec":
-        """This spec restricted to the docs ``doc_spec`` allows: one row per distinct (doc row, term row) pair of the call's
-        qids; a qid neither spec filters stays unfiltered."""
-        if doc_spec is None:
+    def with_base(self, base_spec, queries):
+        """This spec restricted to the docs ``base_spec`` (any spec of the same call, or None) allows: one row per distinct
+        (base row, own row) pair of the call's qids; a qid neither spec filters stays unfiltered."""
+        if base_spec is None:
             return self
         pairs, row_of_qid = {}, {}
         for qid in queries:
-            pair = (doc_spec.row_of_qid[qid], self.row_of_qid[qid])
+            pair = (base_spec.row_of_qid[qid], self.row_of_qid[qid])
             row_of_qid[qid] = -1 if pair == (-1, -1) else pairs.setdefault(pair, len(pairs))
         empty = ((), (), ())
-        rows = [self.rows[t] if t >= 0 else empty for _, t in pairs] or [empty]
-        return TermFilterSpec(rows, row_of_qid, doc_spec, [d for d, _ in pairs] or [-1])
+        spec = copy.copy(self)
+        spec.rows, spec.row_of_qid = [self.rows[own] if own >= 0 else empty for _, own in pairs] or [empty], row_of_qid
+        spec.base, spec.base_rows = base_spec, [b for b, _ in pairs] or [-1]
+        return spec
+
+
+class TermFilterSpec(RowFilterSpec):
+    """The ``must_terms`` / ``any_terms`` / ``must_not_terms`` keywords of one API call, resolved on the host: the ids of ``rows``
+    are term ids (-1: an out-of-vocabulary word).  ``sparse`` () -> the DeviceIndex whose postings answer "doc has term" (None:
+    the index :meth:`on_device` is given)."""
+
+    def __init__(self, rows, row_of_qid, base=None, base_rows=None):
+        super().__init__(rows, row_of_qid, base, base_rows)
+        self.sparse = None
 
     def on_device(self, index):
         """The :class:`~.filter.DocFilter` of the rows (``srx_filter_from_terms`` on the sparse index), for ``index``: the sparse
@@ -486,28 +492,14 @@ def term_filter_spec(vocabulary, queries, must_terms=None, any_terms=None, must_
     return TermFilterSpec(rows, row_of_qid) if rows else None
 
 
-class FieldFilterSpec:
+class FieldFilterSpec(RowFilterSpec):
     """The ``where`` keyword of one API call, resolved on the host: ``resolver`` = the :class:`~.fields.WhereResolver` that holds
-    the call's clause records, ``rows`` = one (all, any, none) triple of its clause ids per filter row, ``row_of_qid`` = every qid's
-    row (-1: not filtered).  With a base (:meth:`with_base`): ``base`` = the call's :class:`DocFilterSpec` or
-    :class:`TermFilterSpec`, ``base_rows`` = its row for every row here (-1: none).  ``table`` () -> the
-    :class:`~.fields.FieldTable` of the corpus.  Memory on the device: len(rows) * n_docs / 8 bytes."""
+    the call's clause records, the ids of ``rows`` are its clause ids.  ``table`` () -> the :class:`~.fields.FieldTable` of the
+    corpus."""
 
     def __init__(self, resolver, rows, row_of_qid, base=None, base_rows=None):
-        self.resolver, self.rows, self.row_of_qid, self.base, self.base_rows, self.table = resolver, rows, row_of_qid, base, base_rows, None
-
-    def with_base(self, base_spec, queries) -> "FieldFilterSpec":
-        """This spec restricted to the docs ``base_spec`` allows: one row per distinct (base row, field row) pair of the call's
-        qids; a qid neither spec filters stays unfiltered."""
-        if base_spec is None:
-            return self
-        pairs, row_of_qid = {}, {}
-        for qid in queries:
-            pair = (base_spec.row_of_qid[qid], self.row_of_qid[qid])
-            row_of_qid[qid] = -1 if pair == (-1, -1) else pairs.setdefault(pair, len(pairs))
-        empty = ((), (), ())
-        rows = [self.rows[f] if f >= 0 else empty for _, f in pairs] or [empty]
-        return FieldFilterSpec(self.resolver, rows, row_of_qid, base_spec, [b for b, _ in pairs] or [-1])
+        super().__init__(rows, row_of_qid, base, base_rows)
+        self.resolver, self.table = resolver, None
 
     def on_device(self, index):
         """The :class:`~.filter.DocFilter` of the rows (``srx_filter_from_fields`` on the field table), for ``index``: any index of

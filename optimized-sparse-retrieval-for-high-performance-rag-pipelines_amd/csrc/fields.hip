@@ -45,7 +45,6 @@ constexpr int FD_MAX_COLS = 32;
 constexpr int FD_CHUNKS_PER_ROW = 8;                     // rows per batch = chunks / 8, at least 1 ...
 constexpr int FD_MAX_BATCH_ROWS = 16;                    // ... and at most 16
 constexpr int FD_MAX_ROWS_Y = 65535;                     // grid.y; more batches than that are looped over
-constexpr int64_t FD_MAX_DOCS = 0x7FFFFFFFll - 1;        // n_docs of a filter row: [1, 2^31 - 2]
 
 struct FieldsArgs {
     srx_field_col cols[FD_MAX_COLS];
@@ -164,12 +163,6 @@ __device__ __forceinline__ uint4 clause_docs(const FieldsArgs &a, int c, int lan
     return m;
 }
 
-// the bits of docs below n_docs in the word that starts at doc d
-__device__ __forceinline__ uint32_t word_docs(int64_t n_docs, int64_t d) {
-    const int64_t left = n_docs - d;
-    return left >= 32 ? 0xFFFFFFFFu : left > 0 ? (1u << (int)left) - 1u : 0u;
-}
-
 __device__ __forceinline__ bool any_bit(const uint4 &k) { return __ballot((k.x | k.y | k.z | k.w) != 0u) != 0ull; }
 
 __global__ __launch_bounds__(THREADS) void srx_fields_kernel(FieldsArgs a) {
@@ -187,8 +180,8 @@ __global__ __launch_bounds__(THREADS) void srx_fields_kernel(FieldsArgs a) {
     const int64_t w_lane = w_wave + 4 * lane;                                            // lanes 0 .. FD_WAVE_WORDS / 4 - 1 store
     const bool stores = lane < FD_WAVE_WORDS / 4 && w_lane < a.words;                    // words is a multiple of 4
     uint4 docs = make_uint4(0u, 0u, 0u, 0u);                                             // the docs below n_docs in the lane's words
-    if (stores) docs = make_uint4(word_docs(a.n_docs, w_lane * 32), word_docs(a.n_docs, w_lane * 32 + 32), word_docs(a.n_docs, w_lane * 32 + 64),
-                                  word_docs(a.n_docs, w_lane * 32 + 96));
+    if (stores) docs = make_uint4(srx_filter_word_docs(a.n_docs, w_lane * 32), srx_filter_word_docs(a.n_docs, w_lane * 32 + 32), srx_filter_word_docs(a.n_docs, w_lane * 32 + 64),
+                                  srx_filter_word_docs(a.n_docs, w_lane * 32 + 96));
     const bool wave_live = d_wave < a.n_docs;  // uniform; else the wave lies in the tail of the last chunk: zeros
     for (int b = batch0; b < a.n_batches; b += gridDim.y) {
         const int64_t r_last = ((int64_t)b + 1) * a.batch_rows;
@@ -196,8 +189,7 @@ __global__ __launch_bounds__(THREADS) void srx_fields_kernel(FieldsArgs a) {
         for (int r = (int)((int64_t)b * a.batch_rows); r < r_end; ++r) {
             uint4 acc = docs;
             if (wave_live) {
-                int br = a.base_bits != nullptr ? 0 : -1;
-                if (a.base_bits != nullptr && a.base_q != nullptr) br = cload_i32(a.base_q + r);
+                const int br = srx_filter_base_row(a.base_bits, a.base_q, r);
                 if (br >= 0 && stores) {
                     const uint4 bw = fload_words(a.base_bits + (int64_t)br * a.words, w_lane);
                     acc.x &= bw.x, acc.y &= bw.y, acc.z &= bw.z, acc.w &= bw.w;
@@ -241,7 +233,7 @@ SRX_API int srx_filter_from_fields(int32_t device, int64_t n_docs, const srx_fie
                                    const int32_t *any_ptr, const int32_t *any_clause, const int32_t *none_ptr, const int32_t *none_clause,
                                    const srx_doc_filter *base, uint32_t *out_bits, void *stream_v) {
     const char *who = "srx_filter_from_fields";
-    if (n_docs < 1 || n_docs > FD_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
+    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
     if (n_cols < 1 || n_cols > FD_MAX_COLS) return fail(SRX_ERR_INVALID, "%s: n_cols must be in [1, 32]", who);
     if (!cols) return fail(SRX_ERR_INVALID, "%s: null cols", who);
     for (int i = 0; i < n_cols; ++i) {
@@ -255,15 +247,8 @@ SRX_API int srx_filter_from_fields(int32_t device, int64_t n_docs, const srx_fie
     }
     if (n_clauses < 0) return fail(SRX_ERR_INVALID, "%s: n_clauses < 0", who);
     if (n_clauses > 0 && !clauses) return fail(SRX_ERR_INVALID, "%s: null clauses", who);
-    if (n_rows < 0) return fail(SRX_ERR_INVALID, "%s: n_rows < 0", who);
-    if (!all_ptr != !all_clause || !any_ptr != !any_clause || !none_ptr != !none_clause)
-        return fail(SRX_ERR_INVALID, "%s: the ptr and clause arrays of a list go together (both or neither)", who);
-    if (!out_bits) return fail(SRX_ERR_INVALID, "%s: null out_bits", who);
-    if ((uintptr_t)out_bits & 15) return fail(SRX_ERR_INVALID, "%s: filter rows must be 16-byte aligned", who);
-    if (base) {
-        const int rc = srx_check_filter(who, base);
-        if (rc != SRX_OK) return rc;
-    }
+    const int rc = srx_check_row_builder(who, "clause", n_rows, all_ptr, all_clause, any_ptr, any_clause, none_ptr, none_clause, out_bits, base);
+    if (rc != SRX_OK) return rc;
     if (n_rows == 0) return SRX_OK;
     HIP_TRY(hipSetDevice(device));
     FieldsArgs a;

@@ -7,7 +7,6 @@
 #include "filter_common.h"
 
 namespace {
-constexpr int64_t FILTER_MAX_DOCS = 0x7FFFFFFFll - 1;  // n_docs of every index and dense corpus: [1, 2^31 - 2]
 constexpr unsigned FILTER_MAX_GRID = 256 * 16;          // grid-stride loops: 16 workgroups per CU at most
 
 // Every word of every row: ones below n_docs when value is set, zeros above and in the padding words.
@@ -105,7 +104,7 @@ __global__ __launch_bounds__(THREADS) void srx_filtered_topk_kernel(const float 
 }
 
 int check_rows(const char *who, const void *bits, int64_t n_docs) {
-    if (n_docs < 1 || n_docs > FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
+    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
     if (!bits) return fail(SRX_ERR_INVALID, "%s: null pointer", who);
     if ((uintptr_t)bits & 15) return fail(SRX_ERR_INVALID, "%s: filter rows must be 16-byte aligned", who);
     return SRX_OK;
@@ -124,6 +123,19 @@ int srx_check_filter(const char *who, const srx_doc_filter *f) {
     return SRX_OK;
 }
 
+int srx_check_row_builder(const char *who, const char *ids, int32_t n_rows, const int32_t *all_ptr, const int32_t *all_ids,
+                          const int32_t *any_ptr, const int32_t *any_ids, const int32_t *none_ptr, const int32_t *none_ids,
+                          const uint32_t *out_bits, const srx_doc_filter *base) {
+    if (n_rows < 0) return fail(SRX_ERR_INVALID, "%s: n_rows < 0", who);
+    if (!all_ptr != !all_ids || !any_ptr != !any_ids || !none_ptr != !none_ids) {
+        snprintf(g_err, sizeof(g_err), "%s: the ptr and %s arrays of a list go together (both or neither)", who, ids);
+        return SRX_ERR_INVALID;
+    }
+    if (!out_bits) return fail(SRX_ERR_INVALID, "%s: null out_bits", who);
+    if ((uintptr_t)out_bits & 15) return fail(SRX_ERR_INVALID, "%s: filter rows must be 16-byte aligned", who);
+    return base ? srx_check_filter(who, base) : SRX_OK;
+}
+
 int srx_launch_filtered_topk(const float *scores, int64_t ld, int64_t n_docs, int nq, int k, int n_splits, int64_t doc_base,
                              const srx_doc_filter &filter, int q0, const srx_rows &cand, hipStream_t stream) {
     hipLaunchKernelGGL(srx_filtered_topk_kernel, dim3((unsigned)((int64_t)nq * n_splits)), dim3(THREADS), 0, stream, scores, ld, n_docs, nq, k,
@@ -133,7 +145,7 @@ int srx_launch_filtered_topk(const float *scores, int64_t ld, int64_t n_docs, in
 }
 
 SRX_API int64_t srx_filter_words(int64_t n_docs) {
-    if (n_docs < 1 || n_docs > FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "srx_filter_words: n_docs must be in [1, 2^31 - 2]%s");
+    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "srx_filter_words: n_docs must be in [1, 2^31 - 2]%s");
     return srx_filter_row_words(n_docs);
 }
 

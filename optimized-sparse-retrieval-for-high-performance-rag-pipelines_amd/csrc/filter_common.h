@@ -1,6 +1,6 @@
 // filter_common.h -- what the translation units of a filtered search (sparse_rx_filter.h) share: sparse_rx.hip and dense.hip
-// (the drivers), filter.hip (rows, checks, the dense rank kernel) and tier2_filter.hip (the filtered tier-2 instances).  Host
-// functions with hidden visibility, not part of the C ABI.  Kept out of srx_common.h: that header and the three kernel files it
+// (the drivers), filter.hip (rows, checks, the dense rank kernel), tier2_filter.hip (the filtered tier-2 instances) and the row
+// builders terms.hip and fields.hip.  Host functions with hidden visibility, not part of the C ABI.  Kept out of srx_common.h: that header and the three kernel files it
 // is hashed with (wave_kernel.hip, tier2_kernel.hip, merge.hip) identify the build a profile was taken from, and a filtered
 // search changes nothing in what they compile to.
 #pragma once
@@ -10,8 +10,32 @@
 // words of one filter row: ceil(n_docs / 32) rounded up to a multiple of 4 (srx_filter_words)
 inline int64_t srx_filter_row_words(int64_t n_docs) { return ((n_docs + 31) / 32 + 3) / 4 * 4; }
 
+constexpr int64_t SRX_FILTER_MAX_DOCS = 0x7FFFFFFFll - 1;  // n_docs of a filter row, of every index and dense corpus: [1, 2^31 - 2]
+
+// the bits of docs below n_docs in the word that starts at doc d.  fields.hip calls it; the fill and count kernels (filter.hip)
+// and the terms kernel keep the expression written out: called from there it is the same value and other gfx950 code.
+__host__ __device__ __forceinline__ uint32_t srx_filter_word_docs(int64_t n_docs, int64_t d) {
+    const int64_t left = n_docs - d;
+    return left >= 32 ? 0xFFFFFFFFu : left > 0 ? (1u << (int)left) - 1u : 0u;
+}
+
+// the base row of output row r of a row builder (terms.hip, fields.hip): base_q[r], or row 0 without base_q; < 0 = none (no
+// base, or base_q[r] = -1).  The row's number, not its address: a helper that returns base_bits + row * words (null: none) makes
+// the callers test a pointer where they tested the number, and both kernels compile to other code.
+__device__ __forceinline__ int srx_filter_base_row(const uint32_t *base_bits, const int32_t *base_q, int r) {
+    int br = base_bits != nullptr ? 0 : -1;
+    if (base_bits != nullptr && base_q != nullptr) br = cload_i32(base_q + r);
+    return br;
+}
+
 // filter.hip: what every filtered entry point checks of its filter before anything touches a device
 int srx_check_filter(const char *who, const srx_doc_filter *f);
+
+// filter.hip: what the srx_filter_from_* entry points check of what they share -- n_rows, the three (ptr, ids) list pairs
+// (`ids` is the word their message has for the second array: "term", "clause"), out_bits and base (null: none)
+int srx_check_row_builder(const char *who, const char *ids, int32_t n_rows, const int32_t *all_ptr, const int32_t *all_ids,
+                          const int32_t *any_ptr, const int32_t *any_ids, const int32_t *none_ptr, const int32_t *none_ids,
+                          const uint32_t *out_bits, const srx_doc_filter *base);
 
 // tier2_filter.hip: the tier-2 kernel of a filtered search.  `a` is the descriptor of the search as srx_launch_score_kernel
 // takes it (after_doc / after_score given or both null); the filter's rows are over a.w.ix.n_docs local docs.

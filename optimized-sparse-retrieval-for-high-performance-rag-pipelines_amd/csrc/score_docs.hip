@@ -16,7 +16,7 @@
 // final position, which is always inside the array: every position <= term_ptr[vocab] is followed by SRX_BLOCK_PAD
 // sentinel blocks -- their contributions are kept in registers and added in term order.  No LDS, no atomics, no
 // cross-lane operation: any (nq, m) is the same code.
-#include "srx_common.h"
+#include "desc_check.h"
 
 namespace {
 
@@ -149,22 +149,26 @@ int launch_score_docs(const ScoreDocsArgs &a, hipStream_t stream) {
 
 }  // namespace
 
+int srx_check_index_desc(const char *who, const srx_index_desc *d) {
+    if (!d) return fail(SRX_ERR_INVALID, "%s: null descriptor", who);
+    if (d->val_type != SRX_VAL_F32 && d->val_type != SRX_VAL_F16) return fail(SRX_ERR_INVALID, "%s: bad val_type", who);
+    if (d->n_docs <= 0 || d->n_docs >= 0x7FFFFFFFll || d->vocab <= 0) return fail(SRX_ERR_INVALID, "%s: n_docs / vocab out of range", who);
+    if (d->tile_log2 < 6 || d->tile_log2 > SRX_MAX_TILE_LOG2) return fail(SRX_ERR_INVALID, "%s: tile_log2 must be in [6, 14]", who);
+    if ((int64_t)d->n_tiles != (d->n_docs + (1ll << d->tile_log2) - 1) >> d->tile_log2)
+        return fail(SRX_ERR_INVALID, "%s: n_tiles != ceil(n_docs / 2^tile_log2)", who);
+    if (d->unit_tiles < 1 || d->unit_tiles > MAX_TPS) return fail(SRX_ERR_INVALID, "%s: unit_tiles must be in [1, 64]", who);
+    if (!d->post && !d->post16) return fail(SRX_ERR_INVALID, "%s: the descriptor has neither post nor post16", who);
+    if (d->post16 && ((int64_t)d->unit_tiles << d->tile_log2) > W_UNIT_MAX_DOCS)
+        return fail(SRX_ERR_INVALID, "%s: a compact copy (post16) needs units of <= 49152 docs", who);
+    if (!d->term_ptr || !d->tile_skip || !d->idf) return fail(SRX_ERR_INVALID, "%s: null term_ptr / tile_skip / idf", who);
+    return SRX_OK;
+}
+
 SRX_API int srx_score_docs(const srx_index_desc *d, const int32_t *q_ptr, const int32_t *q_term, const float *q_weight,
                            int32_t nq, const int32_t *cand_doc, const int32_t *cand_count, int32_t m, float *out_score,
                            void *stream_v) {
-    if (!d) return fail(SRX_ERR_INVALID, "srx_score_docs: null descriptor%s");
-    if (d->val_type != SRX_VAL_F32 && d->val_type != SRX_VAL_F16) return fail(SRX_ERR_INVALID, "srx_score_docs: bad val_type%s");
-    if (d->n_docs <= 0 || d->n_docs >= 0x7FFFFFFFll || d->vocab <= 0)
-        return fail(SRX_ERR_INVALID, "srx_score_docs: n_docs / vocab out of range%s");
-    if (d->tile_log2 < 6 || d->tile_log2 > SRX_MAX_TILE_LOG2)
-        return fail(SRX_ERR_INVALID, "srx_score_docs: tile_log2 must be in [6, 14]%s");
-    if ((int64_t)d->n_tiles != (d->n_docs + (1ll << d->tile_log2) - 1) >> d->tile_log2)
-        return fail(SRX_ERR_INVALID, "srx_score_docs: n_tiles != ceil(n_docs / 2^tile_log2)%s");
-    if (d->unit_tiles < 1 || d->unit_tiles > MAX_TPS) return fail(SRX_ERR_INVALID, "srx_score_docs: unit_tiles must be in [1, 64]%s");
-    if (!d->post && !d->post16) return fail(SRX_ERR_INVALID, "srx_score_docs: the descriptor has neither post nor post16%s");
-    if (d->post16 && ((int64_t)d->unit_tiles << d->tile_log2) > W_UNIT_MAX_DOCS)
-        return fail(SRX_ERR_INVALID, "srx_score_docs: a compact copy (post16) needs units of <= 49152 docs%s");
-    if (!d->term_ptr || !d->tile_skip || !d->idf) return fail(SRX_ERR_INVALID, "srx_score_docs: null term_ptr / tile_skip / idf%s");
+    const int rc = srx_check_index_desc("srx_score_docs", d);
+    if (rc != SRX_OK) return rc;
     if (nq < 0) return fail(SRX_ERR_INVALID, "srx_score_docs: nq < 0%s");
     if (m < 1) return fail(SRX_ERR_INVALID, "srx_score_docs: m must be >= 1%s");
     if ((int64_t)nq * (int64_t)m > 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "srx_score_docs: nq * m must fit int32%s");

@@ -20,6 +20,7 @@
 //
 // A term id outside [0, vocab) is read as "no doc has it" (-1 is the legal spelling; any other is a precondition violation that
 // the kernel does not turn into a wild read).
+#include "desc_check.h"
 #include "filter_common.h"
 #include "sparse_rx_terms.h"
 
@@ -27,7 +28,6 @@ namespace {
 
 constexpr int TM_WORDS = W_UNIT_MAX_DOCS / 32 + 4;  // a chunk's words, plus the <= 3 padding words of a row that ends in it
 constexpr int TM_MAX_ROWS_Y = 65535;                // grid.y; more rows than that are looped over
-constexpr int64_t TM_MAX_DOCS = 0x7FFFFFFFll - 1;   // n_docs of a filter row: [1, 2^31 - 2]
 
 struct TermsArgs {
     const int64_t *term_ptr;
@@ -95,8 +95,7 @@ __global__ __launch_bounds__(THREADS) void srx_terms_kernel(TermsArgs a) {
     const int64_t w0 = (int64_t)u * cw;                                 // the chunk's first word of a row
     const int nw = u == a.n_chunks - 1 ? (int)(a.words - w0) : cw;      // the last chunk also owns the padding words: <= cw + 3
     for (int r = blockIdx.y; r < a.n_rows; r += gridDim.y) {
-        int br = a.base_bits != nullptr ? 0 : -1;
-        if (a.base_bits != nullptr && a.base_q != nullptr) br = cload_i32(a.base_q + r);
+        const int br = srx_filter_base_row(a.base_bits, a.base_q, r);
         const uint32_t *brow = br >= 0 ? a.base_bits + (int64_t)br * a.words + w0 : nullptr;
         // word w of acc / tmp belongs to thread w % THREADS until the store
         for (int w = tid; w < nw; w += THREADS) {
@@ -168,7 +167,7 @@ int launch_terms(const TermsArgs &a, hipStream_t stream) {
 }  // namespace
 
 SRX_API int64_t srx_filter_from_terms_bytes(int64_t n_rows, int64_t n_docs) {
-    if (n_rows < 0 || n_docs < 1 || n_docs > TM_MAX_DOCS)
+    if (n_rows < 0 || n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS)
         return fail(SRX_ERR_INVALID, "srx_filter_from_terms_bytes: need n_rows >= 0 and n_docs in [1, 2^31 - 2]%s");
     const int64_t row_bytes = srx_filter_row_words(n_docs) * 4;
     if (n_rows > INT64_MAX / row_bytes) return fail(SRX_ERR_INVALID, "srx_filter_from_terms_bytes: the size does not fit int64%s");
@@ -179,27 +178,9 @@ SRX_API int srx_filter_from_terms(const srx_index_desc *d, int32_t n_rows, const
                                   const int32_t *any_ptr, const int32_t *any_term, const int32_t *none_ptr, const int32_t *none_term,
                                   const srx_doc_filter *base, uint32_t *out_bits, void *stream_v) {
     const char *who = "srx_filter_from_terms";
-    // the descriptor, as srx_score_docs checks it
-    if (!d) return fail(SRX_ERR_INVALID, "%s: null descriptor", who);
-    if (d->val_type != SRX_VAL_F32 && d->val_type != SRX_VAL_F16) return fail(SRX_ERR_INVALID, "%s: bad val_type", who);
-    if (d->n_docs <= 0 || d->n_docs >= 0x7FFFFFFFll || d->vocab <= 0) return fail(SRX_ERR_INVALID, "%s: n_docs / vocab out of range", who);
-    if (d->tile_log2 < 6 || d->tile_log2 > SRX_MAX_TILE_LOG2) return fail(SRX_ERR_INVALID, "%s: tile_log2 must be in [6, 14]", who);
-    if ((int64_t)d->n_tiles != (d->n_docs + (1ll << d->tile_log2) - 1) >> d->tile_log2)
-        return fail(SRX_ERR_INVALID, "%s: n_tiles != ceil(n_docs / 2^tile_log2)", who);
-    if (d->unit_tiles < 1 || d->unit_tiles > MAX_TPS) return fail(SRX_ERR_INVALID, "%s: unit_tiles must be in [1, 64]", who);
-    if (!d->post && !d->post16) return fail(SRX_ERR_INVALID, "%s: the descriptor has neither post nor post16", who);
-    const bool unit_fits = ((int64_t)d->unit_tiles << d->tile_log2) <= W_UNIT_MAX_DOCS;
-    if (d->post16 && !unit_fits) return fail(SRX_ERR_INVALID, "%s: a compact copy (post16) needs units of <= 49152 docs", who);
-    if (!d->term_ptr || !d->tile_skip || !d->idf) return fail(SRX_ERR_INVALID, "%s: null term_ptr / tile_skip / idf", who);
-    if (n_rows < 0) return fail(SRX_ERR_INVALID, "%s: n_rows < 0", who);
-    if (!all_ptr != !all_term || !any_ptr != !any_term || !none_ptr != !none_term)
-        return fail(SRX_ERR_INVALID, "%s: the ptr and term arrays of a list go together (both or neither)", who);
-    if (!out_bits) return fail(SRX_ERR_INVALID, "%s: null out_bits", who);
-    if ((uintptr_t)out_bits & 15) return fail(SRX_ERR_INVALID, "%s: filter rows must be 16-byte aligned", who);
-    if (base) {
-        const int rc = srx_check_filter(who, base);
-        if (rc != SRX_OK) return rc;
-    }
+    int rc = srx_check_index_desc(who, d);
+    if (rc == SRX_OK) rc = srx_check_row_builder(who, "term", n_rows, all_ptr, all_term, any_ptr, any_term, none_ptr, none_term, out_bits, base);
+    if (rc != SRX_OK) return rc;
     if (n_rows == 0) return SRX_OK;
     HIP_TRY(hipSetDevice(d->device));
     const bool compact = d->post16 != nullptr;
@@ -219,6 +200,7 @@ SRX_API int srx_filter_from_terms(const srx_index_desc *d, int32_t n_rows, const
     a.n_rows = n_rows;
     a.n_tiles = d->n_tiles;
     a.tile_log2 = d->tile_log2;
+    const bool unit_fits = ((int64_t)d->unit_tiles << d->tile_log2) <= W_UNIT_MAX_DOCS;
     a.chunk_tiles = unit_fits ? d->unit_tiles : W_UNIT_MAX_DOCS >> d->tile_log2;  // the canonical copy in units too large for the bitmaps
     a.n_chunks = (d->n_tiles + a.chunk_tiles - 1) / a.chunk_tiles;
     hipStream_t stream = (hipStream_t)stream_v;

@@ -10,7 +10,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from .filter import q_filter_to_device, resolve_filter
+from .filter import host_q_filter, resolve_filter
 from .index import (_candidate_block, _check_k, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, rows_to_dict,
                     validate_candidates)
 
@@ -268,14 +268,6 @@ class _DenseIndex:
     def _launch_filtered(self, *args):
         raise ValueError(f"{type(self).__name__} has no filtered search")
 
-    def _host_q_filter(self, filter, q_filter, nq: int):
-        """The host-array doors: ``q_filter`` validated and uploaded (None without a filter)"""
-        if filter is None:
-            if q_filter is not None:
-                raise ValueError("q_filter picks rows of a filter: it needs filter=")
-            return None
-        return q_filter_to_device(filter.for_index(self), q_filter, nq)
-
     def _padded(self, torch, queries, dtype):
         q = torch.zeros((int(queries.shape[0]), self.dim_pad), dtype=dtype, device=self.device)
         q[:, : self.dim] = queries
@@ -502,7 +494,7 @@ class DenseUint8Index(_DenseIndex):
         """queries u8[nq, dim] + f32[nq, 2] (scale, min) as the reference's search builds them (:486-491); host arrays out.
         ``q_filter``: a host sequence of row numbers, validated here."""
         q = self._queries_to_device(queries_uint8, query_scales)
-        return self._host(self.search_device(q, k, filter=filter, q_filter=self._host_q_filter(filter, q_filter, int(q.shape[0]))))
+        return self._host(self.search_device(q, k, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0]))))
 
     def _queries_to_device(self, queries_uint8, query_scales):
         """The de-quantized f32 query block on the device"""
@@ -724,7 +716,7 @@ class DenseF32Index(_DenseIndex, _MmrSelect):
 
     def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
         q = self._queries_to_device(queries)
-        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=self._host_q_filter(filter, q_filter, int(q.shape[0]))))
+        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0]))))
 
     def _queries_to_device(self, queries):
         q = np.ascontiguousarray(queries, dtype=np.float32)
@@ -842,7 +834,7 @@ class DenseHalfIndex(_DenseIndex, _MmrSelect):
     def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
         """Host arrays in, host arrays out; ``q_filter``: a host sequence of row numbers, validated here."""
         q = self._queries_to_device(queries)
-        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=self._host_q_filter(filter, q_filter, int(q.shape[0]))))
+        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0]))))
 
     def _queries_to_device(self, queries):
         q = np.ascontiguousarray(queries, dtype=np.float32)

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from .filter import DocFilter, filter_words, pack_masks, q_filter_to_device
+from .filter import BASE_NAMES, DocFilter, build_rows, filter_words, host_q_filter, pack_masks
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -515,40 +515,12 @@ class FieldTable:
             raise ValueError("clauses must be int64 [n_clauses, 3]")
         if values is not None:
             values = check(values, torch.int64, "values")
-        n_rows, ptrs = None, []
-        for name, pair in (("all", all), ("any", any), ("none", none)):
-            if pair is None:
-                ptrs += [None, None]
-                continue
-            ptr, ids = check(pair[0], torch.int32, name), check(pair[1], torch.int32, name)
-            if ptr.numel() < 1 or (n_rows is not None and ptr.numel() - 1 != n_rows):
-                raise ValueError("the clause lists must have one ptr entry per output row, plus one, and agree on the row count")
-            n_rows = ptr.numel() - 1
-            ptrs += [ptr, ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)]
-        if n_rows is None:
-            raise ValueError("give at least one of all / any / none (an empty list is a ptr of zeros)")
-        if n_rows < 1:
-            raise ValueError("a filter needs at least one row")
-        bdesc, keep = None, None
-        if base is not None:
-            if not isinstance(base, DocFilter):
-                raise ValueError("base must be a DocFilter")
-            bdesc, keep = base.for_index(self).launch_args(q_base, n_rows)
-        elif q_base is not None:
-            raise ValueError("q_base picks rows of a base filter: it needs base=")
-        with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((n_rows, filter_words(self.n_docs)), dtype=torch.int32, device=self.device)
-            f = DocFilter(out, self.n_docs, self.doc_base)
-            if f.n_filters != n_rows or f.device != self.device:
-                raise ValueError(f"out must be an int32 tensor [{n_rows}, {f.words}] on {self.device}")
-            ptr_of = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = _capi.lib().srx_filter_from_fields(self.device.index or 0, self.n_docs, descs, len(names), ptr_of(clauses), int(clauses.shape[0]),
-                                                    ptr_of(values), n_rows, *[None if t is None else t.data_ptr() for t in ptrs], bdesc,
-                                                    out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(rc, "srx_filter_from_fields")
-        del keep
-        return f
+        ptr_of = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+
+        def launch(n_rows, lists, bdesc, out_ptr, stream):
+            return _capi.lib().srx_filter_from_fields(self.device.index or 0, self.n_docs, descs, len(names), ptr_of(clauses), int(clauses.shape[0]),
+                                                      ptr_of(values), n_rows, *lists, bdesc, out_ptr, stream)
+        return build_rows(self, "srx_filter_from_fields", launch, (all, any, none), "clause", base, q_base, out)
 
     def filter_arrays(self, clauses, values, all=None, any=None, none=None, columns=None, base=None, q_base=None) -> DocFilter:
         """:meth:`filter_device` from host arrays, validated first (:func:`check_records`: cols, ops against the column types, IN
@@ -562,13 +534,7 @@ class FieldTable:
         clauses = np.ascontiguousarray(clauses, dtype=np.int64).reshape(-1, 3)
         check_records([self.columns[n].type for n in names], clauses, len(values), (all, any, none))
         n_rows = next(len(p[0]) - 1 for p in (all, any, none) if p is not None)
-        qb = None
-        if base is not None:
-            if not isinstance(base, DocFilter):
-                raise ValueError("base must be a DocFilter")
-            qb = q_filter_to_device(base.for_index(self), q_base, n_rows)
-        elif q_base is not None:
-            raise ValueError("q_base picks rows of a base filter: it needs base=")
+        qb = host_q_filter(self, base, q_base, n_rows, BASE_NAMES)
         up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)
         pairs = [None if p is None else (up(p[0], np.int32), up(p[1], np.int32)) for p in (all, any, none)]
         return self.filter_device(up(clauses, np.int64), up(values, np.int64) if len(values) else None, *pairs, columns=names, base=base, q_base=qb)

@@ -169,19 +169,86 @@ class DocFilter:
         return ctypes.byref(desc), (desc, q_filter)
 
 
-def resolve_filter(index, filter, q_filter, nq: int):
-    """What the search doors of the indexes do with their ``filter`` / ``q_filter`` keywords: (None, None) when there is no filter,
-    else (pointer to the call's struct, keep-alive)."""
+SEARCH_NAMES = ("filter", "q_filter", "a filter")   # what the messages call (the filter, its row picker, the thing picked from) ...
+BASE_NAMES = ("base", "q_base", "a base filter")    # ... at a search door and at a row builder's door
+
+
+def _checked(index, filter, q_filter, names):
+    """The filter keyword of a door, checked against ``index``; None when neither keyword is given"""
+    name, q_name, picked_from = names
     if filter is None:
         if q_filter is not None:
-            raise ValueError("q_filter picks rows of a filter: it needs filter=")
-        return None, None
+            raise ValueError(f"{q_name} picks rows of {picked_from}: it needs {name}=")
+        return None
     if not isinstance(filter, DocFilter):
-        raise ValueError("filter must be a DocFilter")
-    return filter.for_index(index).launch_args(q_filter, nq)
+        raise ValueError(f"{name} must be a DocFilter")
+    return filter.for_index(index)
+
+
+def resolve_filter(index, filter, q_filter, nq: int, names=SEARCH_NAMES):
+    """What the device doors do with their ``filter`` / ``q_filter`` (a row builder: ``base`` / ``q_base``) keywords: (None, None)
+    when there is no filter, else (pointer to the call's struct, keep-alive)."""
+    f = _checked(index, filter, q_filter, names)
+    return (None, None) if f is None else f.launch_args(q_filter, nq)
+
+
+def host_q_filter(index, filter, q_filter, nq: int, names=SEARCH_NAMES):
+    """What the host-array doors do with the same keywords: the host ``q_filter`` validated (:func:`validate_q_filter`) and
+    uploaded for the device door; None without a filter, and for None"""
+    f = _checked(index, filter, q_filter, names)
+    return None if f is None else q_filter_to_device(f, q_filter, nq)
 
 
 def q_filter_to_device(filter: DocFilter, q_filter, nq: int):
     """A host ``q_filter`` validated (:func:`validate_q_filter`) and uploaded; None stays None."""
     q = validate_q_filter(q_filter, nq, filter.n_filters)
     return None if q is None else _torch().as_tensor(q, device=filter.device)
+
+
+# -- the door of the row builders (DeviceIndex.term_filter_device, FieldTable.filter_device) ---------------------------------------
+def builder_lists(device, lists, ids: str):
+    """The ``all`` / ``any`` / ``none`` keywords of a row builder -- each None or a ``(ptr, ids)`` pair of 1-D int32 tensors on
+    ``device``, a CSR over the output rows -- as (n_rows, the six tensors in the order the C entry points take them; None: list not
+    given).  An empty id tensor is passed as a one-element placeholder (the entry points take "ptr and ids, both or neither").
+    ``ids``: the word the messages have for the second tensor ("term", "clause").  ValueError: a pair that is not such tensors,
+    lists that disagree on the row count, no list, no row."""
+    torch = _torch()
+    n_rows, tensors = None, []
+    for name, pair in zip(("all", "any", "none"), lists):
+        if pair is None:
+            tensors += [None, None]
+            continue
+        ptr, row_ids = pair
+        for t in (ptr, row_ids):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != device or t.dim() != 1:
+                raise ValueError(f"{name} must be a (ptr, {ids}) pair of 1-D int32 tensors on {device}")
+        if ptr.numel() < 1 or (n_rows is not None and ptr.numel() - 1 != n_rows):
+            raise ValueError(f"the {ids} lists must have one ptr entry per output row, plus one, and agree on the row count")
+        n_rows = ptr.numel() - 1
+        tensors += [ptr.contiguous(), row_ids.contiguous() if row_ids.numel() else torch.zeros(1, dtype=torch.int32, device=device)]
+    if n_rows is None:
+        raise ValueError("give at least one of all / any / none (an empty list is a ptr of zeros)")
+    if n_rows < 1:
+        raise ValueError("a filter needs at least one row")
+    return n_rows, tensors
+
+
+def build_rows(owner, entry: str, launch, lists, ids: str, base, q_base, out) -> DocFilter:
+    """The door of a row builder, for ``owner`` (``device``, ``n_docs``, ``doc_base``: the sparse index, a field table):
+    :func:`builder_lists`, the ``base`` / ``q_base`` keywords (:func:`resolve_filter`), ``out`` allocated or checked, then
+    ``launch(n_rows, the six list pointers, the base struct or None, out's pointer, the current stream)`` -> the return code of
+    the C entry point ``entry``.  Returns the DocFilter over ``out``."""
+    torch = _torch()
+    n_rows, tensors = builder_lists(owner.device, lists, ids)
+    bdesc, keep = resolve_filter(owner, base, q_base, n_rows, BASE_NAMES)  # keep: alive until the call below has been issued
+    with torch.cuda.device(owner.device):
+        if out is None:
+            out = torch.empty((n_rows, filter_words(owner.n_docs)), dtype=torch.int32, device=owner.device)
+        f = DocFilter(out, owner.n_docs, owner.doc_base)
+        if f.n_filters != n_rows or f.device != owner.device:
+            raise ValueError(f"out must be an int32 tensor [{n_rows}, {f.words}] on {owner.device}")
+        rc = launch(n_rows, [None if t is None else t.data_ptr() for t in tensors], bdesc, out.data_ptr(),
+                    torch.cuda.current_stream(owner.device).cuda_stream)
+        _capi.check(rc, entry)
+    del keep
+    return f

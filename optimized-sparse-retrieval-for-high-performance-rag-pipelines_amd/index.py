@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from .filter import DocFilter, filter_words, q_filter_to_device, resolve_filter
+from .filter import BASE_NAMES, DocFilter, build_rows, host_q_filter, q_filter_to_device, resolve_filter
 
 BLOCK_PAD = 256  # SRX_BLOCK_PAD in include/sparse_rx.h: all-sentinel blocks behind the last run
 _TOKEN_RE = re.compile(r"\b\w+\b")
@@ -754,42 +754,9 @@ class DeviceIndex:
         [n_rows, filter_words(n_docs)], every word is written); asynchronous on the current stream.  Precondition (NOT checked
         here, the tensors never leave the device): ptr starts at 0 and ascends, -1 <= term < vocab, q_base in [-1, n_filters).
         Memory: n_rows * n_docs / 8 bytes -- 1.25 MB per row at 10 M docs."""
-        torch = _torch()
-        n_rows, ptrs = None, []
-        for name, pair in (("all", all), ("any", any), ("none", none)):
-            if pair is None:
-                ptrs += [None, None]
-                continue
-            ptr, term = pair
-            for t in (ptr, term):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or t.dim() != 1:
-                    raise ValueError(f"{name} must be a (ptr, term) pair of 1-D int32 tensors on {self.device}")
-            if ptr.numel() < 1 or (n_rows is not None and ptr.numel() - 1 != n_rows):
-                raise ValueError("the term lists must have one ptr entry per output row, plus one, and agree on the row count")
-            n_rows = ptr.numel() - 1
-            ptrs += [ptr.contiguous(), term.contiguous() if term.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)]
-        if n_rows is None:
-            raise ValueError("give at least one of all / any / none (an empty list is a ptr of zeros)")
-        if n_rows < 1:
-            raise ValueError("a filter needs at least one row")
-        bdesc, keep = None, None
-        if base is not None:
-            if not isinstance(base, DocFilter):
-                raise ValueError("base must be a DocFilter")
-            bdesc, keep = base.for_index(self).launch_args(q_base, n_rows)
-        elif q_base is not None:
-            raise ValueError("q_base picks rows of a base filter: it needs base=")
-        with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((n_rows, filter_words(self.n_docs)), dtype=torch.int32, device=self.device)
-            f = DocFilter(out, self.n_docs, self.doc_base)
-            if f.n_filters != n_rows or f.device != self.device:
-                raise ValueError(f"out must be an int32 tensor [{n_rows}, {f.words}] on {self.device}")
-            rc = _capi.lib().srx_filter_from_terms(ctypes.byref(self._desc), n_rows, *[_ptr(t) for t in ptrs], bdesc, _ptr(out),
-                                                   _stream_ptr(torch, self.device))
-            _capi.check(rc, "srx_filter_from_terms")
-        del keep
-        return f
+        def launch(n_rows, lists, bdesc, out_ptr, stream):
+            return _capi.lib().srx_filter_from_terms(ctypes.byref(self._desc), n_rows, *lists, bdesc, out_ptr, stream)
+        return build_rows(self, "srx_filter_from_terms", launch, (all, any, none), "term", base, q_base, out)
 
     def term_filter(self, all_terms=None, any_terms=None, none_terms=None, base=None, q_base=None) -> DocFilter:
         """:meth:`term_filter_device` from host lists: each keyword is None or a list of lists of term ids, one per output row
@@ -808,14 +775,7 @@ class DeviceIndex:
             pairs.append((torch.as_tensor(ptr, device=self.device), torch.as_tensor(term, device=self.device)))
         if n_rows is None:
             raise ValueError("give at least one of all_terms / any_terms / none_terms")
-        qb = None
-        if base is not None:
-            if not isinstance(base, DocFilter):
-                raise ValueError("base must be a DocFilter")
-            qb = q_filter_to_device(base.for_index(self), q_base, n_rows)
-        elif q_base is not None:
-            raise ValueError("q_base picks rows of a base filter: it needs base=")
-        return self.term_filter_device(*pairs, base=base, q_base=qb)
+        return self.term_filter_device(*pairs, base=base, q_base=host_q_filter(self, base, q_base, n_rows, BASE_NAMES))
 
     def profile_read(self):
         """Average kernel durations (ms) over the profiled searches since the last read."""

@@ -57,8 +57,7 @@ class _SparseRetrieverBase(SparseIndexViews):
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
-        spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, self._be.doc_filter_spec(queries, allowed_docs, excluded_docs))
-        spec = self._be.field_filter_spec(queries, where, spec, "search")
+        spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")
         if spec is not None:
             return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec)
         # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional

@@ -136,8 +136,7 @@ class RetrievalService(SparseIndexViews):
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
-        spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, self._be.doc_filter_spec(queries, allowed_docs, excluded_docs))
-        spec = self._be.field_filter_spec(queries, where, spec, "search_bm25")
+        spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
@@ -252,9 +251,7 @@ class RetrievalService(SparseIndexViews):
         if allowed_docs is None and excluded_docs is None and not terms and where is None:
             return None
         if self.host is not None:
-            spec = self._be.doc_filter_spec(queries, allowed_docs, excluded_docs)
-            spec = self._be.term_filter_spec(queries, must_terms, any_terms, must_not_terms, spec)
-            spec = self._be.field_filter_spec(queries, where, spec, call)
+            spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
         elif where is not None:
             raise ValueError(f"{call}(where=...) needs the docs' fields: call build_bm25_index() and set_doc_fields() first")
         elif terms:
