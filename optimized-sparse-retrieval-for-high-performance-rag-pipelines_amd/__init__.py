@@ -10,7 +10,7 @@ from .dense import (DenseF32Index, DenseHalfIndex, DenseInt8Index, DenseUint8Ind
                     quantize_query_asymmetric, quantize_query_symmetric, quantize_symmetric, quantize_symmetric_device)
 from .distributed import (ShardedSearcher, shard_range, global_df, global_avgdl, global_term_bounds, bm25_idf_from_df,
                           build_sharded_host_index)
-from .backend import SparseBackend
+from .backend import SparseBackend, collapse_deep, collapse_pool_depth
 from .filter import DocFilter
 from .late import TokenIndex, check_late_shape, late_pool_depth
 from .fields import FieldTable, columns_from_metadata
@@ -22,4 +22,4 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "quantize_asymmetric", "quantize_query_asymmetric",
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
            "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape",
-           "late_pool_depth", "FieldTable", "columns_from_metadata"]
+           "late_pool_depth", "FieldTable", "columns_from_metadata", "collapse_deep", "collapse_pool_depth"]

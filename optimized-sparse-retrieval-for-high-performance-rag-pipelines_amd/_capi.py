@@ -1,6 +1,6 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
-include/sparse_rx_terms.h, include/sparse_rx_maxsim.h and include/sparse_rx_fields.h).
+include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h and include/sparse_rx_collapse.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -183,6 +183,14 @@ SRX_FIELD_I32, SRX_FIELD_I64, SRX_FIELD_F32, SRX_FIELD_SET64 = 0, 1, 2, 3       
 SRX_FOP_RANGE, SRX_FOP_IN, SRX_FOP_MASK_ANY, SRX_FOP_MASK_ALL = 0, 1, 2, 3        # clause ops
 SRX_FIELDS_MAX_COLS = 32                                                          # columns one call takes
 
+# every symbol include/sparse_rx_collapse.h declares (the tenth header of the same library)
+COLLAPSE_SYMBOLS = {
+    "srx_collapse_topk": (ctypes.c_int, [_I32, ctypes.POINTER(FieldColDesc), _I64, _I64, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP,
+                                         _VP, _VP, _VP]),
+}
+SRX_COLLAPSE_NULL_OWN, SRX_COLLAPSE_NULL_ONE, SRX_COLLAPSE_NULL_DROP = 0, 1, 2    # what a doc without a key is
+SRX_COLLAPSE_MAX_M = 2048                                                         # positions per list (pinned to the header by tests/test_collapse_cpu.py)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -211,7 +219,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_mmr.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_terms.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_maxsim.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_fields.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_fields.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_collapse.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -260,7 +269,7 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
-                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS}.items():
+                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

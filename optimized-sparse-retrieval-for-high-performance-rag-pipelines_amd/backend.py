@@ -201,8 +201,55 @@ class SparseBackend:
             self._field_table = FieldTable.from_columns(self._fields, device=self.dev.device if self.dev is not None else self.device, doc_base=self.doc_base)
         return self._field_table
 
+    def collapse_spec(self, by, per_group=1, nulls="own", depth=None, top_k: int = 10, call: str = "search") -> Optional["CollapseSpec"]:
+        """The collapse keywords of one API call (``collapse_by``, ``per_group``, ``collapse_nulls``, ``collapse_depth``) as a
+        :class:`CollapseSpec`, or None when ``by`` is None (the other three are then not looked at).  ValueError: a sharded index,
+        no fields (the message names ``call``), what :func:`~.fields.check_collapse_args` refuses, ``top_k`` above the engine's
+        list depth, a depth below 1."""
+        if by is None:
+            return None
+        from . import _capi
+        from .fields import check_collapse_args
+        if self._fields is None:
+            raise ValueError(f"{call}(collapse_by=...) needs the docs' fields: call set_doc_fields() first")
+        check_collapse_args(self._fields, by, per_group, nulls)
+        if int(top_k) > _capi.SRX_MAX_K:
+            raise ValueError(f"{call}(collapse_by=...) returns at most {_capi.SRX_MAX_K} rows per query, got top_k={top_k}")
+        if depth is not None and int(depth) < 1:
+            raise ValueError(f"collapse_depth must be >= 1, got {depth}")
+        self._refuse_sharded("collapse_by= needs")
+        return CollapseSpec(by, int(per_group), nulls, None if depth is None else int(depth))
+
+    def collapsed_search_arrays(self, q_ptr, q_term, q_weight, k: int, collapse: "CollapseSpec", filter=None, q_filter=None):
+        """Host CSR batch -> host rows (doc, score, count) of the top ``k`` of the COLLAPSED complete ranking, exact:
+        :func:`collapse_deep` over this index's device search (under ``filter`` / ``q_filter``, a DocFilter and the host row
+        numbers, when given) and the field table's ``collapse_device``.  ``first`` = min(max(4 k, 64), 1024, n_docs)."""
+        import torch
+        from . import _capi
+        from .filter import q_filter_to_device
+        from .index import _batch_to_device, _to_host, validate_query_batch
+        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
+        nq = len(q_ptr) - 1
+        if nq == 0:
+            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
+        dev, table = self.dev, self.field_table()
+        flt = {}
+        if filter is not None:
+            flt = {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
+
+        def search_fn(qp, qt, qw, kk, after=None):
+            return dev.search_device(qp, qt, qw, kk, after=after, **flt)
+
+        def collapse_fn(d, s, c, kk):
+            return table.collapse_device(collapse.by, d, s, c, kk, collapse.per_group, collapse.nulls)
+
+        first = min(max(4 * k, 64), _capi.SRX_MAX_K, self.n_docs_total)
+        out = collapse_deep(search_fn, collapse_fn, *_batch_to_device(torch, q_ptr, q_term, q_weight, dev.device), k, first,
+                            page=_capi.SRX_MAX_K, max_depth=collapse.depth)
+        return _to_host(torch, dev.device, out)
+
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
-                     blank: str = "empty", filter: Optional["DocFilterSpec"] = None):
+                     blank: str = "empty", filter: Optional["DocFilterSpec"] = None, collapse: Optional["CollapseSpec"] = None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
         in the caller's order, one batched search for all texts the cache does not hold (equal texts share one row).  What
         the call sites of the reference do differently is named here:
@@ -222,8 +269,11 @@ class SparseBackend:
 
         ``filter`` (:meth:`filter_spec`): the search is restricted to each query's allowed docs (``srx_search_filtered``).
         A filtered call neither reads nor writes the cache -- its key is the query text --, and equal texts share a row only
-        under the same filter row."""
-        if filter is not None:
+        under the same filter row.
+
+        ``collapse`` (:meth:`collapse_spec`): every row is the top ``top_k`` of the COLLAPSED complete ranking
+        (:meth:`collapsed_search_arrays`), under ``filter`` when given; such a call bypasses the cache as a filtered one does."""
+        if filter is not None or collapse is not None:
             cache = None
         k_eff = min(int(top_k), self.n_docs_total)  # any depth: search_arrays pages past the engine's 1024-row lists
         results: Dict[str, Dict[str, float]] = {}
@@ -255,7 +305,11 @@ class SparseBackend:
             pending[key].append(qid)
         if texts and k_eff > 0:
             q_ptr, q_term, q_weight = encode_queries(texts, self.host.vocabulary, order=order)
-            if filter is None:
+            if collapse is not None:
+                docs, scores, counts = self.collapsed_search_arrays(q_ptr, q_term, q_weight, k_eff, collapse,
+                                                                    filter=None if filter is None else filter.on_device(self.dev),
+                                                                    q_filter=None if filter is None else np.asarray(frows, dtype=np.int32))
+            elif filter is None:
                 docs, scores, counts = self.search_arrays(q_ptr, q_term, q_weight, k_eff)
             else:
                 docs, scores, counts = self.dev.search(q_ptr, q_term, q_weight, k_eff, filter=filter.on_device(self.dev),
@@ -296,6 +350,72 @@ class SparseBackend:
             self.dev.close()
             self.dev = None
         self.searcher = None
+
+
+class CollapseSpec:
+    """The collapse keywords of one API call, checked (:meth:`SparseBackend.collapse_spec`): ``by`` = the column, ``per_group``,
+    ``nulls`` ("own", "one", "drop") and ``depth`` = how deep the ranking may be read (None: until it is exhausted)."""
+
+    def __init__(self, by: str, per_group: int = 1, nulls: str = "own", depth: Optional[int] = None):
+        self.by, self.per_group, self.nulls, self.depth = by, per_group, nulls, depth
+
+
+def collapse_pool_depth(top_k: int, collapse_pool, n_docs: int) -> int:
+    """Rows of the fused ranking a hybrid search collapses, or ``ValueError``: ``collapse_pool`` when given (1 .. 1024: a
+    deeper pool is refused, not truncated), else ``min(max(4 * top_k, 100), 1024)``; never more than ``n_docs``."""
+    from . import _capi
+    if collapse_pool is None:
+        pool = min(max(4 * int(top_k), 100), _capi.SRX_MAX_K)
+    else:
+        pool = int(collapse_pool)
+        if not (1 <= pool <= _capi.SRX_MAX_K):
+            raise ValueError(f"collapse_pool must be in [1, {_capi.SRX_MAX_K}], got {collapse_pool}")
+    return max(1, min(pool, n_docs))
+
+
+def collapse_deep(search_fn, collapse_fn, q_ptr, q_term, q_weight, k: int, first: int, page: int = 1024, max_depth: Optional[int] = None):
+    """The top ``k`` of the COLLAPSED complete ranking, exact, on top of a search limited to ``page`` rows per call:
+    ``search_fn(q_ptr, q_term, q_weight, kk, after=None | (doc i32[nq], score f32[nq]))`` as :func:`~.index.deep_search` takes it,
+    ``collapse_fn(doc [nq, m], score [nq, m], count [nq] | None, kk) -> (doc [nq, kk], score [nq, kk], count [nq])`` with the
+    contract of ``srx_collapse_topk`` (include/sparse_rx_collapse.h: a doc id of -1 is a dead position), torch tensors throughout.
+
+    The first ``first`` rows are fetched and collapsed.  A query is done when its count reached ``k`` or its last page came back
+    short (its ranking is exhausted).  For the others the next page is the rows ranked strictly after their last row, and
+    ``concat(kept so far, page)`` is collapsed: a query that continues was not cut at ``k``, and for such a list A
+    ``collapse(collapse(A) ++ B) == collapse(A ++ B)``.  A finished query's bound is score 0 -- nothing ranks after it --, so
+    its page is empty and its kept rows stay as they are.  One synchronisation per page (the "is anyone left" test), as in
+    ``deep_search``.
+
+    ``max_depth`` None reads until every query is done; a number stops after that many rows of the ranking, and a query may
+    then come back with FEWER than ``k`` rows although more groups exist further down: that is the caller's trade, not an error.
+    ``m`` stays below ``k + page`` <= 2048 for k, page <= 1024."""
+    import torch
+    first = int(first) if max_depth is None else min(int(first), int(max_depth))
+
+    def collapsed(d, s, c):  # k columns, whatever the list's depth
+        kk = min(k, int(d.shape[1]))
+        od, os_, oc = collapse_fn(d, s, c, kk)[:3]
+        if kk < k:
+            od = torch.cat([od, torch.full((od.shape[0], k - kk), -1, dtype=od.dtype, device=od.device)], dim=1)
+            os_ = torch.cat([os_, torch.zeros((os_.shape[0], k - kk), dtype=os_.dtype, device=os_.device)], dim=1)
+        return od, os_, oc
+
+    d, s, c = search_fn(q_ptr, q_term, q_weight, first)
+    kd, ks, kc = collapsed(d, s, c)
+    active = (kc < k) & (c == first)
+    depth, kk = first, first
+    while max_depth is None or depth < max_depth:
+        if int(active.sum().item()) == 0:  # every query done: one sync per page
+            break
+        a_doc = torch.where(active, d[:, kk - 1], torch.zeros_like(c, dtype=torch.int32)).to(torch.int32).contiguous()
+        a_score = torch.where(active, s[:, kk - 1], torch.zeros_like(c, dtype=torch.float32)).contiguous()
+        kk = page if max_depth is None else min(page, max_depth - depth)
+        d, s, c = search_fn(q_ptr, q_term, q_weight, kk, after=(a_doc, a_score))
+        depth += kk
+        # the padding of the kept rows lies in front of the page: no count, a doc id of -1 is dead
+        kd, ks, kc = collapsed(torch.cat([kd, d], dim=1).contiguous(), torch.cat([ks, s], dim=1).contiguous(), None)
+        active = active & (kc < k) & (c == kk)
+    return kd, ks, kc
 
 
 class RowOfIds:

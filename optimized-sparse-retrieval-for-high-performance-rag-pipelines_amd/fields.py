@@ -23,6 +23,7 @@ from .filter import BASE_NAMES, DocFilter, build_rows, filter_words, host_q_filt
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
 GROUP_KEYS = ("must", "should", "must_not")
+NULL_POLICIES = {"own": _capi.SRX_COLLAPSE_NULL_OWN, "one": _capi.SRX_COLLAPSE_NULL_ONE, "drop": _capi.SRX_COLLAPSE_NULL_DROP}
 _RANGE_KEYS = ("gte", "gt", "lte", "lt")
 _TEST_KEYS = _RANGE_KEYS + ("eq", "in", "any_of", "all_of", "exists")
 
@@ -439,6 +440,24 @@ def check_records(types, clauses, n_values: int, lists) -> None:
         raise ValueError("give at least one of the all / any / none lists")
 
 
+def check_collapse_args(columns, column, per_group, nulls) -> int:
+    """What every collapse door checks of its keywords before anything is launched: ``column`` names a column of ``columns``
+    (name -> :class:`HostColumn`) that can be a group key -- int32 / int64 / bool values or a category (collapsed by its code);
+    a float32 and a set column are refused by name --, ``per_group`` >= 1 and ``nulls`` is "own", "one" or "drop".  Returns the
+    SRX_COLLAPSE_NULL_* value.  Raises ValueError."""
+    if column not in columns:
+        raise ValueError(f"unknown field {column!r}")
+    kind = columns[column].kind
+    if kind in ("float32", "set"):
+        raise ValueError(f"{column!r} is a {'float' if kind == 'float32' else 'set'} column: results collapse by an int32, int64 or category "
+                         "column (float and set columns are no group keys)")
+    if isinstance(per_group, bool) or not isinstance(per_group, (int, np.integer)) or not (1 <= int(per_group) <= I32_MAX):
+        raise ValueError(f"per_group must be an integer in [1, {I32_MAX}], got {per_group!r}")
+    if nulls not in NULL_POLICIES:
+        raise ValueError(f"nulls must be one of {', '.join(NULL_POLICIES)}, got {nulls!r}")
+    return NULL_POLICIES[nulls]
+
+
 class FieldTable:
     """Typed metadata columns of ``n_docs`` docs, resident on ``device``; row i of every column belongs to the doc with the GLOBAL
     id ``doc_base + i``.  ``columns`` name -> :class:`HostColumn` (kind, dictionary; its arrays are dropped after the upload)."""
@@ -568,3 +587,70 @@ class FieldTable:
         if len(names) > _capi.SRX_FIELDS_MAX_COLS:
             raise ValueError(f"the predicate names {len(names)} fields: one call takes at most {_capi.SRX_FIELDS_MAX_COLS}")
         return self.filter_arrays(rec, values, *lists, columns=names, base=base, q_base=q_base)
+
+    # -- collapsing ranked lists by a column (include/sparse_rx_collapse.h) ---------------------------------------------------
+    def collapse_device(self, column: str, doc, score, count, k: int, per_group: int = 1, nulls: str = "own", want_pos: bool = False,
+                        want_group_size: bool = False):
+        """``srx_collapse_topk`` on device tensors: the first ``k`` positions of every list that have fewer than ``per_group``
+        earlier positions of their group, the group being the value ``column`` holds for the doc (a category column collapses
+        by its code).  ``doc`` i32[nq, m] GLOBAL ids, ``score`` f32[nq, m], ``count`` i32[nq] or None: the triple of any search,
+        of the fusion or of a reranker as it is, m <= 2048, 1 <= k <= m.  A position at or past the count, or with an id outside
+        the table, is skipped; scores are copied, never looked at.  ``nulls``: a doc without a value is a group of its "own"
+        (it always survives), all of them are "one" group, or they "drop" out.  Returns device tensors ``(doc i32[nq, k], score
+        f32[nq, k], count i32[nq])`` -- a subsequence of each list, rows padded with -1 / 0 --, then ``pos`` i32[nq, k] (the
+        survivor's position in the list given) with ``want_pos`` and ``group_size`` i32[nq, k] (the live positions OF THE LIST
+        GIVEN in its group) with ``want_group_size``.  Asynchronous on the current stream, one launch.  ValueError: an unknown
+        column, a float or set column, m > 2048, k outside [1, m], tensors of another dtype, shape or device."""
+        torch = _torch()
+        policy = check_collapse_args(self.columns, column, per_group, nulls)
+        if column not in self._tensors:
+            raise ValueError("the table is closed")
+        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32:
+            raise ValueError("collapse_device: doc must be an int32 tensor [nq, m]")
+        nq, m = int(doc.shape[0]), int(doc.shape[1])
+        if not (1 <= m <= _capi.SRX_COLLAPSE_MAX_M):
+            raise ValueError(f"collapse_device takes lists of 1 to {_capi.SRX_COLLAPSE_MAX_M} positions, got {m} (no silent truncation)")
+        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or tuple(score.shape) != (nq, m):
+            raise ValueError("collapse_device: score must be a float32 tensor of doc's shape")
+        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
+            raise ValueError("collapse_device: count must be an int32 tensor [nq]")
+        for t, what in ((doc, "doc"), (score, "score"), (count, "count")):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"collapse_device: {what} is on {t.device}, the table on {self.device}")
+        k = int(k)
+        if not (1 <= k <= m):
+            raise ValueError(f"collapse_device: k must be in [1, m = {m}], got {k}")
+        desc = self._col_descs([column])
+        with torch.cuda.device(self.device):
+            doc, score = doc.contiguous(), score.contiguous()
+            count = None if count is None else count.contiguous()
+            outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                    torch.empty((nq,), dtype=torch.int32, device=self.device)]
+            pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
+            size = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_group_size else None
+            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = _capi.lib().srx_collapse_topk(self.device.index or 0, desc, self.n_docs, self.doc_base, ptr(doc), ptr(score), ptr(count), nq, m, k,
+                                               int(per_group), policy, *[ptr(o) for o in outs], ptr(pos), ptr(size),
+                                               torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_collapse_topk")
+        return tuple(outs + [t for t in (pos, size) if t is not None])
+
+    def collapse(self, column: str, doc, score, count, k: int, per_group: int = 1, nulls: str = "own", want_pos: bool = False,
+                 want_group_size: bool = False):
+        """Host arrays in (the candidates validated by :func:`~.index.validate_candidates`), host arrays out:
+        :meth:`collapse_device` with one synchronisation and one copy back."""
+        from .index import validate_candidates
+        torch = _torch()
+        check_collapse_args(self.columns, column, per_group, nulls)
+        d = np.asarray(doc)
+        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
+        if d.shape[1] > _capi.SRX_COLLAPSE_MAX_M:
+            raise ValueError(f"collapse takes lists of at most {_capi.SRX_COLLAPSE_MAX_M} positions, got {d.shape[1]} (no silent truncation)")
+        s = np.ascontiguousarray(score, dtype=np.float32)
+        if s.shape != d.shape:
+            raise ValueError("score must have doc's shape")
+        cc = None if c is None else torch.as_tensor(c, device=self.device)
+        out = self.collapse_device(column, torch.as_tensor(d, device=self.device), torch.as_tensor(s, device=self.device), cc, k, per_group, nulls,
+                                   want_pos, want_group_size)
+        torch.cuda.synchronize(self.device)
+        return tuple(t.cpu().numpy() for t in out)

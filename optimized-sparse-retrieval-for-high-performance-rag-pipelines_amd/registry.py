@@ -47,19 +47,24 @@ class _SparseRetrieverBase(SparseIndexViews):
         self._be.upload(self.mode, self.k1, self.b)
 
     def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
-               must_not_terms=None, operators: bool = False, where=None) -> Dict[str, Dict[str, float]]:
+               must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None, per_group: int = 1,
+               collapse_nulls: str = "own", collapse_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """``allowed_docs`` / ``excluded_docs`` (no reference counterpart): as ``RetrievalService.search_bm25`` -- the top
         ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call.
         ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators``: term constraints, as ``RetrievalService.search_bm25``
         (rows built on the GPU from the posting lists, n_docs / 8 bytes per distinct constraint; scores unchanged; no cache).
-        ``where``: a field predicate over the columns of :meth:`set_doc_fields`, as ``RetrievalService.search_bm25``."""
+        ``where``: a field predicate over the columns of :meth:`set_doc_fields`, as ``RetrievalService.search_bm25``.
+        ``collapse_by`` / ``per_group`` / ``collapse_nulls`` / ``collapse_depth``: the top ``top_k`` of the ranking collapsed by a
+        column of :meth:`set_doc_fields`, exact, as ``RetrievalService.search_bm25`` (``top_k`` <= 1024; no cache)."""
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")
-        if spec is not None:
-            return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec)
+        collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search")
+        if spec is not None or collapse is not None:
+            return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
+                                         collapse=collapse)
         # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional
         return self._be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock,
                                      strip_key=self.strip_cache_key, blank="empty")

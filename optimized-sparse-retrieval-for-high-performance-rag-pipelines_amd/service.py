@@ -107,7 +107,8 @@ class RetrievalService(SparseIndexViews):
 
     # -- search -----------------------------------------------------------------------------------------
     def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None,
-                    any_terms=None, must_not_terms=None, operators: bool = False, where=None) -> Dict[str, Dict[str, float]]:
+                    any_terms=None, must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None,
+                    per_group: int = 1, collapse_nulls: str = "own", collapse_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
 
         ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
@@ -131,19 +132,32 @@ class RetrievalService(SparseIndexViews):
         ``qid -> group``; the clauses are :meth:`~.fields.FieldTable.filter`'s.  The rows are built on the GPU
         (``srx_filter_from_fields``, include/sparse_rx_fields.h) and restrict the doc set only.  It combines with the doc and the
         term keywords (doc filter, then term rows, then field rows) and behaves like them otherwise: no cache, a sharded index
-        refuses; without :meth:`set_doc_fields` it raises ``ValueError``."""
+        refuses; without :meth:`set_doc_fields` it raises ``ValueError``.
+
+        ``collapse_by`` (default None: nothing changes; no reference counterpart): the name of an int32 / int64 / category column
+        of :meth:`set_doc_fields` -- a parent document, an author, a source.  The result is then the top ``top_k`` of the
+        COLLAPSED complete ranking, exact: the ranking with every doc removed that has ``per_group`` better-ranked docs of its
+        group (``srx_collapse_topk``, include/sparse_rx_collapse.h).  The ranking is read in pages on the GPU
+        (:func:`~.backend.collapse_deep`: first ``min(max(4 * top_k, 64), 1024, n_docs)`` rows, then 1 024 at a time with
+        ``srx_search_after``) until every query has ``top_k`` groups or its ranking ends.  ``collapse_nulls``: a doc without a
+        value is a group of its "own" (default), all of them are "one" group, or they "drop" out.  ``collapse_depth`` (default
+        None: no limit) stops reading after that many rows of the ranking; a query may then return FEWER than ``top_k`` docs
+        although more groups exist further down -- that is not an error.  It works under the doc, term and field keywords (the
+        collapsed ranking of the allowed docs) and bypasses the query cache as they do.  ``ValueError``: ``top_k`` above
+        1 024, an unknown, float or set column, no :meth:`set_doc_fields`, a sharded index (columns are shard-local)."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
+        collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search_bm25")
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
             self._upload()  # k1 / b are plain attributes on the reference (:116-117): impacts depend on them
         # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on
-        if spec is not None:
-            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec)
+        if spec is not None or collapse is not None:
+            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse)
         return self._be.search_dicts(queries, top_k, order="term", cache=self.query_cache, lock=self.cache_lock, strip_key=True,
                                      blank="whitespace")
 
@@ -276,7 +290,9 @@ class RetrievalService(SparseIndexViews):
                       candidates: Optional[int] = None, rescore: bool = False, allowed_docs=None,
                       excluded_docs=None, mmr_lambda: Optional[float] = None, mmr_pool: Optional[int] = None,
                       mmr_similarity: str = "cosine", must_terms=None, any_terms=None, must_not_terms=None,
-                      operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None, where=None) -> Dict[str, Dict[str, float]]:
+                      operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None, where=None,
+                      collapse_by: Optional[str] = None, per_group: int = 1, collapse_nulls: str = "own",
+                      collapse_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -318,7 +334,17 @@ class RetrievalService(SparseIndexViews):
         values are MaxSim scores.  Works with ``rescore=True`` and the filter / term keywords; together with ``mmr_lambda`` it
         raises ``ValueError`` (chain :meth:`rerank_late` and :meth:`diversify` instead).
         ``where`` as in :meth:`search_bm25`: the field-built rows go to both sides like a doc filter's (``rescore=True``,
-        ``mmr_lambda`` and ``late_query_tokens`` included) and combine with the doc and the term keywords."""
+        ``mmr_lambda`` and ``late_query_tokens`` included) and combine with the doc and the term keywords.
+        ``collapse_by`` / ``per_group`` / ``collapse_nulls`` (default None: nothing changes) as in :meth:`search_bm25`: at most
+        ``per_group`` docs per value of the column.  The fused ranking is then taken ``collapse_pool`` deep (default
+        ``min(max(4 * top_k, 100), 1024, n_docs)``; more than 1024 raises ``ValueError``), ``candidates`` defaults to at least the
+        pool, and the pool is collapsed on the device (``srx_collapse_topk``) before the one copy back.  Unlike
+        :meth:`search_bm25`'s the result is POOL-RELATIVE, not the collapsed complete ranking: it is what
+        ``collapse(search_hybrid(top_k=collapse_pool, ...), collapse_by, top_k, ...)`` returns, and it can be SHORTER than
+        ``top_k`` when the pool holds fewer groups.  With ``late_query_tokens`` the order is fuse, rerank the whole ``late_pool``,
+        collapse to ``top_k`` (``collapse_pool`` is not used): ``collapse(rerank_late(search_hybrid(top_k=late_pool, ...), tokens,
+        late_pool), ...)``.  With ``mmr_lambda`` it is fuse ``collapse_pool`` deep, collapse to ``mmr_pool``, MMR to ``top_k``:
+        ``diversify(collapse(search_hybrid(top_k=collapse_pool, ...), collapse_by, mmr_pool, ...), top_k, ...)``."""
         if late_query_tokens is not None and mmr_lambda is not None:
             raise ValueError("late_query_tokens and mmr_lambda do not combine in one call: chain rerank_late() and diversify()")
         if operators:
@@ -345,6 +371,13 @@ class RetrievalService(SparseIndexViews):
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")
         self._ensure_dense()
+        collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, None, top_k, "search_hybrid")
+        cpool = None
+        if collapse is not None:
+            from .backend import collapse_pool_depth
+            cpool = late if late is not None else collapse_pool_depth(top_k, collapse_pool, self._be.n_docs_total)
+            if candidates is None:
+                cand = hybrid_depths(top_k, max(int(top_k), cpool, pool or 1, 1), self._be.n_docs_total)[1]
         results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
         live = [(qid, text) for qid, text in queries.items() if text and text.strip()]
         if k <= 0 or not live:
@@ -375,6 +408,10 @@ class RetrievalService(SparseIndexViews):
             import torch
             return self._dense.score_docs_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), cand_doc, cand_count)
 
+        def collapsed(f_doc, f_score, f_count, kk):  # a ranked triple still on the device -> its first kk survivors
+            return self._be.field_table().collapse_device(collapse.by, f_doc, f_score, f_count, min(kk, int(f_doc.shape[1])), collapse.per_group,
+                                                          collapse.nulls)
+
         if late is not None:
             import torch
             from .late import stack_query_tokens
@@ -382,21 +419,31 @@ class RetrievalService(SparseIndexViews):
             q_tok, q_cnt = stack_query_tokens(late_query_tokens, [qid for qid, _ in live], tokens.dim)
 
             def reranked(f_doc, f_score, f_count):  # the fused triple, pool deep, still on the device
-                return tokens.rerank_device(torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device),
-                                            f_doc, f_count, min(k, late))
+                q_t, q_c = torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device)
+                if collapse is None:
+                    return tokens.rerank_device(q_t, q_c, f_doc, f_count, min(k, late))
+                return collapsed(*tokens.rerank_device(q_t, q_c, f_doc, f_count, late), k)  # the whole pool reranked, then collapsed
 
             doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, late, fusion,
                                               (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=reranked, **flt)
-        elif pool is None:
+        elif pool is None and collapse is None:
             doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
                                               (sparse_weight, dense_weight), rrf_c, rescore, dense_score, **flt)
+        elif pool is None:
+            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, cpool, fusion,
+                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score,
+                                              post=lambda f_doc, f_score, f_count: collapsed(f_doc, f_score, f_count, k), **flt)
         else:
-            def diversified(f_doc, f_score, f_count):  # the fused triple, pool deep, still on the device
-                d, r, _, n = self._dense.mmr_device(f_doc, f_score, f_count, min(k, pool), mmr_lambda, mmr_similarity)
+            def diversified(f_doc, f_score, f_count):  # the fused triple, pool (or collapse_pool) deep, still on the device
+                kk = min(k, pool)
+                if collapse is not None:
+                    f_doc, f_score, f_count = collapsed(f_doc, f_score, f_count, pool)
+                    kk = min(k, int(f_doc.shape[1]))  # the collapsed pool has min(mmr_pool, collapse_pool) columns
+                d, r, _, n = self._dense.mmr_device(f_doc, f_score, f_count, kk, mmr_lambda, mmr_similarity)
                 return d, r, n
 
-            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, pool, fusion,
-                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=diversified, **flt)
+            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, pool if collapse is None else cpool,
+                                              fusion, (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=diversified, **flt)
         for i, (qid, _) in enumerate(live):
             results[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return results
@@ -462,6 +509,44 @@ class RetrievalService(SparseIndexViews):
         doc, score, _, count = self._dense.mmr(cand_doc, rel, cand_count, min(int(top_k), m), mmr_lambda, similarity)
         for i, (qid, _, _) in enumerate(live):
             out[qid] = {(doc_ids[int(doc[i, j])] if doc_ids is not None else str(int(doc[i, j]))): float(score[i, j]) for j in range(int(count[i]))}
+        return out
+
+    def collapse(self, results, by: str, top_k: int = 10, per_group: int = 1, nulls: str = "own"):
+        """Collapse ranked lists by a field (no reference counterpart: it does not group results): at most ``per_group`` docs per
+        value of the column ``by`` of :meth:`set_doc_fields`, over ``results`` = ``{qid: {doc_id: score}}`` as any search of this
+        service, :meth:`rerank_late` or :meth:`diversify` returns it (the dict order is the list order), on the GPU
+        (``srx_collapse_topk``, include/sparse_rx_collapse.h).  A value may also be :meth:`search_by_vector`'s list of
+        ``{"doc_id", "score"}`` dicts and comes back in that shape.  All lists of the call run as one batch.
+
+        Returns the first ``top_k`` survivors of every list in list order -- a subsequence, every value as it was given; the
+        scores are never looked at.  ``nulls``: a doc without a value is a group of its "own" (default), all of them are "one"
+        group, or they "drop" out.  The result is relative to the lists GIVEN: a deeper list can hold more groups
+        (:meth:`search_bm25`'s ``collapse_by=`` reads the ranking as deep as it takes).  ``{}`` stays ``{}``, ``top_k <= 0`` gives
+        an empty list per query.  ``ValueError``: an unknown doc id, a list longer than 2 048 docs (no silent truncation), an
+        unknown, float or set column, ``per_group`` < 1, no :meth:`set_doc_fields`, a sharded index."""
+        from . import _capi
+        from .fields import check_collapse_args
+        if self._be._fields is None:
+            raise ValueError("collapse(...) needs the docs' fields: call set_doc_fields() first")
+        check_collapse_args(self._be._fields, by, per_group, nulls)
+        if self._be.sharded():
+            raise ValueError("collapse needs the whole index on one GPU (the columns are shard-local)")
+        if not results:
+            return {}
+        as_rows = {qid: isinstance(row, (list, tuple)) for qid, row in results.items()}
+        lists = {qid: ([r["doc_id"] for r in row] if as_rows[qid] else list(row)) for qid, row in results.items()}
+        _, live, cand_doc, cand_count = self._be.candidate_block(results, lists)
+        m = int(cand_doc.shape[1])
+        if m > _capi.SRX_COLLAPSE_MAX_M:
+            raise ValueError(f"collapse takes lists of at most {_capi.SRX_COLLAPSE_MAX_M} docs, got one of {m} (no silent truncation)")
+        out = {qid: ([] if as_rows[qid] else {}) for qid in results}
+        if not live or int(top_k) <= 0:
+            return out
+        score = np.zeros(cand_doc.shape, dtype=np.float32)  # never looked at: the values come back by position
+        _, _, count, pos = self._be.field_table().collapse(by, cand_doc, score, cand_count, min(int(top_k), m), per_group, nulls, want_pos=True)
+        for i, (qid, _, cands) in enumerate(live):
+            kept = [int(pos[i, j]) for j in range(int(count[i]))]
+            out[qid] = [results[qid][p] for p in kept] if as_rows[qid] else {cands[p]: results[qid][cands[p]] for p in kept}
         return out
 
     # -- late interaction (no reference counterpart) -----------------------------------------------------------

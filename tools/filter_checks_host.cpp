@@ -1,13 +1,13 @@
-// The argument checks that the filter builders and srx_score_docs share, run on the host under AddressSanitizer and UBSan: every
+// The argument checks that the filter builders and srx_score_docs share, and those of srx_collapse_topk, run on the host under AddressSanitizer and UBSan: every
 // refusal below returns before anything touches a device, so the program needs no GPU.  Build and run from the repository root
 // (PKG = the package directory):
 //
-//   for u in filter terms fields score_docs; do
+//   for u in filter terms fields score_docs collapse; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -fPIC -Xarch_host -fsanitize=address,undefined \
 //           -Iinclude -I$PKG/csrc -c $PKG/csrc/$u.hip -o /tmp/fc_$u.o; done
 //   clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -Iinclude -c tools/filter_checks_host.cpp -o /tmp/fc_main.o
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/fc_main.o /tmp/fc_filter.o /tmp/fc_terms.o /tmp/fc_fields.o \
-//         /tmp/fc_score_docs.o -o /tmp/filter_checks_host && /tmp/filter_checks_host
+//         /tmp/fc_score_docs.o /tmp/fc_collapse.o -o /tmp/filter_checks_host && /tmp/filter_checks_host
 //
 // (clang++ is the one hipcc drives, <rocm>/llvm/bin/clang++: the two sanitizer runtimes must be the same.)
 //
@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "sparse_rx.h"
+#include "sparse_rx_collapse.h"
 #include "sparse_rx_fields.h"
 #include "sparse_rx_filter.h"
 #include "sparse_rx_terms.h"
@@ -118,6 +119,50 @@ int main() {
         // n_rows = 0 with everything else in order: nothing to do, no device touched
         ++n_seen;
         if (call(0, p, p, nullptr, nullptr, nullptr, nullptr, &base, out) != SRX_OK) ++n_bad, printf("BAD  %s: n_rows = 0 refused\n", who);
+    }
+    // srx_collapse_topk: its checks are its own
+    {
+        float *fs = reinterpret_cast<float *>(mem);
+        int32_t *o = mem;
+        auto call = [&](const srx_field_col *c, int64_t n_docs, int64_t doc_base, const int32_t *cd, const float *cs, int32_t nq, int32_t m, int32_t k,
+                        int32_t per_group, int32_t policy, int32_t *od, float *os, int32_t *oc) {
+            return srx_collapse_topk(0, c, n_docs, doc_base, cd, cs, nullptr, nq, m, k, per_group, policy, od, os, oc, nullptr, nullptr, nullptr);
+        };
+        const char *who = "srx_collapse_topk";
+        char msg[256];
+        auto said = [&](const char *what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return msg; };
+        srx_field_col c64 = {mem, reinterpret_cast<const uint32_t *>(mem), SRX_FIELD_I64}, b = c64;
+        expect(call(nullptr, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("null col"));
+        b.type = SRX_FIELD_F32;
+        expect(call(&b, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("the column must be SRX_FIELD_I32 or SRX_FIELD_I64 (F32 and SET64 columns are no group keys)"));
+        b.type = SRX_FIELD_SET64;
+        expect(call(&b, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("the column must be SRX_FIELD_I32 or SRX_FIELD_I64 (F32 and SET64 columns are no group keys)"));
+        b = c64, b.data = nullptr;
+        expect(call(&b, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("a column with null data"));
+        b = c64, b.data = mem + 1;
+        expect(call(&b, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("column data must be aligned for its type"));
+        b = c64, b.valid = odd;
+        expect(call(&b, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("a validity row must be 16-byte aligned"));
+        expect(call(&c64, 0, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("n_docs must be in [1, 2^31 - 2]"));
+        expect(call(&c64, 0x7FFFFFFFll, 0, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("n_docs must be in [1, 2^31 - 2]"));
+        expect(call(&c64, 1000, -1, p, fs, 1, 8, 4, 1, 0, o, fs, o), said("negative doc_base"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 0, 1, 1, 0, o, fs, o), said("m must be in [1, 2048]"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 2049, 1, 1, 0, o, fs, o), said("m must be in [1, 2048]"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 0, 1, 0, o, fs, o), said("k must be in [1, m]"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 9, 1, 0, o, fs, o), said("k must be in [1, m]"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 4, 0, 0, o, fs, o), said("per_group must be >= 1"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 4, 1, 3, o, fs, o), said("unknown null_policy"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 4, 1, -1, o, fs, o), said("unknown null_policy"));
+        expect(call(&c64, 1000, 0, p, fs, -1, 8, 4, 1, 0, o, fs, o), said("nq < 0"));
+        expect(call(&c64, 1000, 0, p, fs, 1 << 20, 2048, 4, 1, 0, o, fs, o), said("nq * m must not exceed 2^31 - 1"));
+        expect(call(&c64, 1000, 0, nullptr, fs, 1, 8, 4, 1, 0, o, fs, o), said("null cand_doc / cand_score"));
+        expect(call(&c64, 1000, 0, p, nullptr, 1, 8, 4, 1, 0, o, fs, o), said("null cand_doc / cand_score"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 4, 1, 0, nullptr, fs, o), said("null out_doc / out_score / out_count"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, nullptr, o), said("null out_doc / out_score / out_count"));
+        expect(call(&c64, 1000, 0, p, fs, 1, 8, 4, 1, 0, o, fs, nullptr), said("null out_doc / out_score / out_count"));
+        // nq = 0 with everything else in order: nothing to do, no device touched
+        ++n_seen;
+        if (call(&c64, 1000, 0, nullptr, nullptr, 0, 2048, 2048, 0x7FFFFFFF, 2, nullptr, nullptr, nullptr) != SRX_OK) ++n_bad, printf("BAD  %s: nq = 0 refused\n", who);
     }
     if (n_bad) {
         printf("%d of %d checks differ\n", n_bad, n_seen);
