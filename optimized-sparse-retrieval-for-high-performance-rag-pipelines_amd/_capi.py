@@ -1,6 +1,7 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
-include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h and include/sparse_rx_collapse.h).
+include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h and
+include/sparse_rx_facets.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -19,7 +20,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -191,6 +192,21 @@ COLLAPSE_SYMBOLS = {
 SRX_COLLAPSE_NULL_OWN, SRX_COLLAPSE_NULL_ONE, SRX_COLLAPSE_NULL_DROP = 0, 1, 2    # what a doc without a key is
 SRX_COLLAPSE_MAX_M = 2048                                                         # positions per list (pinned to the header by tests/test_collapse_cpu.py)
 
+
+class FacetBins(ctypes.Structure):
+    """``srx_facet_bins`` (include/sparse_rx_facets.h): a host struct; ``edges`` is a device pointer"""
+    _fields_ = [("mode", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("origin", ctypes.c_int64), ("edges", ctypes.c_void_p)]
+
+
+# every symbol include/sparse_rx_facets.h declares (the eleventh header of the same library)
+_CP, _BP = ctypes.POINTER(FieldColDesc), ctypes.POINTER(FacetBins)
+FACET_SYMBOLS = {
+    "srx_facet_counts": (ctypes.c_int, [_I32, _CP, _I64, _BP, _FP, _I32, _VP, _VP, _VP]),
+    "srx_facet_counts_lists": (ctypes.c_int, [_I32, _CP, _I64, _I64, _BP, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
+}
+SRX_FACET_CODES, SRX_FACET_LABELS, SRX_FACET_EDGES = 0, 1, 2                      # srx_facet_bins.mode
+SRX_FACET_MAX_BINS = 8192                                                         # bins per facet (pinned to the header by tests/test_facets_cpu.py)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -220,7 +236,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_terms.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_maxsim.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_fields.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_collapse.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_collapse.h"),
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_facets.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -269,7 +286,7 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
-                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS}.items():
+                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

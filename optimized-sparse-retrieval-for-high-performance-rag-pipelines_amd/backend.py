@@ -248,6 +248,107 @@ class SparseBackend:
                             page=_capi.SRX_MAX_K, max_depth=collapse.depth)
         return _to_host(torch, dev.device, out)
 
+    def facet_specs(self, fields, call: str = "facets"):
+        """``fields`` of a facet door -- one name, a sequence of names, or a dict name -> binning spec (None: the column's own
+        bins) -- as ``{name: fields.FacetSpec}`` (:func:`~.fields.check_facet_args`).  ValueError: no :meth:`set_fields` (the
+        message names ``call``), a sharded index, no field, an unknown field, a spec that does not fit."""
+        from .fields import check_facet_args
+        if self._fields is None:
+            raise ValueError(f"{call}(...) needs the docs' fields: call set_doc_fields() first")
+        if self.sharded():
+            raise ValueError(f"{call} needs the whole index on one GPU (the columns and the filter rows are shard-local)")
+        if isinstance(fields, str):
+            fields = [fields]
+        given = dict(fields) if isinstance(fields, dict) else {name: None for name in (fields or ())}
+        if not given:
+            raise ValueError(f"{call} needs at least one field")
+        return {name: check_facet_args(self._fields, name, spec) for name, spec in given.items()}
+
+    def facets(self, queries, fields, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None,
+               where=None, top=None, call: str = "facets"):
+        """Facet counts per query (``srx_facet_counts``, include/sparse_rx_facets.h): ``{qid: {field: {"counts": {value: n},
+        "missing": n, "other": n, "total": n}}}`` over each query's doc set.  The set is built as one row per distinct
+        constraint with the :meth:`filter_spec` chain (doc keywords, then term rows, then field rows); ``match`` adds the query's
+        own text to it: "any" -- the docs that hold at least one of its known terms (the text joins the ``any`` list; giving
+        ``any_terms`` too is a ValueError), "all" -- the docs that hold every term (the text joins the ``must`` list), None --
+        the text is ignored.  Under "any" / "all" a text without a token has the empty set.  One ``facet_device`` per field over
+        the same rows, one copy back.  ``top``: keep the ``top`` largest bins of every field (:func:`facet_dict`)."""
+        specs = self.facet_specs(fields, call)
+        if match not in ("any", "all", None):
+            raise ValueError(f"match must be \"any\", \"all\" or None, got {match!r}")
+        if match == "any" and any_terms is not None:
+            raise ValueError(f"{call}: match=\"any\" puts the query's own terms into the any list; give match=None (or \"all\") with "
+                             "any_terms=, or match=\"any\" without it")
+        if top is not None and int(top) < 1:
+            raise ValueError(f"top must be >= 1, got {top}")
+        if self.host is None or self.dev is None:
+            raise ValueError(f"{call} needs the sparse index: build it first")
+        empty = {qid for qid, text in queries.items() if match is not None and not (isinstance(text, str) and tokenize(text))}
+        live = {qid: text for qid, text in queries.items() if qid not in empty}
+        out = {qid: {name: facet_dict(fs, None, (0, 0, 0), top) for name, fs in specs.items()} for qid in queries}
+        if not live:
+            return out
+        if match is not None:
+            given = must_terms if match == "all" else None
+            if isinstance(given, (str, bytes)):
+                raise ValueError("must_terms must be a sequence of strings or a dict qid -> sequence, not one string")
+            own = {qid: (list(given.get(qid, ())) if isinstance(given, dict) else list(given or ())) + [text] for qid, text in live.items()}
+            if match == "all":
+                must_terms = own
+            else:
+                any_terms = own
+        spec = self.filter_spec(live, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
+        import torch
+        table = self.field_table()
+        if spec is None:
+            flt, rows, row_of = None, [0], {qid: 0 for qid in live}
+        else:
+            flt = spec.on_device(self.dev)
+            rows = sorted({spec.row_of_qid[qid] for qid in live})
+            row_of = {qid: rows.index(spec.row_of_qid[qid]) for qid in live}
+        qf = None if flt is None else torch.as_tensor(np.asarray(rows, dtype=np.int32), device=table.device)
+        parts = []
+        for name, fs in specs.items():
+            parts.extend(table.facet_device(name, fs, filter=flt, q_filter=qf, n_rows=len(rows)))
+        block = torch.cat(parts, dim=1).cpu().numpy()  # the one copy back
+        at = 0
+        for name, fs in specs.items():
+            counts, extra = block[:, at: at + fs.n_bins], block[:, at + fs.n_bins: at + fs.n_bins + 3]
+            at += fs.n_bins + 3
+            for qid in live:
+                out[qid][name] = facet_dict(fs, counts[row_of[qid]], extra[row_of[qid]], top)
+        return out
+
+    def facets_of(self, results, fields, top=None, call: str = "facets_of"):
+        """Facet counts over the docs of result lists (``srx_facet_counts_lists``): ``results`` = ``{qid: {doc_id: score}}`` as any
+        search returns it (or ``search_by_vector``'s lists of ``{"doc_id", "score"}`` dicts) -> the dict of :meth:`facets`.  One
+        upload of the lists, one launch per field, one copy back.  ValueError: an unknown doc id, and what :meth:`facet_specs`
+        refuses."""
+        specs = self.facet_specs(fields, call)
+        if top is not None and int(top) < 1:
+            raise ValueError(f"top must be >= 1, got {top}")
+        out = {qid: {name: facet_dict(fs, None, (0, 0, 0), top) for name, fs in specs.items()} for qid in (results or {})}
+        if not results:
+            return out
+        lists = {qid: ([r["doc_id"] for r in row] if isinstance(row, (list, tuple)) else list(row)) for qid, row in results.items()}
+        _, live, cand_doc, cand_count = self.candidate_block(results, lists)
+        if not live:
+            return out
+        import torch
+        table = self.field_table()
+        doc = torch.as_tensor(cand_doc + np.int32(self.doc_base), device=table.device)
+        cnt = torch.as_tensor(cand_count, device=table.device)
+        parts = []
+        for name, fs in specs.items():
+            parts.extend(table.facet_lists_device(name, doc, cnt, fs))
+        block = torch.cat(parts, dim=1).cpu().numpy()
+        at = 0
+        for name, fs in specs.items():
+            for i, (qid, _, _) in enumerate(live):
+                out[qid][name] = facet_dict(fs, block[i, at: at + fs.n_bins], block[i, at + fs.n_bins: at + fs.n_bins + 3], top)
+            at += fs.n_bins + 3
+        return out
+
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
                      blank: str = "empty", filter: Optional["DocFilterSpec"] = None, collapse: Optional["CollapseSpec"] = None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
@@ -416,6 +517,18 @@ def collapse_deep(search_fn, collapse_fn, q_ptr, q_term, q_weight, k: int, first
         kd, ks, kc = collapsed(torch.cat([kd, d], dim=1).contiguous(), torch.cat([ks, s], dim=1).contiguous(), None)
         active = active & (kc < k) & (c == kk)
     return kd, ks, kc
+
+
+def facet_dict(spec, counts, extra, top=None) -> dict:
+    """One row of a facet call decoded: ``{"counts": {value: n, ...}, "missing": n, "other": n, "total": n}``.  ``spec``: the
+    :class:`~.fields.FacetSpec` (``values[i]`` = what bin i stands for: a category string, a label, an int, a ``(lo, hi)`` pair of
+    the caller's edges); ``counts``: the row's n_bins numbers, or None for a row that was not counted; ``extra``: (missing, other,
+    total).  Only bins with a count above 0 are listed, by count descending, then by bin ascending, cut to ``top``."""
+    listed = {}
+    if counts is not None:
+        order = sorted((i for i in range(spec.n_bins) if int(counts[i]) > 0), key=lambda i: (-int(counts[i]), i))
+        listed = {spec.values[i]: int(counts[i]) for i in (order if top is None else order[: int(top)])}
+    return {"counts": listed, "missing": int(extra[0]), "other": int(extra[1]), "total": int(extra[2])}
 
 
 class RowOfIds:

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from .filter import BASE_NAMES, DocFilter, build_rows, filter_words, host_q_filter, pack_masks
+from .filter import BASE_NAMES, DocFilter, build_rows, filter_words, host_q_filter, pack_masks, q_filter_to_device
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -458,6 +458,93 @@ def check_collapse_args(columns, column, per_group, nulls) -> int:
     return NULL_POLICIES[nulls]
 
 
+class FacetSpec:
+    """A binning spec resolved against one column (:func:`check_facet_args`): ``mode`` (SRX_FACET_*), ``n_bins``, ``origin`` (CODES),
+    ``edges`` (EDGES: int64[n_bins + 1] as the device compares them -- exact bounds of the column's type, a float32's bits in the
+    low 32 --, else None) and ``values`` = what bin i stands for in a result: a category string, a label, False / True, an int, or
+    the ``(lo, hi)`` pair of the caller's own edges."""
+
+    def __init__(self, mode: int, n_bins: int, origin: int = 0, edges: Optional[np.ndarray] = None, values=None):
+        self.mode, self.n_bins, self.origin, self.edges, self.values = mode, n_bins, origin, edges, values
+
+
+def _resolve_edges(column: str, kind: str, edges):
+    """The caller's edges e_0 <= .. <= e_n as the int64 entries the device compares with, so that bin j holds exactly the column
+    values >= e_j and < e_(j+1) in exact arithmetic: the smallest value of the column's type that is >= e_j."""
+    if isinstance(edges, (str, bytes)) or not hasattr(edges, "__iter__"):
+        raise ValueError(f"edges for {column!r} must be a sequence of at least two numbers")
+    given = [_number(e, f"an edge for {column!r}") for e in edges]
+    if len(given) < 2:
+        raise ValueError(f"edges for {column!r} must be a sequence of at least two numbers (n + 1 edges make n bins)")
+    if len(given) - 1 > _capi.SRX_FACET_MAX_BINS:
+        raise ValueError(f"{len(given) - 1} bins for {column!r}: a facet takes at most {_capi.SRX_FACET_MAX_BINS}")
+    if any(isinstance(e, float) and math.isnan(e) for e in given):
+        raise ValueError(f"edges for {column!r} hold a NaN")
+    if any(b < a for a, b in zip(given, given[1:])):
+        raise ValueError(f"edges for {column!r} must ascend")
+    out = np.zeros(len(given), dtype=np.int64)
+    for j, e in enumerate(given):
+        if kind == "float32":
+            out[j] = f32_bits(f32_at_least(e))
+        else:
+            c = _int_ceil(e)
+            if c > I64_MAX:
+                if kind == "int64":
+                    raise ValueError(f"the edge {e!r} for {column!r} lies above the int64 range: no int64 entry stands for it (leave the last bin to "
+                                     f"end at {I64_MAX} and read the rest from \"other\")")
+                c = I64_MAX  # above every int32 value either way
+            out[j] = max(c, I64_MIN)
+    return out, [(a, b) for a, b in zip(given, given[1:])]
+
+
+def check_facet_args(columns, column, spec=None) -> FacetSpec:
+    """What every facet door checks before anything is launched: ``column`` names a column of ``columns`` (name ->
+    :class:`HostColumn`) and ``spec`` fits its kind.
+
+      * category: no spec -- one bin per dictionary entry (SRX_FACET_CODES, origin 0); more than 8 192 entries raise ValueError;
+      * bool: no spec -- the bins False and True;
+      * set: no spec -- one bin per label (SRX_FACET_LABELS);
+      * int32 / int64: ``{"origin": o, "bins": n}`` -- the bins o, o + 1, .., o + n - 1 (SRX_FACET_CODES) -- or ``{"edges": [...]}``;
+      * float32: ``{"edges": [e_0, .., e_n]}`` -- bin j is [e_j, e_(j+1)) (SRX_FACET_EDGES), compared exactly: an edge that is no
+        value of the column's type is rounded up to the next one (:func:`f32_at_least`, ``ceil``).
+
+    ValueError: an unknown column, a spec that does not fit, edges that do not ascend or hold a NaN, more than 8 192 bins."""
+    if column not in columns:
+        raise ValueError(f"unknown field {column!r}")
+    col = columns[column]
+    kind = col.kind
+    if kind in ("category", "bool", "set"):
+        if spec is not None:
+            raise ValueError(f"{column!r} is a {kind} column: its bins are its {'labels' if kind == 'set' else 'values'}, it takes no spec")
+        if kind == "set":
+            if not (1 <= len(col.dictionary) <= 64):
+                raise ValueError(f"{column!r} has {len(col.dictionary)} labels: a set facet takes 1 to 64")
+            return FacetSpec(_capi.SRX_FACET_LABELS, len(col.dictionary), values=list(col.dictionary))
+        if kind == "bool":
+            return FacetSpec(_capi.SRX_FACET_CODES, 2, 0, values=[False, True])
+        if not (1 <= len(col.dictionary) <= _capi.SRX_FACET_MAX_BINS):
+            raise ValueError(f"{column!r} has {len(col.dictionary)} distinct values: a facet takes at most {_capi.SRX_FACET_MAX_BINS} bins (a column "
+                             "with more is a key to collapse by)")
+        return FacetSpec(_capi.SRX_FACET_CODES, len(col.dictionary), 0, values=list(col.dictionary))
+    if not isinstance(spec, dict) or not (set(spec) == {"edges"} or set(spec) == {"origin", "bins"}):
+        raise ValueError(f"{column!r} is a {kind} column: give {{\"edges\": [...]}}" + ("" if kind == "float32" else " or {\"origin\": o, \"bins\": n}"))
+    if "edges" in spec:
+        edges, pairs = _resolve_edges(column, kind, spec["edges"])
+        return FacetSpec(_capi.SRX_FACET_EDGES, len(pairs), edges=edges, values=pairs)
+    if kind == "float32":
+        raise ValueError(f"{column!r} is a float32 column: give {{\"edges\": [...]}} (a float is no bin number)")
+    o, n = spec["origin"], spec["bins"]
+    for x, what in ((o, "origin"), (n, "bins")):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise ValueError(f"{what} for {column!r} must be an integer, got {x!r}")
+    o, n = int(o), int(n)
+    if not (I64_MIN <= o <= I64_MAX):
+        raise ValueError(f"origin for {column!r} lies outside int64")
+    if not (1 <= n <= _capi.SRX_FACET_MAX_BINS):
+        raise ValueError(f"{n} bins for {column!r}: a facet takes 1 to {_capi.SRX_FACET_MAX_BINS}")
+    return FacetSpec(_capi.SRX_FACET_CODES, n, o, values=[o + i for i in range(n)])
+
+
 class FieldTable:
     """Typed metadata columns of ``n_docs`` docs, resident on ``device``; row i of every column belongs to the doc with the GLOBAL
     id ``doc_base + i``.  ``columns`` name -> :class:`HostColumn` (kind, dictionary; its arrays are dropped after the upload)."""
@@ -654,3 +741,111 @@ class FieldTable:
                                    want_pos, want_group_size)
         torch.cuda.synchronize(self.device)
         return tuple(t.cpu().numpy() for t in out)
+
+    # -- facet counts over filter rows and result lists (include/sparse_rx_facets.h) -------------------------------------------
+    def _facet_call(self, column: str, spec):
+        """(the resolved :class:`FacetSpec`, the column descriptor, the ``srx_facet_bins`` struct, what must stay alive)"""
+        torch = _torch()
+        fs = spec if isinstance(spec, FacetSpec) else check_facet_args(self.columns, column, spec)
+        if column not in self.columns:
+            raise ValueError(f"unknown field {column!r}")
+        if column not in self._tensors:
+            raise ValueError("the table is closed")
+        desc = self._col_descs([column])
+        edges = None if fs.edges is None else torch.as_tensor(fs.edges, device=self.device)
+        bins = _capi.FacetBins(mode=fs.mode, n_bins=fs.n_bins, origin=fs.origin, edges=None if edges is None else edges.data_ptr())
+        return fs, desc, bins, edges
+
+    def facet_device(self, column: str, spec=None, filter=None, q_filter=None, n_rows=None):
+        """``srx_facet_counts``: how the docs of filter rows distribute over ``column``.  ``spec`` as :func:`check_facet_args` takes
+        it (or its result); ``filter``: a :class:`~.filter.DocFilter` over this table's docs, or None = every doc; ``q_filter``: an
+        int32 device tensor [n_rows], the filter row of every output row (-1: every doc), or None.  ``n_rows`` defaults to the
+        filter's row count with ``q_filter`` = 0, 1, .. when neither is given, to ``q_filter``'s length when it is, and to 1 without
+        a filter.  Returns device tensors ``(counts i32[n_rows, n_bins], extra i32[n_rows, 3])``, extra = (missing, other, total)
+        per row; asynchronous on the current stream."""
+        import ctypes
+        torch = _torch()
+        fs, desc, bins, edges = self._facet_call(column, spec)
+        if filter is None:
+            if q_filter is not None:
+                raise ValueError("q_filter picks rows of a filter: it needs filter=")
+            n_rows = 1 if n_rows is None else int(n_rows)
+        else:
+            if not isinstance(filter, DocFilter):
+                raise ValueError("filter must be a DocFilter")
+            filter.for_index(self)
+            if n_rows is None:
+                n_rows = filter.n_filters if q_filter is None else int(q_filter.numel())
+            n_rows = int(n_rows)
+            if q_filter is None:
+                if n_rows > 1 or filter.n_filters > 1:  # row r of the output is row r of the filter
+                    if n_rows > filter.n_filters:
+                        raise ValueError(f"n_rows = {n_rows} exceeds the filter's {filter.n_filters} rows: give q_filter")
+                    q_filter = torch.arange(n_rows, dtype=torch.int32, device=self.device)
+        if n_rows < 0:
+            raise ValueError("n_rows must be >= 0")
+        fdesc, keep = (None, None) if filter is None else filter.launch_args(q_filter, n_rows)
+        with torch.cuda.device(self.device):
+            counts = torch.empty((n_rows, fs.n_bins), dtype=torch.int32, device=self.device)
+            extra = torch.empty((n_rows, 3), dtype=torch.int32, device=self.device)
+            rc = _capi.lib().srx_facet_counts(self.device.index or 0, desc, self.n_docs, ctypes.byref(bins), fdesc, n_rows,
+                                              counts.data_ptr() if n_rows else None, extra.data_ptr() if n_rows else None,
+                                              torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_facet_counts")
+        del keep, edges
+        return counts, extra
+
+    def facet_lists_device(self, column: str, doc, count, spec=None):
+        """``srx_facet_counts_lists``: how the docs of result lists distribute over ``column``.  ``doc`` i32[nq, m] GLOBAL ids and
+        ``count`` i32[nq] or None: the lists of any search as they are (a position at or past the count, or with an id outside the
+        table, is skipped; a doc listed twice counts twice).  Returns ``(counts i32[nq, n_bins], extra i32[nq, 3])`` on the device;
+        asynchronous on the current stream."""
+        import ctypes
+        torch = _torch()
+        fs, desc, bins, edges = self._facet_call(column, spec)
+        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32 or int(doc.shape[1]) < 1:
+            raise ValueError("facet_lists_device: doc must be an int32 tensor [nq, m >= 1]")
+        nq, m = int(doc.shape[0]), int(doc.shape[1])
+        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
+            raise ValueError("facet_lists_device: count must be an int32 tensor [nq]")
+        for t, what in ((doc, "doc"), (count, "count")):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"facet_lists_device: {what} is on {t.device}, the table on {self.device}")
+        with torch.cuda.device(self.device):
+            doc = doc.contiguous()
+            count = None if count is None else count.contiguous()
+            counts = torch.empty((nq, fs.n_bins), dtype=torch.int32, device=self.device)
+            extra = torch.empty((nq, 3), dtype=torch.int32, device=self.device)
+            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = _capi.lib().srx_facet_counts_lists(self.device.index or 0, desc, self.n_docs, self.doc_base, ctypes.byref(bins), ptr(doc), ptr(count),
+                                                    nq, m, ptr(counts), ptr(extra), torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_facet_counts_lists")
+        del edges
+        return counts, extra
+
+    def facet(self, column: str, spec=None, filter=None, q_filter=None, n_rows=None):
+        """:meth:`facet_device` with a host ``q_filter`` (validated: integers in [-1, n_filters)) and host arrays back: one
+        synchronisation, one copy."""
+        torch = _torch()
+        qf = None
+        if q_filter is not None:
+            if not isinstance(filter, DocFilter):
+                raise ValueError("q_filter picks rows of a filter: it needs filter=")
+            q = np.asarray(q_filter)
+            qf = q_filter_to_device(filter, q, int(q.shape[0]) if q.ndim == 1 else -1)
+        counts, extra = self.facet_device(column, spec, filter, qf, n_rows)
+        both = torch.cat([counts, extra], dim=1).cpu().numpy()
+        return both[:, : counts.shape[1]], both[:, counts.shape[1]:]
+
+    def facet_lists(self, column: str, doc, count=None, spec=None):
+        """:meth:`facet_lists_device` from host arrays (the candidates validated by :func:`~.index.validate_candidates`), host arrays
+        back: one synchronisation, one copy."""
+        from .index import validate_candidates
+        torch = _torch()
+        fs = spec if isinstance(spec, FacetSpec) else check_facet_args(self.columns, column, spec)
+        d = np.asarray(doc)
+        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
+        cc = None if c is None else torch.as_tensor(c, device=self.device)
+        counts, extra = self.facet_lists_device(column, torch.as_tensor(d, device=self.device), cc, fs)
+        both = torch.cat([counts, extra], dim=1).cpu().numpy()
+        return both[:, : counts.shape[1]], both[:, counts.shape[1]:]

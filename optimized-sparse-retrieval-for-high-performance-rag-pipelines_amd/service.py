@@ -549,6 +549,37 @@ class RetrievalService(SparseIndexViews):
             out[qid] = [results[qid][p] for p in kept] if as_rows[qid] else {cands[p]: results[qid][cands[p]] for p in kept}
         return out
 
+    def facets(self, queries: Dict[str, str], fields, *, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
+               must_not_terms=None, operators: bool = False, where=None, top: Optional[int] = None):
+        """Facet counts (no reference counterpart: it does not aggregate results): how the docs of each query's doc set distribute
+        over metadata columns of :meth:`set_doc_fields`, counted on the GPU (``srx_facet_counts``, include/sparse_rx_facets.h).
+        ``fields``: one name, a sequence of names, or a dict name -> binning spec (:func:`~.fields.check_facet_args`: a category,
+        bool or set column takes none; an int column ``{"origin": o, "bins": n}`` or ``{"edges": [...]}``; a float32 column
+        ``{"edges": [...]}``).  Returns ``{qid: {field: {"counts": {value: n, ...}, "missing": n, "other": n, "total": n}}}``: only
+        bins with a count above 0, by count descending, then by bin ascending, cut to ``top``; a value is a category string, a
+        label, False / True, an int, or the ``(lo, hi)`` pair of the caller's own edges; ``missing`` = docs without a value,
+        ``other`` = docs whose value lies in no bin, ``total`` = docs of the set.
+
+        The doc set: the doc, term and field keywords as in the searches, chained; and ``match`` for the query's own text --
+        ``"any"`` (default): the docs that contain at least one known term of the text.  That is the query's candidate set BY
+        TERMS, a superset of the docs the search returns under its ``score > 0`` rule.  The terms join the ``any`` list: giving
+        ``any_terms=`` as well raises ``ValueError``.  ``"all"``: the docs that contain every term (they join the ``must`` list; an
+        unknown word empties the set).  ``None``: the text is ignored.  Under "any" / "all" a text without a token has the empty
+        set.  ``ValueError``: no :meth:`set_doc_fields`, an unknown field, a spec that does not fit its column, a sharded index."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        if operators:
+            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
+        return self._be.facets(queries, fields, match, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, top, "facets")
+
+    def facets_of(self, results, fields, top: Optional[int] = None):
+        """Facet counts over the docs of result lists: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object,
+        a reranker or ``collapse`` returns it -> the dict of :meth:`facets` (``srx_facet_counts_lists``: every listed doc counts,
+        whatever its score).  ``ValueError``: an unknown doc id, no :meth:`set_doc_fields`, an unknown field, a sharded index."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        return self._be.facets_of(results, fields, top, "facets_of")
+
     # -- late interaction (no reference counterpart) -----------------------------------------------------------
     def set_token_embeddings(self, token_embeddings, storage: str = "f16") -> None:
         """Put the TOKEN vectors of the docs on the GPU for :meth:`rerank_late` (:class:`~.late.TokenIndex`; rounded to
