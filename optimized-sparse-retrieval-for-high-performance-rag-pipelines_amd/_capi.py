@@ -1,7 +1,7 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
-include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h and
-include/sparse_rx_facets.h).
+include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
+include/sparse_rx_facets.h and include/ext/sparse_rx_feedback.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -207,6 +207,32 @@ FACET_SYMBOLS = {
 SRX_FACET_CODES, SRX_FACET_LABELS, SRX_FACET_EDGES = 0, 1, 2                      # srx_facet_bins.mode
 SRX_FACET_MAX_BINS = 8192                                                         # bins per facet (pinned to the header by tests/test_facets_cpu.py)
 
+
+
+class ForwardDesc(ctypes.Structure):
+    """``srx_forward_desc`` (include/ext/sparse_rx_feedback.h): a host struct of device pointers"""
+    _fields_ = [("device", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_docs", ctypes.c_int64), ("vocab", ctypes.c_int64),
+                ("doc_base", ctypes.c_int64), ("row_ptr", ctypes.c_void_p), ("term", ctypes.c_void_p), ("value", ctypes.c_void_p),
+                ("doc_len", ctypes.c_void_p)]
+
+
+class FeedbackParams(ctypes.Structure):
+    """``srx_feedback_params`` (include/ext/sparse_rx_feedback.h): a host struct"""
+    _fields_ = [("fb_docs", ctypes.c_int32), ("row_cap", ctypes.c_int32), ("n_terms", ctypes.c_int32), ("doc_weight", ctypes.c_int32),
+                ("term_weight", ctypes.c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float)]
+
+
+# every symbol include/ext/sparse_rx_feedback.h declares (the twelfth header of the same library)
+FEEDBACK_SYMBOLS = {
+    "srx_feedback_workspace_bytes": (_I64, [_I32]),
+    "srx_feedback_expand": (ctypes.c_int, [ctypes.POINTER(ForwardDesc), ctypes.POINTER(FeedbackParams), _VP, _VP, _VP, _VP, _I32, _I64, _VP, _VP, _VP,
+                                           _I32, _VP, _VP, _VP, _I64, _VP, _VP, _I64, _VP]),
+}
+SRX_FB_BY_SCORE, SRX_FB_UNIFORM = 0, 1                                            # srx_feedback_params.doc_weight
+SRX_FB_RM, SRX_FB_RAW = 0, 1                                                      # srx_feedback_params.term_weight
+SRX_FEEDBACK_MAX_DOCS, SRX_FEEDBACK_MAX_ENTRIES = 32, 4096                        # pinned to the header by tests/test_feedback_cpu.py
+SRX_FEEDBACK_MAX_TERMS, SRX_FEEDBACK_MAX_QTERMS = 128, 128
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -237,7 +263,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_maxsim.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_fields.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_collapse.h"),
-                                                            os.path.join(INCLUDE_DIR, "sparse_rx_facets.h")]
+                                                            os.path.join(INCLUDE_DIR, "sparse_rx_facets.h"),
+                                                            os.path.join(INCLUDE_DIR, "ext", "sparse_rx_feedback.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -286,7 +313,7 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
-                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS}.items():
+                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -51,6 +51,10 @@ class SparseBackend:
         self._fields = None        # set_fields: the docs' metadata columns on the host (fields.HostColumn by name) ...
         self._field_table = None   # ... and on the device, uploaded by the first call that filters with them
         self._rows = None          # _row_table
+        self._forward = None       # enable_feedback: the doc-major forward index (feedback.ForwardIndex) and its term gains
+        self._fb_gain = None
+        self._fb_term_weight = "rm"
+        self._words = None         # expand_queries: term id -> word
 
     def world(self) -> int:
         try:
@@ -349,8 +353,179 @@ class SparseBackend:
             at += fs.n_bins + 3
         return out
 
+    # -- relevance feedback (include/ext/sparse_rx_feedback.h) ----------------------------------------------------------------
+    def enable_feedback(self, mode: str = "bm25") -> None:
+        """Build the doc-major forward index (:class:`~.feedback.ForwardIndex`: 8 bytes per posting + 12 per doc) from the host
+        CSR, on the device of the index.  ``mode`` "bm25": rows hold tf, contributions are tf / doc_len (RM) and a term's gain is
+        ``max(idf, 0)`` -- a term with a non-positive idf is never an expansion term; "dot": raw values and a gain of 1.
+        :meth:`upload` and :meth:`close` drop it.  ValueError: no index, a sharded index."""
+        from .feedback import ForwardIndex
+        if self.host is None or self.dev is None:
+            raise ValueError("enable_feedback() needs the sparse index: build it first")
+        if self.sharded():
+            raise ValueError("relevance feedback needs the whole index on one GPU (a forward index is shard-local, a query's feedback docs are not)")
+        self._drop_forward()
+        import torch
+        h = self.host
+        self._forward = ForwardIndex.from_csr(h.indptr, h.indices, h.data, h.idf, doc_lengths=h.doc_lengths if mode == "bm25" else None,
+                                              device=self.dev.device, doc_base=self.doc_base)
+        self._fb_gain = torch.clamp(torch.as_tensor(np.ascontiguousarray(h.idf, dtype=np.float32), device=self.dev.device), min=0.0) if mode == "bm25" else None
+        self._fb_term_weight = "rm" if mode == "bm25" else "raw"
+
+    def _drop_forward(self) -> None:
+        if self._forward is not None:
+            self._forward.close()
+        self._forward = self._fb_gain = None
+
+    def _need_forward(self, call: str, what: str):
+        if self.sharded():
+            raise ValueError(f"{call}({what}) needs the whole index on one GPU (a sharded index has no forward index)")
+        if self._forward is None:
+            raise ValueError(f"{call}({what}) needs the forward index: call enable_feedback() first")
+        return self._forward
+
+    def expand_spec(self, expand_docs, expand_terms=10, expand_weight=0.5, expand_by="score", call: str = "search") -> Optional["ExpandSpec"]:
+        """The expansion keywords of one API call as an :class:`ExpandSpec`, or None when ``expand_docs`` is None (the other three
+        are then not looked at).  ValueError: what :func:`~.feedback.check_expand_args` refuses, a sharded index, no
+        :meth:`enable_feedback`."""
+        if expand_docs is None:
+            return None
+        from .feedback import check_expand_args
+        spec = ExpandSpec(*check_expand_args(expand_docs, expand_terms, expand_weight, expand_by))
+        self._need_forward(call, "expand_docs=...")
+        return spec
+
+    def _search_expanded(self, batch, k: int, filter=None, q_filter=None, collapse=None):
+        """The second pass: an expanded batch still on the device -> host rows.  k <= 1024: nothing is copied back in between;
+        deeper: the batch goes to the host once and takes the paged route of :meth:`~.index.DeviceIndex.search`."""
+        import torch
+        from . import _capi
+        from .filter import q_filter_to_device
+        from .index import _to_host
+        e_ptr, e_term, e_weight, _ = batch
+        dev = self.dev
+        nq = e_ptr.numel() - 1
+        if k > _capi.SRX_MAX_K:
+            p = e_ptr.cpu().numpy()
+            n = int(p[-1])
+            return dev.search(p, e_term[:n].cpu().numpy(), e_weight[:n].cpu().numpy(), k, filter=filter, q_filter=q_filter)
+        flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
+        if collapse is None:
+            return _to_host(torch, dev.device, dev.search_device(e_ptr, e_term, e_weight, k, **flt))
+        table = self.field_table()
+        first = min(max(4 * k, 64), _capi.SRX_MAX_K, self.n_docs_total)
+        out = collapse_deep(lambda qp, qt, qw, kk, after=None: dev.search_device(qp, qt, qw, kk, after=after, **flt),
+                            lambda d, s, c, kk: table.collapse_device(collapse.by, d, s, c, kk, collapse.per_group, collapse.nulls),
+                            e_ptr, e_term, e_weight, k, first, page=_capi.SRX_MAX_K, max_depth=collapse.depth)
+        return _to_host(torch, dev.device, out)
+
+    def expanded_search_arrays(self, q_ptr, q_term, q_weight, k: int, expand: "ExpandSpec", filter=None, q_filter=None, collapse=None):
+        """Host CSR batch -> host rows (doc, score, count) of the search of the EXPANDED batch: a first pass ``expand.docs`` deep
+        (under ``filter`` / ``q_filter``, never collapsed), ``srx_feedback_expand`` with alpha = 1 - weight, beta = weight and
+        row_cap = min(max_row_terms, 4096 // expand.docs), then the existing search of the expanded batch at ``k`` under the same
+        filter, collapsed when ``collapse`` is given.  The lists of the first pass and the expanded batch stay on the device."""
+        import torch
+        from .filter import q_filter_to_device
+        from .index import _batch_to_device, validate_query_batch
+        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
+        nq = len(q_ptr) - 1
+        if nq == 0:
+            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
+        dev, fwd = self.dev, self._forward
+        flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
+        qp, qt, qw = _batch_to_device(torch, q_ptr, q_term, q_weight, dev.device)
+        d, s, c = dev.search_device(qp, qt, qw, min(expand.docs, self.n_docs_total), **flt)
+        batch = fwd.expand_device(qp, qt, qw, d, s, c, fb_docs=expand.docs, n_terms=expand.terms, alpha=1.0 - expand.weight, beta=expand.weight,
+                                  doc_weight=expand.by, term_weight=self._fb_term_weight, term_gain=self._fb_gain)
+        return self._search_expanded(batch, k, filter, q_filter, collapse)
+
+    def _seed_block(self, lists, call: str, what: str):
+        """{qid: sequence of doc ids} -> (qids, doc i32[nq, m] GLOBAL row ids padded with -1, count i32[nq]); at most 32 per qid"""
+        from . import _capi
+        row_of = self._row_table().row_of
+        qids, rows = list(lists), []
+        for qid in qids:
+            ids = lists[qid]
+            if isinstance(ids, (str, bytes)):
+                raise ValueError(f"{what}[{qid!r}] must be a sequence of doc ids, not one string")
+            try:
+                rows.append([row_of[d] + self.doc_base for d in ids])
+            except KeyError as e:
+                raise ValueError(f"unknown doc id {e.args[0]!r} among the {what} of {qid!r}") from None
+            if len(rows[-1]) > _capi.SRX_FEEDBACK_MAX_DOCS:
+                raise ValueError(f"{call} takes at most {_capi.SRX_FEEDBACK_MAX_DOCS} {what} per query, got {len(rows[-1])} for {qid!r} (no silent truncation)")
+        m = max((len(r) for r in rows), default=1) or 1
+        doc = np.full((len(rows), m), -1, dtype=np.int32)
+        for i, r in enumerate(rows):
+            doc[i, : len(r)] = r
+        return qids, doc, np.asarray([len(r) for r in rows], dtype=np.int32)
+
+    def more_like_this(self, seeds, top_k: int = 10, terms: int = 25, include_seeds: bool = False, allowed_docs=None, excluded_docs=None,
+                       must_terms=None, any_terms=None, must_not_terms=None, where=None, call: str = "more_like_this"):
+        """``{qid: [doc_id, ...]}`` -> ``{qid: {doc_id: score}}``: the docs most like each query's seed docs.  The query is built
+        on the GPU from the seeds alone -- empty input queries, the seeds as UNIFORM feedback docs, beta = 1: the ``terms`` terms
+        that characterise them best, weights summing to 1 -- and searched with the seeds denied per query (``excluded_docs``
+        machinery) unless ``include_seeds``.  The filter keywords are those of the searches.  ValueError: no
+        :meth:`enable_feedback`, a sharded index, an unknown doc id, more than 32 seeds, ``terms`` outside 1..128."""
+        import torch
+        from .feedback import check_expand_args
+        check_expand_args(1, terms, 1.0, "uniform")
+        fwd = self._need_forward(call, "...")
+        if isinstance(seeds, (str, bytes)) or not isinstance(seeds, dict):
+            raise ValueError("seeds must be a dict qid -> sequence of doc ids")
+        qids, doc, count = self._seed_block(seeds, call, "seeds")
+        queries = {qid: "" for qid in qids}
+        if not include_seeds:
+            allowed_docs, excluded_docs = _without_seeds(seeds, qids, allowed_docs, excluded_docs)
+        spec = self.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
+        out = {qid: {} for qid in qids}
+        k_eff = min(int(top_k), self.n_docs_total)
+        if not qids or k_eff <= 0:
+            return out
+        dev = self.dev
+        nq = len(qids)
+        qp = torch.zeros(nq + 1, dtype=torch.int32, device=dev.device)
+        qt, qw = torch.empty(0, dtype=torch.int32, device=dev.device), torch.empty(0, dtype=torch.float32, device=dev.device)
+        batch = fwd.expand_device(qp, qt, qw, torch.as_tensor(doc, device=dev.device), None, torch.as_tensor(count, device=dev.device),
+                                  fb_docs=max(1, int(doc.shape[1])), n_terms=int(terms), alpha=0.0, beta=1.0, doc_weight="uniform",
+                                  term_weight=self._fb_term_weight, term_gain=self._fb_gain)
+        rows = None if spec is None else np.asarray([spec.row_of_qid[qid] for qid in qids], dtype=np.int32)
+        docs, scores, counts = self._search_expanded(batch, k_eff, None if spec is None else spec.on_device(dev), rows)
+        for i, qid in enumerate(qids):
+            c = int(counts[i])
+            out[qid] = self.to_dict(docs[i, :c].astype(np.int64), scores[i, :c])
+        return out
+
+    def expand_queries(self, queries, results, expand_terms=10, expand_weight=0.5, expand_by="score", order: str = "term", call: str = "expand_queries"):
+        """What the queries are expanded to: ``queries`` {qid: text}, ``results`` {qid: {doc_id: score}} as a search returned
+        them (the feedback docs, in dict order, at most 32 per query) -> ``{qid: {word: weight}}`` in ascending term id, the
+        batch ``search(..., expand_docs=len(results[qid]))`` searches in its second pass.  A qid without results gets its
+        normalised query."""
+        from .feedback import check_expand_args
+        _, n_terms, weight, by = check_expand_args(1, expand_terms, expand_weight, expand_by)
+        fwd = self._need_forward(call, "...")
+        lists = {qid: list((results or {}).get(qid, {}) or {}) for qid in queries}
+        qids, doc, count = self._seed_block(lists, call, "results")
+        if not qids:
+            return {}
+        score = np.zeros(doc.shape, dtype=np.float32)
+        for i, qid in enumerate(qids):
+            score[i, : count[i]] = [results[qid][d] for d in lists[qid]]
+        q_ptr, q_term, q_weight = encode_queries([queries[qid] or "" for qid in qids], self.host.vocabulary, order=order)
+        e_ptr, e_term, e_weight, _ = fwd.expand(q_ptr, q_term, q_weight, doc, score, count, fb_docs=max(1, int(doc.shape[1])), n_terms=n_terms,
+                                                alpha=1.0 - weight, beta=weight, doc_weight=by, term_weight=self._fb_term_weight,
+                                                term_gain=None if self._fb_gain is None else self._fb_gain.cpu().numpy())
+        if self._words is None or self._words[0] is not self.host.vocabulary:
+            words = [None] * self.host.vocab_size
+            for w, t in self.host.vocabulary.items():
+                words[t] = w
+            self._words = (self.host.vocabulary, words)
+        words = self._words[1]
+        return {qid: {words[int(t)]: float(w) for t, w in zip(e_term[e_ptr[i]: e_ptr[i + 1]], e_weight[e_ptr[i]: e_ptr[i + 1]])} for i, qid in enumerate(qids)}
+
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
-                     blank: str = "empty", filter: Optional["DocFilterSpec"] = None, collapse: Optional["CollapseSpec"] = None):
+                     blank: str = "empty", filter: Optional["DocFilterSpec"] = None, collapse: Optional["CollapseSpec"] = None,
+                     expand: Optional["ExpandSpec"] = None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
         in the caller's order, one batched search for all texts the cache does not hold (equal texts share one row).  What
         the call sites of the reference do differently is named here:
@@ -373,8 +548,11 @@ class SparseBackend:
         under the same filter row.
 
         ``collapse`` (:meth:`collapse_spec`): every row is the top ``top_k`` of the COLLAPSED complete ranking
-        (:meth:`collapsed_search_arrays`), under ``filter`` when given; such a call bypasses the cache as a filtered one does."""
-        if filter is not None or collapse is not None:
+        (:meth:`collapsed_search_arrays`), under ``filter`` when given; such a call bypasses the cache as a filtered one does.
+
+        ``expand`` (:meth:`expand_spec`): every row is the search of the query EXPANDED from its own first results
+        (:meth:`expanded_search_arrays`), under ``filter`` and ``collapse`` when given; such a call bypasses the cache too."""
+        if filter is not None or collapse is not None or expand is not None:
             cache = None
         k_eff = min(int(top_k), self.n_docs_total)  # any depth: search_arrays pages past the engine's 1024-row lists
         results: Dict[str, Dict[str, float]] = {}
@@ -406,7 +584,12 @@ class SparseBackend:
             pending[key].append(qid)
         if texts and k_eff > 0:
             q_ptr, q_term, q_weight = encode_queries(texts, self.host.vocabulary, order=order)
-            if collapse is not None:
+            if expand is not None:
+                docs, scores, counts = self.expanded_search_arrays(q_ptr, q_term, q_weight, k_eff, expand,
+                                                                   filter=None if filter is None else filter.on_device(self.dev),
+                                                                   q_filter=None if filter is None else np.asarray(frows, dtype=np.int32),
+                                                                   collapse=collapse)
+            elif collapse is not None:
                 docs, scores, counts = self.collapsed_search_arrays(q_ptr, q_term, q_weight, k_eff, collapse,
                                                                     filter=None if filter is None else filter.on_device(self.dev),
                                                                     q_filter=None if filter is None else np.asarray(frows, dtype=np.int32))
@@ -447,6 +630,7 @@ class SparseBackend:
 
     def close(self) -> None:
         self._drop_field_table()
+        self._drop_forward()
         if self.dev is not None:
             self.dev.close()
             self.dev = None
@@ -459,6 +643,29 @@ class CollapseSpec:
 
     def __init__(self, by: str, per_group: int = 1, nulls: str = "own", depth: Optional[int] = None):
         self.by, self.per_group, self.nulls, self.depth = by, per_group, nulls, depth
+
+
+def _without_seeds(seeds, qids, allowed_docs, excluded_docs):
+    """The two doc keywords of ``more_like_this`` with every qid's seeds denied: an allow list loses the seeds, otherwise the seeds
+    join the exclude list (per qid; a sequence counts for every qid).  An ``allowed_docs`` dict must name every qid: a qid it
+    leaves out could lose its seeds through an exclude list only, and the two keywords do not combine."""
+    for what, given in (("allowed_docs", allowed_docs), ("excluded_docs", excluded_docs)):
+        if isinstance(given, (str, bytes)):
+            raise ValueError(f"{what} must be a sequence of doc ids or a dict qid -> sequence, not one string")
+    of = lambda given, qid: list(given.get(qid, ())) if isinstance(given, dict) else list(given)
+    if allowed_docs is None:
+        return None, {qid: list(seeds[qid]) + ([] if excluded_docs is None else of(excluded_docs, qid)) for qid in qids}
+    if isinstance(allowed_docs, dict) and any(qid not in allowed_docs for qid in qids):
+        raise ValueError("more_like_this: an allowed_docs dict must name every qid (or pass include_seeds=True)")
+    return {qid: [d for d in of(allowed_docs, qid) if d not in set(seeds[qid])] for qid in qids}, excluded_docs
+
+
+class ExpandSpec:
+    """The expansion keywords of one API call, checked (:meth:`SparseBackend.expand_spec`): ``docs`` = feedback docs per query,
+    ``terms`` = expansion terms, ``weight`` = the feedback model's share of the expanded query, ``by`` = "score" or "uniform"."""
+
+    def __init__(self, docs: int, terms: int = 10, weight: float = 0.5, by: str = "score"):
+        self.docs, self.terms, self.weight, self.by = docs, terms, weight, by
 
 
 def collapse_pool_depth(top_k: int, collapse_pool, n_docs: int) -> int:

@@ -17,7 +17,7 @@ import hashlib
 import threading
 import time
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -48,20 +48,30 @@ class _SparseRetrieverBase(SparseIndexViews):
 
     def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
                must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None, per_group: int = 1,
-               collapse_nulls: str = "own", collapse_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+               collapse_nulls: str = "own", collapse_depth: Optional[int] = None, expand_docs: Optional[int] = None, expand_terms: int = 10,
+               expand_weight: float = 0.5, expand_by: str = "score") -> Dict[str, Dict[str, float]]:
         """``allowed_docs`` / ``excluded_docs`` (no reference counterpart): as ``RetrievalService.search_bm25`` -- the top
         ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call.
         ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators``: term constraints, as ``RetrievalService.search_bm25``
         (rows built on the GPU from the posting lists, n_docs / 8 bytes per distinct constraint; scores unchanged; no cache).
         ``where``: a field predicate over the columns of :meth:`set_doc_fields`, as ``RetrievalService.search_bm25``.
         ``collapse_by`` / ``per_group`` / ``collapse_nulls`` / ``collapse_depth``: the top ``top_k`` of the ranking collapsed by a
-        column of :meth:`set_doc_fields`, exact, as ``RetrievalService.search_bm25`` (``top_k`` <= 1024; no cache)."""
+        column of :meth:`set_doc_fields`, exact, as ``RetrievalService.search_bm25`` (``top_k`` <= 1024; no cache).
+        ``expand_docs`` / ``expand_terms`` / ``expand_weight`` / ``expand_by``: pseudo-relevance feedback as
+        ``RetrievalService.search_bm25`` (needs :meth:`enable_feedback`; no cache): the search of the query expanded on the GPU from
+        its own first ``expand_docs`` results.  In dot mode a contribution is the doc's raw value and every term's gain is 1
+        (Rocchio-style); in BM25 mode tf / doc_len and max(idf, 0).  The scores are those of the expanded query, whose weights
+        sum to at most 1: not comparable to the scores of a plain search."""
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search")
+        expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search")
+        if expand is not None:
+            return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
+                                         collapse=collapse, expand=expand)
         if spec is not None or collapse is not None:
             return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
                                          collapse=collapse)
@@ -75,6 +85,36 @@ class _SparseRetrieverBase(SparseIndexViews):
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         self._be.set_fields(columns)
+
+    def enable_feedback(self) -> None:
+        """Opt in to relevance feedback (no reference counterpart): build the doc-major forward index of the corpus on the GPU
+        (:class:`~.feedback.ForwardIndex`, include/ext/sparse_rx_feedback.h: 8 bytes per posting and 12 per doc next to the
+        index) for ``expand_docs=``, :meth:`more_like_this` and :meth:`expand_queries`.  A rebuilt or re-uploaded index and
+        :meth:`close` drop it.  ``ValueError``: no index, a sharded index."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        self._be.enable_feedback(self.mode)
+
+    def more_like_this(self, seeds: Dict[str, Sequence[str]], top_k: int = 10, terms: int = 25, include_seeds: bool = False, *, allowed_docs=None,
+                       excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> Dict[str, Dict[str, float]]:
+        """More like these docs (Lucene's ``more_like_this``; no reference counterpart): ``seeds`` = ``{qid: [doc_id, ...]}``, at
+        most 32 per query -> ``{qid: {doc_id: score}}``.  The query is built on the GPU from the seeds alone: the ``terms`` terms
+        that characterise them best (``srx_feedback_expand`` with empty queries, the seeds as uniformly weighted feedback docs,
+        beta = 1), weights summing to 1; it is searched with the seeds themselves denied per query unless ``include_seeds``.  The
+        filter keywords are those of the searches.  ``ValueError``: no :meth:`enable_feedback`, a sharded index, an unknown doc
+        id, more than 32 seeds, ``terms`` outside 1..128."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        return self._be.more_like_this(seeds, top_k, terms, include_seeds, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where)
+
+    def expand_queries(self, queries: Dict[str, str], results: Dict[str, Dict[str, float]], *, expand_terms: int = 10, expand_weight: float = 0.5,
+                       expand_by: str = "score") -> Dict[str, Dict[str, float]]:
+        """What queries are expanded to: ``results`` = ``{qid: {doc_id: score}}`` as a search returned them are the feedback docs
+        (dict order, at most 32 per query) -> ``{qid: {word: weight}}`` in ascending term id: the batch the second pass of
+        ``expand_docs=len(results[qid])`` searches.  ``ValueError`` as :meth:`more_like_this`."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        return self._be.expand_queries(queries, results, expand_terms, expand_weight, expand_by, order=self.term_order)
 
     def facets(self, queries: Dict[str, str], fields, *, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
                must_not_terms=None, operators: bool = False, where=None, top: Optional[int] = None):

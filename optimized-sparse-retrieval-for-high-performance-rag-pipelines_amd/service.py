@@ -108,7 +108,8 @@ class RetrievalService(SparseIndexViews):
     # -- search -----------------------------------------------------------------------------------------
     def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None,
                     any_terms=None, must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None,
-                    per_group: int = 1, collapse_nulls: str = "own", collapse_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+                    per_group: int = 1, collapse_nulls: str = "own", collapse_depth: Optional[int] = None, expand_docs: Optional[int] = None,
+                    expand_terms: int = 10, expand_weight: float = 0.5, expand_by: str = "score") -> Dict[str, Dict[str, float]]:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
 
         ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
@@ -144,17 +145,32 @@ class RetrievalService(SparseIndexViews):
         None: no limit) stops reading after that many rows of the ranking; a query may then return FEWER than ``top_k`` docs
         although more groups exist further down -- that is not an error.  It works under the doc, term and field keywords (the
         collapsed ranking of the allowed docs) and bypasses the query cache as they do.  ``ValueError``: ``top_k`` above
-        1 024, an unknown, float or set column, no :meth:`set_doc_fields`, a sharded index (columns are shard-local)."""
+        1 024, an unknown, float or set column, no :meth:`set_doc_fields`, a sharded index (columns are shard-local).
+
+        ``expand_docs`` (default None: nothing changes; no reference counterpart): pseudo-relevance feedback, RM3.  With
+        ``expand_docs=R`` (1..32; needs :meth:`enable_feedback`) the query is first searched ``R`` deep under the call's doc, term
+        and field keywords (never collapsed); the query is then rebuilt on the GPU from its own terms and the ``expand_terms``
+        (1..128) terms its ``R`` docs characterise best (``srx_feedback_expand``, include/ext/sparse_rx_feedback.h: alpha =
+        1 - ``expand_weight``, beta = ``expand_weight`` in [0, 1], docs weighted by ``expand_by`` "score" or "uniform"), and the
+        result is the existing search of that expanded query at ``top_k`` under the same keywords, ``collapse_by`` included.
+        Nothing is copied back between the two passes for ``top_k`` <= 1 024.  The scores are those of the EXPANDED query, whose
+        weights sum to at most 1: they are NOT comparable to plain BM25 scores.  Such a call bypasses the query cache.
+        ``ValueError``: no :meth:`enable_feedback`, a sharded index, a keyword out of range."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search_bm25")
+        expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search_bm25")
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
             self._upload()  # k1 / b are plain attributes on the reference (:116-117): impacts depend on them
+            if expand is not None:
+                self._be.enable_feedback("bm25")  # the upload dropped the forward index; its rows do not depend on k1 / b
+        if expand is not None:
+            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse, expand=expand)
         # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on
         if spec is not None or collapse is not None:
             return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse)
@@ -173,6 +189,37 @@ class RetrievalService(SparseIndexViews):
         if (self.k1, self.b) != self._built_k1b:
             self._upload()
         return self._be.score_dicts(queries, candidates, order="term")
+
+    # -- relevance feedback (no reference counterpart) --------------------------------------------------------
+    def enable_feedback(self) -> None:
+        """Opt in to relevance feedback (no reference counterpart): build the doc-major forward index of the corpus on the GPU
+        (:class:`~.feedback.ForwardIndex`, include/ext/sparse_rx_feedback.h: 8 bytes per posting and 12 per doc next to the
+        index) for ``expand_docs=``, :meth:`more_like_this` and :meth:`expand_queries`.  A rebuilt or re-uploaded index and
+        :meth:`close` drop it.  ``ValueError``: no index, a sharded index."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        self._be.enable_feedback("bm25")
+
+    def more_like_this(self, seeds: Dict[str, Sequence[str]], top_k: int = 10, terms: int = 25, include_seeds: bool = False, *, allowed_docs=None,
+                       excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> Dict[str, Dict[str, float]]:
+        """More like these docs (Lucene's ``more_like_this``; no reference counterpart): ``seeds`` = ``{qid: [doc_id, ...]}``, at
+        most 32 per query -> ``{qid: {doc_id: score}}``.  The query is built on the GPU from the seeds alone: the ``terms`` terms
+        that characterise them best (``srx_feedback_expand`` with empty queries, the seeds as uniformly weighted feedback docs,
+        beta = 1), weights summing to 1; it is searched with the seeds themselves denied per query unless ``include_seeds``.  The
+        filter keywords are those of the searches.  ``ValueError``: no :meth:`enable_feedback`, a sharded index, an unknown doc
+        id, more than 32 seeds, ``terms`` outside 1..128."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        return self._be.more_like_this(seeds, top_k, terms, include_seeds, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where)
+
+    def expand_queries(self, queries: Dict[str, str], results: Dict[str, Dict[str, float]], *, expand_terms: int = 10, expand_weight: float = 0.5,
+                       expand_by: str = "score") -> Dict[str, Dict[str, float]]:
+        """What queries are expanded to: ``results`` = ``{qid: {doc_id: score}}`` as a search returned them are the feedback docs
+        (dict order, at most 32 per query) -> ``{qid: {word: weight}}`` in ascending term id: the batch the second pass of
+        ``expand_docs=len(results[qid])`` searches.  ``ValueError`` as :meth:`more_like_this`."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        return self._be.expand_queries(queries, results, expand_terms, expand_weight, expand_by)
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
