@@ -1,7 +1,7 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
-include/sparse_rx_facets.h and include/ext/sparse_rx_feedback.h).
+include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h and include/order/sparse_rx_order.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -233,6 +233,25 @@ SRX_FB_RM, SRX_FB_RAW = 0, 1                                                    
 SRX_FEEDBACK_MAX_DOCS, SRX_FEEDBACK_MAX_ENTRIES = 32, 4096                        # pinned to the header by tests/test_feedback_cpu.py
 SRX_FEEDBACK_MAX_TERMS, SRX_FEEDBACK_MAX_QTERMS = 128, 128
 
+# every symbol include/order/sparse_rx_order.h declares (the thirteenth header of the same library)
+ORDER_SYMBOLS = {
+    "srx_order_workspace_bytes": (_I64, [_I64, _I32, _I32]),
+    "srx_order_topk": (ctypes.c_int, [_I32, _CP, _I64, _I64, _I32, _I32, _FP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "srx_order_lists": (ctypes.c_int, [_I32, _CP, _I64, _I64, _I32, _I32, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+}
+SRX_ORDER_ASC, SRX_ORDER_DESC = 0, 1                                              # order
+SRX_ORDER_NULLS_LAST, SRX_ORDER_NULLS_FIRST, SRX_ORDER_NULLS_DROP = 0, 1, 2       # where the docs without a value go
+SRX_ORDER_MAX_M = 2048                                                            # positions per list (pinned to the header by tests/test_order_cpu.py)
+SRX_ORDER_MIN_SEG, SRX_ORDER_CHUNK = 32768, 8192                                  # the scan's segment rule (order_plan)
+
+
+def order_plan(n_docs: int, n_rows: int, k: int):
+    """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
+    ``srx_order_workspace_bytes`` by tests/test_order_cpu.py).  A segment is what one workgroup scans for one row."""
+    seg_docs = -(-max(SRX_ORDER_MIN_SEG, 64 * int(k)) // SRX_ORDER_CHUNK) * SRX_ORDER_CHUNK
+    segments = -(-int(n_docs) // seg_docs)
+    return segments, int(n_rows) * segments * (12 * int(k) + 8)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -264,7 +283,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_fields.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_collapse.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_facets.h"),
-                                                            os.path.join(INCLUDE_DIR, "ext", "sparse_rx_feedback.h")]
+                                                            os.path.join(INCLUDE_DIR, "ext", "sparse_rx_feedback.h"),
+                                                            os.path.join(INCLUDE_DIR, "order", "sparse_rx_order.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -313,7 +333,8 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
-                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS}.items():
+                                   **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
+                                   **ORDER_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -268,30 +268,21 @@ class SparseBackend:
             raise ValueError(f"{call} needs at least one field")
         return {name: check_facet_args(self._fields, name, spec) for name, spec in given.items()}
 
-    def facets(self, queries, fields, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None,
-               where=None, top=None, call: str = "facets"):
-        """Facet counts per query (``srx_facet_counts``, include/sparse_rx_facets.h): ``{qid: {field: {"counts": {value: n},
-        "missing": n, "other": n, "total": n}}}`` over each query's doc set.  The set is built as one row per distinct
-        constraint with the :meth:`filter_spec` chain (doc keywords, then term rows, then field rows); ``match`` adds the query's
-        own text to it: "any" -- the docs that hold at least one of its known terms (the text joins the ``any`` list; giving
-        ``any_terms`` too is a ValueError), "all" -- the docs that hold every term (the text joins the ``must`` list), None --
-        the text is ignored.  Under "any" / "all" a text without a token has the empty set.  One ``facet_device`` per field over
-        the same rows, one copy back.  ``top``: keep the ``top`` largest bins of every field (:func:`facet_dict`)."""
-        specs = self.facet_specs(fields, call)
-        if match not in ("any", "all", None):
-            raise ValueError(f"match must be \"any\", \"all\" or None, got {match!r}")
-        if match == "any" and any_terms is not None:
-            raise ValueError(f"{call}: match=\"any\" puts the query's own terms into the any list; give match=None (or \"all\") with "
-                             "any_terms=, or match=\"any\" without it")
-        if top is not None and int(top) < 1:
-            raise ValueError(f"top must be >= 1, got {top}")
+    def match_rows(self, queries, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None,
+                   where=None, call: str = "facets"):
+        """The doc sets of :meth:`facets` and :meth:`search_sorted` as filter rows: ``(live, filter, rows, row_of)`` -- ``live`` the
+        queries that have a set at all (under match "any" / "all" a text without a token has none), ``filter`` the
+        :class:`~.filter.DocFilter` of the :meth:`filter_spec` chain with the query's own text joined to its ``any`` ("any") or
+        ``must`` ("all") list, or None when nothing constrains a query (every doc), ``rows`` the distinct filter rows in use and
+        ``row_of`` qid -> its place in ``rows``.  ValueError: a bad ``match``, match="any" with ``any_terms=``, no index, and what
+        :meth:`filter_spec` refuses."""
+        check_match(match, any_terms, call)
         if self.host is None or self.dev is None:
             raise ValueError(f"{call} needs the sparse index: build it first")
         empty = {qid for qid, text in queries.items() if match is not None and not (isinstance(text, str) and tokenize(text))}
         live = {qid: text for qid, text in queries.items() if qid not in empty}
-        out = {qid: {name: facet_dict(fs, None, (0, 0, 0), top) for name, fs in specs.items()} for qid in queries}
         if not live:
-            return out
+            return live, None, [0], {}
         if match is not None:
             given = must_terms if match == "all" else None
             if isinstance(given, (str, bytes)):
@@ -302,14 +293,31 @@ class SparseBackend:
             else:
                 any_terms = own
         spec = self.filter_spec(live, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
+        if spec is None:
+            return live, None, [0], {qid: 0 for qid in live}
+        flt = spec.on_device(self.dev)
+        rows = sorted({spec.row_of_qid[qid] for qid in live})
+        return live, flt, rows, {qid: rows.index(spec.row_of_qid[qid]) for qid in live}
+
+    def facets(self, queries, fields, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None,
+               where=None, top=None, call: str = "facets"):
+        """Facet counts per query (``srx_facet_counts``, include/sparse_rx_facets.h): ``{qid: {field: {"counts": {value: n},
+        "missing": n, "other": n, "total": n}}}`` over each query's doc set.  The set is built as one row per distinct
+        constraint with the :meth:`filter_spec` chain (doc keywords, then term rows, then field rows); ``match`` adds the query's
+        own text to it: "any" -- the docs that hold at least one of its known terms (the text joins the ``any`` list; giving
+        ``any_terms`` too is a ValueError), "all" -- the docs that hold every term (the text joins the ``must`` list), None --
+        the text is ignored.  Under "any" / "all" a text without a token has the empty set.  One ``facet_device`` per field over
+        the same rows, one copy back.  ``top``: keep the ``top`` largest bins of every field (:func:`facet_dict`)."""
+        specs = self.facet_specs(fields, call)
+        check_match(match, any_terms, call)  # before `top`, as ever: the ValueError of a call with two bad keywords stays the same
+        if top is not None and int(top) < 1:
+            raise ValueError(f"top must be >= 1, got {top}")
+        out = {qid: {name: facet_dict(fs, None, (0, 0, 0), top) for name, fs in specs.items()} for qid in queries}
+        live, flt, rows, row_of = self.match_rows(queries, match, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
+        if not live:
+            return out
         import torch
         table = self.field_table()
-        if spec is None:
-            flt, rows, row_of = None, [0], {qid: 0 for qid in live}
-        else:
-            flt = spec.on_device(self.dev)
-            rows = sorted({spec.row_of_qid[qid] for qid in live})
-            row_of = {qid: rows.index(spec.row_of_qid[qid]) for qid in live}
         qf = None if flt is None else torch.as_tensor(np.asarray(rows, dtype=np.int32), device=table.device)
         parts = []
         for name, fs in specs.items():
@@ -351,6 +359,99 @@ class SparseBackend:
             for i, (qid, _, _) in enumerate(live):
                 out[qid][name] = facet_dict(fs, block[i, at: at + fs.n_bins], block[i, at + fs.n_bins: at + fs.n_bins + 3], top)
             at += fs.n_bins + 3
+        return out
+
+    # -- order by a field (include/order/sparse_rx_order.h) -------------------------------------------------------------------
+    def _order_column(self, by, order, nulls, call: str):
+        """The column ``by`` of :meth:`set_fields` for an ordering door; ValueError: no fields (the message names ``call``), a sharded
+        index, and what :func:`~.fields.check_order_args` refuses."""
+        from .fields import check_order_args
+        if self._fields is None:
+            raise ValueError(f"{call}(...) needs the docs' fields: call set_doc_fields() first")
+        if self.sharded():
+            raise ValueError(f"{call} needs the whole index on one GPU (the columns and the filter rows are shard-local)")
+        check_order_args(self._fields, by, order, nulls)
+        return self._fields[by]
+
+    def search_sorted(self, queries, by, order="desc", top_k=10, match="any", nulls="last", allowed_docs=None, excluded_docs=None, must_terms=None,
+                      any_terms=None, must_not_terms=None, where=None, call: str = "search_sorted"):
+        """The first ``top_k`` docs of each query's doc set in the order of the field ``by`` instead of relevance
+        (``srx_order_topk``, include/order/sparse_rx_order.h): ``{qid: {doc_id: value}}`` in rank order.  The doc set is the one of
+        :meth:`facets` (:meth:`match_rows`: the same ``match`` and filter keywords; under "any" / "all" a text without a token gives
+        ``{}``).  ``order`` "asc" / "desc"; docs with equal values come in corpus order (ascending row), in both directions.
+        ``nulls``: docs without a value come "last", "first", or "drop" out.  The value is a Python int (int32 / int64), bool, float
+        (float32), the dictionary string of a category column (ordered as strings: its codes are the places in the sorted
+        dictionary) or None for a doc without one.  ``top_k`` above 1024 pages with the cursor until ``top_k`` docs or the set is
+        exhausted.  ValueError: no :meth:`set_fields`, a sharded index, an unknown or set column, a bad keyword."""
+        from . import _capi
+        from .fields import order_has_value, order_values
+        col = self._order_column(by, order, nulls, call)
+        top_k = int(top_k)
+        if top_k < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        out = {qid: {} for qid in queries}
+        live, flt, rows, row_of = self.match_rows(queries, match, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
+        if not live:
+            return out
+        import torch
+        table = self.field_table()
+        qf = None if flt is None else torch.as_tensor(np.asarray(rows, dtype=np.int32), device=table.device)
+        ids, base = self.host.doc_ids, self.doc_base
+        got = [[] for _ in rows]  # per row: (doc row, value) in rank order
+        open_rows, after = list(range(len(rows))), None
+        while open_rows:  # one page of at most 1024 per round, for the rows that may go on
+            k = min(top_k - min(len(got[r]) for r in open_rows), _capi.SRX_MAX_K)
+            sel = None if qf is None else qf[torch.as_tensor(open_rows, device=table.device)]
+            doc, key, extra = table.top_by_device(by, k, order, nulls, filter=flt, q_filter=sel, n_rows=len(open_rows), after=after)
+            doc, key, extra = doc.cpu().numpy(), key.cpu().numpy(), extra.cpu().numpy()
+            has = order_has_value(extra, nulls, k)
+            still, cursor = [], []
+            for i, r in enumerate(open_rows):
+                n = int(extra[i, 0])
+                take = min(n, top_k - len(got[r]))
+                got[r].extend(zip((int(d) - base for d in doc[i, :take]), order_values(col, key[i, :take], has[i, :take])))
+                if n == k and len(got[r]) < top_k:  # a full page and more wanted: the set may go on behind its last doc
+                    still.append(r)
+                    cursor.append(int(doc[i, n - 1]))
+            open_rows, after = still, torch.as_tensor(np.asarray(cursor, dtype=np.int32), device=table.device)
+        for qid in live:
+            out[qid] = {ids[d]: v for d, v in got[row_of[qid]]}
+        return out
+
+    def sort_results(self, results, by, order="desc", nulls="last", top_k=None, call: str = "sort_results"):
+        """Result lists reordered by the field ``by`` (``srx_order_lists``): ``results`` = ``{qid: {doc_id: score}}`` as any search
+        returns it (or ``search_by_vector``'s lists of ``{"doc_id", "score"}`` dicts) -> ``{qid: {doc_id: score}}`` with the
+        original scores, the first ``top_k`` (None: all) in the order of the value; docs with equal values, and docs without one,
+        keep the order they came in.  One upload, one launch, one copy back.  ValueError: a list deeper than 2048, an unknown doc
+        id, and what :meth:`search_sorted` refuses of ``by`` / ``order`` / ``nulls``."""
+        from . import _capi
+        self._order_column(by, order, nulls, call)
+        if top_k is not None and int(top_k) < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        out = {qid: {} for qid in (results or {})}
+        if not results:
+            return out
+        as_pairs = lambda row: [(r["doc_id"], r["score"]) for r in row] if isinstance(row, (list, tuple)) else list(row.items())
+        pairs = {qid: as_pairs(row) for qid, row in results.items()}
+        deepest = max((len(p) for p in pairs.values()), default=0)
+        if deepest > _capi.SRX_ORDER_MAX_M:
+            raise ValueError(f"{call} takes lists of at most {_capi.SRX_ORDER_MAX_M} docs, got {deepest} (no silent truncation)")
+        _, live, cand_doc, cand_count = self.candidate_block(results, {qid: [d for d, _ in p] for qid, p in pairs.items()})
+        if not live:
+            return out
+        import torch
+        table = self.field_table()
+        m = cand_doc.shape[1]
+        score = np.zeros((len(live), m), dtype=np.float32)
+        for i, (qid, _, _) in enumerate(live):
+            score[i, : len(pairs[qid])] = [s for _, s in pairs[qid]]
+        k = m if top_k is None else min(int(top_k), m)
+        d, _, _, extra, pos = table.sort_lists_device(by, torch.as_tensor(cand_doc + np.int32(self.doc_base), device=table.device),
+                                                      torch.as_tensor(score, device=table.device), torch.as_tensor(cand_count, device=table.device), k,
+                                                      order, nulls, want_pos=True)
+        block = torch.cat([pos, extra], dim=1).cpu().numpy()
+        for i, (qid, _, _) in enumerate(live):
+            out[qid] = {pairs[qid][int(p)][0]: pairs[qid][int(p)][1] for p in block[i, : int(block[i, k])]}
         return out
 
     # -- relevance feedback (include/ext/sparse_rx_feedback.h) ----------------------------------------------------------------
@@ -635,6 +736,15 @@ class SparseBackend:
             self.dev.close()
             self.dev = None
         self.searcher = None
+
+
+def check_match(match, any_terms, call: str) -> None:
+    """The ``match`` keyword of :meth:`SparseBackend.facets` / ``search_sorted`` next to ``any_terms``; raises ValueError"""
+    if match not in ("any", "all", None):
+        raise ValueError(f"match must be \"any\", \"all\" or None, got {match!r}")
+    if match == "any" and any_terms is not None:
+        raise ValueError(f"{call}: match=\"any\" puts the query's own terms into the any list; give match=None (or \"all\") with "
+                         "any_terms=, or match=\"any\" without it")
 
 
 class CollapseSpec:

@@ -24,6 +24,8 @@ I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
 GROUP_KEYS = ("must", "should", "must_not")
 NULL_POLICIES = {"own": _capi.SRX_COLLAPSE_NULL_OWN, "one": _capi.SRX_COLLAPSE_NULL_ONE, "drop": _capi.SRX_COLLAPSE_NULL_DROP}
+ORDERS = {"asc": _capi.SRX_ORDER_ASC, "desc": _capi.SRX_ORDER_DESC}
+ORDER_NULLS = {"last": _capi.SRX_ORDER_NULLS_LAST, "first": _capi.SRX_ORDER_NULLS_FIRST, "drop": _capi.SRX_ORDER_NULLS_DROP}
 _RANGE_KEYS = ("gte", "gt", "lte", "lt")
 _TEST_KEYS = _RANGE_KEYS + ("eq", "in", "any_of", "all_of", "exists")
 
@@ -458,6 +460,30 @@ def check_collapse_args(columns, column, per_group, nulls) -> int:
     return NULL_POLICIES[nulls]
 
 
+def check_order_args(columns, column, order, nulls):
+    """What every ordering door checks of its keywords before anything is launched: ``column`` names a column of ``columns``
+    (name -> :class:`HostColumn`) that has an order -- int32 / int64 / bool / float32 values or a category (ordered by its code,
+    which is the string's place in the sorted dictionary); a set column is refused by name --, ``order`` is "asc" or "desc" and
+    ``nulls`` is "last", "first" or "drop".  Returns ``(SRX_ORDER_*, SRX_ORDER_NULLS_*)``.  Raises ValueError."""
+    if column not in columns:
+        raise ValueError(f"unknown field {column!r}")
+    if columns[column].kind == "set":
+        raise ValueError(f"{column!r} is a set column: a label set has no order (order by a number or category column)")
+    if not isinstance(order, str) or order not in ORDERS:
+        raise ValueError(f"order must be one of {', '.join(ORDERS)}, got {order!r}")
+    if not isinstance(nulls, str) or nulls not in ORDER_NULLS:
+        raise ValueError(f"nulls must be one of {', '.join(ORDER_NULLS)}, got {nulls!r}")
+    return ORDERS[order], ORDER_NULLS[nulls]
+
+
+def decode_order_key(col: HostColumn, key: np.ndarray) -> np.ndarray:
+    """``out_key`` words (int64) as values of the column's dtype: int32 narrowed, float32 from the bits in the low 32"""
+    key = np.ascontiguousarray(key, dtype=np.int64)
+    if col.type == _capi.SRX_FIELD_F32:
+        return key.astype(np.uint32).view(np.float32)
+    return key.astype(np.int32) if col.type == _capi.SRX_FIELD_I32 else key
+
+
 class FacetSpec:
     """A binning spec resolved against one column (:func:`check_facet_args`): ``mode`` (SRX_FACET_*), ``n_bins``, ``origin`` (CODES),
     ``edges`` (EDGES: int64[n_bins + 1] as the device compares them -- exact bounds of the column's type, a float32's bits in the
@@ -849,3 +875,151 @@ class FieldTable:
         counts, extra = self.facet_lists_device(column, torch.as_tensor(d, device=self.device), cc, fs)
         both = torch.cat([counts, extra], dim=1).cpu().numpy()
         return both[:, : counts.shape[1]], both[:, counts.shape[1]:]
+
+    # -- ordering filter rows and result lists by a column (include/order/sparse_rx_order.h) ------------------------------------
+    def top_by_device(self, column: str, k: int, order: str = "desc", nulls: str = "last", filter=None, q_filter=None, n_rows=None, after=None):
+        """``srx_order_topk``: the first ``k`` docs (1 <= k <= 1024) of filter rows in the order of ``column`` -- "asc" or "desc",
+        equal values by ascending doc id; docs without a value (a float NaN is one) ``nulls`` = "last", "first", or "drop"ped.
+        ``filter`` / ``q_filter`` / ``n_rows`` as :meth:`facet_device` takes them.  ``after``: an int32 device tensor [n_rows] of
+        GLOBAL doc ids, the cursor of every row (-1: none; the last doc of the previous page continues it), or None.  Returns
+        device tensors ``(doc i32[n_rows, k], key i64[n_rows, k], extra i32[n_rows, 3])``, extra = (count, valued, total) per
+        row, rows padded with -1 / 0; asynchronous on the current stream, no synchronisation."""
+        torch = _torch()
+        o, nl = check_order_args(self.columns, column, order, nulls)
+        if column not in self._tensors:
+            raise ValueError("the table is closed")
+        k = int(k)
+        if not (1 <= k <= _capi.SRX_MAX_K):
+            raise ValueError(f"top_by_device: k must be in [1, {_capi.SRX_MAX_K}], got {k} (page with after=)")
+        if filter is None:
+            if q_filter is not None:
+                raise ValueError("q_filter picks rows of a filter: it needs filter=")
+            n_rows = 1 if n_rows is None else int(n_rows)
+        else:
+            if not isinstance(filter, DocFilter):
+                raise ValueError("filter must be a DocFilter")
+            filter.for_index(self)
+            if n_rows is None:
+                n_rows = filter.n_filters if q_filter is None else int(q_filter.numel())
+            n_rows = int(n_rows)
+            if q_filter is None and (n_rows > 1 or filter.n_filters > 1):  # row r of the output is row r of the filter
+                if n_rows > filter.n_filters:
+                    raise ValueError(f"n_rows = {n_rows} exceeds the filter's {filter.n_filters} rows: give q_filter")
+                q_filter = torch.arange(n_rows, dtype=torch.int32, device=self.device)
+        if n_rows < 0:
+            raise ValueError("n_rows must be >= 0")
+        if after is not None and (not isinstance(after, torch.Tensor) or after.dtype != torch.int32 or after.numel() != n_rows or after.device != self.device):
+            raise ValueError(f"top_by_device: after must be an int32 tensor [n_rows] on {self.device}")
+        desc = self._col_descs([column])
+        fdesc, keep = (None, None) if filter is None else filter.launch_args(q_filter, n_rows)
+        _, ws_bytes = _capi.order_plan(self.n_docs, n_rows, k)
+        with torch.cuda.device(self.device):
+            after = None if after is None else after.contiguous()
+            doc = torch.empty((n_rows, k), dtype=torch.int32, device=self.device)
+            key = torch.empty((n_rows, k), dtype=torch.int64, device=self.device)
+            extra = torch.empty((n_rows, 3), dtype=torch.int32, device=self.device)
+            ws = torch.empty(((ws_bytes + 15) // 8,), dtype=torch.int64, device=self.device)
+            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = _capi.lib().srx_order_topk(self.device.index or 0, desc, self.n_docs, self.doc_base, o, nl, fdesc, n_rows, k, ptr(after), ptr(doc),
+                                            ptr(key), ptr(extra), ws.data_ptr(), ws.numel() * 8, torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_order_topk")
+        del keep
+        return doc, key, extra
+
+    def top_by(self, column: str, k: int, order: str = "desc", nulls: str = "last", filter=None, q_filter=None, n_rows=None, after=None):
+        """:meth:`top_by_device` with host ``q_filter`` / ``after`` sequences (validated) and host arrays back: ``(doc i32[n_rows, k],
+        key [n_rows, k] in the column's dtype, has_value bool[n_rows, k], extra i32[n_rows, 3])``.  One synchronisation."""
+        torch = _torch()
+        check_order_args(self.columns, column, order, nulls)
+        qf = None
+        if q_filter is not None:
+            if not isinstance(filter, DocFilter):
+                raise ValueError("q_filter picks rows of a filter: it needs filter=")
+            q = np.asarray(q_filter)
+            qf = q_filter_to_device(filter, q, int(q.shape[0]) if q.ndim == 1 else -1)
+        af = None
+        if after is not None:
+            a = np.asarray(after)
+            if a.ndim != 1 or a.dtype.kind not in "iu" or (len(a) and (int(a.min()) < I32_MIN or int(a.max()) > I32_MAX)):
+                raise ValueError("after must be a 1-D sequence of int32 doc ids (-1: no cursor)")
+            af = torch.as_tensor(a.astype(np.int32), device=self.device)
+        doc, key, extra = self.top_by_device(column, k, order, nulls, filter, qf, n_rows, af)
+        torch.cuda.synchronize(self.device)
+        doc, key, extra = doc.cpu().numpy(), key.cpu().numpy(), extra.cpu().numpy()
+        return doc, decode_order_key(self.columns[column], key), order_has_value(extra, nulls, doc.shape[1]), extra
+
+    def sort_lists_device(self, column: str, doc, score, count, k: int, order: str = "desc", nulls: str = "last", want_pos: bool = False):
+        """``srx_order_lists`` on device tensors: the first ``k`` live positions of every list, STABLY sorted by the value
+        ``column`` holds for the doc (equal values and valueless docs keep their list order).  ``doc`` i32[nq, m] GLOBAL ids,
+        ``score`` f32[nq, m], ``count`` i32[nq] or None, as :meth:`collapse_device` takes them; m <= 2048, 1 <= k <= m.  Returns
+        device tensors ``(doc i32[nq, k], score f32[nq, k], key i64[nq, k], extra i32[nq, 3])``, extra = (count, valued, live),
+        then ``pos`` i32[nq, k] with ``want_pos``; rows padded with -1 / 0 / 0 / -1.  Asynchronous on the current stream, one launch."""
+        torch = _torch()
+        o, nl = check_order_args(self.columns, column, order, nulls)
+        if column not in self._tensors:
+            raise ValueError("the table is closed")
+        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32:
+            raise ValueError("sort_lists_device: doc must be an int32 tensor [nq, m]")
+        nq, m = int(doc.shape[0]), int(doc.shape[1])
+        if not (1 <= m <= _capi.SRX_ORDER_MAX_M):
+            raise ValueError(f"sort_lists_device takes lists of 1 to {_capi.SRX_ORDER_MAX_M} positions, got {m} (no silent truncation)")
+        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or tuple(score.shape) != (nq, m):
+            raise ValueError("sort_lists_device: score must be a float32 tensor of doc's shape")
+        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
+            raise ValueError("sort_lists_device: count must be an int32 tensor [nq]")
+        for t, what in ((doc, "doc"), (score, "score"), (count, "count")):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"sort_lists_device: {what} is on {t.device}, the table on {self.device}")
+        k = int(k)
+        if not (1 <= k <= m):
+            raise ValueError(f"sort_lists_device: k must be in [1, m = {m}], got {k}")
+        desc = self._col_descs([column])
+        with torch.cuda.device(self.device):
+            doc, score = doc.contiguous(), score.contiguous()
+            count = None if count is None else count.contiguous()
+            outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                    torch.empty((nq, k), dtype=torch.int64, device=self.device)]
+            pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
+            extra = torch.empty((nq, 3), dtype=torch.int32, device=self.device)
+            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = _capi.lib().srx_order_lists(self.device.index or 0, desc, self.n_docs, self.doc_base, o, nl, ptr(doc), ptr(score), ptr(count), nq, m, k,
+                                             *[ptr(t) for t in outs], ptr(pos), ptr(extra), torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_order_lists")
+        return tuple(outs + [extra] + ([pos] if want_pos else []))
+
+    def sort_lists(self, column: str, doc, score, count, k: int, order: str = "desc", nulls: str = "last", want_pos: bool = False):
+        """Host arrays in (the candidates validated by :func:`~.index.validate_candidates`), host arrays out:
+        :meth:`sort_lists_device` with one synchronisation and one copy back; ``key`` stays int64 (:func:`decode_order_key`)."""
+        from .index import validate_candidates
+        torch = _torch()
+        check_order_args(self.columns, column, order, nulls)
+        d = np.asarray(doc)
+        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
+        if d.shape[1] > _capi.SRX_ORDER_MAX_M:
+            raise ValueError(f"sort_lists takes lists of at most {_capi.SRX_ORDER_MAX_M} positions, got {d.shape[1]} (no silent truncation)")
+        s = np.ascontiguousarray(score, dtype=np.float32)
+        if s.shape != d.shape:
+            raise ValueError("score must have doc's shape")
+        cc = None if c is None else torch.as_tensor(c, device=self.device)
+        out = self.sort_lists_device(column, torch.as_tensor(d, device=self.device), torch.as_tensor(s, device=self.device), cc, k, order, nulls, want_pos)
+        torch.cuda.synchronize(self.device)
+        return tuple(t.cpu().numpy() for t in out)
+
+
+def order_has_value(extra: np.ndarray, nulls: str, k: int) -> np.ndarray:
+    """bool[rows, k]: which returned entries have a value, from ``extra`` = (count, valued, ..) -- the valueless entries are the
+    last ``count - valued`` of a row under "last" / "drop" and the first under "first"."""
+    i = np.arange(int(k))[None, :]
+    count, valued = extra[:, 0:1], extra[:, 1:2]
+    return (i >= count - valued) & (i < count) if nulls == "first" else i < valued
+
+
+def order_values(col: HostColumn, key: np.ndarray, has: np.ndarray) -> list:
+    """``out_key`` words of one row as what a result dict holds: a Python int (int32 / int64), bool, float (float32), the
+    dictionary string of a category column, None where ``has`` is False"""
+    vals = decode_order_key(col, key).tolist()
+    if col.kind == "bool":
+        vals = [bool(v) for v in vals]
+    elif col.kind == "category":
+        vals = [col.dictionary[v] if h else None for v, h in zip(vals, has)]
+    return [v if h else None for v, h in zip(vals, has)]

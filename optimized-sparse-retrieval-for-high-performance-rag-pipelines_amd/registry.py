@@ -147,6 +147,29 @@ class _SparseRetrieverBase(SparseIndexViews):
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         return self._be.facets_of(results, fields, top, "facets_of")
 
+    def search_sorted(self, queries: Dict[str, str], by: str, *, order: str = "desc", top_k: int = 10, match="any", nulls: str = "last",
+                      allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None):
+        """Order by a field instead of relevance (no reference counterpart): the first ``top_k`` docs of each query's doc set by the
+        value the column ``by`` of :meth:`set_doc_fields` holds for them, selected on the GPU (``srx_order_topk``,
+        include/order/sparse_rx_order.h) -> ``{qid: {doc_id: value}}`` in rank order.  The doc set and ``match`` are those of
+        :meth:`facets`.  ``order`` "asc" / "desc"; docs with equal values come in corpus order; ``nulls``: docs without a value come
+        "last", "first" or "drop" out (their value is None).  A value is an int, bool, float or a category's string (categories
+        order alphabetically).  ``top_k`` above 1024 pages with a cursor.  ``ValueError``: no :meth:`set_doc_fields`, a sharded
+        index, an unknown field, a set column, a bad keyword."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        return self._be.search_sorted(queries, by, order, top_k, match, nulls, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms,
+                                      where, "search_sorted")
+
+    def sort_results(self, results, by: str, *, order: str = "desc", nulls: str = "last", top_k: Optional[int] = None):
+        """Result lists reordered by a field: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it ->
+        the same dicts, scores unchanged, in the order of the column ``by`` (``srx_order_lists``; equal values keep their relevance
+        order), cut to ``top_k``.  ``ValueError``: a list deeper than 2048, an unknown doc id, and what :meth:`search_sorted`
+        refuses."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        return self._be.sort_results(results, by, order, nulls, top_k, "sort_results")
+
     def score(self, queries: Dict[str, str], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
         """The exact score of caller-named documents: ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in
         the caller's order and the arithmetic of :meth:`search` (``srx_score_docs``; the accumulation order is this
