@@ -1,7 +1,7 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
-include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h and include/order/sparse_rx_order.h).
+include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h and include/boost/sparse_rx_boost.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -245,6 +245,25 @@ SRX_ORDER_MAX_M = 2048                                                          
 SRX_ORDER_MIN_SEG, SRX_ORDER_CHUNK = 32768, 8192                                  # the scan's segment rule (order_plan)
 
 
+class BoostClause(ctypes.Structure):
+    """``srx_boost_clause`` (include/boost/sparse_rx_boost.h): a DEVICE array element of 40 bytes"""
+    _fields_ = [("col", ctypes.c_int32), ("flags", ctypes.c_int32), ("origin", ctypes.c_int64), ("inv_step", ctypes.c_float),
+                ("weight", ctypes.c_float), ("missing", ctypes.c_float), ("knot0", ctypes.c_int32), ("n_seg", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+# every symbol include/boost/sparse_rx_boost.h declares (the fourteenth header of the same library)
+BOOST_SYMBOLS = {
+    "srx_boost_topk": (ctypes.c_int, [_I32, _CP, _I32, _I64, _I64, _VP, _I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32,
+                                      _VP, _VP, _VP, _VP, _VP]),
+}
+SRX_BOOST_SCORE_MULTIPLY, SRX_BOOST_SCORE_SUM, SRX_BOOST_SCORE_MAX, SRX_BOOST_SCORE_MIN = 0, 1, 2, 3  # score_mode
+SRX_BOOST_MULTIPLY, SRX_BOOST_SUM, SRX_BOOST_REPLACE = 0, 1, 2                                        # boost_mode
+SRX_BOOST_ABS = 1                                                                                     # clause flags
+SRX_BOOST_MAX_M, SRX_BOOST_MAX_CLAUSES, SRX_BOOST_MAX_COLS = 2048, 8, 8                               # pinned to the header by tests/test_boost_cpu.py
+SRX_BOOST_MAX_KNOTS = 1 << 24
+
+
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
     ``srx_order_workspace_bytes`` by tests/test_order_cpu.py).  A segment is what one workgroup scans for one row."""
@@ -284,7 +303,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_collapse.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_facets.h"),
                                                             os.path.join(INCLUDE_DIR, "ext", "sparse_rx_feedback.h"),
-                                                            os.path.join(INCLUDE_DIR, "order", "sparse_rx_order.h")]
+                                                            os.path.join(INCLUDE_DIR, "order", "sparse_rx_order.h"),
+                                                            os.path.join(INCLUDE_DIR, "boost", "sparse_rx_boost.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -334,7 +354,7 @@ def lib() -> ctypes.CDLL:
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
-                                   **ORDER_SYMBOLS}.items():
+                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

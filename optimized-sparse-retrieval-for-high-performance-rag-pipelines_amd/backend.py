@@ -20,6 +20,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from .boost import boost_deep  # beside collapse_deep: the same search_fn contract
 from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, parse_operators, score_host_batch, search_host_batch, tokenize
 
 
@@ -251,6 +252,104 @@ class SparseBackend:
         out = collapse_deep(search_fn, collapse_fn, *_batch_to_device(torch, q_ptr, q_term, q_weight, dev.device), k, first,
                             page=_capi.SRX_MAX_K, max_depth=collapse.depth)
         return _to_host(torch, dev.device, out)
+
+    # -- boosts by field values (include/boost/sparse_rx_boost.h) ---------------------------------------------------------------
+    boost_page = 1024  # rows per page of the exact boosted search (the engine's list depth; a test may lower it)
+
+    def boost_spec(self, boost, depth=None, top_k: int = 10, call: str = "search", collapse=None, exact: bool = True):
+        """The boost keywords of one API call (``boost``, ``boost_depth``) as a :class:`~.boost.BoostResolver` with a ``depth``
+        attribute, or None when ``boost`` is None.  ``exact``: the call is an exact door (:func:`~.boost.boost_deep`), which has
+        no bound for ``boost_mode`` "replace" nor for a factor that can be negative under "multiply".  ValueError: no fields (the
+        message names ``call``), a sharded index, what the resolver refuses (an unknown or set column among it), ``top_k`` above
+        the engine's list depth, a depth below 1, ``collapse_by=`` in the same call."""
+        if boost is None:
+            return None
+        from . import _capi
+        from .boost import BoostResolver
+        if self._fields is None:
+            raise ValueError(f"{call}(boost=...) needs the docs' fields: call set_doc_fields() first")
+        self._refuse_sharded("boost= needs")
+        res = boost if isinstance(boost, BoostResolver) else BoostResolver(self._fields, boost)
+        if int(top_k) > _capi.SRX_MAX_K:
+            raise ValueError(f"{call}(boost=...) returns at most {_capi.SRX_MAX_K} rows per query, got top_k={top_k}")
+        if depth is not None and int(depth) < 1:
+            raise ValueError(f"boost_depth must be >= 1, got {depth}")
+        if collapse is not None:
+            raise ValueError(f"{call}: boost= and collapse_by= do not combine in one call (chain collapse() over the boosted result)")
+        if exact:
+            if res.boost_mode_name == "replace":
+                raise ValueError(f"{call}(boost=...): boost_mode \"replace\" drops the relevance score, so no page of the ranking bounds the "
+                                 "rest (search_sorted orders by a field alone; boost_results reorders a given list)")
+            if res.boost_mode_name == "multiply" and not float(res.F_lo) >= 0.0:
+                raise ValueError(f"{call}(boost=...): under boost_mode \"multiply\" the factor must not be negative (F_lo = {float(res.F_lo)!r})")
+        res.depth = None if depth is None else int(depth)
+        return res
+
+    def _boost_deep(self, batch, k: int, boost, flt):
+        """:func:`~.boost.boost_deep` over this index's device search (``flt``: its filter keywords) -> device rows"""
+        from . import _capi
+        from .boost import BoostFn
+        dev = self.dev
+        page = min(int(self.boost_page), _capi.SRX_MAX_K)
+        first = min(max(4 * k, 64), max(page, k), self.n_docs_total)
+        return boost_deep(lambda qp, qt, qw, kk, after=None: dev.search_device(qp, qt, qw, kk, after=after, **flt),
+                          BoostFn(self.field_table(), boost), *batch, k, first, page=page, max_depth=boost.depth)
+
+    def boosted_search_arrays(self, q_ptr, q_term, q_weight, k: int, boost, filter=None, q_filter=None):
+        """Host CSR batch -> host rows (doc, score, count) of the top ``k`` of the BOOSTED complete ranking, exact:
+        :func:`~.boost.boost_deep` over this index's device search (under ``filter`` / ``q_filter`` when given) and the field
+        table's ``boost_device``.  ``first`` = min(max(4 k, 64), 1024, n_docs); the scores are the boosted ones."""
+        import torch
+        from .filter import q_filter_to_device
+        from .index import _batch_to_device, _to_host, validate_query_batch
+        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
+        nq = len(q_ptr) - 1
+        if nq == 0:
+            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
+        dev = self.dev
+        flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
+        return _to_host(torch, dev.device, self._boost_deep(_batch_to_device(torch, q_ptr, q_term, q_weight, dev.device), k, boost, flt))
+
+    def boost_results(self, results, boost, top_k=None, call: str = "boost_results"):
+        """Result lists re-scored and re-ranked by a boost (``srx_boost_topk``): ``results`` = ``{qid: {doc_id: score}}`` as any
+        search returns it (or ``search_by_vector``'s lists of ``{"doc_id", "score"}`` dicts) -> ``{qid: {doc_id: new score}}``,
+        the first ``top_k`` (None: all) by (new score descending, corpus order).  It is relative to THE LISTS GIVEN; every
+        ``boost_mode`` is allowed.  One upload, one launch, one copy back.  ValueError: a list deeper than 2048, an unknown doc
+        id, and what :meth:`boost_spec` refuses of ``boost``."""
+        from . import _capi
+        res = self.boost_spec(boost, None, 1, call, exact=False)
+        if res is None:
+            raise ValueError(f"{call} needs a boost")
+        if top_k is not None and int(top_k) < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        out = {qid: {} for qid in (results or {})}
+        if not results:
+            return out
+        as_pairs = lambda row: [(r["doc_id"], r["score"]) for r in row] if isinstance(row, (list, tuple)) else list(row.items())
+        pairs = {qid: as_pairs(row) for qid, row in results.items()}
+        deepest = max((len(p) for p in pairs.values()), default=0)
+        if deepest > _capi.SRX_BOOST_MAX_M:
+            raise ValueError(f"{call} takes lists of at most {_capi.SRX_BOOST_MAX_M} docs, got {deepest} (no silent truncation)")
+        _, live, cand_doc, cand_count = self.candidate_block(results, {qid: [d for d, _ in p] for qid, p in pairs.items()})
+        if not live:
+            return out
+        import torch
+        from .boost import BoostFn
+        table = self.field_table()
+        m = cand_doc.shape[1]
+        score = np.zeros((len(live), m), dtype=np.float32)
+        for i, (qid, _, _) in enumerate(live):
+            score[i, : len(pairs[qid])] = [s for _, s in pairs[qid]]
+        k = m if top_k is None else min(int(top_k), m)
+        _, ns, cnt, pos = BoostFn(table, res)(torch.as_tensor(cand_doc + np.int32(self.doc_base), device=table.device),
+                                              torch.as_tensor(score, device=table.device), torch.as_tensor(cand_count, device=table.device), k,
+                                              want_pos=True)
+        block = torch.cat([pos, cnt.reshape(-1, 1), ns.view(torch.int32)], dim=1).cpu().numpy()
+        for i, (qid, _, _) in enumerate(live):
+            n = int(block[i, k])
+            new = block[i, k + 1: k + 1 + n].copy().view(np.float32)
+            out[qid] = {pairs[qid][int(p)][0]: float(v) for p, v in zip(block[i, :n], new)}
+        return out
 
     def facet_specs(self, fields, call: str = "facets"):
         """``fields`` of a facet door -- one name, a sequence of names, or a dict name -> binning spec (None: the column's own
@@ -496,7 +595,7 @@ class SparseBackend:
         self._need_forward(call, "expand_docs=...")
         return spec
 
-    def _search_expanded(self, batch, k: int, filter=None, q_filter=None, collapse=None):
+    def _search_expanded(self, batch, k: int, filter=None, q_filter=None, collapse=None, boost=None):
         """The second pass: an expanded batch still on the device -> host rows.  k <= 1024: nothing is copied back in between;
         deeper: the batch goes to the host once and takes the paged route of :meth:`~.index.DeviceIndex.search`."""
         import torch
@@ -511,6 +610,8 @@ class SparseBackend:
             n = int(p[-1])
             return dev.search(p, e_term[:n].cpu().numpy(), e_weight[:n].cpu().numpy(), k, filter=filter, q_filter=q_filter)
         flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
+        if boost is not None:
+            return _to_host(torch, dev.device, self._boost_deep((e_ptr, e_term, e_weight), k, boost, flt))
         if collapse is None:
             return _to_host(torch, dev.device, dev.search_device(e_ptr, e_term, e_weight, k, **flt))
         table = self.field_table()
@@ -520,11 +621,12 @@ class SparseBackend:
                             e_ptr, e_term, e_weight, k, first, page=_capi.SRX_MAX_K, max_depth=collapse.depth)
         return _to_host(torch, dev.device, out)
 
-    def expanded_search_arrays(self, q_ptr, q_term, q_weight, k: int, expand: "ExpandSpec", filter=None, q_filter=None, collapse=None):
+    def expanded_search_arrays(self, q_ptr, q_term, q_weight, k: int, expand: "ExpandSpec", filter=None, q_filter=None, collapse=None, boost=None):
         """Host CSR batch -> host rows (doc, score, count) of the search of the EXPANDED batch: a first pass ``expand.docs`` deep
         (under ``filter`` / ``q_filter``, never collapsed), ``srx_feedback_expand`` with alpha = 1 - weight, beta = weight and
         row_cap = min(max_row_terms, 4096 // expand.docs), then the existing search of the expanded batch at ``k`` under the same
-        filter, collapsed when ``collapse`` is given.  The lists of the first pass and the expanded batch stay on the device."""
+        filter, collapsed when ``collapse`` is given, boosted (exact) when ``boost`` is.  The lists of the first pass and the expanded
+        batch stay on the device."""
         import torch
         from .filter import q_filter_to_device
         from .index import _batch_to_device, validate_query_batch
@@ -538,7 +640,7 @@ class SparseBackend:
         d, s, c = dev.search_device(qp, qt, qw, min(expand.docs, self.n_docs_total), **flt)
         batch = fwd.expand_device(qp, qt, qw, d, s, c, fb_docs=expand.docs, n_terms=expand.terms, alpha=1.0 - expand.weight, beta=expand.weight,
                                   doc_weight=expand.by, term_weight=self._fb_term_weight, term_gain=self._fb_gain)
-        return self._search_expanded(batch, k, filter, q_filter, collapse)
+        return self._search_expanded(batch, k, filter, q_filter, collapse, boost)
 
     def _seed_block(self, lists, call: str, what: str):
         """{qid: sequence of doc ids} -> (qids, doc i32[nq, m] GLOBAL row ids padded with -1, count i32[nq]); at most 32 per qid"""
@@ -626,7 +728,7 @@ class SparseBackend:
 
     def search_dicts(self, queries, top_k: int, *, order: str = "term", cache=None, lock=None, strip_key: bool = True,
                      blank: str = "empty", filter: Optional["DocFilterSpec"] = None, collapse: Optional["CollapseSpec"] = None,
-                     expand: Optional["ExpandSpec"] = None):
+                     expand: Optional["ExpandSpec"] = None, boost=None):
         """The cached batched search the API mirrors share: ``queries`` {qid: text} -> {qid: {doc_id: score}} with every qid
         in the caller's order, one batched search for all texts the cache does not hold (equal texts share one row).  What
         the call sites of the reference do differently is named here:
@@ -652,8 +754,11 @@ class SparseBackend:
         (:meth:`collapsed_search_arrays`), under ``filter`` when given; such a call bypasses the cache as a filtered one does.
 
         ``expand`` (:meth:`expand_spec`): every row is the search of the query EXPANDED from its own first results
-        (:meth:`expanded_search_arrays`), under ``filter`` and ``collapse`` when given; such a call bypasses the cache too."""
-        if filter is not None or collapse is not None or expand is not None:
+        (:meth:`expanded_search_arrays`), under ``filter`` and ``collapse`` when given; such a call bypasses the cache too.
+
+        ``boost`` (:meth:`boost_spec`): every row is the top ``top_k`` of the BOOSTED complete ranking with its boosted scores
+        (:meth:`boosted_search_arrays`), under ``filter`` and ``expand`` when given; such a call bypasses the cache too."""
+        if filter is not None or collapse is not None or expand is not None or boost is not None:
             cache = None
         k_eff = min(int(top_k), self.n_docs_total)  # any depth: search_arrays pages past the engine's 1024-row lists
         results: Dict[str, Dict[str, float]] = {}
@@ -689,7 +794,11 @@ class SparseBackend:
                 docs, scores, counts = self.expanded_search_arrays(q_ptr, q_term, q_weight, k_eff, expand,
                                                                    filter=None if filter is None else filter.on_device(self.dev),
                                                                    q_filter=None if filter is None else np.asarray(frows, dtype=np.int32),
-                                                                   collapse=collapse)
+                                                                   collapse=collapse, boost=boost)
+            elif boost is not None:
+                docs, scores, counts = self.boosted_search_arrays(q_ptr, q_term, q_weight, k_eff, boost,
+                                                                  filter=None if filter is None else filter.on_device(self.dev),
+                                                                  q_filter=None if filter is None else np.asarray(frows, dtype=np.int32))
             elif collapse is not None:
                 docs, scores, counts = self.collapsed_search_arrays(q_ptr, q_term, q_weight, k_eff, collapse,
                                                                     filter=None if filter is None else filter.on_device(self.dev),

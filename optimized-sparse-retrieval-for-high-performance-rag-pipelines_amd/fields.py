@@ -1005,6 +1005,102 @@ class FieldTable:
         torch.cuda.synchronize(self.device)
         return tuple(t.cpu().numpy() for t in out)
 
+    # -- boosting ranked lists by column values (include/boost/sparse_rx_boost.h) ----------------------------------------------
+    def boost_device(self, columns, clauses, knots, score_mode: int, boost_mode: int, doc, score, count, k: int, carry=None,
+                     want_pos: bool = False):
+        """``srx_boost_topk`` on device tensors: the raw scores of every list moved by the clauses' curves over ``columns`` (the
+        names a clause's ``col`` indexes, 1 to 8, none a set column), and the first ``k`` by (new score descending, doc id
+        ascending).  ``clauses``: a uint8 tensor [n_clauses, 40], the records of ``srx_boost_clause`` (``boost.CLAUSE_DTYPE``);
+        ``knots``: float32 [n_knots]; ``score_mode`` / ``boost_mode``: SRX_BOOST_*.  ``doc`` i32[nq, m] GLOBAL ids, ``score``
+        f32[nq, m] RAW scores in any order, ``count`` i32[nq] or None.  ``carry``: None or ``(doc i32[nq, kc], score f32[nq, kc],
+        count i32[nq] | None)`` whose scores are FINAL; m + kc <= 2048, 1 <= k <= m + kc.  Returns device tensors ``(doc i32[nq, k],
+        score f32[nq, k], count i32[nq])`` padded with -1 / 0, then ``pos`` i32[nq, k] (the position in carry ++ candidates)
+        with ``want_pos``.  Asynchronous on the current stream, one launch.  Precondition (NOT checked here, the tensors never
+        leave the device): what :func:`~.boost.check_clause_arrays` checks of host arrays."""
+        torch = _torch()
+        names = [columns] if isinstance(columns, str) else list(columns)
+        if not (1 <= len(names) <= _capi.SRX_BOOST_MAX_COLS):
+            raise ValueError(f"a boost takes 1 to {_capi.SRX_BOOST_MAX_COLS} columns, got {len(names)}")
+        for name in names:
+            if name not in self.columns:
+                raise ValueError(f"unknown field {name!r}")
+            if self.columns[name].kind == "set":
+                raise ValueError(f"{name!r} is a set column: a label set is no number to boost by")
+        descs = self._col_descs(names)
+
+        def check(t, dtype, what, shape=None, dim=None):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or (shape is not None and tuple(t.shape) != shape) or (dim is not None and t.dim() != dim):
+                raise ValueError(f"boost_device: {what} must be a {dtype} tensor" + (f" of shape {shape}" if shape is not None else f" with {dim} dims"))
+            if t.device != self.device:
+                raise ValueError(f"boost_device: {what} is on {t.device}, the table on {self.device}")
+            return t.contiguous()
+
+        clauses = check(clauses, torch.uint8, "clauses", dim=2)
+        if clauses.shape[1] != 40 or not (1 <= int(clauses.shape[0]) <= _capi.SRX_BOOST_MAX_CLAUSES):
+            raise ValueError(f"boost_device: clauses must be uint8 [1 .. {_capi.SRX_BOOST_MAX_CLAUSES}, 40]")
+        knots = check(knots, torch.float32, "knots", dim=1)
+        if not (2 <= knots.numel() <= _capi.SRX_BOOST_MAX_KNOTS):
+            raise ValueError("boost_device: knots must hold 2 to 2^24 entries")
+        doc = check(doc, torch.int32, "doc", dim=2)
+        nq, m = int(doc.shape[0]), int(doc.shape[1])
+        score = check(score, torch.float32, "score", shape=(nq, m))
+        if count is not None:
+            count = check(count.reshape(-1) if isinstance(count, torch.Tensor) else count, torch.int32, "count", shape=(nq,))
+        cd = cs = cc = None
+        kc = 0
+        if carry is not None:
+            cd = check(carry[0], torch.int32, "carry doc", dim=2)
+            kc = int(cd.shape[1])
+            if int(cd.shape[0]) != nq or kc < 1:
+                raise ValueError("boost_device: carry doc must be int32 [nq, kc >= 1]")
+            cs = check(carry[1], torch.float32, "carry score", shape=(nq, kc))
+            if len(carry) > 2 and carry[2] is not None:
+                cc = check(carry[2].reshape(-1) if isinstance(carry[2], torch.Tensor) else carry[2], torch.int32, "carry count", shape=(nq,))
+        if m < 1 or m + kc > _capi.SRX_BOOST_MAX_M:
+            raise ValueError(f"boost_device takes lists of 1 to {_capi.SRX_BOOST_MAX_M} positions, carry included, got {m} + {kc} (no silent truncation)")
+        k = int(k)
+        if not (1 <= k <= m + kc):
+            raise ValueError(f"boost_device: k must be in [1, m + kc = {m + kc}], got {k}")
+        with torch.cuda.device(self.device):
+            outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                    torch.empty((nq,), dtype=torch.int32, device=self.device)]
+            pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
+            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = _capi.lib().srx_boost_topk(self.device.index or 0, descs, len(names), self.n_docs, self.doc_base, ptr(clauses), int(clauses.shape[0]),
+                                            ptr(knots), int(knots.numel()), int(score_mode), int(boost_mode), ptr(doc), ptr(score), ptr(count),
+                                            ptr(cd), ptr(cs), ptr(cc), nq, m, kc, k, *[ptr(o) for o in outs], ptr(pos),
+                                            torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_boost_topk")
+        return tuple(outs + ([pos] if want_pos else []))
+
+    def boost(self, boost, doc, score, count, k: int, carry=None, want_pos: bool = False):
+        """Host arrays in, host arrays out: ``boost`` is a spec :class:`~.boost.BoostResolver` takes (or a resolver over this
+        table's columns), the candidates (and the carry's) are validated by :func:`~.index.validate_candidates`, the clause
+        records by :func:`~.boost.check_clause_arrays`; then :meth:`boost_device` with one synchronisation and one copy back."""
+        from .boost import BoostFn, BoostResolver, check_clause_arrays
+        from .index import validate_candidates
+        torch = _torch()
+        res = boost if isinstance(boost, BoostResolver) else BoostResolver(self.columns, boost)
+        check_clause_arrays([self.columns[n].type for n in res.names], res.clauses, res.knots)
+
+        def triple(d, s, c, what):
+            d = np.asarray(d)
+            d, c = validate_candidates(d, c, int(d.shape[0]) if d.ndim == 2 else 0)
+            s = np.ascontiguousarray(s, dtype=np.float32)
+            if s.shape != d.shape:
+                raise ValueError(f"{what} score must have doc's shape")
+            return (torch.as_tensor(d, device=self.device), torch.as_tensor(s, device=self.device),
+                    None if c is None else torch.as_tensor(c, device=self.device))
+
+        cand = triple(doc, score, count, "the")
+        kc = 0 if carry is None else int(np.asarray(carry[0]).shape[1])
+        if int(cand[0].shape[1]) + kc > _capi.SRX_BOOST_MAX_M:
+            raise ValueError(f"boost takes lists of at most {_capi.SRX_BOOST_MAX_M} positions, carry included (no silent truncation)")
+        cr = None if carry is None else triple(carry[0], carry[1], carry[2] if len(carry) > 2 else None, "the carry's")
+        out = BoostFn(self, res)(*cand, k, carry=cr, want_pos=want_pos)
+        torch.cuda.synchronize(self.device)
+        return tuple(t.cpu().numpy() for t in out)
+
 
 def order_has_value(extra: np.ndarray, nulls: str, k: int) -> np.ndarray:
     """bool[rows, k]: which returned entries have a value, from ``extra`` = (count, valued, ..) -- the valueless entries are the

@@ -49,7 +49,7 @@ class _SparseRetrieverBase(SparseIndexViews):
     def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
                must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None, per_group: int = 1,
                collapse_nulls: str = "own", collapse_depth: Optional[int] = None, expand_docs: Optional[int] = None, expand_terms: int = 10,
-               expand_weight: float = 0.5, expand_by: str = "score") -> Dict[str, Dict[str, float]]:
+               expand_weight: float = 0.5, expand_by: str = "score", boost=None, boost_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """``allowed_docs`` / ``excluded_docs`` (no reference counterpart): as ``RetrievalService.search_bm25`` -- the top
         ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call.
         ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators``: term constraints, as ``RetrievalService.search_bm25``
@@ -61,7 +61,9 @@ class _SparseRetrieverBase(SparseIndexViews):
         ``RetrievalService.search_bm25`` (needs :meth:`enable_feedback`; no cache): the search of the query expanded on the GPU from
         its own first ``expand_docs`` results.  In dot mode a contribution is the doc's raw value and every term's gain is 1
         (Rocchio-style); in BM25 mode tf / doc_len and max(idf, 0).  The scores are those of the expanded query, whose weights
-        sum to at most 1: not comparable to the scores of a plain search."""
+        sum to at most 1: not comparable to the scores of a plain search.
+        ``boost`` / ``boost_depth``: the top ``top_k`` of the ranking boosted by field values, exact, with the boosted scores, as
+        ``RetrievalService.search_bm25`` (needs raw scores > 0, which the search guarantees; not with ``collapse_by``; no cache)."""
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         if operators:
@@ -69,12 +71,13 @@ class _SparseRetrieverBase(SparseIndexViews):
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search")
         expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search")
+        boosted = self._be.boost_spec(boost, boost_depth, top_k, "search", collapse)
         if expand is not None:
             return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
-                                         collapse=collapse, expand=expand)
-        if spec is not None or collapse is not None:
+                                         collapse=collapse, expand=expand, boost=boosted)
+        if spec is not None or collapse is not None or boosted is not None:
             return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
-                                         collapse=collapse)
+                                         collapse=collapse, boost=boosted)
         # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional
         return self._be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock,
                                      strip_key=self.strip_cache_key, blank="empty")
@@ -169,6 +172,13 @@ class _SparseRetrieverBase(SparseIndexViews):
         if self.host is None:
             raise ValueError("Index not built. Call build_index_from_corpus() first.")
         return self._be.sort_results(results, by, order, nulls, top_k, "sort_results")
+
+    def boost_results(self, results, boost, top_k: Optional[int] = None):
+        """Result lists re-scored by field values, as ``RetrievalService.boost_results`` (``srx_boost_topk``): ``{qid: {doc_id:
+        boosted score}}``, the first ``top_k`` by boosted score, relative to the lists given."""
+        if self.host is None:
+            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        return self._be.boost_results(results, boost, top_k, "boost_results")
 
     def score(self, queries: Dict[str, str], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
         """The exact score of caller-named documents: ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in

@@ -109,7 +109,8 @@ class RetrievalService(SparseIndexViews):
     def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None,
                     any_terms=None, must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None,
                     per_group: int = 1, collapse_nulls: str = "own", collapse_depth: Optional[int] = None, expand_docs: Optional[int] = None,
-                    expand_terms: int = 10, expand_weight: float = 0.5, expand_by: str = "score") -> Dict[str, Dict[str, float]]:
+                    expand_terms: int = 10, expand_weight: float = 0.5, expand_by: str = "score", boost=None,
+                    boost_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
 
         ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
@@ -155,7 +156,18 @@ class RetrievalService(SparseIndexViews):
         result is the existing search of that expanded query at ``top_k`` under the same keywords, ``collapse_by`` included.
         Nothing is copied back between the two passes for ``top_k`` <= 1 024.  The scores are those of the EXPANDED query, whose
         weights sum to at most 1: they are NOT comparable to plain BM25 scores.  Such a call bypasses the query cache.
-        ``ValueError``: no :meth:`enable_feedback`, a sharded index, a keyword out of range."""
+        ``ValueError``: no :meth:`enable_feedback`, a sharded index, a keyword out of range.
+
+        ``boost`` (default None: nothing changes; no reference counterpart): a spec :class:`~.boost.BoostResolver` takes --
+        ``{"functions": [{"decay": {...}} | {"field_value": {...}} | {"curve": {...}}, ...], "score_mode", "boost_mode"}`` over the
+        number columns of :meth:`set_doc_fields`: "prefer recent", "prefer popular".  The result is the top ``top_k`` of the
+        BOOSTED complete ranking with its boosted scores, exact (``srx_boost_topk``, include/boost/sparse_rx_boost.h): the
+        ranking is read in pages on the GPU (:func:`~.boost.boost_deep`) until no unseen doc can reach a query's k-th boosted
+        score.  ``boost_depth`` (default None: no limit) stops after that many rows of the ranking; the result is then the
+        boosted top of the rows read.  It works under the doc, term and field keywords and with ``expand_docs``, and bypasses
+        the query cache.  ``ValueError``: ``collapse_by`` in the same call (chain :meth:`collapse` over the result), ``boost_mode``
+        "replace" or a factor that can be negative under "multiply" (no bound exists), ``top_k`` above 1 024, an unknown or set
+        column, no :meth:`set_doc_fields`, a sharded index."""
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
         if operators:
@@ -163,6 +175,7 @@ class RetrievalService(SparseIndexViews):
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search_bm25")
         expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search_bm25")
+        boosted = self._be.boost_spec(boost, boost_depth, top_k, "search_bm25", collapse)
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
             return {qid: {} for qid in queries}
         if (self.k1, self.b) != self._built_k1b:
@@ -170,10 +183,11 @@ class RetrievalService(SparseIndexViews):
             if expand is not None:
                 self._be.enable_feedback("bm25")  # the upload dropped the forward index; its rows do not depend on k1 / b
         if expand is not None:
-            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse, expand=expand)
+            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse, expand=expand,
+                                         boost=boosted)
         # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on
-        if spec is not None or collapse is not None:
-            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse)
+        if spec is not None or collapse is not None or boosted is not None:
+            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse, boost=boosted)
         return self._be.search_dicts(queries, top_k, order="term", cache=self.query_cache, lock=self.cache_lock, strip_key=True,
                                      blank="whitespace")
 
@@ -339,7 +353,7 @@ class RetrievalService(SparseIndexViews):
                       mmr_similarity: str = "cosine", must_terms=None, any_terms=None, must_not_terms=None,
                       operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None, where=None,
                       collapse_by: Optional[str] = None, per_group: int = 1, collapse_nulls: str = "own",
-                      collapse_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+                      collapse_pool: Optional[int] = None, boost=None, boost_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -391,7 +405,14 @@ class RetrievalService(SparseIndexViews):
         ``top_k`` when the pool holds fewer groups.  With ``late_query_tokens`` the order is fuse, rerank the whole ``late_pool``,
         collapse to ``top_k`` (``collapse_pool`` is not used): ``collapse(rerank_late(search_hybrid(top_k=late_pool, ...), tokens,
         late_pool), ...)``.  With ``mmr_lambda`` it is fuse ``collapse_pool`` deep, collapse to ``mmr_pool``, MMR to ``top_k``:
-        ``diversify(collapse(search_hybrid(top_k=collapse_pool, ...), collapse_by, mmr_pool, ...), top_k, ...)``."""
+        ``diversify(collapse(search_hybrid(top_k=collapse_pool, ...), collapse_by, mmr_pool, ...), top_k, ...)``.
+        ``boost`` (default None: nothing changes) as in :meth:`search_bm25`, every ``boost_mode`` allowed ("replace" too).  The fused
+        ranking is taken ``boost_pool`` deep (default ``min(max(4 * top_k, 100), 1024, n_docs)``; more than 1024 raises
+        ``ValueError``; with ``late_query_tokens`` the pool is ``late_pool``, reranked as a whole first), ``candidates`` defaults to
+        at least the pool, and the pool is boosted on the device (``srx_boost_topk``) before the one copy back.  The result is
+        POOL-RELATIVE: what ``boost_results(search_hybrid(top_k=boost_pool, ...), boost, top_k)`` returns, values = boosted fused
+        scores.  With ``collapse_by`` the whole boosted pool is then collapsed (``collapse_pool`` is not used), with ``mmr_lambda``
+        the boosted (and collapsed) pool's first ``mmr_pool`` rows are diversified."""
         if late_query_tokens is not None and mmr_lambda is not None:
             raise ValueError("late_query_tokens and mmr_lambda do not combine in one call: chain rerank_late() and diversify()")
         if operators:
@@ -425,6 +446,15 @@ class RetrievalService(SparseIndexViews):
             cpool = late if late is not None else collapse_pool_depth(top_k, collapse_pool, self._be.n_docs_total)
             if candidates is None:
                 cand = hybrid_depths(top_k, max(int(top_k), cpool, pool or 1, 1), self._be.n_docs_total)[1]
+        boosted = self._be.boost_spec(boost, None, top_k, "search_hybrid", exact=False)
+        bpool = None
+        if boosted is not None:
+            from .backend import collapse_pool_depth
+            if boost_pool is not None and not (1 <= int(boost_pool) <= 1024):
+                raise ValueError(f"boost_pool must be in [1, 1024], got {boost_pool}")
+            bpool = late if late is not None else collapse_pool_depth(top_k, boost_pool, self._be.n_docs_total)
+            if candidates is None:
+                cand = hybrid_depths(top_k, max(int(top_k), bpool, 1), self._be.n_docs_total)[1]
         results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
         live = [(qid, text) for qid, text in queries.items() if text and text.strip()]
         if k <= 0 or not live:
@@ -459,7 +489,32 @@ class RetrievalService(SparseIndexViews):
             return self._be.field_table().collapse_device(collapse.by, f_doc, f_score, f_count, min(kk, int(f_doc.shape[1])), collapse.per_group,
                                                           collapse.nulls)
 
-        if late is not None:
+        if boosted is not None:
+            import torch
+            from .boost import BoostFn
+            bfn = BoostFn(self._be.field_table(), boosted)
+            if late is not None:
+                from .late import stack_query_tokens
+                tokens = self._ensure_late()
+                q_tok, q_cnt = stack_query_tokens(late_query_tokens, [qid for qid, _ in live], tokens.dim)
+
+            def boosted_pool(f_doc, f_score, f_count):  # the fused triple, bpool deep, still on the device
+                if late is not None:  # the whole pool reranked first
+                    f_doc, f_score, f_count = tokens.rerank_device(torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device),
+                                                                   f_doc, f_count, late)[:3]
+                width = int(f_doc.shape[1])
+                keep = width if collapse is not None else min(pool, width) if pool is not None else min(k, width)
+                f_doc, f_score, f_count = bfn(f_doc, f_score, f_count, keep)
+                if collapse is not None:
+                    f_doc, f_score, f_count = collapsed(f_doc, f_score, f_count, k if pool is None else pool)[:3]
+                if pool is not None:
+                    d, r, _, n = self._dense.mmr_device(f_doc, f_score, f_count, min(k, int(f_doc.shape[1])), mmr_lambda, mmr_similarity)
+                    return d, r, n
+                return f_doc, f_score, f_count
+
+            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, bpool, fusion,
+                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=boosted_pool, **flt)
+        elif late is not None:
             import torch
             from .late import stack_query_tokens
             tokens = self._ensure_late()
@@ -649,6 +704,16 @@ class RetrievalService(SparseIndexViews):
         if self.host is None:
             raise ValueError("BM25 index not built. Call build_bm25_index() first.")
         return self._be.sort_results(results, by, order, nulls, top_k, "sort_results")
+
+    def boost_results(self, results, boost, top_k: Optional[int] = None):
+        """Result lists re-scored by field values: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it
+        -> ``{qid: {doc_id: boosted score}}``, the first ``top_k`` (None: all) by boosted score (``srx_boost_topk``; ties in corpus
+        order).  ``boost`` as :meth:`search_bm25` takes it, every ``boost_mode`` allowed; the result is relative to the lists
+        given.  ``ValueError``: a list deeper than 2048, an unknown doc id, what the spec gets wrong, no :meth:`set_doc_fields`, a
+        sharded index."""
+        if self.host is None:
+            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        return self._be.boost_results(results, boost, top_k, "boost_results")
 
     # -- late interaction (no reference counterpart) -----------------------------------------------------------
     def set_token_embeddings(self, token_embeddings, storage: str = "f16") -> None:
