@@ -289,6 +289,7 @@ def kernel_sources_sha256() -> str:
 def _deps():
     return [os.path.join(CSRC_DIR, f) for f in SOURCES] + [os.path.join(CSRC_DIR, "srx_common.h"), os.path.join(CSRC_DIR, "filter_common.h"),
                                                             os.path.join(CSRC_DIR, "desc_check.h"),
+                                                            os.path.join(CSRC_DIR, "field_common.h"),
                                                             os.path.join(CSRC_DIR, "half_common.h"),
                                                             os.path.join(CSRC_DIR, "mmr_common.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx.h"),

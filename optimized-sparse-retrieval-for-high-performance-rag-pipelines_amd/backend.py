@@ -162,8 +162,7 @@ class SparseBackend:
                 spec = terms.with_base(spec, queries)
                 spec.sparse = lambda: self.dev
         if where is not None:
-            if self._fields is None:
-                raise ValueError(f"{call}(where=...) needs the docs' fields: call set_doc_fields() first")
+            self._need_fields(call, "where=...")
             flds = field_filter_spec(self._fields, queries, where)
             if flds is not None:
                 self._refuse_sharded("where= needs")
@@ -174,6 +173,13 @@ class SparseBackend:
     def _refuse_sharded(self, what_needs: str) -> None:
         if self.sharded():
             raise ValueError(f"{what_needs} the whole index on one GPU (a sharded search takes no doc filter)")
+
+    def _need_fields(self, call: str, what: str, reason: Optional[str] = None) -> None:
+        """ValueError unless :meth:`set_fields` was called (``what``: the message's brackets) and, given a ``reason`` (its parenthesis), the index is on one GPU"""
+        if self._fields is None:
+            raise ValueError(f"{call}({what}) needs the docs' fields: call set_doc_fields() first")
+        if reason is not None and self.sharded():
+            raise ValueError(f"{call} needs the whole index on one GPU ({reason})")
 
     def _row_table(self) -> "RowOfIds":
         """doc id -> row of this index's doc ids, kept between calls"""
@@ -215,8 +221,7 @@ class SparseBackend:
             return None
         from . import _capi
         from .fields import check_collapse_args
-        if self._fields is None:
-            raise ValueError(f"{call}(collapse_by=...) needs the docs' fields: call set_doc_fields() first")
+        self._need_fields(call, "collapse_by=...")
         check_collapse_args(self._fields, by, per_group, nulls)
         if int(top_k) > _capi.SRX_MAX_K:
             raise ValueError(f"{call}(collapse_by=...) returns at most {_capi.SRX_MAX_K} rows per query, got top_k={top_k}")
@@ -224,6 +229,47 @@ class SparseBackend:
             raise ValueError(f"collapse_depth must be >= 1, got {depth}")
         self._refuse_sharded("collapse_by= needs")
         return CollapseSpec(by, int(per_group), nulls, None if depth is None else int(depth))
+
+    def result_lists(self, results, call: str, cap: Optional[int] = None, scored: bool = True):
+        """``results`` = ``{qid: {doc_id: score}}`` (or ``search_by_vector``'s lists of ``{"doc_id", "score"}`` dicts) as one candidate
+        block: ``(pairs = {qid: [(doc_id, score)]}, live, cand_doc, cand_count, score)`` -- the middle three as :func:`candidate_block`
+        returns them, with ``doc_base`` added (GLOBAL ids); ``score`` f32 of cand_doc's shape, 0 behind a list's end (None unless
+        ``scored``).  ValueError: a list deeper than ``cap`` (the message names ``call``), then an unknown doc id."""
+        as_pairs = lambda row: [(r["doc_id"], r["score"] if scored else None) for r in row] if isinstance(row, (list, tuple)) else list(row.items())
+        pairs = {qid: as_pairs(row) for qid, row in results.items()}
+        deepest = max((len(p) for p in pairs.values()), default=0)
+        if cap is not None and deepest > cap:
+            raise ValueError(f"{call} takes lists of at most {cap} docs, got {deepest} (no silent truncation)")
+        _, live, cand_doc, cand_count = self.candidate_block(results, {qid: [d for d, _ in p] for qid, p in pairs.items()})
+        score = np.zeros(cand_doc.shape, dtype=np.float32) if scored else None
+        for i, (qid, _, _) in enumerate(live if scored else ()):
+            score[i, : len(pairs[qid])] = [s for _, s in pairs[qid]]
+        return pairs, live, cand_doc + np.int32(self.doc_base), cand_count, score
+
+    def collapse_results(self, results, by, top_k=10, per_group=1, nulls="own", call: str = "collapse"):
+        """Result lists collapsed by the field ``by`` (``srx_collapse_topk``): what ``RetrievalService.collapse`` documents.  One
+        upload, one launch, one copy back; list-shaped rows come back list-shaped, ``{}`` stays ``{}``."""
+        from . import _capi
+        from .fields import check_collapse_args
+        self._need_fields(call, "...")
+        check_collapse_args(self._fields, by, per_group, nulls)
+        self._need_fields(call, "...", "the columns are shard-local")
+        if not results:
+            return {}
+        _, live, cand_doc, cand_count, _ = self.result_lists(results, call, scored=False)
+        m = int(cand_doc.shape[1])
+        if m > _capi.SRX_COLLAPSE_MAX_M:  # its own line: this door names an unknown doc id first, and words the depth its way
+            raise ValueError(f"{call} takes lists of at most {_capi.SRX_COLLAPSE_MAX_M} docs, got one of {m} (no silent truncation)")
+        as_rows = {qid: isinstance(row, (list, tuple)) for qid, row in results.items()}
+        out = {qid: ([] if as_rows[qid] else {}) for qid in results}
+        if not live or int(top_k) <= 0:
+            return out
+        score = np.zeros(cand_doc.shape, dtype=np.float32)  # never looked at: the values come back by position
+        _, _, count, pos = self.field_table().collapse(by, cand_doc, score, cand_count, min(int(top_k), m), per_group, nulls, want_pos=True)
+        for i, (qid, _, cands) in enumerate(live):
+            kept = [int(pos[i, j]) for j in range(int(count[i]))]
+            out[qid] = [results[qid][p] for p in kept] if as_rows[qid] else {cands[p]: results[qid][cands[p]] for p in kept}
+        return out
 
     def collapsed_search_arrays(self, q_ptr, q_term, q_weight, k: int, collapse: "CollapseSpec", filter=None, q_filter=None):
         """Host CSR batch -> host rows (doc, score, count) of the top ``k`` of the COLLAPSED complete ranking, exact:
@@ -266,8 +312,7 @@ class SparseBackend:
             return None
         from . import _capi
         from .boost import BoostResolver
-        if self._fields is None:
-            raise ValueError(f"{call}(boost=...) needs the docs' fields: call set_doc_fields() first")
+        self._need_fields(call, "boost=...")
         self._refuse_sharded("boost= needs")
         res = boost if isinstance(boost, BoostResolver) else BoostResolver(self._fields, boost)
         if int(top_k) > _capi.SRX_MAX_K:
@@ -325,25 +370,15 @@ class SparseBackend:
         out = {qid: {} for qid in (results or {})}
         if not results:
             return out
-        as_pairs = lambda row: [(r["doc_id"], r["score"]) for r in row] if isinstance(row, (list, tuple)) else list(row.items())
-        pairs = {qid: as_pairs(row) for qid, row in results.items()}
-        deepest = max((len(p) for p in pairs.values()), default=0)
-        if deepest > _capi.SRX_BOOST_MAX_M:
-            raise ValueError(f"{call} takes lists of at most {_capi.SRX_BOOST_MAX_M} docs, got {deepest} (no silent truncation)")
-        _, live, cand_doc, cand_count = self.candidate_block(results, {qid: [d for d, _ in p] for qid, p in pairs.items()})
+        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, _capi.SRX_BOOST_MAX_M)
         if not live:
             return out
         import torch
         from .boost import BoostFn
         table = self.field_table()
         m = cand_doc.shape[1]
-        score = np.zeros((len(live), m), dtype=np.float32)
-        for i, (qid, _, _) in enumerate(live):
-            score[i, : len(pairs[qid])] = [s for _, s in pairs[qid]]
         k = m if top_k is None else min(int(top_k), m)
-        _, ns, cnt, pos = BoostFn(table, res)(torch.as_tensor(cand_doc + np.int32(self.doc_base), device=table.device),
-                                              torch.as_tensor(score, device=table.device), torch.as_tensor(cand_count, device=table.device), k,
-                                              want_pos=True)
+        _, ns, cnt, pos = BoostFn(table, res)(*(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k, want_pos=True)
         block = torch.cat([pos, cnt.reshape(-1, 1), ns.view(torch.int32)], dim=1).cpu().numpy()
         for i, (qid, _, _) in enumerate(live):
             n = int(block[i, k])
@@ -356,10 +391,7 @@ class SparseBackend:
         bins) -- as ``{name: fields.FacetSpec}`` (:func:`~.fields.check_facet_args`).  ValueError: no :meth:`set_fields` (the
         message names ``call``), a sharded index, no field, an unknown field, a spec that does not fit."""
         from .fields import check_facet_args
-        if self._fields is None:
-            raise ValueError(f"{call}(...) needs the docs' fields: call set_doc_fields() first")
-        if self.sharded():
-            raise ValueError(f"{call} needs the whole index on one GPU (the columns and the filter rows are shard-local)")
+        self._need_fields(call, "...", "the columns and the filter rows are shard-local")
         if isinstance(fields, str):
             fields = [fields]
         given = dict(fields) if isinstance(fields, dict) else {name: None for name in (fields or ())}
@@ -441,13 +473,12 @@ class SparseBackend:
         out = {qid: {name: facet_dict(fs, None, (0, 0, 0), top) for name, fs in specs.items()} for qid in (results or {})}
         if not results:
             return out
-        lists = {qid: ([r["doc_id"] for r in row] if isinstance(row, (list, tuple)) else list(row)) for qid, row in results.items()}
-        _, live, cand_doc, cand_count = self.candidate_block(results, lists)
+        _, live, cand_doc, cand_count, _ = self.result_lists(results, call, scored=False)
         if not live:
             return out
         import torch
         table = self.field_table()
-        doc = torch.as_tensor(cand_doc + np.int32(self.doc_base), device=table.device)
+        doc = torch.as_tensor(cand_doc, device=table.device)
         cnt = torch.as_tensor(cand_count, device=table.device)
         parts = []
         for name, fs in specs.items():
@@ -465,10 +496,7 @@ class SparseBackend:
         """The column ``by`` of :meth:`set_fields` for an ordering door; ValueError: no fields (the message names ``call``), a sharded
         index, and what :func:`~.fields.check_order_args` refuses."""
         from .fields import check_order_args
-        if self._fields is None:
-            raise ValueError(f"{call}(...) needs the docs' fields: call set_doc_fields() first")
-        if self.sharded():
-            raise ValueError(f"{call} needs the whole index on one GPU (the columns and the filter rows are shard-local)")
+        self._need_fields(call, "...", "the columns and the filter rows are shard-local")
         check_order_args(self._fields, by, order, nulls)
         return self._fields[by]
 
@@ -530,23 +558,14 @@ class SparseBackend:
         out = {qid: {} for qid in (results or {})}
         if not results:
             return out
-        as_pairs = lambda row: [(r["doc_id"], r["score"]) for r in row] if isinstance(row, (list, tuple)) else list(row.items())
-        pairs = {qid: as_pairs(row) for qid, row in results.items()}
-        deepest = max((len(p) for p in pairs.values()), default=0)
-        if deepest > _capi.SRX_ORDER_MAX_M:
-            raise ValueError(f"{call} takes lists of at most {_capi.SRX_ORDER_MAX_M} docs, got {deepest} (no silent truncation)")
-        _, live, cand_doc, cand_count = self.candidate_block(results, {qid: [d for d, _ in p] for qid, p in pairs.items()})
+        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, _capi.SRX_ORDER_MAX_M)
         if not live:
             return out
         import torch
         table = self.field_table()
         m = cand_doc.shape[1]
-        score = np.zeros((len(live), m), dtype=np.float32)
-        for i, (qid, _, _) in enumerate(live):
-            score[i, : len(pairs[qid])] = [s for _, s in pairs[qid]]
         k = m if top_k is None else min(int(top_k), m)
-        d, _, _, extra, pos = table.sort_lists_device(by, torch.as_tensor(cand_doc + np.int32(self.doc_base), device=table.device),
-                                                      torch.as_tensor(score, device=table.device), torch.as_tensor(cand_count, device=table.device), k,
+        _, _, _, extra, pos = table.sort_lists_device(by, *(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k,
                                                       order, nulls, want_pos=True)
         block = torch.cat([pos, extra], dim=1).cpu().numpy()
         for i, (qid, _, _) in enumerate(live):

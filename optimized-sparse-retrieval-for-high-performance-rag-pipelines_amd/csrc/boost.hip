@@ -23,7 +23,9 @@
 //
 // A sort, not a selection: k goes up to m + kc and the output is ranked, so a selection would still sort its k survivors; the
 // sort network is the one order.hip uses for its lists, restated here for a 64-bit key (that unit is neither edited nor included).
-#include "filter_common.h"
+//
+// The checks of the columns and of n_docs / doc_base and the column helpers are field_common.h's; the carry's checks are woven into the list's, which stay here.
+#include "field_common.h"
 #include "boost/sparse_rx_boost.h"
 
 #pragma clang fp contract(off)
@@ -77,14 +79,15 @@ __device__ __forceinline__ uint32_t bs_unmap(uint32_t u) { return u == 0u ? 0x7F
 // g_c of the header for the local doc d < n_docs
 __device__ __forceinline__ float bs_factor(const BoostCurve &c, uint32_t d) {
     if (c.type < 0) return c.weight * c.missing;
-    if (c.valid != nullptr && !(((uint32_t)gload_i32((const int32_t *)c.valid + (d >> 5)) >> (d & 31)) & 1u)) return c.weight * c.missing;
+    if (c.valid != nullptr && !srx_field_valid_bit(c.valid, d)) return c.weight * c.missing;
     float x;
     if (c.type == SRX_FIELD_F32) {
-        const uint32_t b = (uint32_t)((const SRX_GLOBAL int32_t *)c.data)[d];
+        const uint32_t b = (uint32_t)srx_field_i32(c.data, d);
         if ((b & 0x7FFFFFFFu) > 0x7F800000u) return c.weight * c.missing;
         x = __uint_as_float(b) - __uint_as_float((uint32_t)c.origin);
     } else {
-        const int64_t v = c.type == SRX_FIELD_I64 ? ((const SRX_GLOBAL int64_t *)c.data)[d] : (int64_t)((const SRX_GLOBAL int32_t *)c.data)[d];
+        // written out: through srx_field_load the kernel compiles to other code
+        const int64_t v = c.type == SRX_FIELD_I64 ? srx_field_i64(c.data, d) : (int64_t)srx_field_i32(c.data, d);
         x = (float)((double)v - (double)c.origin);
     }
     if (c.abs) x = fabsf(x);
@@ -228,16 +231,9 @@ SRX_API int srx_boost_topk(int32_t device, const srx_field_col *cols, int32_t n_
     static_assert(sizeof(srx_boost_clause) == 40, "srx_boost_clause is 40 bytes");
     if (!cols) return fail(SRX_ERR_INVALID, "%s: null cols", who);
     if (n_cols < 1 || n_cols > SRX_BOOST_MAX_COLS) return fail(SRX_ERR_INVALID, "%s: n_cols must be in [1, 8]", who);
-    for (int j = 0; j < n_cols; ++j) {
-        const int t = cols[j].type;
-        if (t == SRX_FIELD_SET64) return fail(SRX_ERR_INVALID, "%s: a SET64 column is no number to boost by", who);
-        if (t != SRX_FIELD_I32 && t != SRX_FIELD_I64 && t != SRX_FIELD_F32) return fail(SRX_ERR_INVALID, "%s: unknown column type", who);
-        if (!cols[j].data) return fail(SRX_ERR_INVALID, "%s: a column with null data", who);
-        if ((uintptr_t)cols[j].data & (t == SRX_FIELD_I64 ? 7 : 3)) return fail(SRX_ERR_INVALID, "%s: column data must be aligned for its type", who);
-        if ((uintptr_t)cols[j].valid & 15) return fail(SRX_ERR_INVALID, "%s: a validity row must be 16-byte aligned", who);
-    }
-    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
-    if (doc_base < 0) return fail(SRX_ERR_INVALID, "%s: negative doc_base", who);
+    int rc = srx_check_field_cols(who, cols, n_cols, SRX_FIELD_TYPES_NUMBER, "a SET64 column is no number to boost by");
+    if (rc == SRX_OK) rc = srx_check_field_docs(who, n_docs, doc_base, false);
+    if (rc != SRX_OK) return rc;
     if (n_clauses < 1 || n_clauses > SRX_BOOST_MAX_CLAUSES) return fail(SRX_ERR_INVALID, "%s: n_clauses must be in [1, 8]", who);
     if (n_knots < 2 || n_knots > SRX_BOOST_MAX_KNOTS) return fail(SRX_ERR_INVALID, "%s: n_knots must be in [2, 2^24]", who);
     if (score_mode < SRX_BOOST_SCORE_MULTIPLY || score_mode > SRX_BOOST_SCORE_MIN) return fail(SRX_ERR_INVALID, "%s: unknown score_mode", who);

@@ -22,9 +22,10 @@
 //            list order.  Places below k are stored, the tail of the row from min(k, survivors) on is padded.
 //
 // A list of at most 64 positions is one wavefront: its barriers are wave barriers.
-#include "filter_common.h"
+//
+// The checks of the column, of n_docs / doc_base and of the lists, the validity bit and the column load are field_common.h's.
+#include "field_common.h"
 #include "sparse_rx_collapse.h"
-#include "sparse_rx_fields.h"
 
 namespace {
 
@@ -76,10 +77,10 @@ __global__ __launch_bounds__(NT) void srx_collapse_kernel(CollapseArgs a) {
             const int64_t local = (int64_t)doc[r] - a.doc_base;
             if (local >= 0 && local < a.n_docs) {
                 bool has = true;
-                if (a.valid != nullptr) has = ((uint32_t)gload_i32((const int32_t *)a.valid + (local >> 5)) >> (local & 31)) & 1u;
+                if (a.valid != nullptr) has = srx_field_valid_bit(a.valid, local);
                 if (has) {
                     cls[r] = 1;
-                    key[r] = a.wide ? ((const SRX_GLOBAL int64_t *)a.data)[local] : (int64_t)((const SRX_GLOBAL int32_t *)a.data)[local];
+                    key[r] = srx_field_load(a.data, a.wide, false, local);
                 } else if (a.null_policy != SRX_COLLAPSE_NULL_DROP) {
                     cls[r] = 2;
                     key[r] = a.null_policy == SRX_COLLAPSE_NULL_OWN ? (int64_t)i : 0;
@@ -168,23 +169,16 @@ SRX_API int srx_collapse_topk(int32_t device, const srx_field_col *col, int64_t 
                               int32_t *out_group_size, void *stream_v) {
     const char *who = "srx_collapse_topk";
     if (!col) return fail(SRX_ERR_INVALID, "%s: null col", who);
-    if (col->type != SRX_FIELD_I32 && col->type != SRX_FIELD_I64)
-        return fail(SRX_ERR_INVALID, "%s: the column must be SRX_FIELD_I32 or SRX_FIELD_I64 (F32 and SET64 columns are no group keys)", who);
-    if (!col->data) return fail(SRX_ERR_INVALID, "%s: a column with null data", who);
-    if ((uintptr_t)col->data & (col->type == SRX_FIELD_I64 ? 7 : 3)) return fail(SRX_ERR_INVALID, "%s: column data must be aligned for its type", who);
-    if ((uintptr_t)col->valid & 15) return fail(SRX_ERR_INVALID, "%s: a validity row must be 16-byte aligned", who);
-    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
-    if (doc_base < 0) return fail(SRX_ERR_INVALID, "%s: negative doc_base", who);
-    if (m < 1 || m > CL_MAX_M) return fail(SRX_ERR_INVALID, "%s: m must be in [1, 2048]", who);
-    if (k < 1 || k > m) return fail(SRX_ERR_INVALID, "%s: k must be in [1, m]", who);
+    int rc = srx_check_field_cols(who, col, 1, SRX_FIELD_TYPES_INT,
+                                  "the column must be SRX_FIELD_I32 or SRX_FIELD_I64 (F32 and SET64 columns are no group keys)", true);
+    if (rc == SRX_OK) rc = srx_check_field_docs(who, n_docs, doc_base, false);
+    if (rc == SRX_OK) rc = srx_check_list_shape(who, m, CL_MAX_M, k);
+    if (rc != SRX_OK) return rc;
     if (per_group < 1) return fail(SRX_ERR_INVALID, "%s: per_group must be >= 1", who);
     if (null_policy != SRX_COLLAPSE_NULL_OWN && null_policy != SRX_COLLAPSE_NULL_ONE && null_policy != SRX_COLLAPSE_NULL_DROP)
         return fail(SRX_ERR_INVALID, "%s: unknown null_policy", who);
-    if (nq < 0) return fail(SRX_ERR_INVALID, "%s: nq < 0", who);
-    if ((int64_t)nq * m > 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: nq * m must not exceed 2^31 - 1", who);
-    if (nq == 0) return SRX_OK;
-    if (!cand_doc || !cand_score) return fail(SRX_ERR_INVALID, "%s: null cand_doc / cand_score", who);
-    if (!out_doc || !out_score || !out_count) return fail(SRX_ERR_INVALID, "%s: null out_doc / out_score / out_count", who);
+    rc = srx_check_lists(who, nq, m, cand_doc, cand_score, out_doc && out_score && out_count, "null out_doc / out_score / out_count");
+    if (rc != SRX_OK) return rc < 0 ? rc : SRX_OK;  // SRX_LISTS_EMPTY: nothing to do
     HIP_TRY(hipSetDevice(device));
     CollapseArgs a;
     a.data = col->data, a.valid = col->valid;

@@ -33,7 +33,9 @@
 //
 // List form.  One workgroup per list, the live rule of collapse.hip, gathered values, the same adds; the workgroup owns its
 // output row and stores it: no global atomics.
-#include "filter_common.h"
+//
+// The checks of the column and of n_docs / doc_base and the column helpers are field_common.h's; the list form keeps its list checks (nq before m, no cap).
+#include "field_common.h"
 #include "sparse_rx_facets.h"
 
 namespace {
@@ -68,14 +70,8 @@ struct FacetArgs {
 
 template <int KIND>
 __device__ __forceinline__ int64_t fc_load(const void *data, uint32_t d) {
-    if constexpr (KIND == K_CODES_I32 || KIND == K_EDGES_I32) return (int64_t)((const SRX_GLOBAL int32_t *)data)[d];
-    else if constexpr (KIND == K_EDGES_F32) return (int64_t)(uint32_t)((const SRX_GLOBAL int32_t *)data)[d];  // the float's bits
-    else return ((const SRX_GLOBAL int64_t *)data)[d];
-}
-
-__device__ __forceinline__ uint4 fc_load_words(const uint32_t *row, int64_t w) {  // w a multiple of 4, w + 3 < words
-    const srx_i4u v = gload_i4((const int32_t *)(row + w));
-    return make_uint4((uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w);
+    constexpr bool f32 = KIND == K_EDGES_F32;
+    return srx_field_load(data, !f32 && KIND != K_CODES_I32 && KIND != K_EDGES_I32, f32, d);
 }
 
 // ---- the binning functions: one per mode, shared by both kernels (tests/facets_ref.py restates them)
@@ -197,14 +193,14 @@ __global__ __launch_bounds__(THREADS) void srx_facet_rows_kernel(FacetArgs a) {
                 acc = make_uint4(srx_filter_word_docs(a.n_docs, w_lane * 32), srx_filter_word_docs(a.n_docs, w_lane * 32 + 32),
                                  srx_filter_word_docs(a.n_docs, w_lane * 32 + 64), srx_filter_word_docs(a.n_docs, w_lane * 32 + 96));
                 if (brow != nullptr) {
-                    const uint4 bw = fc_load_words(brow, w_lane);
+                    const uint4 bw = srx_field_row_words(brow, w_lane);
                     acc.x &= bw.x, acc.y &= bw.y, acc.z &= bw.z, acc.w &= bw.w;
                 }
             }
             const uint64_t nz = __ballot((acc.x | acc.y | acc.z | acc.w) != 0u);
             if (nz == 0ull) continue;
             uint4 ok = make_uint4(~0u, ~0u, ~0u, ~0u);
-            if (a.valid != nullptr && inside) ok = fc_load_words(a.valid, w_lane);
+            if (a.valid != nullptr && inside) ok = srx_field_row_words(a.valid, w_lane);
             uint64_t pairs = (nz | (nz >> 1)) & 0x5555555555555555ull;  // bit 2 p: lane 2 p or 2 p + 1 holds a doc
             while (pairs != 0ull) {
                 const int j = __ffsll((unsigned long long)pairs) - 1;  // even: j + 1 <= 63
@@ -285,7 +281,7 @@ __global__ __launch_bounds__(THREADS) void srx_facet_lists_kernel(FacetArgs a) {
             const int64_t local = (int64_t)gload_i32(row_doc + i) - a.doc_base;
             if (local >= 0 && local < a.n_docs) {
                 on = has = true;
-                if (a.valid != nullptr) has = ((uint32_t)gload_i32((const int32_t *)a.valid + (local >> 5)) >> (local & 31)) & 1u;
+                if (a.valid != nullptr) has = srx_field_valid_bit(a.valid, local);
                 if (has) v = fc_load<KIND>(a.data, (uint32_t)local);
             }
         }
@@ -312,12 +308,10 @@ __global__ __launch_bounds__(THREADS) void srx_facet_lists_kernel(FacetArgs a) {
 // what both entry points check of the column and the bins; the binning kind (K_*) or a negative code
 int check_col_bins(const char *who, const srx_field_col *col, int64_t n_docs, const srx_facet_bins *bins) {
     if (!col) return fail(SRX_ERR_INVALID, "%s: null col", who);
+    int rc = srx_check_field_cols(who, col, 1, SRX_FIELD_TYPES_ALL, nullptr);
+    if (rc == SRX_OK) rc = srx_check_field_docs(who, n_docs, 0, false);  // doc_base comes behind the bins (srx_facet_counts_lists)
+    if (rc != SRX_OK) return rc;
     const int t = col->type;
-    if (t != SRX_FIELD_I32 && t != SRX_FIELD_I64 && t != SRX_FIELD_F32 && t != SRX_FIELD_SET64) return fail(SRX_ERR_INVALID, "%s: unknown column type", who);
-    if (!col->data) return fail(SRX_ERR_INVALID, "%s: a column with null data", who);
-    if ((uintptr_t)col->data & (t == SRX_FIELD_I64 || t == SRX_FIELD_SET64 ? 7 : 3)) return fail(SRX_ERR_INVALID, "%s: column data must be aligned for its type", who);
-    if ((uintptr_t)col->valid & 15) return fail(SRX_ERR_INVALID, "%s: a validity row must be 16-byte aligned", who);
-    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
     if (!bins) return fail(SRX_ERR_INVALID, "%s: null bins", who);
     const int mode = bins->mode;
     if (mode != SRX_FACET_CODES && mode != SRX_FACET_LABELS && mode != SRX_FACET_EDGES) return fail(SRX_ERR_INVALID, "%s: unknown bins mode", who);
@@ -416,8 +410,8 @@ SRX_API int srx_facet_counts_lists(int32_t device, const srx_field_col *col, int
     const char *who = "srx_facet_counts_lists";
     const int kind = check_col_bins(who, col, n_docs, bins);
     if (kind < 0) return kind;
-    if (doc_base < 0) return fail(SRX_ERR_INVALID, "%s: negative doc_base", who);
-    if (doc_base + n_docs >= 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: doc_base + n_docs must be below 2^31 - 1", who);
+    const int rc = srx_check_field_docs(who, n_docs, doc_base, true);  // n_docs is checked: what is left is doc_base and the bound
+    if (rc != SRX_OK) return rc;
     if (nq < 0) return fail(SRX_ERR_INVALID, "%s: nq < 0", who);
     if (m < 1) return fail(SRX_ERR_INVALID, "%s: m must be >= 1", who);
     if ((int64_t)nq * m > 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: nq * m must not exceed 2^31 - 1", who);

@@ -32,8 +32,9 @@
 //
 // A clause id outside [0, n_clauses), a col outside [0, n_cols) and an op that does not fit the column's type give "no doc":
 // -1 is the legal spelling of the first, the others are precondition violations that the kernel does not turn into a wild read.
-#include "filter_common.h"
-#include "sparse_rx_fields.h"
+//
+// This unit also defines the host checks of field_common.h, which the units over these columns share.
+#include "field_common.h"
 
 namespace {
 
@@ -57,16 +58,6 @@ struct FieldsArgs {
     int64_t n_docs, words;
     int n_cols, n_clauses, n_rows, batch_rows, n_batches;
 };
-
-// doc indices are 32-bit (n_docs < 2^31, and a chunk's tail lies below 2^31 + 2048): one v_min and one shift-add per load
-__device__ __forceinline__ int32_t fload_i32(const void *p, uint32_t i) { return ((const SRX_GLOBAL int32_t *)p)[i]; }
-__device__ __forceinline__ int64_t fload_i64(const void *p, uint32_t i) { return ((const SRX_GLOBAL int64_t *)p)[i]; }
-__device__ __forceinline__ float fload_f32(const void *p, uint32_t i) { return ((const SRX_GLOBAL float *)p)[i]; }
-// a lane's four words of a filter row (w is a multiple of 4 and w + 3 < words: rows are 16-byte aligned)
-__device__ __forceinline__ uint4 fload_words(const uint32_t *row, int64_t w) {
-    const srx_i4u v = gload_i4((const int32_t *)(row + w));
-    return make_uint4((uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w);
-}
 
 // the 64 doc bits of step s go to lane s >> 1: steps 2 j and 2 j + 1 are the four words lane j stores
 __device__ __forceinline__ void deposit(uint4 &k, int lane, int s, uint64_t bits) {
@@ -95,7 +86,7 @@ __device__ __forceinline__ uint4 clause_docs(const FieldsArgs &a, int c, int lan
     const uint32_t *valid = a.cols[col].valid;
     const int type = a.cols[col].type;
     const uint32_t d_last = (uint32_t)(a.n_docs - 1);
-    uint32_t d[FD_STEPS];
+    uint32_t d[FD_STEPS];  // doc indices are 32-bit (n_docs < 2^31, and a chunk's tail lies below 2^31 + 2048): one v_min and one shift-add per load
 #pragma unroll
     for (int s = 0; s < FD_STEPS; ++s) d[s] = min(d_lane + 64u * s, d_last);
     if (type == SRX_FIELD_I32 || type == SRX_FIELD_I64) {
@@ -103,10 +94,10 @@ __device__ __forceinline__ uint4 clause_docs(const FieldsArgs &a, int c, int lan
         int64_t v[FD_STEPS];
         if (type == SRX_FIELD_I32) {
 #pragma unroll
-            for (int s = 0; s < FD_STEPS; ++s) v[s] = (int64_t)fload_i32(data, d[s]);
+            for (int s = 0; s < FD_STEPS; ++s) v[s] = (int64_t)srx_field_i32(data, d[s]);
         } else {
 #pragma unroll
-            for (int s = 0; s < FD_STEPS; ++s) v[s] = fload_i64(data, d[s]);
+            for (int s = 0; s < FD_STEPS; ++s) v[s] = srx_field_i64(data, d[s]);
         }
         if (op == SRX_FOP_RANGE) {
 #pragma unroll
@@ -127,7 +118,7 @@ __device__ __forceinline__ uint4 clause_docs(const FieldsArgs &a, int c, int lan
         if (op != SRX_FOP_RANGE && op != SRX_FOP_IN) return m;
         float v[FD_STEPS];
 #pragma unroll
-        for (int s = 0; s < FD_STEPS; ++s) v[s] = fload_f32(data, d[s]);
+        for (int s = 0; s < FD_STEPS; ++s) v[s] = srx_field_f32(data, d[s]);
         if (op == SRX_FOP_RANGE) {
             const float flo = __int_as_float((int)lo), fhi = __int_as_float((int)hi);
 #pragma unroll
@@ -150,14 +141,14 @@ __device__ __forceinline__ uint4 clause_docs(const FieldsArgs &a, int c, int lan
         const bool any = op == SRX_FOP_MASK_ANY;
         int64_t v[FD_STEPS];
 #pragma unroll
-        for (int s = 0; s < FD_STEPS; ++s) v[s] = fload_i64(data, d[s]);
+        for (int s = 0; s < FD_STEPS; ++s) v[s] = srx_field_i64(data, d[s]);
 #pragma unroll
         for (int s = 0; s < FD_STEPS; ++s) deposit(m, lane, s, __ballot(((v[s] & lo) == want) != any));
     } else {
         return m;
     }
     if (valid != nullptr && stores) {
-        const uint4 ok = fload_words(valid, w_lane);
+        const uint4 ok = srx_field_row_words(valid, w_lane);
         m.x &= ok.x, m.y &= ok.y, m.z &= ok.z, m.w &= ok.w;
     }
     return m;
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(THREADS) void srx_fields_kernel(FieldsArgs a) {
             if (wave_live) {
                 const int br = srx_filter_base_row(a.base_bits, a.base_q, r);
                 if (br >= 0 && stores) {
-                    const uint4 bw = fload_words(a.base_bits + (int64_t)br * a.words, w_lane);
+                    const uint4 bw = srx_field_row_words(a.base_bits + (int64_t)br * a.words, w_lane);
                     acc.x &= bw.x, acc.y &= bw.y, acc.z &= bw.z, acc.w &= bw.w;
                 }
                 int p0[3], p1[3];
@@ -226,28 +217,62 @@ __global__ __launch_bounds__(THREADS) void srx_fields_kernel(FieldsArgs a) {
     }
 }
 
+int refuse(const char *who, const char *what) {  // SRX_ERR_INVALID with the message "who: what"
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, what);
+    return SRX_ERR_INVALID;
+}
+
 }  // namespace
+
+int srx_check_field_cols(const char *who, const srx_field_col *cols, int n, unsigned admit, const char *unadmitted, bool unadmitted_any) {
+    for (int i = 0; i < n; ++i) {
+        const int t = cols[i].type;
+        const bool known = t >= 0 && t < 32 && (SRX_FIELD_TYPES_ALL >> t & 1u);
+        if (!known || !(admit >> t & 1u)) return refuse(who, known || unadmitted_any ? unadmitted : "unknown column type");
+        if (!cols[i].data) return refuse(who, "a column with null data");
+        if ((uintptr_t)cols[i].data & (t == SRX_FIELD_I64 || t == SRX_FIELD_SET64 ? 7 : 3)) return refuse(who, "column data must be aligned for its type");
+        if ((uintptr_t)cols[i].valid & 15) return refuse(who, "a validity row must be 16-byte aligned");
+    }
+    return SRX_OK;
+}
+
+int srx_check_field_docs(const char *who, int64_t n_docs, int64_t doc_base, bool bound_ids) {
+    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return refuse(who, "n_docs must be in [1, 2^31 - 2]");
+    if (doc_base < 0) return refuse(who, "negative doc_base");
+    if (bound_ids && doc_base + n_docs >= 0x7FFFFFFFll) return refuse(who, "doc_base + n_docs must be below 2^31 - 1");
+    return SRX_OK;
+}
+
+int srx_check_list_shape(const char *who, int32_t m, int32_t m_cap, int32_t k) {
+    if (m < 1 || m > m_cap) {
+        snprintf(g_err, sizeof(g_err), "%s: m must be in [1, %d]", who, m_cap);
+        return SRX_ERR_INVALID;
+    }
+    return k < 1 || k > m ? refuse(who, "k must be in [1, m]") : SRX_OK;
+}
+
+int srx_check_lists(const char *who, int32_t nq, int32_t m, const int32_t *cand_doc, const float *cand_score, bool have_outs, const char *null_outs) {
+    if (nq < 0) return refuse(who, "nq < 0");
+    if ((int64_t)nq * m > 0x7FFFFFFFll) return refuse(who, "nq * m must not exceed 2^31 - 1");
+    if (nq == 0) return SRX_LISTS_EMPTY;
+    if (!cand_doc || !cand_score) return refuse(who, "null cand_doc / cand_score");
+    return have_outs ? SRX_OK : refuse(who, null_outs);
+}
 
 SRX_API int srx_filter_from_fields(int32_t device, int64_t n_docs, const srx_field_col *cols, int32_t n_cols, const srx_field_clause *clauses,
                                    int32_t n_clauses, const int64_t *values, int32_t n_rows, const int32_t *all_ptr, const int32_t *all_clause,
                                    const int32_t *any_ptr, const int32_t *any_clause, const int32_t *none_ptr, const int32_t *none_clause,
                                    const srx_doc_filter *base, uint32_t *out_bits, void *stream_v) {
     const char *who = "srx_filter_from_fields";
-    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
+    int rc = srx_check_field_docs(who, n_docs, 0, false);
+    if (rc != SRX_OK) return rc;
     if (n_cols < 1 || n_cols > FD_MAX_COLS) return fail(SRX_ERR_INVALID, "%s: n_cols must be in [1, 32]", who);
     if (!cols) return fail(SRX_ERR_INVALID, "%s: null cols", who);
-    for (int i = 0; i < n_cols; ++i) {
-        const int t = cols[i].type;
-        if (t != SRX_FIELD_I32 && t != SRX_FIELD_I64 && t != SRX_FIELD_F32 && t != SRX_FIELD_SET64)
-            return fail(SRX_ERR_INVALID, "%s: unknown column type", who);
-        if (!cols[i].data) return fail(SRX_ERR_INVALID, "%s: a column with null data", who);
-        if ((uintptr_t)cols[i].data & (t == SRX_FIELD_I64 || t == SRX_FIELD_SET64 ? 7 : 3))
-            return fail(SRX_ERR_INVALID, "%s: column data must be aligned for its type", who);
-        if ((uintptr_t)cols[i].valid & 15) return fail(SRX_ERR_INVALID, "%s: a validity row must be 16-byte aligned", who);
-    }
+    rc = srx_check_field_cols(who, cols, n_cols, SRX_FIELD_TYPES_ALL, nullptr);
+    if (rc != SRX_OK) return rc;
     if (n_clauses < 0) return fail(SRX_ERR_INVALID, "%s: n_clauses < 0", who);
     if (n_clauses > 0 && !clauses) return fail(SRX_ERR_INVALID, "%s: null clauses", who);
-    const int rc = srx_check_row_builder(who, "clause", n_rows, all_ptr, all_clause, any_ptr, any_clause, none_ptr, none_clause, out_bits, base);
+    rc = srx_check_row_builder(who, "clause", n_rows, all_ptr, all_clause, any_ptr, any_clause, none_ptr, none_clause, out_bits, base);
     if (rc != SRX_OK) return rc;
     if (n_rows == 0) return SRX_OK;
     HIP_TRY(hipSetDevice(device));

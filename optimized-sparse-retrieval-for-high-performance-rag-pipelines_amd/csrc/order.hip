@@ -32,7 +32,9 @@
 // 2048 ranks, the first k are written.
 //
 // Integer work only, LDS atomics only (the list's fill): every workgroup owns the words it writes.
-#include "filter_common.h"
+//
+// The checks of the column, of n_docs / doc_base and of the lists, the validity bit and the column load are field_common.h's.
+#include "field_common.h"
 #include "order/sparse_rx_order.h"
 
 namespace {
@@ -87,13 +89,11 @@ struct OrderShared {
 
 // ---- the value of a doc (tests/order_ref.py restates these)
 __device__ __forceinline__ bool od_valid_bit(const uint32_t *valid, uint32_t d) {
-    return valid == nullptr || (((uint32_t)gload_i32((const int32_t *)valid + (d >> 5)) >> (d & 31)) & 1u);
+    return valid == nullptr || srx_field_valid_bit(valid, d);
 }
 // the value as out_key holds it; d < n_docs
 __device__ __forceinline__ int64_t od_raw(const OrderArgs &a, uint32_t d) {
-    if (a.type == SRX_FIELD_I64) return ((const SRX_GLOBAL int64_t *)a.data)[d];
-    const int32_t w = ((const SRX_GLOBAL int32_t *)a.data)[d];
-    return a.type == SRX_FIELD_F32 ? (int64_t)(uint32_t)w : (int64_t)w;
+    return srx_field_load(a.data, a.type == SRX_FIELD_I64, a.type == SRX_FIELD_F32, d);
 }
 // u of the header comment; false: a NaN, no value
 __device__ __forceinline__ bool od_map(const OrderArgs &a, int64_t raw, uint64_t &u) {
@@ -384,18 +384,11 @@ int64_t od_seg_docs(int k) {
 // what both entry points check of the column, the index and the order
 int check_order(const char *who, const srx_field_col *col, int64_t n_docs, int64_t doc_base, int order, int nulls) {
     if (!col) return fail(SRX_ERR_INVALID, "%s: null col", who);
-    const int t = col->type;
-    if (t == SRX_FIELD_SET64) return fail(SRX_ERR_INVALID, "%s: a SET64 column has no order", who);
-    if (t != SRX_FIELD_I32 && t != SRX_FIELD_I64 && t != SRX_FIELD_F32) return fail(SRX_ERR_INVALID, "%s: unknown column type", who);
-    if (!col->data) return fail(SRX_ERR_INVALID, "%s: a column with null data", who);
-    if ((uintptr_t)col->data & (t == SRX_FIELD_I64 ? 7 : 3)) return fail(SRX_ERR_INVALID, "%s: column data must be aligned for its type", who);
-    if ((uintptr_t)col->valid & 15) return fail(SRX_ERR_INVALID, "%s: a validity row must be 16-byte aligned", who);
+    const int rc = srx_check_field_cols(who, col, 1, SRX_FIELD_TYPES_NUMBER, "a SET64 column has no order");
+    if (rc != SRX_OK) return rc;
     if (order != SRX_ORDER_ASC && order != SRX_ORDER_DESC) return fail(SRX_ERR_INVALID, "%s: unknown order", who);
     if (nulls != SRX_ORDER_NULLS_LAST && nulls != SRX_ORDER_NULLS_FIRST && nulls != SRX_ORDER_NULLS_DROP) return fail(SRX_ERR_INVALID, "%s: unknown nulls mode", who);
-    if (n_docs < 1 || n_docs > SRX_FILTER_MAX_DOCS) return fail(SRX_ERR_INVALID, "%s: n_docs must be in [1, 2^31 - 2]", who);
-    if (doc_base < 0) return fail(SRX_ERR_INVALID, "%s: negative doc_base", who);
-    if (doc_base + n_docs >= 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: doc_base + n_docs must be below 2^31 - 1", who);
-    return SRX_OK;
+    return srx_check_field_docs(who, n_docs, doc_base, true);  // out_doc holds doc_base + d as an int32
 }
 
 void fill_col(OrderArgs &a, const srx_field_col *col, int64_t n_docs, int64_t doc_base, int order, int nulls, int k) {
@@ -464,15 +457,10 @@ SRX_API int srx_order_lists(int32_t device, const srx_field_col *col, int64_t n_
                             const int32_t *cand_doc, const float *cand_score, const int32_t *cand_count, int32_t nq, int32_t m, int32_t k,
                             int32_t *out_doc, float *out_score, int64_t *out_key, int32_t *out_pos, int32_t *out_extra, void *stream_v) {
     const char *who = "srx_order_lists";
-    const int rc = check_order(who, col, n_docs, doc_base, order, nulls);
-    if (rc != SRX_OK) return rc;
-    if (m < 1 || m > SRX_ORDER_MAX_M) return fail(SRX_ERR_INVALID, "%s: m must be in [1, 2048]", who);
-    if (k < 1 || k > m) return fail(SRX_ERR_INVALID, "%s: k must be in [1, m]", who);
-    if (nq < 0) return fail(SRX_ERR_INVALID, "%s: nq < 0", who);
-    if ((int64_t)nq * m > 0x7FFFFFFFll) return fail(SRX_ERR_INVALID, "%s: nq * m must not exceed 2^31 - 1", who);
-    if (nq == 0) return SRX_OK;
-    if (!cand_doc || !cand_score) return fail(SRX_ERR_INVALID, "%s: null cand_doc / cand_score", who);
-    if (!out_doc || !out_score || !out_key || !out_extra) return fail(SRX_ERR_INVALID, "%s: null out_doc / out_score / out_key / out_extra", who);
+    int rc = check_order(who, col, n_docs, doc_base, order, nulls);
+    if (rc == SRX_OK) rc = srx_check_list_shape(who, m, SRX_ORDER_MAX_M, k);
+    if (rc == SRX_OK) rc = srx_check_lists(who, nq, m, cand_doc, cand_score, out_doc && out_score && out_key && out_extra, "null out_doc / out_score / out_key / out_extra");
+    if (rc != SRX_OK) return rc < 0 ? rc : SRX_OK;  // SRX_LISTS_EMPTY: nothing to do
     HIP_TRY(hipSetDevice(device));
     OrderArgs a;
     fill_col(a, col, n_docs, doc_base, order, nulls, k);

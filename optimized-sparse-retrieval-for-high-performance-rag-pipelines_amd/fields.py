@@ -35,6 +35,9 @@ def _torch():
     return torch
 
 
+_ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # what a C entry point takes for an optional or empty tensor
+
+
 class HostColumn:
     """One column on the host: ``kind`` ("int32", "int64", "float32", "bool", "category", "set"), ``type`` (its SRX_FIELD_*),
     ``data`` (the array that goes to the device: int32 / int64 / float32; int64 holds a set's bits), ``valid`` (bool[n_docs],
@@ -624,6 +627,93 @@ class FieldTable:
             arr[i].data, arr[i].valid, arr[i].type = data.data_ptr(), (None if valid is None else valid.data_ptr()), self.columns[name].type
         return arr
 
+    def _col_desc(self, column: str):
+        """The descriptor of one named column; ValueError "unknown field" / "the table is closed" """
+        return self._col_descs([column])
+
+    def _list_triple(self, who: str, cap, doc, score, count, scored: bool = True):
+        """The ``(doc, score, count)`` device tensors of result lists, checked for the door ``who``: doc int32 [nq, m], m in
+        [1, cap] (``cap`` None: m >= 1), score float32 of doc's shape (not looked at unless ``scored``), count int32 [nq] or None,
+        all on the table's device.  Returns them contiguous, then nq and m."""
+        torch = _torch()
+        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32 or (cap is None and int(doc.shape[1]) < 1):
+            raise ValueError(f"{who}: doc must be an int32 tensor [nq, m{'' if cap else ' >= 1'}]")
+        nq, m = int(doc.shape[0]), int(doc.shape[1])
+        if cap is not None and not (1 <= m <= cap):
+            raise ValueError(f"{who} takes lists of 1 to {cap} positions, got {m} (no silent truncation)")
+        if not scored:
+            score = None
+        elif not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or tuple(score.shape) != (nq, m):
+            raise ValueError(f"{who}: score must be a float32 tensor of doc's shape")
+        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
+            raise ValueError(f"{who}: count must be an int32 tensor [nq]")
+        for t, what in ((doc, "doc"), (score, "score"), (count, "count")):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"{who}: {what} is on {t.device}, the table on {self.device}")
+        return doc.contiguous(), None if score is None else score.contiguous(), None if count is None else count.contiguous(), nq, m
+
+    @staticmethod
+    def _check_k(who: str, k, top: int, top_name: str = "m") -> int:
+        k = int(k)
+        if not (1 <= k <= top):
+            raise ValueError(f"{who}: k must be in [1, {top_name} = {top}], got {k}")
+        return k
+
+    def _filter_rows(self, filter, q_filter, n_rows):
+        """The ``filter`` / ``q_filter`` / ``n_rows`` keywords of a door over filter rows (:meth:`facet_device`) resolved: the
+        number of output rows and the device ``q_filter`` of the launch -- 0, 1, .. when output row r is filter row r."""
+        torch = _torch()
+        if filter is None:
+            if q_filter is not None:
+                raise ValueError("q_filter picks rows of a filter: it needs filter=")
+            n_rows = 1 if n_rows is None else int(n_rows)
+        else:
+            if not isinstance(filter, DocFilter):
+                raise ValueError("filter must be a DocFilter")
+            filter.for_index(self)
+            if n_rows is None:
+                n_rows = filter.n_filters if q_filter is None else int(q_filter.numel())
+            n_rows = int(n_rows)
+            if q_filter is None and (n_rows > 1 or filter.n_filters > 1):  # row r of the output is row r of the filter
+                if n_rows > filter.n_filters:
+                    raise ValueError(f"n_rows = {n_rows} exceeds the filter's {filter.n_filters} rows: give q_filter")
+                q_filter = torch.arange(n_rows, dtype=torch.int32, device=self.device)
+        if n_rows < 0:
+            raise ValueError("n_rows must be >= 0")
+        return n_rows, q_filter
+
+    @staticmethod
+    def _host_q_filter(filter, q_filter):
+        """A host ``q_filter`` sequence validated (integers in [-1, n_filters)) and uploaded; None stays None"""
+        if q_filter is None:
+            return None
+        if not isinstance(filter, DocFilter):
+            raise ValueError("q_filter picks rows of a filter: it needs filter=")
+        q = np.asarray(q_filter)
+        return q_filter_to_device(filter, q, int(q.shape[0]) if q.ndim == 1 else -1)
+
+    def _host_lists(self, who: str, cap, doc, score, count, scored: bool = True, score_name: str = "score"):
+        """Host result lists for the door ``who``: validated (:func:`~.index.validate_candidates`), at most ``cap`` positions deep
+        (None: any depth), the score of doc's shape (unless not ``scored``); uploaded as ``(doc, score | None, count | None)``."""
+        from .index import validate_candidates
+        torch = _torch()
+        d = np.asarray(doc)
+        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
+        if cap is not None and d.shape[1] > cap:
+            raise ValueError(f"{who} takes lists of at most {cap} positions, got {d.shape[1]} (no silent truncation)")
+        s = None
+        if scored:
+            s = np.ascontiguousarray(score, dtype=np.float32)
+            if s.shape != d.shape:
+                raise ValueError(f"{score_name} must have doc's shape")
+            s = torch.as_tensor(s, device=self.device)
+        return torch.as_tensor(d, device=self.device), s, None if c is None else torch.as_tensor(c, device=self.device)
+
+    def _to_host(self, tensors):
+        """One synchronisation, then every tensor as a NumPy array"""
+        _torch().cuda.synchronize(self.device)
+        return tuple(t.cpu().numpy() for t in tensors)
+
     def filter_device(self, clauses, values=None, all=None, any=None, none=None, columns=None, base=None, q_base=None, out=None) -> DocFilter:
         """``srx_filter_from_fields`` on device tensors.  ``clauses``: int64 [n_clauses, 3], one (col | op << 32, lo, hi) record
         per row (the 24 bytes of ``srx_field_clause``); ``values``: int64 [n_values] or None; each of ``all`` / ``any`` /
@@ -647,11 +737,10 @@ class FieldTable:
             raise ValueError("clauses must be int64 [n_clauses, 3]")
         if values is not None:
             values = check(values, torch.int64, "values")
-        ptr_of = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
 
         def launch(n_rows, lists, bdesc, out_ptr, stream):
-            return _capi.lib().srx_filter_from_fields(self.device.index or 0, self.n_docs, descs, len(names), ptr_of(clauses), int(clauses.shape[0]),
-                                                      ptr_of(values), n_rows, *lists, bdesc, out_ptr, stream)
+            return _capi.lib().srx_filter_from_fields(self.device.index or 0, self.n_docs, descs, len(names), _ptr(clauses), int(clauses.shape[0]),
+                                                      _ptr(values), n_rows, *lists, bdesc, out_ptr, stream)
         return build_rows(self, "srx_filter_from_fields", launch, (all, any, none), "clause", base, q_base, out)
 
     def filter_arrays(self, clauses, values, all=None, any=None, none=None, columns=None, base=None, q_base=None) -> DocFilter:
@@ -716,34 +805,16 @@ class FieldTable:
         column, a float or set column, m > 2048, k outside [1, m], tensors of another dtype, shape or device."""
         torch = _torch()
         policy = check_collapse_args(self.columns, column, per_group, nulls)
-        if column not in self._tensors:
-            raise ValueError("the table is closed")
-        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32:
-            raise ValueError("collapse_device: doc must be an int32 tensor [nq, m]")
-        nq, m = int(doc.shape[0]), int(doc.shape[1])
-        if not (1 <= m <= _capi.SRX_COLLAPSE_MAX_M):
-            raise ValueError(f"collapse_device takes lists of 1 to {_capi.SRX_COLLAPSE_MAX_M} positions, got {m} (no silent truncation)")
-        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or tuple(score.shape) != (nq, m):
-            raise ValueError("collapse_device: score must be a float32 tensor of doc's shape")
-        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
-            raise ValueError("collapse_device: count must be an int32 tensor [nq]")
-        for t, what in ((doc, "doc"), (score, "score"), (count, "count")):
-            if t is not None and t.device != self.device:
-                raise ValueError(f"collapse_device: {what} is on {t.device}, the table on {self.device}")
-        k = int(k)
-        if not (1 <= k <= m):
-            raise ValueError(f"collapse_device: k must be in [1, m = {m}], got {k}")
-        desc = self._col_descs([column])
+        desc = self._col_desc(column)
+        doc, score, count, nq, m = self._list_triple("collapse_device", _capi.SRX_COLLAPSE_MAX_M, doc, score, count)
+        k = self._check_k("collapse_device", k, m)
         with torch.cuda.device(self.device):
-            doc, score = doc.contiguous(), score.contiguous()
-            count = None if count is None else count.contiguous()
             outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
                     torch.empty((nq,), dtype=torch.int32, device=self.device)]
             pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
             size = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_group_size else None
-            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = _capi.lib().srx_collapse_topk(self.device.index or 0, desc, self.n_docs, self.doc_base, ptr(doc), ptr(score), ptr(count), nq, m, k,
-                                               int(per_group), policy, *[ptr(o) for o in outs], ptr(pos), ptr(size),
+            rc = _capi.lib().srx_collapse_topk(self.device.index or 0, desc, self.n_docs, self.doc_base, _ptr(doc), _ptr(score), _ptr(count), nq, m, k,
+                                               int(per_group), policy, *[_ptr(o) for o in outs], _ptr(pos), _ptr(size),
                                                torch.cuda.current_stream(self.device).cuda_stream)
             _capi.check(rc, "srx_collapse_topk")
         return tuple(outs + [t for t in (pos, size) if t is not None])
@@ -752,32 +823,16 @@ class FieldTable:
                  want_group_size: bool = False):
         """Host arrays in (the candidates validated by :func:`~.index.validate_candidates`), host arrays out:
         :meth:`collapse_device` with one synchronisation and one copy back."""
-        from .index import validate_candidates
-        torch = _torch()
         check_collapse_args(self.columns, column, per_group, nulls)
-        d = np.asarray(doc)
-        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
-        if d.shape[1] > _capi.SRX_COLLAPSE_MAX_M:
-            raise ValueError(f"collapse takes lists of at most {_capi.SRX_COLLAPSE_MAX_M} positions, got {d.shape[1]} (no silent truncation)")
-        s = np.ascontiguousarray(score, dtype=np.float32)
-        if s.shape != d.shape:
-            raise ValueError("score must have doc's shape")
-        cc = None if c is None else torch.as_tensor(c, device=self.device)
-        out = self.collapse_device(column, torch.as_tensor(d, device=self.device), torch.as_tensor(s, device=self.device), cc, k, per_group, nulls,
-                                   want_pos, want_group_size)
-        torch.cuda.synchronize(self.device)
-        return tuple(t.cpu().numpy() for t in out)
+        lists = self._host_lists("collapse", _capi.SRX_COLLAPSE_MAX_M, doc, score, count)
+        return self._to_host(self.collapse_device(column, *lists, k, per_group, nulls, want_pos, want_group_size))
 
     # -- facet counts over filter rows and result lists (include/sparse_rx_facets.h) -------------------------------------------
     def _facet_call(self, column: str, spec):
         """(the resolved :class:`FacetSpec`, the column descriptor, the ``srx_facet_bins`` struct, what must stay alive)"""
         torch = _torch()
         fs = spec if isinstance(spec, FacetSpec) else check_facet_args(self.columns, column, spec)
-        if column not in self.columns:
-            raise ValueError(f"unknown field {column!r}")
-        if column not in self._tensors:
-            raise ValueError("the table is closed")
-        desc = self._col_descs([column])
+        desc = self._col_desc(column)
         edges = None if fs.edges is None else torch.as_tensor(fs.edges, device=self.device)
         bins = _capi.FacetBins(mode=fs.mode, n_bins=fs.n_bins, origin=fs.origin, edges=None if edges is None else edges.data_ptr())
         return fs, desc, bins, edges
@@ -792,24 +847,7 @@ class FieldTable:
         import ctypes
         torch = _torch()
         fs, desc, bins, edges = self._facet_call(column, spec)
-        if filter is None:
-            if q_filter is not None:
-                raise ValueError("q_filter picks rows of a filter: it needs filter=")
-            n_rows = 1 if n_rows is None else int(n_rows)
-        else:
-            if not isinstance(filter, DocFilter):
-                raise ValueError("filter must be a DocFilter")
-            filter.for_index(self)
-            if n_rows is None:
-                n_rows = filter.n_filters if q_filter is None else int(q_filter.numel())
-            n_rows = int(n_rows)
-            if q_filter is None:
-                if n_rows > 1 or filter.n_filters > 1:  # row r of the output is row r of the filter
-                    if n_rows > filter.n_filters:
-                        raise ValueError(f"n_rows = {n_rows} exceeds the filter's {filter.n_filters} rows: give q_filter")
-                    q_filter = torch.arange(n_rows, dtype=torch.int32, device=self.device)
-        if n_rows < 0:
-            raise ValueError("n_rows must be >= 0")
+        n_rows, q_filter = self._filter_rows(filter, q_filter, n_rows)
         fdesc, keep = (None, None) if filter is None else filter.launch_args(q_filter, n_rows)
         with torch.cuda.device(self.device):
             counts = torch.empty((n_rows, fs.n_bins), dtype=torch.int32, device=self.device)
@@ -829,22 +867,12 @@ class FieldTable:
         import ctypes
         torch = _torch()
         fs, desc, bins, edges = self._facet_call(column, spec)
-        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32 or int(doc.shape[1]) < 1:
-            raise ValueError("facet_lists_device: doc must be an int32 tensor [nq, m >= 1]")
-        nq, m = int(doc.shape[0]), int(doc.shape[1])
-        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
-            raise ValueError("facet_lists_device: count must be an int32 tensor [nq]")
-        for t, what in ((doc, "doc"), (count, "count")):
-            if t is not None and t.device != self.device:
-                raise ValueError(f"facet_lists_device: {what} is on {t.device}, the table on {self.device}")
+        doc, _, count, nq, m = self._list_triple("facet_lists_device", None, doc, None, count, scored=False)
         with torch.cuda.device(self.device):
-            doc = doc.contiguous()
-            count = None if count is None else count.contiguous()
             counts = torch.empty((nq, fs.n_bins), dtype=torch.int32, device=self.device)
             extra = torch.empty((nq, 3), dtype=torch.int32, device=self.device)
-            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = _capi.lib().srx_facet_counts_lists(self.device.index or 0, desc, self.n_docs, self.doc_base, ctypes.byref(bins), ptr(doc), ptr(count),
-                                                    nq, m, ptr(counts), ptr(extra), torch.cuda.current_stream(self.device).cuda_stream)
+            rc = _capi.lib().srx_facet_counts_lists(self.device.index or 0, desc, self.n_docs, self.doc_base, ctypes.byref(bins), _ptr(doc), _ptr(count),
+                                                    nq, m, _ptr(counts), _ptr(extra), torch.cuda.current_stream(self.device).cuda_stream)
             _capi.check(rc, "srx_facet_counts_lists")
         del edges
         return counts, extra
@@ -852,28 +880,19 @@ class FieldTable:
     def facet(self, column: str, spec=None, filter=None, q_filter=None, n_rows=None):
         """:meth:`facet_device` with a host ``q_filter`` (validated: integers in [-1, n_filters)) and host arrays back: one
         synchronisation, one copy."""
-        torch = _torch()
-        qf = None
-        if q_filter is not None:
-            if not isinstance(filter, DocFilter):
-                raise ValueError("q_filter picks rows of a filter: it needs filter=")
-            q = np.asarray(q_filter)
-            qf = q_filter_to_device(filter, q, int(q.shape[0]) if q.ndim == 1 else -1)
-        counts, extra = self.facet_device(column, spec, filter, qf, n_rows)
-        both = torch.cat([counts, extra], dim=1).cpu().numpy()
-        return both[:, : counts.shape[1]], both[:, counts.shape[1]:]
+        return self._counts_to_host(*self.facet_device(column, spec, filter, self._host_q_filter(filter, q_filter), n_rows))
 
     def facet_lists(self, column: str, doc, count=None, spec=None):
         """:meth:`facet_lists_device` from host arrays (the candidates validated by :func:`~.index.validate_candidates`), host arrays
         back: one synchronisation, one copy."""
-        from .index import validate_candidates
-        torch = _torch()
         fs = spec if isinstance(spec, FacetSpec) else check_facet_args(self.columns, column, spec)
-        d = np.asarray(doc)
-        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
-        cc = None if c is None else torch.as_tensor(c, device=self.device)
-        counts, extra = self.facet_lists_device(column, torch.as_tensor(d, device=self.device), cc, fs)
-        both = torch.cat([counts, extra], dim=1).cpu().numpy()
+        d, _, c = self._host_lists("facet_lists", None, doc, None, count, scored=False)
+        return self._counts_to_host(*self.facet_lists_device(column, d, c, fs))
+
+    @staticmethod
+    def _counts_to_host(counts, extra):
+        """``(counts, extra)`` of a facet door as host arrays: one copy, which synchronises"""
+        both = _torch().cat([counts, extra], dim=1).cpu().numpy()
         return both[:, : counts.shape[1]], both[:, counts.shape[1]:]
 
     # -- ordering filter rows and result lists by a column (include/order/sparse_rx_order.h) ------------------------------------
@@ -886,31 +905,13 @@ class FieldTable:
         row, rows padded with -1 / 0; asynchronous on the current stream, no synchronisation."""
         torch = _torch()
         o, nl = check_order_args(self.columns, column, order, nulls)
-        if column not in self._tensors:
-            raise ValueError("the table is closed")
+        desc = self._col_desc(column)
         k = int(k)
         if not (1 <= k <= _capi.SRX_MAX_K):
             raise ValueError(f"top_by_device: k must be in [1, {_capi.SRX_MAX_K}], got {k} (page with after=)")
-        if filter is None:
-            if q_filter is not None:
-                raise ValueError("q_filter picks rows of a filter: it needs filter=")
-            n_rows = 1 if n_rows is None else int(n_rows)
-        else:
-            if not isinstance(filter, DocFilter):
-                raise ValueError("filter must be a DocFilter")
-            filter.for_index(self)
-            if n_rows is None:
-                n_rows = filter.n_filters if q_filter is None else int(q_filter.numel())
-            n_rows = int(n_rows)
-            if q_filter is None and (n_rows > 1 or filter.n_filters > 1):  # row r of the output is row r of the filter
-                if n_rows > filter.n_filters:
-                    raise ValueError(f"n_rows = {n_rows} exceeds the filter's {filter.n_filters} rows: give q_filter")
-                q_filter = torch.arange(n_rows, dtype=torch.int32, device=self.device)
-        if n_rows < 0:
-            raise ValueError("n_rows must be >= 0")
+        n_rows, q_filter = self._filter_rows(filter, q_filter, n_rows)
         if after is not None and (not isinstance(after, torch.Tensor) or after.dtype != torch.int32 or after.numel() != n_rows or after.device != self.device):
             raise ValueError(f"top_by_device: after must be an int32 tensor [n_rows] on {self.device}")
-        desc = self._col_descs([column])
         fdesc, keep = (None, None) if filter is None else filter.launch_args(q_filter, n_rows)
         _, ws_bytes = _capi.order_plan(self.n_docs, n_rows, k)
         with torch.cuda.device(self.device):
@@ -919,9 +920,8 @@ class FieldTable:
             key = torch.empty((n_rows, k), dtype=torch.int64, device=self.device)
             extra = torch.empty((n_rows, 3), dtype=torch.int32, device=self.device)
             ws = torch.empty(((ws_bytes + 15) // 8,), dtype=torch.int64, device=self.device)
-            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = _capi.lib().srx_order_topk(self.device.index or 0, desc, self.n_docs, self.doc_base, o, nl, fdesc, n_rows, k, ptr(after), ptr(doc),
-                                            ptr(key), ptr(extra), ws.data_ptr(), ws.numel() * 8, torch.cuda.current_stream(self.device).cuda_stream)
+            rc = _capi.lib().srx_order_topk(self.device.index or 0, desc, self.n_docs, self.doc_base, o, nl, fdesc, n_rows, k, _ptr(after), _ptr(doc),
+                                            _ptr(key), _ptr(extra), ws.data_ptr(), ws.numel() * 8, torch.cuda.current_stream(self.device).cuda_stream)
             _capi.check(rc, "srx_order_topk")
         del keep
         return doc, key, extra
@@ -931,21 +931,14 @@ class FieldTable:
         key [n_rows, k] in the column's dtype, has_value bool[n_rows, k], extra i32[n_rows, 3])``.  One synchronisation."""
         torch = _torch()
         check_order_args(self.columns, column, order, nulls)
-        qf = None
-        if q_filter is not None:
-            if not isinstance(filter, DocFilter):
-                raise ValueError("q_filter picks rows of a filter: it needs filter=")
-            q = np.asarray(q_filter)
-            qf = q_filter_to_device(filter, q, int(q.shape[0]) if q.ndim == 1 else -1)
+        qf = self._host_q_filter(filter, q_filter)
         af = None
         if after is not None:
             a = np.asarray(after)
             if a.ndim != 1 or a.dtype.kind not in "iu" or (len(a) and (int(a.min()) < I32_MIN or int(a.max()) > I32_MAX)):
                 raise ValueError("after must be a 1-D sequence of int32 doc ids (-1: no cursor)")
             af = torch.as_tensor(a.astype(np.int32), device=self.device)
-        doc, key, extra = self.top_by_device(column, k, order, nulls, filter, qf, n_rows, af)
-        torch.cuda.synchronize(self.device)
-        doc, key, extra = doc.cpu().numpy(), key.cpu().numpy(), extra.cpu().numpy()
+        doc, key, extra = self._to_host(self.top_by_device(column, k, order, nulls, filter, qf, n_rows, af))
         return doc, decode_order_key(self.columns[column], key), order_has_value(extra, nulls, doc.shape[1]), extra
 
     def sort_lists_device(self, column: str, doc, score, count, k: int, order: str = "desc", nulls: str = "last", want_pos: bool = False):
@@ -956,54 +949,25 @@ class FieldTable:
         then ``pos`` i32[nq, k] with ``want_pos``; rows padded with -1 / 0 / 0 / -1.  Asynchronous on the current stream, one launch."""
         torch = _torch()
         o, nl = check_order_args(self.columns, column, order, nulls)
-        if column not in self._tensors:
-            raise ValueError("the table is closed")
-        if not isinstance(doc, torch.Tensor) or doc.dim() != 2 or doc.dtype != torch.int32:
-            raise ValueError("sort_lists_device: doc must be an int32 tensor [nq, m]")
-        nq, m = int(doc.shape[0]), int(doc.shape[1])
-        if not (1 <= m <= _capi.SRX_ORDER_MAX_M):
-            raise ValueError(f"sort_lists_device takes lists of 1 to {_capi.SRX_ORDER_MAX_M} positions, got {m} (no silent truncation)")
-        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or tuple(score.shape) != (nq, m):
-            raise ValueError("sort_lists_device: score must be a float32 tensor of doc's shape")
-        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != nq):
-            raise ValueError("sort_lists_device: count must be an int32 tensor [nq]")
-        for t, what in ((doc, "doc"), (score, "score"), (count, "count")):
-            if t is not None and t.device != self.device:
-                raise ValueError(f"sort_lists_device: {what} is on {t.device}, the table on {self.device}")
-        k = int(k)
-        if not (1 <= k <= m):
-            raise ValueError(f"sort_lists_device: k must be in [1, m = {m}], got {k}")
-        desc = self._col_descs([column])
+        desc = self._col_desc(column)
+        doc, score, count, nq, m = self._list_triple("sort_lists_device", _capi.SRX_ORDER_MAX_M, doc, score, count)
+        k = self._check_k("sort_lists_device", k, m)
         with torch.cuda.device(self.device):
-            doc, score = doc.contiguous(), score.contiguous()
-            count = None if count is None else count.contiguous()
             outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
                     torch.empty((nq, k), dtype=torch.int64, device=self.device)]
             pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
             extra = torch.empty((nq, 3), dtype=torch.int32, device=self.device)
-            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = _capi.lib().srx_order_lists(self.device.index or 0, desc, self.n_docs, self.doc_base, o, nl, ptr(doc), ptr(score), ptr(count), nq, m, k,
-                                             *[ptr(t) for t in outs], ptr(pos), ptr(extra), torch.cuda.current_stream(self.device).cuda_stream)
+            rc = _capi.lib().srx_order_lists(self.device.index or 0, desc, self.n_docs, self.doc_base, o, nl, _ptr(doc), _ptr(score), _ptr(count), nq, m, k,
+                                             *[_ptr(t) for t in outs], _ptr(pos), _ptr(extra), torch.cuda.current_stream(self.device).cuda_stream)
             _capi.check(rc, "srx_order_lists")
         return tuple(outs + [extra] + ([pos] if want_pos else []))
 
     def sort_lists(self, column: str, doc, score, count, k: int, order: str = "desc", nulls: str = "last", want_pos: bool = False):
         """Host arrays in (the candidates validated by :func:`~.index.validate_candidates`), host arrays out:
         :meth:`sort_lists_device` with one synchronisation and one copy back; ``key`` stays int64 (:func:`decode_order_key`)."""
-        from .index import validate_candidates
-        torch = _torch()
         check_order_args(self.columns, column, order, nulls)
-        d = np.asarray(doc)
-        d, c = validate_candidates(d, count, int(d.shape[0]) if d.ndim == 2 else 0)
-        if d.shape[1] > _capi.SRX_ORDER_MAX_M:
-            raise ValueError(f"sort_lists takes lists of at most {_capi.SRX_ORDER_MAX_M} positions, got {d.shape[1]} (no silent truncation)")
-        s = np.ascontiguousarray(score, dtype=np.float32)
-        if s.shape != d.shape:
-            raise ValueError("score must have doc's shape")
-        cc = None if c is None else torch.as_tensor(c, device=self.device)
-        out = self.sort_lists_device(column, torch.as_tensor(d, device=self.device), torch.as_tensor(s, device=self.device), cc, k, order, nulls, want_pos)
-        torch.cuda.synchronize(self.device)
-        return tuple(t.cpu().numpy() for t in out)
+        lists = self._host_lists("sort_lists", _capi.SRX_ORDER_MAX_M, doc, score, count)
+        return self._to_host(self.sort_lists_device(column, *lists, k, order, nulls, want_pos))
 
     # -- boosting ranked lists by column values (include/boost/sparse_rx_boost.h) ----------------------------------------------
     def boost_device(self, columns, clauses, knots, score_mode: int, boost_mode: int, doc, score, count, k: int, carry=None,
@@ -1058,17 +1022,14 @@ class FieldTable:
                 cc = check(carry[2].reshape(-1) if isinstance(carry[2], torch.Tensor) else carry[2], torch.int32, "carry count", shape=(nq,))
         if m < 1 or m + kc > _capi.SRX_BOOST_MAX_M:
             raise ValueError(f"boost_device takes lists of 1 to {_capi.SRX_BOOST_MAX_M} positions, carry included, got {m} + {kc} (no silent truncation)")
-        k = int(k)
-        if not (1 <= k <= m + kc):
-            raise ValueError(f"boost_device: k must be in [1, m + kc = {m + kc}], got {k}")
+        k = self._check_k("boost_device", k, m + kc, "m + kc")
         with torch.cuda.device(self.device):
             outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
                     torch.empty((nq,), dtype=torch.int32, device=self.device)]
             pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
-            ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = _capi.lib().srx_boost_topk(self.device.index or 0, descs, len(names), self.n_docs, self.doc_base, ptr(clauses), int(clauses.shape[0]),
-                                            ptr(knots), int(knots.numel()), int(score_mode), int(boost_mode), ptr(doc), ptr(score), ptr(count),
-                                            ptr(cd), ptr(cs), ptr(cc), nq, m, kc, k, *[ptr(o) for o in outs], ptr(pos),
+            rc = _capi.lib().srx_boost_topk(self.device.index or 0, descs, len(names), self.n_docs, self.doc_base, _ptr(clauses), int(clauses.shape[0]),
+                                            _ptr(knots), int(knots.numel()), int(score_mode), int(boost_mode), _ptr(doc), _ptr(score), _ptr(count),
+                                            _ptr(cd), _ptr(cs), _ptr(cc), nq, m, kc, k, *[_ptr(o) for o in outs], _ptr(pos),
                                             torch.cuda.current_stream(self.device).cuda_stream)
             _capi.check(rc, "srx_boost_topk")
         return tuple(outs + ([pos] if want_pos else []))
@@ -1078,28 +1039,15 @@ class FieldTable:
         table's columns), the candidates (and the carry's) are validated by :func:`~.index.validate_candidates`, the clause
         records by :func:`~.boost.check_clause_arrays`; then :meth:`boost_device` with one synchronisation and one copy back."""
         from .boost import BoostFn, BoostResolver, check_clause_arrays
-        from .index import validate_candidates
-        torch = _torch()
         res = boost if isinstance(boost, BoostResolver) else BoostResolver(self.columns, boost)
         check_clause_arrays([self.columns[n].type for n in res.names], res.clauses, res.knots)
-
-        def triple(d, s, c, what):
-            d = np.asarray(d)
-            d, c = validate_candidates(d, c, int(d.shape[0]) if d.ndim == 2 else 0)
-            s = np.ascontiguousarray(s, dtype=np.float32)
-            if s.shape != d.shape:
-                raise ValueError(f"{what} score must have doc's shape")
-            return (torch.as_tensor(d, device=self.device), torch.as_tensor(s, device=self.device),
-                    None if c is None else torch.as_tensor(c, device=self.device))
-
-        cand = triple(doc, score, count, "the")
+        cand = self._host_lists("boost", None, doc, score, count, score_name="the score")  # the depth cap counts the carry in: below
         kc = 0 if carry is None else int(np.asarray(carry[0]).shape[1])
         if int(cand[0].shape[1]) + kc > _capi.SRX_BOOST_MAX_M:
             raise ValueError(f"boost takes lists of at most {_capi.SRX_BOOST_MAX_M} positions, carry included (no silent truncation)")
-        cr = None if carry is None else triple(carry[0], carry[1], carry[2] if len(carry) > 2 else None, "the carry's")
-        out = BoostFn(self, res)(*cand, k, carry=cr, want_pos=want_pos)
-        torch.cuda.synchronize(self.device)
-        return tuple(t.cpu().numpy() for t in out)
+        cr = None if carry is None else self._host_lists("boost", None, carry[0], carry[1], carry[2] if len(carry) > 2 else None,
+                                                         score_name="the carry's score")
+        return self._to_host(BoostFn(self, res)(*cand, k, carry=cr, want_pos=want_pos))
 
 
 def order_has_value(extra: np.ndarray, nulls: str, k: int) -> np.ndarray:

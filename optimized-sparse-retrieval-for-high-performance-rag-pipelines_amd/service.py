@@ -626,30 +626,7 @@ class RetrievalService(SparseIndexViews):
         (:meth:`search_bm25`'s ``collapse_by=`` reads the ranking as deep as it takes).  ``{}`` stays ``{}``, ``top_k <= 0`` gives
         an empty list per query.  ``ValueError``: an unknown doc id, a list longer than 2 048 docs (no silent truncation), an
         unknown, float or set column, ``per_group`` < 1, no :meth:`set_doc_fields`, a sharded index."""
-        from . import _capi
-        from .fields import check_collapse_args
-        if self._be._fields is None:
-            raise ValueError("collapse(...) needs the docs' fields: call set_doc_fields() first")
-        check_collapse_args(self._be._fields, by, per_group, nulls)
-        if self._be.sharded():
-            raise ValueError("collapse needs the whole index on one GPU (the columns are shard-local)")
-        if not results:
-            return {}
-        as_rows = {qid: isinstance(row, (list, tuple)) for qid, row in results.items()}
-        lists = {qid: ([r["doc_id"] for r in row] if as_rows[qid] else list(row)) for qid, row in results.items()}
-        _, live, cand_doc, cand_count = self._be.candidate_block(results, lists)
-        m = int(cand_doc.shape[1])
-        if m > _capi.SRX_COLLAPSE_MAX_M:
-            raise ValueError(f"collapse takes lists of at most {_capi.SRX_COLLAPSE_MAX_M} docs, got one of {m} (no silent truncation)")
-        out = {qid: ([] if as_rows[qid] else {}) for qid in results}
-        if not live or int(top_k) <= 0:
-            return out
-        score = np.zeros(cand_doc.shape, dtype=np.float32)  # never looked at: the values come back by position
-        _, _, count, pos = self._be.field_table().collapse(by, cand_doc, score, cand_count, min(int(top_k), m), per_group, nulls, want_pos=True)
-        for i, (qid, _, cands) in enumerate(live):
-            kept = [int(pos[i, j]) for j in range(int(count[i]))]
-            out[qid] = [results[qid][p] for p in kept] if as_rows[qid] else {cands[p]: results[qid][cands[p]] for p in kept}
-        return out
+        return self._be.collapse_results(results, by, top_k, per_group, nulls, "collapse")
 
     def facets(self, queries: Dict[str, str], fields, *, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
                must_not_terms=None, operators: bool = False, where=None, top: Optional[int] = None):

@@ -352,6 +352,35 @@ def test_lists_nulls_at_the_cut():
             col.lists(DESC, nulls, k, doc, rng.random((3, m)), None, label="ten valued positions")
 
 
+def test_field_table_host_doors_at_the_smallest_shape():
+    """``FieldTable.sort_lists`` and ``top_by`` with a host ``q_filter``: host arrays in and out over a 70-doc table with a
+    doc_base, whose validity row ends in a partial word; nq = 2, m = 3, k = 2."""
+    from sparse_rx.fields import FieldTable
+    from sparse_rx.filter import DocFilter
+    n_docs, base = 70, 1000
+    rng = np.random.default_rng(70)
+    values, missing = rng.integers(-5, 5, n_docs).astype(np.int64), np.arange(n_docs) % 7 == 6  # doc 69 has no value
+    valid = ~missing
+    table = FieldTable.from_columns({"stamp": np.ma.array(values, mask=missing)}, device=DEVICE, doc_base=base)
+    doc = np.array([[base + 69, base + 3, base + 64], [base + 5, base - 1, base + 68]], dtype=np.int32)  # one id outside the table
+    score = np.array([[3.0, 2.0, 1.0], [0.5, -1.0, np.nan]], dtype=np.float32)
+    for count in (None, np.array([3, 2], dtype=np.int32)):
+        for order, o in (("asc", ASC), ("desc", DESC)):
+            for nulls, nl in (("last", NULLS_LAST), ("first", NULLS_FIRST), ("drop", NULLS_DROP)):
+                got = table.sort_lists("stamp", doc, score, count, 2, order=order, nulls=nulls, want_pos=True)
+                ed, es, ek, ep, ee = order_ref.order_lists(I64, values, valid, base, o, nl, doc, score, count, 2)
+                assert all(isinstance(a, np.ndarray) for a in got) and len(got) == 5
+                assert np.array_equal(got[0], ed) and np.array_equal(got[1].view(np.uint32), es) and np.array_equal(got[2], ek), (order, nulls)
+                assert np.array_equal(got[3], ee) and np.array_equal(got[4], ep), (order, nulls)
+    masks = np.zeros((2, n_docs), dtype=bool)
+    masks[0, ::2], masks[1, 60:] = True, True
+    flt = DocFilter.from_masks(masks, device=DEVICE, doc_base=base)
+    got_doc, got_key, has, extra = table.top_by("stamp", 2, order="asc", nulls="last", filter=flt, q_filter=[1, -1, 0])
+    ed, ek, ee = order_ref.order_topk(I64, values, valid, base, ASC, NULLS_LAST, 2, masks, [1, -1, 0], 3)
+    assert np.array_equal(got_doc, ed) and np.array_equal(got_key, ek) and np.array_equal(extra, ee) and has.all()
+    table.close()
+
+
 # ---- 5. the doors on tests/golden/text_small.json -------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def text(golden_dir):
