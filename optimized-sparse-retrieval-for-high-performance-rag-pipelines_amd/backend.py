@@ -16,12 +16,12 @@ from __future__ import annotations
 
 import copy
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
 from .boost import boost_deep  # beside collapse_deep: the same search_fn contract
-from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, parse_operators, score_host_batch, search_host_batch, tokenize
+from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, parse_operators, pool_depth, score_host_batch, search_host_batch, tokenize
 
 
 class SparseBackend:
@@ -906,17 +906,11 @@ class ExpandSpec:
         self.docs, self.terms, self.weight, self.by = docs, terms, weight, by
 
 
-def collapse_pool_depth(top_k: int, collapse_pool, n_docs: int) -> int:
-    """Rows of the fused ranking a hybrid search collapses, or ``ValueError``: ``collapse_pool`` when given (1 .. 1024: a
-    deeper pool is refused, not truncated), else ``min(max(4 * top_k, 100), 1024)``; never more than ``n_docs``."""
+def collapse_pool_depth(top_k: int, collapse_pool, n_docs: int, name: str = "collapse_pool") -> int:
+    """Rows of the fused ranking a hybrid search collapses -- or boosts, under the ``name`` "boost_pool" -- (:func:`~.index.pool_depth`):
+    ``collapse_pool`` in 1 .. 1024, else ``min(max(4 * top_k, 100), 1024)``."""
     from . import _capi
-    if collapse_pool is None:
-        pool = min(max(4 * int(top_k), 100), _capi.SRX_MAX_K)
-    else:
-        pool = int(collapse_pool)
-        if not (1 <= pool <= _capi.SRX_MAX_K):
-            raise ValueError(f"collapse_pool must be in [1, {_capi.SRX_MAX_K}], got {collapse_pool}")
-    return max(1, min(pool, n_docs))
+    return pool_depth(name, collapse_pool, max(4 * int(top_k), 100), _capi.SRX_MAX_K, n_docs)
 
 
 def collapse_deep(search_fn, collapse_fn, q_ptr, q_term, q_weight, k: int, first: int, page: int = 1024, max_depth: Optional[int] = None):
@@ -1242,8 +1236,16 @@ def scores_to_dicts(results, live, scores):
 
 
 class SparseIndexViews:
-    """The reference's attribute names as read-only views of ``self._be`` (a :class:`SparseBackend`): shared by
-    ``RetrievalService`` and the registry mirrors."""
+    """The reference's attribute names as read-only views of ``self._be`` (a :class:`SparseBackend`), and the doors that only check
+    for an index and hand on to it: shared by ``RetrievalService`` and the registry mirrors.  What differs between them:"""
+
+    not_built = "Index not built. Call build_index_from_corpus() first."  # what a door says before the build call
+    mode = "bm25"  # how the index scores ("bm25" or "dot"): the feedback's forward index follows it
+    term_order = "term"  # accumulation order of a doc's contributions (index.encode_queries)
+
+    def _need_index(self) -> None:
+        if self.host is None:
+            raise ValueError(self.not_built)
 
     @property
     def host(self) -> Optional[HostIndex]:
@@ -1271,3 +1273,99 @@ class SparseIndexViews:
 
     def _to_dict(self, idx, sc) -> Dict[str, float]:
         return self._be.to_dict(idx, sc)
+
+    # -- the shared doors (no reference counterpart) ----------------------------------------------------------------
+    def set_doc_fields(self, columns) -> None:
+        """The docs' metadata as typed columns for the ``where=`` keyword of the searches (no reference counterpart: nothing
+        reads its ``metadata`` dicts).  ``columns``: name -> a sequence with one entry per doc, in the order of the corpus the
+        build call was given (:func:`~.fields.columns_from_metadata` makes them from the corpus; the type mapping is
+        :meth:`~.fields.FieldTable.from_columns`'s).  A length that is not the index's raises ``ValueError``.  The columns go to
+        the GPU with the first ``where=`` call and stay there; a rebuilt index drops them."""
+        self._need_index()
+        self._be.set_fields(columns)
+
+    def enable_feedback(self) -> None:
+        """Opt in to relevance feedback (no reference counterpart): build the doc-major forward index of the corpus on the GPU
+        (:class:`~.feedback.ForwardIndex`, include/ext/sparse_rx_feedback.h: 8 bytes per posting and 12 per doc next to the
+        index) for ``expand_docs=``, :meth:`more_like_this` and :meth:`expand_queries`.  A rebuilt or re-uploaded index and
+        :meth:`close` drop it.  ``ValueError``: no index, a sharded index."""
+        self._need_index()
+        self._be.enable_feedback(self.mode)
+
+    def more_like_this(self, seeds: Dict[str, Sequence[str]], top_k: int = 10, terms: int = 25, include_seeds: bool = False, *, allowed_docs=None,
+                       excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> Dict[str, Dict[str, float]]:
+        """More like these docs (Lucene's ``more_like_this``; no reference counterpart): ``seeds`` = ``{qid: [doc_id, ...]}``, at
+        most 32 per query -> ``{qid: {doc_id: score}}``.  The query is built on the GPU from the seeds alone: the ``terms`` terms
+        that characterise them best (``srx_feedback_expand`` with empty queries, the seeds as uniformly weighted feedback docs,
+        beta = 1), weights summing to 1; it is searched with the seeds themselves denied per query unless ``include_seeds``.  The
+        filter keywords are those of the searches.  ``ValueError``: no :meth:`enable_feedback`, a sharded index, an unknown doc
+        id, more than 32 seeds, ``terms`` outside 1..128."""
+        self._need_index()
+        return self._be.more_like_this(seeds, top_k, terms, include_seeds, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where)
+
+    def expand_queries(self, queries: Dict[str, str], results: Dict[str, Dict[str, float]], *, expand_terms: int = 10, expand_weight: float = 0.5,
+                       expand_by: str = "score") -> Dict[str, Dict[str, float]]:
+        """What queries are expanded to: ``results`` = ``{qid: {doc_id: score}}`` as a search returned them are the feedback docs
+        (dict order, at most 32 per query) -> ``{qid: {word: weight}}`` in ascending term id: the batch the second pass of
+        ``expand_docs=len(results[qid])`` searches.  ``ValueError`` as :meth:`more_like_this`."""
+        self._need_index()
+        return self._be.expand_queries(queries, results, expand_terms, expand_weight, expand_by, order=self.term_order)
+
+    def facets(self, queries: Dict[str, str], fields, *, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
+               must_not_terms=None, operators: bool = False, where=None, top: Optional[int] = None):
+        """Facet counts (no reference counterpart: it does not aggregate results): how the docs of each query's doc set distribute
+        over metadata columns of :meth:`set_doc_fields`, counted on the GPU (``srx_facet_counts``, include/sparse_rx_facets.h).
+        ``fields``: one name, a sequence of names, or a dict name -> binning spec (:func:`~.fields.check_facet_args`: a category,
+        bool or set column takes none; an int column ``{"origin": o, "bins": n}`` or ``{"edges": [...]}``; a float32 column
+        ``{"edges": [...]}``).  Returns ``{qid: {field: {"counts": {value: n, ...}, "missing": n, "other": n, "total": n}}}``: only
+        bins with a count above 0, by count descending, then by bin ascending, cut to ``top``; a value is a category string, a
+        label, False / True, an int, or the ``(lo, hi)`` pair of the caller's own edges; ``missing`` = docs without a value,
+        ``other`` = docs whose value lies in no bin, ``total`` = docs of the set.
+
+        The doc set: the doc, term and field keywords as in the searches, chained; and ``match`` for the query's own text --
+        ``"any"`` (default): the docs that contain at least one known term of the text.  That is the query's candidate set BY
+        TERMS, a superset of the docs the search returns under its ``score > 0`` rule.  The terms join the ``any`` list: giving
+        ``any_terms=`` as well raises ``ValueError``.  ``"all"``: the docs that contain every term (they join the ``must`` list; an
+        unknown word empties the set).  ``None``: the text is ignored.  Under "any" / "all" a text without a token has the empty
+        set.  ``ValueError``: no :meth:`set_doc_fields`, an unknown field, a spec that does not fit its column, a sharded index."""
+        self._need_index()
+        if operators:
+            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
+        return self._be.facets(queries, fields, match, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, top, "facets")
+
+    def facets_of(self, results, fields, top: Optional[int] = None):
+        """Facet counts over the docs of result lists: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object,
+        a reranker or ``collapse`` returns it -> the dict of :meth:`facets` (``srx_facet_counts_lists``: every listed doc counts,
+        whatever its score).  ``ValueError``: an unknown doc id, no :meth:`set_doc_fields`, an unknown field, a sharded index."""
+        self._need_index()
+        return self._be.facets_of(results, fields, top, "facets_of")
+
+    def search_sorted(self, queries: Dict[str, str], by: str, *, order: str = "desc", top_k: int = 10, match="any", nulls: str = "last",
+                      allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None):
+        """Order by a field instead of relevance (no reference counterpart): the first ``top_k`` docs of each query's doc set by the
+        value the column ``by`` of :meth:`set_doc_fields` holds for them, selected on the GPU (``srx_order_topk``,
+        include/order/sparse_rx_order.h) -> ``{qid: {doc_id: value}}`` in rank order.  The doc set and ``match`` are those of
+        :meth:`facets`.  ``order`` "asc" / "desc"; docs with equal values come in corpus order; ``nulls``: docs without a value come
+        "last", "first" or "drop" out (their value is None).  A value is an int, bool, float or a category's string (categories
+        order alphabetically).  ``top_k`` above 1024 pages with a cursor.  ``ValueError``: no :meth:`set_doc_fields`, a sharded
+        index, an unknown field, a set column, a bad keyword."""
+        self._need_index()
+        return self._be.search_sorted(queries, by, order, top_k, match, nulls, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms,
+                                      where, "search_sorted")
+
+    def sort_results(self, results, by: str, *, order: str = "desc", nulls: str = "last", top_k: Optional[int] = None):
+        """Result lists reordered by a field: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it ->
+        the same dicts, scores unchanged, in the order of the column ``by`` (``srx_order_lists``; equal values keep their relevance
+        order), cut to ``top_k``.  ``ValueError``: a list deeper than 2048, an unknown doc id, and what :meth:`search_sorted`
+        refuses."""
+        self._need_index()
+        return self._be.sort_results(results, by, order, nulls, top_k, "sort_results")
+
+    def boost_results(self, results, boost, top_k: Optional[int] = None):
+        """Result lists re-scored by field values: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it
+        -> ``{qid: {doc_id: boosted score}}``, the first ``top_k`` (None: all) by boosted score (``srx_boost_topk``; ties in corpus
+        order).  ``boost`` as the searches take it, every ``boost_mode`` allowed; the result is relative to the lists given.
+        ``ValueError``: a list deeper than 2048, an unknown doc id, what the spec gets wrong, no :meth:`set_doc_fields`, a sharded
+        index."""
+        self._need_index()
+        return self._be.boost_results(results, boost, top_k, "boost_results")

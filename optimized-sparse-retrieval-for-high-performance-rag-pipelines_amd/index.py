@@ -1128,17 +1128,22 @@ def hybrid_depths(top_k: int, candidates, n_docs: int) -> Tuple[int, int]:
     return min(top_k, n_docs), min(cand, n_docs, max_k)
 
 
-def mmr_pool_depth(top_k: int, mmr_pool, n_docs: int) -> int:
-    """Rows of the fused ranking an MMR selection of ``top_k`` picks from, or ``ValueError``: ``mmr_pool`` when given (1 ..
-    256: a deeper pool is refused, not truncated), else ``min(max(4 * top_k, top_k), 256)``; never more than ``n_docs``."""
-    max_m = _capi.SRX_MMR_MAX_M
-    if mmr_pool is None:
-        pool = min(max(4 * int(top_k), int(top_k)), max_m)
+def pool_depth(name: str, given, default: int, cap: int, n_docs: int) -> int:
+    """Rows of the fused ranking a stage of a hybrid search works on, or ``ValueError``: the keyword ``name`` when ``given`` (1 ..
+    ``cap``: a deeper pool is refused, not truncated), else ``min(default, cap)``; never more than ``n_docs``."""
+    if given is None:
+        pool = min(default, cap)
     else:
-        pool = int(mmr_pool)
-        if not (1 <= pool <= max_m):
-            raise ValueError(f"mmr_pool must be in [1, {max_m}], got {mmr_pool}")
+        pool = int(given)
+        if not (1 <= pool <= cap):
+            raise ValueError(f"{name} must be in [1, {cap}], got {given}")
     return max(1, min(pool, n_docs))
+
+
+def mmr_pool_depth(top_k: int, mmr_pool, n_docs: int) -> int:
+    """Rows of the fused ranking an MMR selection of ``top_k`` picks from (:func:`pool_depth`): ``mmr_pool`` in 1 .. 256, else
+    ``min(max(4 * top_k, top_k), 256)``."""
+    return pool_depth("mmr_pool", mmr_pool, max(4 * int(top_k), int(top_k)), _capi.SRX_MMR_MAX_M, n_docs)
 
 
 def combine_term_bounds(fine_tables, world: int = None):

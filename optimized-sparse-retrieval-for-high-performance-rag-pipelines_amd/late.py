@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _capi
 from .dense import HALF_TYPES, DenseHalfIndex, _require_f32, check_half_dtype
-from .index import _candidate_block, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, validate_candidates
+from .index import _candidate_block, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, pool_depth, validate_candidates
 
 LATE_MAX_M = _capi.SRX_MAX_K  # candidates per list of the rerank form
 
@@ -38,15 +38,9 @@ def check_late_shape(tq: int, dim_pad: int, m: Optional[int] = None, k=None) -> 
 
 
 def late_pool_depth(top_k: int, late_pool, n_docs: int) -> int:
-    """Rows of the fused ranking a late-interaction rerank of ``top_k`` reorders, or ``ValueError``: ``late_pool`` when given
-    (1 .. 1024: a deeper pool is refused, not truncated), else ``min(max(top_k, 100), 1024)``; never more than ``n_docs``."""
-    if late_pool is None:
-        pool = min(max(int(top_k), 100), LATE_MAX_M)
-    else:
-        pool = int(late_pool)
-        if not (1 <= pool <= LATE_MAX_M):
-            raise ValueError(f"late_pool must be in [1, {LATE_MAX_M}], got {late_pool}")
-    return max(1, min(pool, n_docs))
+    """Rows of the fused ranking a late-interaction rerank of ``top_k`` reorders (:func:`~.index.pool_depth`): ``late_pool`` in
+    1 .. 1024, else ``min(max(top_k, 100), 1024)``."""
+    return pool_depth("late_pool", late_pool, max(int(top_k), 100), LATE_MAX_M, n_docs)
 
 
 def doc_token_ptr(doc_token_counts, n_tok: int) -> np.ndarray:

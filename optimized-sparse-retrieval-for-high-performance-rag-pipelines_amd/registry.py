@@ -17,7 +17,7 @@ import hashlib
 import threading
 import time
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -30,9 +30,7 @@ _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
 class _SparseRetrieverBase(SparseIndexViews):
     """Shared batched search: cache semantics of the reference call sites, one srx_search per call."""
 
-    mode = "bm25"
-    strip_cache_key = True
-    term_order = "term"  # accumulation order of a doc's contributions (index.encode_queries)
+    strip_cache_key = True  # mode, term_order and the doors that only hand on to the backend: backend.SparseIndexViews
 
     def __init__(self, k1: float, b: float, device: Optional[str], tile_log2: int, use_cache: bool = True, group=None,
                  shard_searcher_factory=None, sharded: Optional[bool] = None, one_copy: bool = True):
@@ -64,129 +62,24 @@ class _SparseRetrieverBase(SparseIndexViews):
         sum to at most 1: not comparable to the scores of a plain search.
         ``boost`` / ``boost_depth``: the top ``top_k`` of the ranking boosted by field values, exact, with the boosted scores, as
         ``RetrievalService.search_bm25`` (needs raw scores > 0, which the search guarantees; not with ``collapse_by``; no cache)."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        self._need_index()
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search")
         expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search")
         boosted = self._be.boost_spec(boost, boost_depth, top_k, "search", collapse)
-        if expand is not None:
-            return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
-                                         collapse=collapse, expand=expand, boost=boosted)
-        if spec is not None or collapse is not None or boosted is not None:
-            return self._be.search_dicts(queries, top_k, order=self.term_order, strip_key=self.strip_cache_key, blank="empty", filter=spec,
-                                         collapse=collapse, boost=boosted)
-        # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional
+        # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional, and
+        # search_dicts leaves it alone when one of the four specs is given
         return self._be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock,
-                                     strip_key=self.strip_cache_key, blank="empty")
-
-    def set_doc_fields(self, columns) -> None:
-        """The docs' metadata as typed columns for ``where=``, as ``RetrievalService.set_doc_fields``: one entry per doc in the
-        order of the corpus ``build_index_from_corpus`` was given; another length raises ValueError."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        self._be.set_fields(columns)
-
-    def enable_feedback(self) -> None:
-        """Opt in to relevance feedback (no reference counterpart): build the doc-major forward index of the corpus on the GPU
-        (:class:`~.feedback.ForwardIndex`, include/ext/sparse_rx_feedback.h: 8 bytes per posting and 12 per doc next to the
-        index) for ``expand_docs=``, :meth:`more_like_this` and :meth:`expand_queries`.  A rebuilt or re-uploaded index and
-        :meth:`close` drop it.  ``ValueError``: no index, a sharded index."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        self._be.enable_feedback(self.mode)
-
-    def more_like_this(self, seeds: Dict[str, Sequence[str]], top_k: int = 10, terms: int = 25, include_seeds: bool = False, *, allowed_docs=None,
-                       excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> Dict[str, Dict[str, float]]:
-        """More like these docs (Lucene's ``more_like_this``; no reference counterpart): ``seeds`` = ``{qid: [doc_id, ...]}``, at
-        most 32 per query -> ``{qid: {doc_id: score}}``.  The query is built on the GPU from the seeds alone: the ``terms`` terms
-        that characterise them best (``srx_feedback_expand`` with empty queries, the seeds as uniformly weighted feedback docs,
-        beta = 1), weights summing to 1; it is searched with the seeds themselves denied per query unless ``include_seeds``.  The
-        filter keywords are those of the searches.  ``ValueError``: no :meth:`enable_feedback`, a sharded index, an unknown doc
-        id, more than 32 seeds, ``terms`` outside 1..128."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        return self._be.more_like_this(seeds, top_k, terms, include_seeds, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where)
-
-    def expand_queries(self, queries: Dict[str, str], results: Dict[str, Dict[str, float]], *, expand_terms: int = 10, expand_weight: float = 0.5,
-                       expand_by: str = "score") -> Dict[str, Dict[str, float]]:
-        """What queries are expanded to: ``results`` = ``{qid: {doc_id: score}}`` as a search returned them are the feedback docs
-        (dict order, at most 32 per query) -> ``{qid: {word: weight}}`` in ascending term id: the batch the second pass of
-        ``expand_docs=len(results[qid])`` searches.  ``ValueError`` as :meth:`more_like_this`."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        return self._be.expand_queries(queries, results, expand_terms, expand_weight, expand_by, order=self.term_order)
-
-    def facets(self, queries: Dict[str, str], fields, *, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
-               must_not_terms=None, operators: bool = False, where=None, top: Optional[int] = None):
-        """Facet counts (no reference counterpart: it does not aggregate results): how the docs of each query's doc set distribute
-        over metadata columns of :meth:`set_doc_fields`, counted on the GPU (``srx_facet_counts``, include/sparse_rx_facets.h).
-        ``fields``: one name, a sequence of names, or a dict name -> binning spec (:func:`~.fields.check_facet_args`: a category,
-        bool or set column takes none; an int column ``{"origin": o, "bins": n}`` or ``{"edges": [...]}``; a float32 column
-        ``{"edges": [...]}``).  Returns ``{qid: {field: {"counts": {value: n, ...}, "missing": n, "other": n, "total": n}}}``: only
-        bins with a count above 0, by count descending, then by bin ascending, cut to ``top``; a value is a category string, a
-        label, False / True, an int, or the ``(lo, hi)`` pair of the caller's own edges; ``missing`` = docs without a value,
-        ``other`` = docs whose value lies in no bin, ``total`` = docs of the set.
-
-        The doc set: the doc, term and field keywords as in the searches, chained; and ``match`` for the query's own text --
-        ``"any"`` (default): the docs that contain at least one known term of the text.  That is the query's candidate set BY
-        TERMS, a superset of the docs the search returns under its ``score > 0`` rule.  The terms join the ``any`` list: giving
-        ``any_terms=`` as well raises ``ValueError``.  ``"all"``: the docs that contain every term (they join the ``must`` list; an
-        unknown word empties the set).  ``None``: the text is ignored.  Under "any" / "all" a text without a token has the empty
-        set.  ``ValueError``: no :meth:`set_doc_fields`, an unknown field, a spec that does not fit its column, a sharded index."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        if operators:
-            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
-        return self._be.facets(queries, fields, match, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, top, "facets")
-
-    def facets_of(self, results, fields, top: Optional[int] = None):
-        """Facet counts over the docs of result lists: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object,
-        a reranker or ``collapse`` returns it -> the dict of :meth:`facets` (``srx_facet_counts_lists``: every listed doc counts,
-        whatever its score).  ``ValueError``: an unknown doc id, no :meth:`set_doc_fields`, an unknown field, a sharded index."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        return self._be.facets_of(results, fields, top, "facets_of")
-
-    def search_sorted(self, queries: Dict[str, str], by: str, *, order: str = "desc", top_k: int = 10, match="any", nulls: str = "last",
-                      allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None):
-        """Order by a field instead of relevance (no reference counterpart): the first ``top_k`` docs of each query's doc set by the
-        value the column ``by`` of :meth:`set_doc_fields` holds for them, selected on the GPU (``srx_order_topk``,
-        include/order/sparse_rx_order.h) -> ``{qid: {doc_id: value}}`` in rank order.  The doc set and ``match`` are those of
-        :meth:`facets`.  ``order`` "asc" / "desc"; docs with equal values come in corpus order; ``nulls``: docs without a value come
-        "last", "first" or "drop" out (their value is None).  A value is an int, bool, float or a category's string (categories
-        order alphabetically).  ``top_k`` above 1024 pages with a cursor.  ``ValueError``: no :meth:`set_doc_fields`, a sharded
-        index, an unknown field, a set column, a bad keyword."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        return self._be.search_sorted(queries, by, order, top_k, match, nulls, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms,
-                                      where, "search_sorted")
-
-    def sort_results(self, results, by: str, *, order: str = "desc", nulls: str = "last", top_k: Optional[int] = None):
-        """Result lists reordered by a field: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it ->
-        the same dicts, scores unchanged, in the order of the column ``by`` (``srx_order_lists``; equal values keep their relevance
-        order), cut to ``top_k``.  ``ValueError``: a list deeper than 2048, an unknown doc id, and what :meth:`search_sorted`
-        refuses."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        return self._be.sort_results(results, by, order, nulls, top_k, "sort_results")
-
-    def boost_results(self, results, boost, top_k: Optional[int] = None):
-        """Result lists re-scored by field values, as ``RetrievalService.boost_results`` (``srx_boost_topk``): ``{qid: {doc_id:
-        boosted score}}``, the first ``top_k`` by boosted score, relative to the lists given."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
-        return self._be.boost_results(results, boost, top_k, "boost_results")
+                                     strip_key=self.strip_cache_key, blank="empty", filter=spec, collapse=collapse, expand=expand, boost=boosted)
 
     def score(self, queries: Dict[str, str], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
         """The exact score of caller-named documents: ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in
         the caller's order and the arithmetic of :meth:`search` (``srx_score_docs``; the accumulation order is this
         retriever's ``term_order``).  No ``score > 0`` filter: 0.0 where no query term matches and for a blank or
         all-OOV query; ``{}`` for a qid without candidates; ``ValueError`` for an unknown doc id.  One batch, no cache."""
-        if self.host is None:
-            raise ValueError("Index not built. Call build_index_from_corpus() first.")
+        self._need_index()
         return self._be.score_dicts(queries, candidates, order=self.term_order)
 
     def close(self):

@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .backend import SparseBackend, SparseIndexViews, apply_operators
+from .backend import SparseBackend, SparseIndexViews, apply_operators, collapse_pool_depth
 from .index import check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, mmr_pool_depth, rows_to_dict
 
 logger = logging.getLogger(__name__)
@@ -41,6 +41,8 @@ NUMBA_AVAILABLE = False  # kept for get_stats() key compatibility (retrieval.py:
 
 class RetrievalService(SparseIndexViews):
     """BM25 retrieval with the reference's API; scoring + top-k run on the GPU."""
+
+    not_built = "BM25 index not built. Call build_bm25_index() first."  # mode "bm25", term_order "term": backend.SparseIndexViews
 
     def __init__(self, index_path=None, embedding_path=None, num_workers: int = 4, cache_size: int = 1000, *,
                  device: Optional[str] = None, tile_log2: int = 14, group=None, sharded: Optional[bool] = None,
@@ -94,16 +96,6 @@ class RetrievalService(SparseIndexViews):
         self._built_k1b = (self.k1, self.b)
         with self.cache_lock:
             self.query_cache.clear()
-
-    def set_doc_fields(self, columns) -> None:
-        """The docs' metadata as typed columns for the ``where=`` keyword of the searches (no reference counterpart: nothing
-        reads its ``metadata`` dicts).  ``columns``: name -> a sequence with one entry per doc, in the order of the corpus
-        ``build_bm25_index`` was given (:func:`~.fields.columns_from_metadata` makes them from the corpus; the type mapping is
-        :meth:`~.fields.FieldTable.from_columns`'s).  A length that is not the index's raises ``ValueError``.  The columns go to
-        the GPU with the first ``where=`` call and stay there; a rebuilt index drops them."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        self._be.set_fields(columns)
 
     # -- search -----------------------------------------------------------------------------------------
     def search_bm25(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None,
@@ -168,8 +160,7 @@ class RetrievalService(SparseIndexViews):
         the query cache.  ``ValueError``: ``collapse_by`` in the same call (chain :meth:`collapse` over the result), ``boost_mode``
         "replace" or a factor that can be negative under "multiply" (no bound exists), ``top_k`` above 1 024, an unknown or set
         column, no :meth:`set_doc_fields`, a sharded index."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")  # :205-206
+        self._need_index()  # :205-206
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
@@ -182,14 +173,10 @@ class RetrievalService(SparseIndexViews):
             self._upload()  # k1 / b are plain attributes on the reference (:116-117): impacts depend on them
             if expand is not None:
                 self._be.enable_feedback("bm25")  # the upload dropped the forward index; its rows do not depend on k1 / b
-        if expand is not None:
-            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse, expand=expand,
-                                         boost=boosted)
-        # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on
-        if spec is not None or collapse is not None or boosted is not None:
-            return self._be.search_dicts(queries, top_k, order="term", strip_key=True, blank="whitespace", filter=spec, collapse=collapse, boost=boosted)
+        # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on, and
+        # search_dicts leaves it alone when one of the four specs is given
         return self._be.search_dicts(queries, top_k, order="term", cache=self.query_cache, lock=self.cache_lock, strip_key=True,
-                                     blank="whitespace")
+                                     blank="whitespace", filter=spec, collapse=collapse, expand=expand, boost=boosted)
 
     def score_bm25(self, queries: Dict[str, str], candidates: Dict[str, Sequence[str]]) -> Dict[str, Dict[str, float]]:
         """The exact BM25 score of caller-named documents (no reference counterpart: it can only rank):
@@ -198,42 +185,10 @@ class RetrievalService(SparseIndexViews):
         ``score > 0`` filter: a doc no query term matches scores 0.0, as does every doc for a blank or all-OOV query; a qid
         without candidates gives ``{}``; an unknown doc id raises ``ValueError``.  All queries of the call run as one batch
         (ragged lists padded); the query cache is not used.  Sharded: every rank makes the same call and gets the same dict."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        self._need_index()
         if (self.k1, self.b) != self._built_k1b:
             self._upload()
         return self._be.score_dicts(queries, candidates, order="term")
-
-    # -- relevance feedback (no reference counterpart) --------------------------------------------------------
-    def enable_feedback(self) -> None:
-        """Opt in to relevance feedback (no reference counterpart): build the doc-major forward index of the corpus on the GPU
-        (:class:`~.feedback.ForwardIndex`, include/ext/sparse_rx_feedback.h: 8 bytes per posting and 12 per doc next to the
-        index) for ``expand_docs=``, :meth:`more_like_this` and :meth:`expand_queries`.  A rebuilt or re-uploaded index and
-        :meth:`close` drop it.  ``ValueError``: no index, a sharded index."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        self._be.enable_feedback("bm25")
-
-    def more_like_this(self, seeds: Dict[str, Sequence[str]], top_k: int = 10, terms: int = 25, include_seeds: bool = False, *, allowed_docs=None,
-                       excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> Dict[str, Dict[str, float]]:
-        """More like these docs (Lucene's ``more_like_this``; no reference counterpart): ``seeds`` = ``{qid: [doc_id, ...]}``, at
-        most 32 per query -> ``{qid: {doc_id: score}}``.  The query is built on the GPU from the seeds alone: the ``terms`` terms
-        that characterise them best (``srx_feedback_expand`` with empty queries, the seeds as uniformly weighted feedback docs,
-        beta = 1), weights summing to 1; it is searched with the seeds themselves denied per query unless ``include_seeds``.  The
-        filter keywords are those of the searches.  ``ValueError``: no :meth:`enable_feedback`, a sharded index, an unknown doc
-        id, more than 32 seeds, ``terms`` outside 1..128."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        return self._be.more_like_this(seeds, top_k, terms, include_seeds, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where)
-
-    def expand_queries(self, queries: Dict[str, str], results: Dict[str, Dict[str, float]], *, expand_terms: int = 10, expand_weight: float = 0.5,
-                       expand_by: str = "score") -> Dict[str, Dict[str, float]]:
-        """What queries are expanded to: ``results`` = ``{qid: {doc_id: score}}`` as a search returned them are the feedback docs
-        (dict order, at most 32 per query) -> ``{qid: {word: weight}}`` in ascending term id: the batch the second pass of
-        ``expand_docs=len(results[qid])`` searches.  ``ValueError`` as :meth:`more_like_this`."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        return self._be.expand_queries(queries, results, expand_terms, expand_weight, expand_by)
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
@@ -412,7 +367,10 @@ class RetrievalService(SparseIndexViews):
         at least the pool, and the pool is boosted on the device (``srx_boost_topk``) before the one copy back.  The result is
         POOL-RELATIVE: what ``boost_results(search_hybrid(top_k=boost_pool, ...), boost, top_k)`` returns, values = boosted fused
         scores.  With ``collapse_by`` the whole boosted pool is then collapsed (``collapse_pool`` is not used), with ``mmr_lambda``
-        the boosted (and collapsed) pool's first ``mmr_pool`` rows are diversified."""
+        the boosted (and collapsed) pool's first ``mmr_pool`` rows are diversified.
+        In one sentence: the steps run in the order late rerank, boost, collapse, MMR, each only if its keyword is given; the fusion
+        is as deep as the FIRST step's pool, and a step keeps all its rows for a boost or collapse behind it, ``mmr_pool`` rows for MMR
+        behind it, ``top_k`` rows as the last -- never more than it was handed."""
         if late_query_tokens is not None and mmr_lambda is not None:
             raise ValueError("late_query_tokens and mmr_lambda do not combine in one call: chain rerank_late() and diversify()")
         if operators:
@@ -420,41 +378,31 @@ class RetrievalService(SparseIndexViews):
         fusion = str(fusion).lower()
         check_fuse_args(fusion, (sparse_weight, dense_weight), rrf_c)
         rescore = check_rescore_args(fusion, rescore)
-        k, cand = hybrid_depths(top_k, candidates, self._be.n_docs_total)
-        pool = None
+        n_docs = self._be.n_docs_total
+        k, cand = hybrid_depths(top_k, candidates, n_docs)
+        pools = {}  # stage -> the depth its pool keyword gives: the first stage's is the fused depth, MMR's is also what is kept for it
         if mmr_lambda is not None:
             from .dense import check_mmr_args
             check_mmr_args(mmr_lambda, mmr_similarity)
-            pool = mmr_pool_depth(top_k, mmr_pool, self._be.n_docs_total)
-            if candidates is None:
-                cand = hybrid_depths(top_k, max(int(top_k), pool, 1), self._be.n_docs_total)[1]
-        late = None
+            pools["mmr"] = mmr_pool_depth(top_k, mmr_pool, n_docs)
         if late_query_tokens is not None:
             from .late import late_pool_depth
-            late = late_pool_depth(top_k, late_pool, self._be.n_docs_total)
-            if candidates is None:
-                cand = hybrid_depths(top_k, max(int(top_k), late, 1), self._be.n_docs_total)[1]
+            pools["late"] = late_pool_depth(top_k, late_pool, n_docs)
         if self._be.sharded():
             raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        self._need_index()
         self._ensure_dense()
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, None, top_k, "search_hybrid")
-        cpool = None
-        if collapse is not None:
-            from .backend import collapse_pool_depth
-            cpool = late if late is not None else collapse_pool_depth(top_k, collapse_pool, self._be.n_docs_total)
-            if candidates is None:
-                cand = hybrid_depths(top_k, max(int(top_k), cpool, pool or 1, 1), self._be.n_docs_total)[1]
+        if collapse is not None and late_query_tokens is None:
+            pools["collapse"] = collapse_pool_depth(top_k, collapse_pool, n_docs)
         boosted = self._be.boost_spec(boost, None, top_k, "search_hybrid", exact=False)
-        bpool = None
-        if boosted is not None:
-            from .backend import collapse_pool_depth
-            if boost_pool is not None and not (1 <= int(boost_pool) <= 1024):
-                raise ValueError(f"boost_pool must be in [1, 1024], got {boost_pool}")
-            bpool = late if late is not None else collapse_pool_depth(top_k, boost_pool, self._be.n_docs_total)
-            if candidates is None:
-                cand = hybrid_depths(top_k, max(int(top_k), bpool, 1), self._be.n_docs_total)[1]
+        if boosted is not None:  # range-checked under late_query_tokens too, where it is not used
+            pools["boost"] = collapse_pool_depth(top_k, boost_pool, n_docs, "boost_pool")
+        stages = [name for name, given in (("late", late_query_tokens), ("boost", boosted), ("collapse", collapse), ("mmr", mmr_lambda)) if given is not None]
+        depth = pools[stages[0]] if stages else k  # how deep the fusion is taken
+        if stages and candidates is None:
+            # at least the fused depth.  Collapse + MMR alone also reach for mmr_pool: an irregularity, but it decides which rows are fetched
+            cand = hybrid_depths(top_k, max(int(top_k), depth, pools["mmr"] if stages == ["collapse", "mmr"] else 1), n_docs)[1]
         results: Dict[str, Dict[str, float]] = {qid: {} for qid in queries}
         live = [(qid, text) for qid, text in queries.items() if text and text.strip()]
         if k <= 0 or not live:
@@ -485,67 +433,34 @@ class RetrievalService(SparseIndexViews):
             import torch
             return self._dense.score_docs_device(torch.as_tensor(np.stack(vecs), device=self._dense.device), cand_doc, cand_count)
 
-        def collapsed(f_doc, f_score, f_count, kk):  # a ranked triple still on the device -> its first kk survivors
-            return self._be.field_table().collapse_device(collapse.by, f_doc, f_score, f_count, min(kk, int(f_doc.shape[1])), collapse.per_group,
-                                                          collapse.nulls)
-
         if boosted is not None:
-            import torch
             from .boost import BoostFn
             bfn = BoostFn(self._be.field_table(), boosted)
-            if late is not None:
-                from .late import stack_query_tokens
-                tokens = self._ensure_late()
-                q_tok, q_cnt = stack_query_tokens(late_query_tokens, [qid for qid, _ in live], tokens.dim)
-
-            def boosted_pool(f_doc, f_score, f_count):  # the fused triple, bpool deep, still on the device
-                if late is not None:  # the whole pool reranked first
-                    f_doc, f_score, f_count = tokens.rerank_device(torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device),
-                                                                   f_doc, f_count, late)[:3]
-                width = int(f_doc.shape[1])
-                keep = width if collapse is not None else min(pool, width) if pool is not None else min(k, width)
-                f_doc, f_score, f_count = bfn(f_doc, f_score, f_count, keep)
-                if collapse is not None:
-                    f_doc, f_score, f_count = collapsed(f_doc, f_score, f_count, k if pool is None else pool)[:3]
-                if pool is not None:
-                    d, r, _, n = self._dense.mmr_device(f_doc, f_score, f_count, min(k, int(f_doc.shape[1])), mmr_lambda, mmr_similarity)
-                    return d, r, n
-                return f_doc, f_score, f_count
-
-            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, bpool, fusion,
-                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=boosted_pool, **flt)
-        elif late is not None:
-            import torch
+        if late_query_tokens is not None:
             from .late import stack_query_tokens
             tokens = self._ensure_late()
             q_tok, q_cnt = stack_query_tokens(late_query_tokens, [qid for qid, _ in live], tokens.dim)
 
-            def reranked(f_doc, f_score, f_count):  # the fused triple, pool deep, still on the device
-                q_t, q_c = torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device)
-                if collapse is None:
-                    return tokens.rerank_device(q_t, q_c, f_doc, f_count, min(k, late))
-                return collapsed(*tokens.rerank_device(q_t, q_c, f_doc, f_count, late), k)  # the whole pool reranked, then collapsed
+        def post(f_doc, f_score, f_count):  # the fused triple, depth wide, still on the device, through the stages
+            import torch
+            width = depth  # every stage returns as many columns as it is asked to keep
+            for stage, follower in zip(stages, stages[1:] + [None]):
+                keep = min(k, width) if follower is None else min(pools["mmr"], width) if follower == "mmr" else width
+                if stage == "late":
+                    f_doc, f_score, f_count = tokens.rerank_device(torch.as_tensor(q_tok, device=tokens.device), torch.as_tensor(q_cnt, device=tokens.device),
+                                                                   f_doc, f_count, keep)
+                elif stage == "boost":
+                    f_doc, f_score, f_count = bfn(f_doc, f_score, f_count, keep)
+                elif stage == "collapse":
+                    f_doc, f_score, f_count = self._be.field_table().collapse_device(collapse.by, f_doc, f_score, f_count, keep, collapse.per_group,
+                                                                                     collapse.nulls)
+                else:
+                    f_doc, f_score, _, f_count = self._dense.mmr_device(f_doc, f_score, f_count, keep, mmr_lambda, mmr_similarity)
+                width = keep
+            return f_doc, f_score, f_count
 
-            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, late, fusion,
-                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=reranked, **flt)
-        elif pool is None and collapse is None:
-            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, k, fusion,
-                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score, **flt)
-        elif pool is None:
-            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, cpool, fusion,
-                                              (sparse_weight, dense_weight), rrf_c, rescore, dense_score,
-                                              post=lambda f_doc, f_score, f_count: collapsed(f_doc, f_score, f_count, k), **flt)
-        else:
-            def diversified(f_doc, f_score, f_count):  # the fused triple, pool (or collapse_pool) deep, still on the device
-                kk = min(k, pool)
-                if collapse is not None:
-                    f_doc, f_score, f_count = collapsed(f_doc, f_score, f_count, pool)
-                    kk = min(k, int(f_doc.shape[1]))  # the collapsed pool has min(mmr_pool, collapse_pool) columns
-                d, r, _, n = self._dense.mmr_device(f_doc, f_score, f_count, kk, mmr_lambda, mmr_similarity)
-                return d, r, n
-
-            doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, pool if collapse is None else cpool,
-                                              fusion, (sparse_weight, dense_weight), rrf_c, rescore, dense_score, post=diversified, **flt)
+        doc, score, count = hybrid_search(self.dev, q_ptr, q_term, q_weight, dense_search, cand, cand, depth, fusion, (sparse_weight, dense_weight),
+                                          rrf_c, rescore, dense_score, **(dict(flt, post=post) if stages else flt))  # no stage: nothing is added
         for i, (qid, _) in enumerate(live):
             results[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return results
@@ -628,70 +543,6 @@ class RetrievalService(SparseIndexViews):
         unknown, float or set column, ``per_group`` < 1, no :meth:`set_doc_fields`, a sharded index."""
         return self._be.collapse_results(results, by, top_k, per_group, nulls, "collapse")
 
-    def facets(self, queries: Dict[str, str], fields, *, match="any", allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
-               must_not_terms=None, operators: bool = False, where=None, top: Optional[int] = None):
-        """Facet counts (no reference counterpart: it does not aggregate results): how the docs of each query's doc set distribute
-        over metadata columns of :meth:`set_doc_fields`, counted on the GPU (``srx_facet_counts``, include/sparse_rx_facets.h).
-        ``fields``: one name, a sequence of names, or a dict name -> binning spec (:func:`~.fields.check_facet_args`: a category,
-        bool or set column takes none; an int column ``{"origin": o, "bins": n}`` or ``{"edges": [...]}``; a float32 column
-        ``{"edges": [...]}``).  Returns ``{qid: {field: {"counts": {value: n, ...}, "missing": n, "other": n, "total": n}}}``: only
-        bins with a count above 0, by count descending, then by bin ascending, cut to ``top``; a value is a category string, a
-        label, False / True, an int, or the ``(lo, hi)`` pair of the caller's own edges; ``missing`` = docs without a value,
-        ``other`` = docs whose value lies in no bin, ``total`` = docs of the set.
-
-        The doc set: the doc, term and field keywords as in the searches, chained; and ``match`` for the query's own text --
-        ``"any"`` (default): the docs that contain at least one known term of the text.  That is the query's candidate set BY
-        TERMS, a superset of the docs the search returns under its ``score > 0`` rule.  The terms join the ``any`` list: giving
-        ``any_terms=`` as well raises ``ValueError``.  ``"all"``: the docs that contain every term (they join the ``must`` list; an
-        unknown word empties the set).  ``None``: the text is ignored.  Under "any" / "all" a text without a token has the empty
-        set.  ``ValueError``: no :meth:`set_doc_fields`, an unknown field, a spec that does not fit its column, a sharded index."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        if operators:
-            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
-        return self._be.facets(queries, fields, match, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, top, "facets")
-
-    def facets_of(self, results, fields, top: Optional[int] = None):
-        """Facet counts over the docs of result lists: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object,
-        a reranker or ``collapse`` returns it -> the dict of :meth:`facets` (``srx_facet_counts_lists``: every listed doc counts,
-        whatever its score).  ``ValueError``: an unknown doc id, no :meth:`set_doc_fields`, an unknown field, a sharded index."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        return self._be.facets_of(results, fields, top, "facets_of")
-
-    def search_sorted(self, queries: Dict[str, str], by: str, *, order: str = "desc", top_k: int = 10, match="any", nulls: str = "last",
-                      allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None):
-        """Order by a field instead of relevance (no reference counterpart): the first ``top_k`` docs of each query's doc set by the
-        value the column ``by`` of :meth:`set_doc_fields` holds for them, selected on the GPU (``srx_order_topk``,
-        include/order/sparse_rx_order.h) -> ``{qid: {doc_id: value}}`` in rank order.  The doc set and ``match`` are those of
-        :meth:`facets`.  ``order`` "asc" / "desc"; docs with equal values come in corpus order; ``nulls``: docs without a value come
-        "last", "first" or "drop" out (their value is None).  A value is an int, bool, float or a category's string (categories
-        order alphabetically).  ``top_k`` above 1024 pages with a cursor.  ``ValueError``: no :meth:`set_doc_fields`, a sharded
-        index, an unknown field, a set column, a bad keyword."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        return self._be.search_sorted(queries, by, order, top_k, match, nulls, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms,
-                                      where, "search_sorted")
-
-    def sort_results(self, results, by: str, *, order: str = "desc", nulls: str = "last", top_k: Optional[int] = None):
-        """Result lists reordered by a field: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it ->
-        the same dicts, scores unchanged, in the order of the column ``by`` (``srx_order_lists``; equal values keep their relevance
-        order), cut to ``top_k``.  ``ValueError``: a list deeper than 2048, an unknown doc id, and what :meth:`search_sorted`
-        refuses."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        return self._be.sort_results(results, by, order, nulls, top_k, "sort_results")
-
-    def boost_results(self, results, boost, top_k: Optional[int] = None):
-        """Result lists re-scored by field values: ``results`` = ``{qid: {doc_id: score}}`` as any search of this object returns it
-        -> ``{qid: {doc_id: boosted score}}``, the first ``top_k`` (None: all) by boosted score (``srx_boost_topk``; ties in corpus
-        order).  ``boost`` as :meth:`search_bm25` takes it, every ``boost_mode`` allowed; the result is relative to the lists
-        given.  ``ValueError``: a list deeper than 2048, an unknown doc id, what the spec gets wrong, no :meth:`set_doc_fields`, a
-        sharded index."""
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
-        return self._be.boost_results(results, boost, top_k, "boost_results")
-
     # -- late interaction (no reference counterpart) -----------------------------------------------------------
     def set_token_embeddings(self, token_embeddings, storage: str = "f16") -> None:
         """Put the TOKEN vectors of the docs on the GPU for :meth:`rerank_late` (:class:`~.late.TokenIndex`; rounded to
@@ -704,8 +555,7 @@ class RetrievalService(SparseIndexViews):
         storage = check_half_dtype(storage)
         if self._be.sharded():
             raise ValueError("late interaction needs the whole index on one GPU (the token store is not sharded)")
-        if self.host is None:
-            raise ValueError("BM25 index not built. Call build_bm25_index() first.")
+        self._need_index()
         ids = self.host.doc_ids
         if isinstance(token_embeddings, dict):
             known = set(ids)

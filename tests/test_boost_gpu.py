@@ -464,3 +464,30 @@ def test_search_hybrid_boost_equals_the_reference_over_the_pool(text):
         svc.search_hybrid(queries, vecs, top_k=5, boost=spec, boost_pool=1025)
     assert same(svc.search_hybrid(queries, vecs, top_k=5, boost=None, boost_pool=7), svc.search_hybrid(queries, vecs, top_k=5))
     svc.close()
+
+
+def test_search_hybrid_three_stages_equal_the_chain_of_the_public_steps(text):
+    """boost + collapse + MMR, and late rerank + boost + collapse: one call = the public doors chained over the pool"""
+    import sparse_rx
+    j, ids, fields = text
+    queries = {q: j["queries"][q] for q in list(j["queries"])[:10]}
+    n_docs, dim = len(ids), 64
+    rng = np.random.default_rng(48)
+    svc = sparse_rx.RetrievalService(device=DEVICE, tile_log2=6)
+    svc.build_bm25_index(j["corpus"])
+    svc.set_embeddings(rng.standard_normal((n_docs, dim)).astype(np.float32))
+    svc.set_doc_fields(fields)
+    vecs = {q: rng.standard_normal(dim).astype(np.float32) for q in queries}
+    spec = {"functions": [{"decay": {"field": "date", "origin": 5000, "scale": 1500, "kind": "exp"}},
+                          {"decay": {"field": "price", "origin": 10.0, "scale": 8.0, "kind": "linear", "weight": 0.5}}], "score_mode": "max"}
+    same = lambda a, b: {q: list(v.items()) for q, v in a.items()} == {q: list(v.items()) for q, v in b.items()}
+    got = svc.search_hybrid(queries, vecs, top_k=5, boost=spec, boost_pool=40, collapse_by="parent", mmr_lambda=0.5, mmr_pool=12)
+    assert all(len(v) == 5 for v in got.values())
+    assert same(got, svc.diversify(svc.collapse(svc.boost_results(svc.search_hybrid(queries, vecs, top_k=40), spec), "parent", top_k=12), top_k=5,
+                                   mmr_lambda=0.5))
+    svc.set_token_embeddings({d: rng.standard_normal((3, 32)).astype(np.float32) for d in ids})
+    qt = {q: rng.standard_normal((4, 32)).astype(np.float32) for q in queries}
+    got = svc.search_hybrid(queries, vecs, top_k=5, boost=spec, collapse_by="parent", late_query_tokens=qt, late_pool=30)
+    assert all(len(v) == 5 for v in got.values())
+    assert same(got, svc.collapse(svc.boost_results(svc.rerank_late(svc.search_hybrid(queries, vecs, top_k=30), qt, top_k=30), spec), "parent", top_k=5))
+    svc.close()
