@@ -932,8 +932,8 @@ __device__ void packed_unit(ScoreShared &S, const IndexView &ix, int nt, int k, 
         __syncthreads();
         if (GP <= (unsigned)DENSE_MIN) {
             hash_unit<VT, AFTER, CP>(S, ix, nt, glen, k, ja << ix.tile_log2);
-        } else {  // one dense tile (gb == ga + 1 by construction)
-            const int tile_base = ga << ix.tile_log2;
+        } else {  // one dense tile, the group's LAST: a group only closes once it holds postings, so empty tiles may come before it
+            const int tile_base = (gb - 1) << ix.tile_log2;
             dense_tile_accumulate<VT, CP>(S, ix, nt, tile_base, true, ja << ix.tile_log2);
             // m_start / m_len are live: the append scan has no overflow area
             if (!(append_scan && dense_tile_append<AFTER>(S, ix, tile_base, k, 1, n_old, 0))) dense_tile_general<AFTER>(S, ix, tile_base, k, 1);

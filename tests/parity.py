@@ -522,3 +522,272 @@ def decode_routes(ws_bytes, p, nq, k):
     n = int(work[0])
     assert 0 <= n <= p["items"], f"work[0] = {n} with {p['items']} items"
     return bits, work[1:1 + n].tolist(), n
+
+
+# ---- tier 2's dispatch, restated (csrc/tier2_kernel.hip: score_block and what it calls; csrc/srx_common.h) ---------------
+# Which of its paths the tier-2 kernel takes for every unit of every work item, and what its selection sites then do.  The
+# path cannot be observed from outside the kernel: tests/test_tier2_routes_cpu.py builds corpora that sit on each comparison
+# below and asserts through tier2_routes that they do; tests/test_tier2_routes_gpu.py runs them bit for bit against the oracle.
+# Every constant is named as in C++ and pinned to the sources by test_tier2_constants_match_the_sources.
+THREADS = 256
+TBL_WORDS = 16384
+SLOTS = 8192  # TBL_WORDS / 2
+HASH_CAP = 4096
+DENSE_MIN = 4096  # = HASH_CAP
+KMAX = 1024  # = SRX_MAX_K
+MAXT = 256
+MAX_TPS = 64
+OVF_CAP = 384
+FLAT_CAP = 8192
+FLAT_MCAP = 2048
+FLAT_MIN_TERMS = 12
+WAVES = 4  # THREADS / 64
+SRX_DBG_TIER2_ONLY, SRX_DBG_NO_TERM_BOUND, SRX_DBG_NO_FLAT_TILES = 8, 16, 128
+SRX_DBG_NO_WAVE_DENSE, SRX_DBG_WAVE_DENSE_MASKED, SRX_DBG_WAVE_DENSE_GENERAL = 2048, 4096, 8192
+
+
+def hash_slot(doc):
+    """hash_unit's home slot of a doc: (doc * 0x9E3779B1 mod 2^32) >> (32 - 13)."""
+    return ((np.asarray(doc, np.int64) * 0x9E3779B1) & 0xFFFFFFFF) >> 19
+
+
+def tier1_cannot_serve(nt, k, tps, tile_log2, vocab, n_tiles, dbg, post16=True):
+    """srx_common.h: tier1_cannot_serve.  dbg is the launch's (search_impl adds SRX_DBG_TIER2_ONLY for a unit override, a
+    search-after and a filtered search)."""
+    return (nt > W_MAXT or k > W1_KMAX or (tps << tile_log2) > W_UNIT_MAX_DOCS or not post16 or (dbg & SRX_DBG_TIER2_ONLY) != 0
+            or vocab * (n_tiles + 1) >= (1 << 30))
+
+
+class _T2List:
+    """The work item's running list, simulated exactly: the docs on it, tau, and the cut every selection site shares (the k
+    best in (score desc, doc asc) order, tau = the k-th score)."""
+
+    def __init__(self, s, tau0, k, bound):
+        self.s, self.tau, self.k, self.bound = s, np.float32(tau0), k, bound
+        self.docs = np.zeros(0, np.int64)
+
+    def cand(self, docs):
+        """The docs of `docs` that can enter: score > 0, bits >= tau (float order for positive scores), after the bound."""
+        docs = np.asarray(docs, np.int64)
+        sc = self.s[docs]
+        ok = (sc > 0) & (sc >= self.tau)
+        if self.bound is not None:
+            ub, ud = self.bound
+            ok &= (sc < ub) | ((sc == ub) & (docs > ud))
+        return docs[ok]
+
+    def select(self, extra=()):
+        d = np.concatenate([self.docs, np.asarray(extra, np.int64)])
+        d = d[np.lexsort((d, -self.s[d].astype(np.float64)))][: self.k]
+        self.docs, self.tau = d, self.s[d[-1]]
+
+    def fold(self, docs, cap=KMAX):
+        """topk_fold<N, LAZY>: nothing / append while the list has room / the selection."""
+        c = self.cand(docs)
+        n_old, n_new = len(self.docs), len(c)
+        if n_new == 0 and n_old <= self.k:
+            return ("fold_none", n_old)
+        if n_old + n_new <= cap:
+            self.docs = np.concatenate([self.docs, c])
+            return ("fold_append", n_old + n_new)
+        self.select(c)
+        return ("fold_select", n_old + n_new)
+
+    def dense_group(self, lo, hi, n_docs, append_scan, ovf_cap):
+        """One dense group [lo, hi) of docs: dense_tile_append, then dense_tile_general when it refuses."""
+        rng = np.arange(lo, min(hi, n_docs))
+        if append_scan:
+            n_old = len(self.docs)
+            for attempt in range(2):
+                c = self.cand(rng)
+                if n_old + len(c) <= KMAX + ovf_cap:
+                    self.docs = np.concatenate([self.docs, c])
+                    return ("append_served", n_old + len(c)) if attempt == 0 else ("append_retry_served", n_old + len(c))
+                if n_old <= self.k:
+                    break
+                self.select()  # list_compact_select(k, n_old)
+                n_old = self.k
+        c = self.cand(rng)  # dense_tile_general
+        n_old, n_new = len(self.docs), len(c)
+        pre = "append_refused -> " if append_scan else ""
+        if n_new == 0 and n_old <= self.k:
+            return (pre + "early_return", n_old)
+        if n_old + n_new <= KMAX:
+            self.docs = np.concatenate([self.docs, c])
+            return (pre + "general_append", n_old + n_new)
+        self.select(c)
+        return (pre + "general_cut", n_old + n_new)
+
+
+def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_tiles, k, p, debug, flags, tps=None, mode="bm25",
+                 val_dtype="f32", k1=1.2, b=0.75, avgdl=1.0, post16=True, after=None, layout=None):
+    """What score_block does for every work item of one search, as an ordered list of steps per item.
+    unit_tiles = the unit the index was built (padded) for, tps = tiles per unit of the search (the plan's; default the same),
+    p = plan(n_tiles, tps, ...), debug = the search's debug bits, flags = bool[items, >= n_super] tier 1's flag bits (from
+    tier1_routes on the CPU, from decode_routes on the GPU), after = None or (score f32[nq], shard-local doc[nq]) of a search-
+    after page, layout = (term_ptr, post, tile_skip, n_blocks) of np_build_blocks on the stored values (built here when None).
+    Steps (tuples):
+      ("skip",)                                              not opened: no flagged unit, or nt == 0
+      ("many_term", ja, jb, n_pass, last_pass_terms, [sel])  nt > 256; one selection outcome per tile (ovf_cap = 0)
+      ("quads_all", ja, jb, masked, [sel], compact)          tier1_cannot_serve and the wave-level dense path
+      (su, "empty") | (su, "flat", P, M, [fold, fold]) | (su, "flat_refused", P, M) then what serves the unit |
+      (su, "hash", P, n_steps, fold) | (su, "quads_unit", ja, jb, masked, [sel], compact) |
+      (su, "packed", [(tiles, GP, "hash" | "dense" | "empty", outcome), ...])
+      ("t1_fold", c1, passed, tau, fold)                     unsplit query whose other units tier 1 served: tier 1's c1 entries, how
+                                                             many reach tier 2's tau, the fold's outcome (before "emit")
+      ("emit", entries, shrunk)                              topk_shrink ran a selection or not
+    A selection outcome is (name, n) with the names of _T2List; `compact` says whether list_compact_select ran at the end of
+    dense_quads.  Also returned per item: tau0 and all_units."""
+    from scipy.sparse import csr_matrix
+    import oracle
+    f = np.float32
+    indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices, np.int32)
+    data, idf = np.asarray(data, np.float32), np.asarray(idf, np.float32)
+    q_ptr, q_term, q_w = (np.asarray(x) for x in q)
+    q_w = q_w.astype(np.float32)
+    nq, n_docs, V = len(q_ptr) - 1, len(indptr) - 1, len(idf)
+    tps = unit_tiles if tps is None else tps
+    G = 1 << tile_log2
+    n_tiles = (n_docs + G - 1) >> tile_log2
+    n_super = p["n_super"]
+    assert n_super == (n_tiles + tps - 1) // tps, "the plan is of another search"
+    sv = stored_values(indptr, data, doc_lengths, mode, val_dtype, k1, b, avgdl)
+    if layout is None:
+        layout = np_build_blocks(indptr, indices, sv, n_docs, V, tile_log2, unit_tiles)
+    term_ptr, post, skip = layout[0], layout[1].reshape(-1, 8), layout[2].reshape(V, n_tiles + 1)
+    post_doc = post[:, :4].reshape(-1)  # the doc of posting position g (negative: run padding)
+    csc = csr_matrix((sv, indices, indptr), shape=(n_docs, V)).tocsc()
+    sdata = sv if mode == "dot" else data
+    dbg = debug | (SRX_DBG_TIER2_ONLY if (after is not None or tps != unit_tiles) else 0)
+    col = bound_column_of(k)
+    bounds_on = not (dbg & SRX_DBG_NO_TERM_BOUND) and after is None and col >= 0 and not np.any(sv < 0)
+    q_of, split_of, nsq_of = item_queries(p, nq)
+    flags = np.asarray(flags, bool)
+    out = {"steps": [], "tau0": [], "all_units": []}
+    per_q = {}
+    for it in range(p["items"]):
+        qi, split, nsq = int(q_of[it]), int(split_of[it]), int(nsq_of[it])
+        terms = q_term[q_ptr[qi]:q_ptr[qi + 1]].astype(np.int64)
+        w = q_w[q_ptr[qi]:q_ptr[qi + 1]]
+        nt = len(terms)
+        su_lo, su_hi = n_super * split // nsq, n_super * (split + 1) // nsq
+        all_units = tier1_cannot_serve(nt, k, tps, tile_log2, V, n_tiles, dbg, post16)
+        any_ = all_units and nt > 0
+        if not all_units and nt > 0 and su_lo < su_hi:  # whole flag words, as the kernel reads them
+            any_ = bool(flags[it, (su_lo >> 5) * 32: ((su_hi - 1) >> 5) * 32 + 32].any())
+        out["all_units"].append(all_units)
+        if not any_:
+            out["steps"].append([("skip",)])
+            out["tau0"].append(f(0))
+            continue
+        if qi not in per_q:  # open_item's tau0, the exact scores in the kernel's order, postings per doc
+            tau0, neg, nonfinite = f(0), False, False
+            m = np.zeros(n_docs, np.int64)
+            for t, wt in zip(terms, w):
+                vals = csc.data[csc.indptr[t]:csc.indptr[t + 1]]
+                np.add.at(m, csc.indices[csc.indptr[t]:csc.indptr[t + 1]], 1)
+                nonfinite = nonfinite or not (abs(idf[t]) <= 3.0e38) or not (abs(wt) <= 3.0e38)
+                if idf[t] < 0 or wt < 0:
+                    neg = True
+                elif bounds_on and idf[t] > 0 and wt > 0:
+                    pos = np.sort(vals[vals > 0])[::-1]
+                    K = BOUND_KS[col]
+                    bnd = pos[K - 1] if len(pos) >= K else f(0)
+                    bb = f(0) + (f(bnd) * idf[t]) * f(wt)
+                    tau0 = max(tau0, bb if bb > 0 else f(0))
+            tau0 = f(0) if (neg or nonfinite or after is not None) else f(tau0)
+            with np.errstate(all="ignore"):
+                s = oracle.scores_given_order(indptr, indices, sdata, doc_lengths, idf, terms.astype(np.int32), w, k1, b, avgdl, tfidf=(mode == "dot"))
+            per_q[qi] = (tau0, nonfinite, s, m)
+        tau0, nonfinite, s, m = per_q[qi]
+        out["tau0"].append(tau0)
+        L = _T2List(s, tau0, k, None if after is None else (f(max(after[0][qi], 0)), int(after[1][qi])))
+        append_scan = not (dbg & SRX_DBG_WAVE_DENSE_GENERAL)
+        steps = []
+
+        def emit():
+            n = len(L.docs)
+            if n > k:
+                L.select()
+            if nsq == 1 and not all_units:
+                # emit_item on an unsplit query: tier 1's list of the same query -- the k best of the docs of the units it
+                # served (exact only where tier 1's threshold starts at 0: debug 16) -- is folded in: its first min(count, k)
+                # entries, those with bits >= tau and != 0, through topk_fold<KPT, false> (capacity k)
+                served = np.flatnonzero(~flags[it, :n_super])
+                d1 = np.concatenate([np.arange(u * tps * G, min((u + 1) * tps * G, n_docs)) for u in served] + [np.zeros(0, np.int64)]).astype(np.int64)
+                d1 = d1[s[d1] > 0]
+                d1 = d1[np.lexsort((d1, -s[d1].astype(np.float64)))][:k]
+                tau_emit = L.tau
+                ok = d1[s[d1] >= tau_emit]
+                steps.append(("t1_fold", len(d1), len(ok), float(tau_emit), L.fold(ok, cap=k)[0]))
+            steps.append(("emit", n, n > k))
+            out["steps"].append(steps)
+
+        if nt > MAXT:
+            ja, jb = su_lo * tps, min(su_hi * tps, n_tiles)
+            sel = [L.dense_group(j * G, (j + 1) * G, n_docs, append_scan, 0) for j in range(ja, jb)]
+            steps.append(("many_term", ja, jb, (nt + MAXT - 1) // MAXT, nt - (nt - 1) // MAXT * MAXT, sel))
+            emit()
+            continue
+        wave_dense = (4 << tile_log2) <= TBL_WORDS and nt <= 64 and not (dbg & SRX_DBG_NO_WAVE_DENSE)
+        masked = not (unit_tiles == 1 and not nonfinite and not (dbg & SRX_DBG_WAVE_DENSE_MASKED))
+
+        def dense_quads(ja, jb):
+            # a wave whose tile is at or beyond jb zeroes its accumulators and adds nothing: the scan sees the tiles below jb only
+            sel = [L.dense_group(j0 * G, min(j0 + WAVES, jb) * G, n_docs, append_scan, OVF_CAP) for j0 in range(ja, jb, WAVES)]
+            compact = len(L.docs) > KMAX
+            if compact:
+                L.select()
+            return ja, jb, masked, sel, compact
+
+        def hash_unit(ja, jb):  # the unit's candidates are the docs of its tiles: a doc without a posting scores 0
+            return L.fold(np.arange(ja * G, min(jb * G, n_docs)))
+
+        if all_units and wave_dense:
+            steps.append(("quads_all",) + dense_quads(su_lo * tps, min(su_hi * tps, n_tiles)))
+            emit()
+            continue
+        for su in range(su_lo, su_hi):
+            if not all_units and not flags[it, su]:
+                continue
+            ja, jb = su * tps, min(su * tps + tps, n_tiles)
+            lens = skip[terms, min(ja + tps, n_tiles)] - skip[terms, min(ja, n_tiles)]
+            P = int(lens.sum())
+            if P == 0:
+                steps.append((su, "empty"))
+                continue
+            if tps == 1 and nt >= FLAT_MIN_TERMS and P <= FLAT_CAP and not (dbg & SRX_DBG_NO_FLAT_TILES):
+                docs = np.concatenate([post_doc[term_ptr[t] + skip[t, ja]: term_ptr[t] + skip[t, ja] + n] for t, n in zip(terms, lens)])
+                docs = docs[docs >= 0]
+                M = int((m[docs] >= 2).sum())
+                if M <= FLAT_MCAP:
+                    u = np.unique(docs)
+                    steps.append((su, "flat", P, M, [L.fold(u[m[u] == 1]), L.fold(u[m[u] >= 2])]))
+                    continue
+                steps.append((su, "flat_refused", P, M))
+            if P <= DENSE_MIN:
+                steps.append((su, "hash", P, int(((lens + THREADS - 1) // THREADS).sum()), hash_unit(ja, jb)))
+            elif wave_dense:
+                steps.append((su, "quads_unit") + dense_quads(ja, jb))
+            else:  # packed_unit: greedy groups of whole tiles
+                ptile = [int((skip[terms, ja + j + 1] - skip[terms, ja + j]).sum()) for j in range(jb - ja)]
+                grp, acc_p = [0], 0
+                for j, pj in enumerate(ptile):
+                    if acc_p > 0 and acc_p + pj > DENSE_MIN:
+                        grp.append(j)
+                        acc_p = 0
+                    acc_p += pj
+                grp.append(jb - ja)
+                groups = []
+                for ga, gb in zip(grp[:-1], grp[1:]):
+                    GP = int((skip[terms, ja + gb] - skip[terms, ja + ga]).sum())
+                    if GP == 0:
+                        groups.append(((ja + ga, ja + gb), 0, "empty", None))
+                    elif GP <= DENSE_MIN:
+                        groups.append(((ja + ga, ja + gb), GP, "hash", hash_unit(ja + ga, ja + gb)))
+                    else:  # one tile above DENSE_MIN, the group's last: only empty tiles can come before it (acc_p == 0 never closes a group)
+                        assert sum(ptile[ga:gb - 1]) == 0 and ptile[gb - 1] == GP
+                        groups.append(((ja + ga, ja + gb), GP, "dense", L.dense_group((ja + gb - 1) * G, (ja + gb) * G, n_docs, append_scan, 0)))
+                steps.append((su, "packed", groups))
+        emit()
+    return out

@@ -193,7 +193,8 @@ def test_tfidf_dot_mode_golden(rx, golden_dir):
 # seeded synthetic corpora vs the oracle (exact)
 # ---------------------------------------------------------------------------------------------------------------
 def test_uniform_sparse_hash_path(rx):
-    """C2-shaped, scaled down: every unit goes through the LDS hash path; several splits; k=100."""
+    """C2-shaped, scaled down: every unit goes through the LDS hash path; several splits; k=100.  (The path is a claim about a
+    random corpus: which path serves which unit is checked in tests/test_tier2_routes_cpu.py / _gpu.py.)"""
     from sparse_rx import synth
     c = synth.uniform_corpus_np(200_000, 20_000, 40, seed=20252)
     _, idf, avgdl = synth.corpus_stats(c)
@@ -218,7 +219,8 @@ def test_uniform_sparse_hash_path(rx):
 
 def test_zipf_dense_and_overflow_paths(rx):
     """C5-shaped, scaled down: hot terms (df ~ n_docs, negative idf) force the dense-tile path and the overflow
-    packer; ties are abundant."""
+    packer; ties are abundant.  (The paths are claims about a random corpus: which path serves which unit, and the packer's
+    group edges, are checked in tests/test_tier2_routes_cpu.py / _gpu.py.)"""
     from sparse_rx import synth
     c = synth.zipf_corpus_np(120_000, 5_000, 60, seed=20255)
     df, idf, avgdl = synth.corpus_stats(c)

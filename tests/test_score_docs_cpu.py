@@ -134,7 +134,7 @@ def test_symbol_is_declared_bound_and_listed():
     from sparse_rx import _capi
     assert "srx_score_docs" in _capi.SYMBOLS and "score_docs.hip" in _capi.SOURCES and len(_capi.SYMBOLS) == 35
     assert _capi.lib().srx_version() == 301
-    assert _capi.kernel_sources_sha256() == "9b7990d8a9cef970ee472fb70a7ce838cc51f69a19cc383a89adf648edb59d06"
+    assert _capi.kernel_sources_sha256() == "5b0819c0690ad23ca713f08faa3b931da0e4d43dc3e56784f282166e1203c030"
 
 
 # ---------------------------------------------------------------------------------------------------------------
