@@ -351,7 +351,10 @@ int srx_dense_search_u8(int32_t device, const uint8_t *corpus, const float *corp
  *   SRX_FUSE_WEIGHTED   c = weight_x * (score / x_score[q][0])   -- divided by the list's best score; a list whose entry 0
  *                       is not used counts as empty in this mode
  *   SRX_FUSE_RRF        c = weight_x / (rrf_c + (float)(r + 1))   -- reciprocal rank fusion; rrf_c is ignored otherwise
- * Fused score of a doc = c_A + c_B when both lists hold it, else its one contribution.  Row q of the outputs
+ * Fused score of a doc = c_A + c_B when both lists hold it, else its one contribution.  A +inf score is used like any
+ * other; in mode SRX_FUSE_WEIGHTED it can make a contribution NaN (+inf / +inf, or a zero weight times an infinite
+ * quotient), and then the fused score is NaN, which is not > 0: the doc is in no result, whichever list the NaN comes
+ * from and whatever the other list says about it.  Row q of the outputs
  * (out_doc / out_score [nq][k], out_count [nq], 1 <= k <= 1024): the k best docs with fused score > 0, ranked (fused score
  * descending, doc ascending), padded with doc -1 / score 0; out_count[q] <= min(k, docs in either list).
  * Note: with one weight 0 the fused SET is the other list's, but score / best can round two different scores to the

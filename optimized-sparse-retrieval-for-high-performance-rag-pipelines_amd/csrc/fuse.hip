@@ -6,10 +6,18 @@
 //               entries of list A are compacted into the wave's LDS list and their list positions entered into an
 //               open-addressing table keyed by doc id; list B probes it: a hit adds its contribution to A's entry, a
 //               miss is appended.  wave_list_select / wave_rank_emit (srx_common.h) select, rank and write the row.
+//               A NaN contribution never enters the list (the selection orders by unsigned bits, and NaN bits sort above
+//               +inf): A's entry is parked instead -- doc only, at the far end of the list, entered into the table -- so
+//               that B's copy is found and dropped; B's NaN is dropped on a miss, and on a hit the sum turns A's entry
+//               NaN and one compaction pass (fuse_wave_drop_nan, only then) takes such entries out.
 //   block form  everything else (<= 2048 candidates, k <= 1024): one 256-thread workgroup per query, candidates in
 //               registers, the same table (aliasing the selection histogram, which is only needed afterwards), topk_fold
 //               keeps the k best and block_rank_emit ranks and writes the row (both srx_common.h: the selection and
-//               ranking of the merge kernel, not a second copy).
+//               ranking of the merge kernel, not a second copy).  A's entries with a NaN contribution are entered like the
+//               others, B's probe like the others; the sum of an entry is formed in registers, and a NaN there is no
+//               candidate.
+// A contribution is NaN only in mode weighted: +inf / +inf, or a zero weight times an infinite quotient.  The contract's
+// c_A + c_B is then NaN, not > 0: the doc is in no result, whichever list the NaN comes from -- as in the scored form below.
 // The table holds positions, not keys (the key of slot value v is the doc stored at position v - 1), so a slot is one
 // word: 8 KiB for 2048 slots, load <= 0.5 because only list A (< 1024 / <= 1024 entries) is entered.
 #include "srx_common.h"
@@ -80,6 +88,30 @@ struct FuseWaveShared {
     unsigned tbl[F_SLOTS];
 };  // 18 KiB per wave, 72 KiB per workgroup: two workgroups per CU
 
+// Take the NaN entries out of the wave's list (count entries in S.lbits / S.ldoc), in place; returns the new count.  Rare, so
+// not inlined.  The compaction of wave_list_select: 64 entries per step are read before any is written, and an entry only
+// moves down.
+__device__ __noinline__ unsigned fuse_wave_drop_nan(FuseWaveShared &S, unsigned count) {
+    const int lane = threadIdx.x & 63;
+    unsigned base = 0;  // wave-uniform running count
+    for (unsigned i0 = 0; i0 < count; i0 += 64) {
+        const unsigned i = i0 + lane;
+        const unsigned x = i < count ? S.lbits[i] : 0u;
+        const int dd = i < count ? S.ldoc[i] : 0;
+        const bool take = i < count && (x & 0x7FFFFFFFu) <= 0x7F800000u;
+        const unsigned long long m = __ballot(take);
+        wsync();
+        if (take) {
+            const unsigned p = base + lane_rank(m);
+            S.lbits[p] = x;
+            S.ldoc[p] = dd;
+        }
+        base += (unsigned)__popcll(m);
+        wsync();
+    }
+    return base;
+}
+
 __global__ __launch_bounds__(THREADS) void srx_fuse_wave_kernel(FuseArgs a) {
     __shared__ FuseWaveShared FW[WAVES];
     const int lane = threadIdx.x & 63;
@@ -118,13 +150,16 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_wave_kernel(FuseArgs a) {
 #pragma unroll
     for (int j = 0; j < F_SLOTS / 256; ++j) reinterpret_cast<uint4 *>(S.tbl)[j * 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
     wsync();
-    // contributions (0 = drop: unused entry, zero weight or underflow; adding it would not change the other side's bits)
+    // contributions: +0 = drop (unused entry, zero weight or underflow; adding it would not change the other side's bits),
+    // NaN (weighted only: +inf / +inf, or a zero weight times an infinite quotient) = the doc leaves the result
+    bool a_nan = false;
 #pragma unroll
     for (int j = 0; j < FW_NPL; ++j) {
         const int c = j * 64 + lane;
         const bool is_a = c < ka;
         const bool used = dd[j] >= 0 && sc[j] > 0.0f && (is_a ? a_on : b_on);
         sc[j] = fuse_contribution(a.mode, used, is_a ? a.wa : a.wb, sc[j], is_a ? ma : mb, is_a ? c : c - ka, a.rrf_c);
+        a_nan |= is_a && sc[j] != sc[j];
     }
     // list A: compact into the list, enter the positions
     unsigned count = 0;  // wave-uniform
@@ -141,17 +176,39 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_wave_kernel(FuseArgs a) {
         }
         count += (unsigned)__popcll(m);
     }
-    wsync();
     const unsigned na = count;
-    // list B: a hit adds to A's entry (docs are unique inside B, so no two lanes hit the same entry), a miss is appended
+    // A's entries with a NaN contribution are parked, docs only, from the list's last slot downwards and entered too, so that
+    // B's copy of such a doc is found and dropped.  They never meet the list: entries of A + parked <= ka, appended <= kb.
+    unsigned parked = 0;  // wave-uniform
+    if (__ballot(a_nan) != 0ull) {
+#pragma unroll
+        for (int j = 0; j < FW_NPL; ++j) {
+            if (j * 64 >= ka) break;
+            const bool ok = j * 64 + lane < ka && sc[j] != sc[j];
+            const unsigned long long m = __ballot(ok);
+            if (ok) {
+                const unsigned p = (unsigned)(FW_CAP - 1) - (parked + lane_rank(m));
+                S.ldoc[p] = dd[j];
+                fuse_insert(S.tbl, dd[j], p);
+            }
+            parked += (unsigned)__popcll(m);
+        }
+    }
+    wsync();
+    // list B: a hit adds to A's entry (docs are unique inside B, so no two lanes hit the same entry) unless that entry is
+    // parked, a miss is appended unless it is NaN.  A NaN that hits makes A's entry NaN: such entries are taken out below.
+    bool nan_hit = false;
 #pragma unroll
     for (int j = 0; j < FW_NPL; ++j) {
         if ((j + 1) * 64 <= ka) continue;
-        const bool isb = j * 64 + lane >= ka && sc[j] > 0.0f;
+        const bool isb = j * 64 + lane >= ka && sc[j] != 0.0f;  // > 0 or NaN
+        const bool b_nan = sc[j] != sc[j];
         int hit = -1;
-        if (isb && na > 0) hit = fuse_find(S.tbl, dd[j], [&](unsigned p) -> int { return S.ldoc[p]; });
-        if (isb && hit >= 0) S.lbits[hit] = __float_as_uint(__uint_as_float(S.lbits[hit]) + sc[j]);
-        const bool app = isb && hit < 0;
+        if (isb && na + parked > 0) hit = fuse_find(S.tbl, dd[j], [&](unsigned p) -> int { return S.ldoc[p]; });
+        const bool add = isb && hit >= 0 && hit < (int)na;
+        if (add) S.lbits[hit] = __float_as_uint(__uint_as_float(S.lbits[hit]) + sc[j]);
+        nan_hit |= add && b_nan;
+        const bool app = isb && hit < 0 && !b_nan;
         const unsigned long long m = __ballot(app);
         if (app) {
             const unsigned p = count + lane_rank(m);
@@ -161,6 +218,7 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_wave_kernel(FuseArgs a) {
         count += (unsigned)__popcll(m);
     }
     wsync();
+    if (__ballot(nan_hit) != 0ull) count = fuse_wave_drop_nan(S, count);
     if (count > (unsigned)k) {
         wave_list_select(S, count, k);
         count = (unsigned)k;
@@ -222,13 +280,13 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_block_kernel(FuseArgs a) {
         const bool is_a = c < ka;
         const bool used = dd[n] >= 0 && sc[n] > 0.0f && (is_a ? a_on : b_on);
         sc[n] = fuse_contribution(a.mode, used, is_a ? a.wa : a.wb, sc[n], is_a ? ma : mb, is_a ? c : c - ka, a.rrf_c);
-        if (is_a && sc[n] > 0.0f) adoc[c] = dd[n];  // c = rank in A < ka <= KMAX
+        if (is_a && sc[n] != 0.0f) adoc[c] = dd[n];  // > 0 or NaN (see the wave form); c = rank in A < ka <= KMAX
     }
     __syncthreads();
 #pragma unroll
     for (int n = 0; n < FB_NPT; ++n) {
         const int c = n * THREADS + tid;
-        if (c < ka && sc[n] > 0.0f) fuse_insert(S.hist, dd[n], (unsigned)c);
+        if (c < ka && sc[n] != 0.0f) fuse_insert(S.hist, dd[n], (unsigned)c);
     }
     __syncthreads();
     unsigned ubits[FB_NPT];
@@ -236,10 +294,10 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_block_kernel(FuseArgs a) {
 #pragma unroll
     for (int n = 0; n < FB_NPT; ++n) {
         const int c = n * THREADS + tid;
-        if (c >= ka && sc[n] > 0.0f) {
+        if (c >= ka && sc[n] != 0.0f) {
             const int hit = fuse_find(S.hist, dd[n], [&](unsigned p) -> int { return adoc[p]; });
             if (hit >= 0) {
-                addc[hit] = sc[n];  // docs are unique inside B: one writer per entry of A
+                addc[hit] = sc[n];  // docs are unique inside B: one writer per entry of A; a NaN makes A's entry NaN
                 sc[n] = 0.0f;
             }
         }
@@ -250,7 +308,7 @@ __global__ __launch_bounds__(THREADS) void srx_fuse_block_kernel(FuseArgs a) {
         const int c = n * THREADS + tid;
         float f = sc[n];
         if (c < ka && f > 0.0f) f = f + addc[c];
-        ubits[n] = f > 0.0f ? __float_as_uint(f) : 0u;
+        ubits[n] = f > 0.0f ? __float_as_uint(f) : 0u;  // a NaN, from either list, is no candidate
         udoc[n] = dd[n];
     }
     __syncthreads();  // the table and list A's arrays are dead: their words become the selection histogram and the sort keys

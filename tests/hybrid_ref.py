@@ -4,6 +4,8 @@ denormals kept), ``sorted`` by (-score, doc).  The GPU tests compare the kernel'
 
 Also here: the host dispatch rule restated (which of the kernel's two forms a shape takes) and the seeded list maker
 the kernel tests share."""
+import functools
+
 import numpy as np
 
 WEIGHTED, RRF = 0, 1
@@ -15,6 +17,56 @@ WAVE_MAX_CANDIDATES, WAVE_MAX_K = 1024, 128
 def form(ka: int, kb: int, k: int) -> str:
     """Which kernel form the host picks: one wavefront per query for small shapes, one workgroup otherwise."""
     return "wave" if ka + kb <= WAVE_MAX_CANDIDATES and k <= WAVE_MAX_K else "block"
+
+
+# ---- the kernels' open-addressing table restated (csrc/fuse.hip: fuse_slot, fuse_insert, fuse_find) -----------------------------
+F_SLOTS, F_SLOT_BITS, F_MULTIPLIER = 2048, 11, 2654435761
+MAX_DOC = 2 ** 31 - 2  # the largest doc id the engine's ranking key (0x7FFFFFFF - doc, 0 = none) can carry
+
+
+def fuse_slot(doc):
+    """home slot of a doc id >= 0: the top F_SLOT_BITS bits of (doc * F_MULTIPLIER mod 2^32)"""
+    return (((np.asarray(doc, np.int64) * F_MULTIPLIER) & 0xFFFFFFFF) >> (32 - F_SLOT_BITS)).astype(np.int64)
+
+
+@functools.lru_cache(maxsize=4)
+def _homes(lo, hi):
+    ids = np.arange(lo, hi, dtype=np.int64)
+    return ids, fuse_slot(ids).astype(np.int16)
+
+
+def docs_homed_at(slots, n, lo, hi):
+    """the n smallest doc ids of [lo, hi) whose home slot is `slots` (one slot) or one of `slots`, ascending, int32"""
+    ids, home = _homes(lo, hi)
+    pick = ids[home == slots] if np.isscalar(slots) else ids[np.isin(home, np.asarray(list(slots), np.int64))]
+    assert len(pick) >= n, (slots, n, lo, hi, len(pick))
+    return pick[:n].astype(np.int32)
+
+
+def probe_layout(docs):
+    """int64[F_SLOTS]: the doc each slot holds (-1 = empty) after the docs are entered by linear probing with wrap.  Which
+    doc lands where depends on the order of insertion; WHICH SLOTS are occupied does not."""
+    tbl = np.full(F_SLOTS, -1, np.int64)
+    assert len(docs) < F_SLOTS
+    for d, h in zip(np.asarray(docs).tolist(), fuse_slot(docs).tolist()):
+        while tbl[h] >= 0:
+            h = (h + 1) & (F_SLOTS - 1)
+        tbl[h] = d
+    return tbl
+
+
+def probe_walk(tbl, doc):
+    """(found, slots visited in order) of fuse_find's walk for `doc`: from its home slot to its own slot or the first empty one"""
+    h = int(fuse_slot(doc))
+    seen = []
+    for _ in range(F_SLOTS):
+        seen.append(h)
+        if tbl[h] < 0:
+            return False, seen
+        if tbl[h] == doc:
+            return True, seen
+        h = (h + 1) & (F_SLOTS - 1)
+    return False, seen
 
 
 def _used(doc, score, count, kx):
