@@ -1,7 +1,8 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
-include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h and include/boost/sparse_rx_boost.h).
+include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h and
+include/ltr/sparse_rx_ltr.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -20,7 +21,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -264,6 +265,30 @@ SRX_BOOST_MAX_M, SRX_BOOST_MAX_CLAUSES, SRX_BOOST_MAX_COLS = 2048, 8, 8         
 SRX_BOOST_MAX_KNOTS = 1 << 24
 
 
+class LtrFeature(ctypes.Structure):
+    """``srx_ltr_feature`` (include/ltr/sparse_rx_ltr.h): a HOST array element of 8 bytes"""
+    _fields_ = [("kind", ctypes.c_int32), ("index", ctypes.c_int32)]
+
+
+class LtrNode(ctypes.Structure):
+    """``srx_ltr_node`` (include/ltr/sparse_rx_ltr.h): a DEVICE array element of 16 bytes"""
+    _fields_ = [("feature", ctypes.c_int32), ("value", ctypes.c_float), ("left", ctypes.c_int32), ("right", ctypes.c_int32)]
+
+
+# every symbol include/ltr/sparse_rx_ltr.h declares (the fifteenth header of the same library)
+_LTR_HEAD = [_I32, _CP, _I32, _I64, _I64, ctypes.POINTER(LtrFeature), _I32, _VP, _I32, _VP, _I32, _VP, _I32, _F32, _I32, _I32, _VP, _VP, _VP]  # device .. cand_count
+LTR_SYMBOLS = {
+    "srx_ltr_topk": (ctypes.c_int, [*_LTR_HEAD, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "srx_ltr_score": (ctypes.c_int, [*_LTR_HEAD, _I32, _I32, _VP, _VP]),
+}
+SRX_LTR_F_SCORE, SRX_LTR_F_RANK, SRX_LTR_F_COLUMN, SRX_LTR_F_EXTRA = 0, 1, 2, 3                       # srx_ltr_feature.kind
+SRX_LTR_LE, SRX_LTR_LT = 0, 1                                                                         # cmp
+SRX_LTR_REPLACE, SRX_LTR_SUM = 0, 1                                                                   # mode
+SRX_LTR_MISSING_LEFT = 1 << 30                                                                        # bit 30 of srx_ltr_node.feature
+SRX_LTR_MAX_M, SRX_LTR_MAX_COLS, SRX_LTR_MAX_FEATURES, SRX_LTR_MAX_EXTRA = 2048, 8, 32, 32            # pinned to the header by tests/test_ltr_cpu.py
+SRX_LTR_MAX_TREES, SRX_LTR_MAX_NODES = 4096, 1 << 22
+
+
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
     ``srx_order_workspace_bytes`` by tests/test_order_cpu.py).  A segment is what one workgroup scans for one row."""
@@ -305,7 +330,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_facets.h"),
                                                             os.path.join(INCLUDE_DIR, "ext", "sparse_rx_feedback.h"),
                                                             os.path.join(INCLUDE_DIR, "order", "sparse_rx_order.h"),
-                                                            os.path.join(INCLUDE_DIR, "boost", "sparse_rx_boost.h")]
+                                                            os.path.join(INCLUDE_DIR, "boost", "sparse_rx_boost.h"),
+                                                            os.path.join(INCLUDE_DIR, "ltr", "sparse_rx_ltr.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -355,7 +381,7 @@ def lib() -> ctypes.CDLL:
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
-                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS}.items():
+                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -50,6 +50,7 @@ class SparseBackend:
         self.n_docs_total = 0
         self._doc_lengths_all = None
         self._fields = None        # set_fields: the docs' metadata columns on the host (fields.HostColumn by name) ...
+        self._rank_model = None    # set_rank_model: (ltr.ForestModel, feature names)
         self._field_table = None   # ... and on the device, uploaded by the first call that filters with them
         self._rows = None          # _row_table
         self._forward = None       # enable_feedback: the doc-major forward index (feedback.ForwardIndex) and its term gains
@@ -379,6 +380,91 @@ class SparseBackend:
         m = cand_doc.shape[1]
         k = m if top_k is None else min(int(top_k), m)
         _, ns, cnt, pos = BoostFn(table, res)(*(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k, want_pos=True)
+        block = torch.cat([pos, cnt.reshape(-1, 1), ns.view(torch.int32)], dim=1).cpu().numpy()
+        for i, (qid, _, _) in enumerate(live):
+            n = int(block[i, k])
+            new = block[i, k + 1: k + 1 + n].copy().view(np.float32)
+            out[qid] = {pairs[qid][int(p)][0]: float(v) for p, v in zip(block[i, :n], new)}
+        return out
+
+    # -- reranking with a tree-ensemble model (include/ltr/sparse_rx_ltr.h) -------------------------------------------------------
+    def set_rank_model(self, model, features) -> None:
+        """The model and the feature list of the ``rank_model=True`` keyword and of :meth:`rerank_model_results`: a
+        :class:`~.ltr.ForestModel` and what :func:`~.ltr.resolve_features` takes (plus "sparse_score" / "dense_score", which only a
+        hybrid search fills).  The names are resolved against the docs' fields at every call: they may be set later."""
+        from .ltr import HYBRID_FEATURES, resolve_features
+        named = isinstance(features, (list, tuple)) and any(isinstance(f, str) and f in HYBRID_FEATURES for f in features)
+        resolve_features(self._fields, features, model, HYBRID_FEATURES if named else (), any_column=self._fields is None)
+        self._rank_model = (model, list(features))
+
+    def rank_table(self):
+        """:meth:`field_table`, or a table without columns when no fields are set (a model over scores, ranks and extras)"""
+        if self._fields is not None:
+            return self.field_table()
+        from .fields import FieldTable
+        return FieldTable.without_columns(self.n_docs_total, device=self.dev.device if self.dev is not None else self.device, doc_base=self.doc_base)
+
+    def rank_spec(self, rank_model, rank_pool=None, top_k: int = 10, call: str = "search", boost=None, hybrid: bool = False):
+        """The model keywords of one API call (``rank_model``, ``rank_pool``) as a :class:`~.ltr.RankFn` with a ``pool`` attribute
+        (``rank_pool`` in 1 .. 1024, default ``min(max(4 * top_k, 100), 1024, n_docs)``), or None when ``rank_model`` is false.
+        ValueError: no :meth:`set_rank_model`, a sharded index, ``boost=`` in the same call, a feature that names a column without
+        the docs' fields, an unknown or set column, "sparse_score" / "dense_score" unless ``hybrid``, an ``("extra", i)`` feature when
+        ``hybrid`` (such a search has no extras to give), a pool above 1 024."""
+        if not rank_model:  # rank_pool is then not looked at, like boost_pool without boost
+            return None
+        from .ltr import HYBRID_FEATURES, RankFn
+        if getattr(self, "_rank_model", None) is None:
+            raise ValueError(f"{call}(rank_model=True) needs a model: call set_rank_model() first")
+        self._refuse_sharded("rank_model= needs")
+        if boost is not None:
+            raise ValueError(f"{call}: rank_model= and boost= do not combine in one call (chain boost_results() over the reranked result)")
+        model, features = self._rank_model
+        if self._fields is None and any(isinstance(f, str) and f not in ("score", "rank", *HYBRID_FEATURES) for f in features):
+            self._need_fields(call, "rank_model=True")
+        if hybrid and any(isinstance(f, (tuple, list)) for f in features):
+            raise ValueError(f"{call}(rank_model=True) cannot fill (\"extra\", i) features: a hybrid search supplies \"sparse_score\" and "
+                             "\"dense_score\" only (chain rerank_model(results, top_k, extra=...) over its result)")
+        pool = collapse_pool_depth(top_k, rank_pool, self.n_docs_total, "rank_pool")
+        named = HYBRID_FEATURES if hybrid and any(isinstance(f, str) and f in HYBRID_FEATURES for f in features) else ()
+        fn = RankFn(self.rank_table, model, features, named, columns=self._fields if self._fields is not None else {})
+        fn.pool = pool
+        return fn
+
+    def rerank_model_results(self, results, top_k=None, extra=None, mode: str = "replace", call: str = "rerank_model"):
+        """Result lists re-scored and re-ranked by the model of :meth:`set_rank_model` (``srx_ltr_topk``): ``results`` =
+        ``{qid: {doc_id: score}}`` as any search returns it (or ``search_by_vector``'s lists of ``{"doc_id", "score"}`` dicts) ->
+        ``{qid: {doc_id: model score}}``, the first ``top_k`` (None: all) by (new score descending, corpus order).  The feature
+        "score" is the value given, "rank" the position in the list given.  ``extra``: ``{qid: {doc_id: sequence of floats}}``, the
+        values of the ``("extra", i)`` features (a doc or a value left out is missing: NaN).  One upload, one launch, one copy
+        back.  ValueError: a list deeper than 2048, an unknown doc id, what :meth:`rank_spec` refuses."""
+        from . import _capi
+        from .ltr import check_mode
+        fn = self.rank_spec(True, None, 1, call)
+        check_mode(mode)
+        if top_k is not None and int(top_k) < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        out = {qid: {} for qid in (results or {})}
+        if not results:
+            return out
+        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, _capi.SRX_LTR_MAX_M)
+        if not live:
+            return out
+        import torch
+        from .ltr import resolve_features
+        table = fn.table
+        n_extra = resolve_features(table.columns, fn.features, fn.model)[2]
+        m = cand_doc.shape[1]
+        plane = None
+        if n_extra:
+            host = np.full((len(live), m, n_extra), np.nan, dtype=np.float32)
+            for i, (qid, _, _) in enumerate(live):
+                row = (extra or {}).get(qid, {})
+                for c, (doc_id, _) in enumerate(pairs[qid]):
+                    vals = np.asarray(row.get(doc_id, ()), dtype=np.float32).reshape(-1)[:n_extra]
+                    host[i, c, : len(vals)] = vals
+            plane = torch.as_tensor(host, device=table.device)
+        k = m if top_k is None else min(int(top_k), m)
+        _, ns, cnt, pos = fn(*(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k, extra=plane, mode=mode, want_pos=True)
         block = torch.cat([pos, cnt.reshape(-1, 1), ns.view(torch.int32)], dim=1).cpu().numpy()
         for i, (qid, _, _) in enumerate(live):
             n = int(block[i, k])
@@ -1369,3 +1455,21 @@ class SparseIndexViews:
         index."""
         self._need_index()
         return self._be.boost_results(results, boost, top_k, "boost_results")
+
+    def set_rank_model(self, model, features) -> None:
+        """The learned reranker of ``rank_model=True`` and :meth:`rerank_model` (no reference counterpart): ``model`` a
+        :class:`~.ltr.ForestModel` (``ForestModel.from_sklearn`` / ``from_arrays``), ``features`` the list whose entry f is the
+        model's feature f -- "score", "rank", the name of a number column of :meth:`set_doc_fields`, ``("extra", i)``, and in
+        ``search_hybrid`` "sparse_score" / "dense_score".  ``ValueError``: no ForestModel, a list that does not fit the model."""
+        self._be.set_rank_model(model, features)
+
+    def rerank_model(self, results, top_k: Optional[int] = None, extra=None, mode: str = "replace"):
+        """Result lists re-scored by the model of :meth:`set_rank_model`: ``results`` = ``{qid: {doc_id: score}}`` as any search of
+        this object returns it -> ``{qid: {doc_id: model score}}``, the first ``top_k`` (None: all) by model score
+        (``srx_ltr_topk``, include/ltr/sparse_rx_ltr.h; ties in corpus order).  ``mode`` "replace": the model's output; "sum": the
+        score given plus it.  ``extra``: ``{qid: {doc_id: [floats]}}`` for the ``("extra", i)`` features.  The result is relative to
+        the lists given.  ``ValueError``: no :meth:`set_rank_model`, a list deeper than 2048, an unknown doc id, a feature that names
+        a column without :meth:`set_doc_fields`, a set column, "sparse_score" / "dense_score" (``search_hybrid`` only), a sharded
+        index."""
+        self._need_index()
+        return self._be.rerank_model_results(results, top_k, extra, mode, "rerank_model")

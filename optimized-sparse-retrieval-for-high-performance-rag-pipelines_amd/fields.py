@@ -1049,6 +1049,97 @@ class FieldTable:
                                                          score_name="the carry's score")
         return self._to_host(BoostFn(self, res)(*cand, k, carry=cr, want_pos=want_pos))
 
+    # -- reranking ranked lists with a tree-ensemble model (include/ltr/sparse_rx_ltr.h) ----------------------------------------
+    @classmethod
+    def without_columns(cls, n_docs: int, device="cuda:0", doc_base: int = 0) -> "FieldTable":
+        """A table of ``n_docs`` docs that holds no column: what :meth:`rank_model_device` needs when no feature names one"""
+        filter_words(int(n_docs))  # n_docs in [1, 2^31 - 2]
+        table = cls.__new__(cls)
+        table.columns, table._tensors = {}, {}
+        table.device, table.doc_base, table.n_docs = _torch().device(device), int(doc_base), int(n_docs)
+        return table
+
+    def _rank_call(self, who: str, model, features, doc, score, count, extra, mode, named_extra):
+        """What the two model doors share: the features resolved against this table's columns, the column descriptors, the lists
+        through the one list door, the extra plane checked -> the leading arguments of ``srx_ltr_topk`` / ``srx_ltr_score`` up to
+        ``m``, and what must stay alive until the launch."""
+        from .ltr import ForestModel, check_mode, feature_array, resolve_features, CMPS
+        torch = _torch()
+        if not isinstance(model, ForestModel):
+            raise ValueError(f"{who}: model must be a ForestModel (ForestModel.from_arrays / from_sklearn)")
+        mode_id = check_mode(mode)
+        records, names, n_extra = resolve_features(self.columns, features, model, named_extra)
+        descs = self._col_descs(names) if names else None
+        doc, score, count, nq, m = self._list_triple(who, _capi.SRX_LTR_MAX_M, doc, score, count)
+        if n_extra == 0:
+            extra = None  # not looked at
+        else:
+            if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.dim() != 3 or tuple(extra.shape[:2]) != (nq, m):
+                raise ValueError(f"{who}: the features name extra values: extra must be a float32 tensor [nq, m, n_extra]")
+            if not (n_extra <= int(extra.shape[2]) <= _capi.SRX_LTR_MAX_EXTRA):
+                raise ValueError(f"{who}: extra holds {int(extra.shape[2])} values per position, the features need {n_extra} (at most {_capi.SRX_LTR_MAX_EXTRA})")
+            if extra.device != self.device:
+                raise ValueError(f"{who}: extra is on {extra.device}, the table on {self.device}")
+            extra = extra.contiguous()
+        nodes, tree_ptr = model.to_device(self.device)
+        feats = feature_array(records)
+        head = (self.device.index or 0, descs, len(names), self.n_docs, self.doc_base, feats, len(records), _ptr(extra),
+                0 if extra is None else int(extra.shape[2]), nodes.data_ptr(), model.n_nodes, tree_ptr.data_ptr(), model.n_trees,
+                float(model.base), CMPS[model.cmp], mode_id, _ptr(doc), _ptr(score), _ptr(count), nq, m)
+        return head, nq, m, (descs, feats, extra, nodes, tree_ptr, doc, score, count)
+
+    def rank_model_device(self, model, features, doc, score, count, k: int, extra=None, mode: str = "replace", want_pos: bool = False,
+                          named_extra=()):
+        """``srx_ltr_topk`` on device tensors: the score of every live position of every list replaced by (``mode`` "replace") or
+        moved by (``mode`` "sum": raw score + model) the output of ``model`` (a :class:`~.ltr.ForestModel`) over ``features`` --
+        a list whose entry f is the model's feature f: "score" (the raw score), "rank" (the position), the name of a number column
+        of this table (a doc without a value, or a float NaN, is MISSING), or ``("extra", i)`` = ``extra[q, c, i]`` of the float32
+        device tensor ``extra`` [nq, m, n_extra <= 32] (a NaN is missing) -- and the first ``k`` by (new score descending, doc id
+        ascending).  ``doc`` i32[nq, m] GLOBAL ids, ``score`` f32[nq, m], ``count`` i32[nq] or None, m <= 2048, 1 <= k <= m.
+        Returns device tensors ``(doc i32[nq, k], score f32[nq, k], count i32[nq])`` padded with -1 / 0, then ``pos`` i32[nq, k]
+        (the position in the list given) with ``want_pos``.  Asynchronous on the current stream, one launch.  ``named_extra``:
+        names that stand for the first extra slots (:func:`~.ltr.resolve_features`)."""
+        torch = _torch()
+        head, nq, m, keep = self._rank_call("rank_model_device", model, features, doc, score, count, extra, mode, named_extra)
+        k = self._check_k("rank_model_device", k, m)
+        with torch.cuda.device(self.device):
+            outs = [torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                    torch.empty((nq,), dtype=torch.int32, device=self.device)]
+            pos = torch.empty((nq, k), dtype=torch.int32, device=self.device) if want_pos else None
+            rc = _capi.lib().srx_ltr_topk(*head, k, *[_ptr(o) for o in outs], _ptr(pos), torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_ltr_topk")
+        del keep
+        return tuple(outs + ([pos] if want_pos else []))
+
+    def model_scores_device(self, model, features, doc, score, count, extra=None, mode: str = "replace", named_extra=()):
+        """``srx_ltr_score`` on device tensors: the inputs of :meth:`rank_model_device` without ``k`` -> float32 [nq, m], the new
+        score of every live position in place, +0 at the dead ones.  Asynchronous on the current stream, one launch."""
+        torch = _torch()
+        head, nq, m, keep = self._rank_call("model_scores_device", model, features, doc, score, count, extra, mode, named_extra)
+        with torch.cuda.device(self.device):
+            out = torch.empty((nq, m), dtype=torch.float32, device=self.device)
+            rc = _capi.lib().srx_ltr_score(*head, _ptr(out), torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(rc, "srx_ltr_score")
+        del keep
+        return out
+
+    def rank_model(self, model, features, doc, score, count, k: int, extra=None, mode: str = "replace", want_pos: bool = False):
+        """Host arrays in (the candidates validated by :func:`~.index.validate_candidates`, ``extra`` a float32 array [nq, m,
+        n_extra] or None), host arrays out: :meth:`rank_model_device` with one synchronisation and one copy back."""
+        from .ltr import check_mode, resolve_features
+        check_mode(mode)
+        _, _, n_extra = resolve_features(self.columns, features, model)
+        lists = self._host_lists("rank_model", _capi.SRX_LTR_MAX_M, doc, score, count)
+        ex = None
+        if n_extra:
+            if extra is None:
+                raise ValueError("rank_model: the features name extra values: give extra [nq, m, n_extra]")
+            ex = np.ascontiguousarray(extra, dtype=np.float32)
+            if ex.ndim != 3 or ex.shape[:2] != tuple(lists[0].shape):
+                raise ValueError("rank_model: extra must be a float32 array [nq, m, n_extra]")
+            ex = _torch().as_tensor(ex, device=self.device)
+        return self._to_host(self.rank_model_device(model, features, *lists, k, extra=ex, mode=mode, want_pos=want_pos))
+
 
 def order_has_value(extra: np.ndarray, nulls: str, k: int) -> np.ndarray:
     """bool[rows, k]: which returned entries have a value, from ``extra`` = (count, valued, ..) -- the valueless entries are the

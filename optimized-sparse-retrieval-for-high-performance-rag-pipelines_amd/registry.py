@@ -47,7 +47,8 @@ class _SparseRetrieverBase(SparseIndexViews):
     def search(self, queries: Dict[str, str], top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
                must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None, per_group: int = 1,
                collapse_nulls: str = "own", collapse_depth: Optional[int] = None, expand_docs: Optional[int] = None, expand_terms: int = 10,
-               expand_weight: float = 0.5, expand_by: str = "score", boost=None, boost_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+               expand_weight: float = 0.5, expand_by: str = "score", boost=None, boost_depth: Optional[int] = None, rank_model: bool = False,
+               rank_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """``allowed_docs`` / ``excluded_docs`` (no reference counterpart): as ``RetrievalService.search_bm25`` -- the top
         ``top_k`` of the allowed docs, exact; both given or an unknown doc id raise ValueError; no cache for a filtered call.
         ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``operators``: term constraints, as ``RetrievalService.search_bm25``
@@ -61,8 +62,19 @@ class _SparseRetrieverBase(SparseIndexViews):
         (Rocchio-style); in BM25 mode tf / doc_len and max(idf, 0).  The scores are those of the expanded query, whose weights
         sum to at most 1: not comparable to the scores of a plain search.
         ``boost`` / ``boost_depth``: the top ``top_k`` of the ranking boosted by field values, exact, with the boosted scores, as
-        ``RetrievalService.search_bm25`` (needs raw scores > 0, which the search guarantees; not with ``collapse_by``; no cache)."""
+        ``RetrievalService.search_bm25`` (needs raw scores > 0, which the search guarantees; not with ``collapse_by``; no cache).
+        ``rank_model`` / ``rank_pool``: the first ``rank_pool`` rows of this search re-scored by the model of :meth:`set_rank_model`
+        and cut to ``top_k``, as ``RetrievalService.search_bm25`` (pool-relative; not with ``boost``)."""
         self._need_index()
+        ranked = self._be.rank_spec(rank_model, rank_pool, top_k, "search", boost)
+        if ranked is not None:
+            if min(int(top_k), self._be.n_docs_total) <= 0:
+                return {qid: {} for qid in queries}
+            pooled = self.search(queries, ranked.pool, allowed_docs=allowed_docs, excluded_docs=excluded_docs, must_terms=must_terms, any_terms=any_terms,
+                                 must_not_terms=must_not_terms, operators=operators, where=where, collapse_by=collapse_by, per_group=per_group,
+                                 collapse_nulls=collapse_nulls, collapse_depth=collapse_depth, expand_docs=expand_docs, expand_terms=expand_terms,
+                                 expand_weight=expand_weight, expand_by=expand_by)
+            return self._be.rerank_model_results(pooled, top_k, call="search")
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")

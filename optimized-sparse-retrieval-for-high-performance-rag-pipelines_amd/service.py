@@ -102,7 +102,7 @@ class RetrievalService(SparseIndexViews):
                     any_terms=None, must_not_terms=None, operators: bool = False, where=None, collapse_by: Optional[str] = None,
                     per_group: int = 1, collapse_nulls: str = "own", collapse_depth: Optional[int] = None, expand_docs: Optional[int] = None,
                     expand_terms: int = 10, expand_weight: float = 0.5, expand_by: str = "score", boost=None,
-                    boost_depth: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+                    boost_depth: Optional[int] = None, rank_model: bool = False, rank_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """retrieval.py:203-231 semantics; one batched GPU call for all uncached queries.
 
         ``allowed_docs`` / ``excluded_docs`` (no reference counterpart: it has no filters): restrict the search to, or keep
@@ -159,8 +159,25 @@ class RetrievalService(SparseIndexViews):
         boosted top of the rows read.  It works under the doc, term and field keywords and with ``expand_docs``, and bypasses
         the query cache.  ``ValueError``: ``collapse_by`` in the same call (chain :meth:`collapse` over the result), ``boost_mode``
         "replace" or a factor that can be negative under "multiply" (no bound exists), ``top_k`` above 1 024, an unknown or set
-        column, no :meth:`set_doc_fields`, a sharded index."""
+        column, no :meth:`set_doc_fields`, a sharded index.
+
+        ``rank_model`` (default False: nothing changes; no reference counterpart): rerank with the learned model of
+        :meth:`set_rank_model` (``srx_ltr_topk``, include/ltr/sparse_rx_ltr.h).  The result is POOL-RELATIVE: the first ``rank_pool``
+        rows of this search under the call's other keywords (default ``min(max(4 * top_k, 100), 1024, n_docs)``), re-scored by the
+        model and cut to ``top_k`` -- what ``rerank_model(search_bm25(top_k=rank_pool, ...), top_k)`` returns; the values are the
+        model's scores.  ``ValueError``: no :meth:`set_rank_model`, a feature that names a column without :meth:`set_doc_fields`,
+        a set column, "sparse_score" / "dense_score" (:meth:`search_hybrid` only), ``rank_pool`` above 1 024, ``boost=`` in the same
+        call (chain :meth:`boost_results`), a sharded index."""
         self._need_index()  # :205-206
+        ranked = self._be.rank_spec(rank_model, rank_pool, top_k, "search_bm25", boost)
+        if ranked is not None:
+            if min(int(top_k), self._be.n_docs_total) <= 0:
+                return {qid: {} for qid in queries}
+            pooled = self.search_bm25(queries, ranked.pool, allowed_docs=allowed_docs, excluded_docs=excluded_docs, must_terms=must_terms,
+                                      any_terms=any_terms, must_not_terms=must_not_terms, operators=operators, where=where, collapse_by=collapse_by,
+                                      per_group=per_group, collapse_nulls=collapse_nulls, collapse_depth=collapse_depth, expand_docs=expand_docs,
+                                      expand_terms=expand_terms, expand_weight=expand_weight, expand_by=expand_by)
+            return self._be.rerank_model_results(pooled, top_k, call="search_bm25")
         if operators:
             queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
         spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
@@ -308,7 +325,8 @@ class RetrievalService(SparseIndexViews):
                       mmr_similarity: str = "cosine", must_terms=None, any_terms=None, must_not_terms=None,
                       operators: bool = False, late_query_tokens=None, late_pool: Optional[int] = None, where=None,
                       collapse_by: Optional[str] = None, per_group: int = 1, collapse_nulls: str = "own",
-                      collapse_pool: Optional[int] = None, boost=None, boost_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+                      collapse_pool: Optional[int] = None, boost=None, boost_pool: Optional[int] = None, rank_model: bool = False,
+                      rank_pool: Optional[int] = None) -> Dict[str, Dict[str, float]]:
         """Hybrid retrieval (no reference counterpart: its ``hybrid`` retriever type is configured but not implemented):
         the BM25 top list of every query text and the f32 ``embedding_index`` top list of its vector in
         ``query_vectors[qid]``, fused on the GPU into one ranking (``srx_fuse_topk``; include/sparse_rx.h has the exact
@@ -368,9 +386,15 @@ class RetrievalService(SparseIndexViews):
         POOL-RELATIVE: what ``boost_results(search_hybrid(top_k=boost_pool, ...), boost, top_k)`` returns, values = boosted fused
         scores.  With ``collapse_by`` the whole boosted pool is then collapsed (``collapse_pool`` is not used), with ``mmr_lambda``
         the boosted (and collapsed) pool's first ``mmr_pool`` rows are diversified.
-        In one sentence: the steps run in the order late rerank, boost, collapse, MMR, each only if its keyword is given; the fusion
-        is as deep as the FIRST step's pool, and a step keeps all its rows for a boost or collapse behind it, ``mmr_pool`` rows for MMR
-        behind it, ``top_k`` rows as the last -- never more than it was handed."""
+        ``rank_model`` (default False: nothing changes) as in :meth:`search_bm25`: the fused ranking is taken ``rank_pool`` deep
+        (default ``min(max(4 * top_k, 100), 1024, n_docs)``; more than 1024 raises ``ValueError``; with ``late_query_tokens`` the pool
+        is ``late_pool``) and re-scored by the model of :meth:`set_rank_model` on the device (``srx_ltr_topk``).  "score" is the
+        fused (or late) score and "rank" the pool position; the feature names "sparse_score" and "dense_score" are the EXACT BM25
+        and embedding scores of the pool's docs (``srx_score_docs``, ``srx_dense_score_docs_f32`` / ``_half``), computed on the
+        device and stacked into the model's extra plane, so nothing is copied back before the cut.  Not with ``boost=``.
+        In one sentence: the steps run in the order late rerank, boost or model, collapse, MMR, each only if its keyword is given; the
+        fusion is as deep as the FIRST step's pool, and a step keeps all its rows for a boost, model or collapse behind it, ``mmr_pool``
+        rows for MMR behind it, ``top_k`` rows as the last -- never more than it was handed."""
         if late_query_tokens is not None and mmr_lambda is not None:
             raise ValueError("late_query_tokens and mmr_lambda do not combine in one call: chain rerank_late() and diversify()")
         if operators:
@@ -398,7 +422,11 @@ class RetrievalService(SparseIndexViews):
         boosted = self._be.boost_spec(boost, None, top_k, "search_hybrid", exact=False)
         if boosted is not None:  # range-checked under late_query_tokens too, where it is not used
             pools["boost"] = collapse_pool_depth(top_k, boost_pool, n_docs, "boost_pool")
-        stages = [name for name, given in (("late", late_query_tokens), ("boost", boosted), ("collapse", collapse), ("mmr", mmr_lambda)) if given is not None]
+        ranked = self._be.rank_spec(rank_model, rank_pool, top_k, "search_hybrid", boost, hybrid=True)
+        if ranked is not None:
+            pools["model"] = ranked.pool
+        stages = [name for name, given in (("late", late_query_tokens), ("boost", boosted), ("model", ranked), ("collapse", collapse),
+                                           ("mmr", mmr_lambda)) if given is not None]
         depth = pools[stages[0]] if stages else k  # how deep the fusion is taken
         if stages and candidates is None:
             # at least the fused depth.  Collapse + MMR alone also reach for mmr_pool: an irregularity, but it decides which rows are fetched
@@ -451,6 +479,11 @@ class RetrievalService(SparseIndexViews):
                                                                    f_doc, f_count, keep)
                 elif stage == "boost":
                     f_doc, f_score, f_count = bfn(f_doc, f_score, f_count, keep)
+                elif stage == "model":  # the pool's exact scores of both sides become the first two extra slots
+                    from .index import _batch_to_device
+                    exact = None if not ranked.named_extra else torch.stack([self.dev.score_docs_device(*_batch_to_device(torch, q_ptr, q_term, q_weight, self.dev.device), f_doc, f_count),
+                                         dense_score(f_doc, f_count)], dim=2)
+                    f_doc, f_score, f_count = ranked(f_doc.contiguous(), f_score.contiguous(), f_count, keep, extra=exact)
                 elif stage == "collapse":
                     f_doc, f_score, f_count = self._be.field_table().collapse_device(collapse.by, f_doc, f_score, f_count, keep, collapse.per_group,
                                                                                      collapse.nulls)
