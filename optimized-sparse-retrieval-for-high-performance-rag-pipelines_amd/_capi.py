@@ -1,8 +1,8 @@
 """ctypes binding of libsparse_rx.so (C ABI declared in include/sparse_rx.h, include/sparse_rx_rescore.h,
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
-include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h and
-include/ltr/sparse_rx_ltr.h).
+include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
+include/ltr/sparse_rx_ltr.h and include/eval/sparse_rx_eval.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -21,7 +21,8 @@ LIB_PATH = os.path.join(_PKG_DIR, "libsparse_rx.so")
 CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
-           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip"]  # one translation unit each, compiled in parallel
+           "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
+           "eval.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -288,6 +289,16 @@ SRX_LTR_MISSING_LEFT = 1 << 30                                                  
 SRX_LTR_MAX_M, SRX_LTR_MAX_COLS, SRX_LTR_MAX_FEATURES, SRX_LTR_MAX_EXTRA = 2048, 8, 32, 32            # pinned to the header by tests/test_ltr_cpu.py
 SRX_LTR_MAX_TREES, SRX_LTR_MAX_NODES = 4096, 1 << 22
 
+# every symbol include/eval/sparse_rx_eval.h declares (the sixteenth header of the same library)
+EVAL_SYMBOLS = {
+    "srx_eval_workspace_bytes": (_I64, [_I32, _I32]),
+    "srx_eval_lists": (ctypes.c_int, [_I32, _VP, _VP, _VP, _VP, _I32, _I64, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _I32, _I32, ctypes.POINTER(_I32), _I32,
+                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+}
+SRX_EVAL_NDCG, SRX_EVAL_AP, SRX_EVAL_RECALL, SRX_EVAL_P, SRX_EVAL_RR, SRX_EVAL_SUCCESS, SRX_EVAL_DCG, SRX_EVAL_IDCG = range(8)  # the last axis of out
+SRX_EVAL_METRICS, SRX_EVAL_MAX_M, SRX_EVAL_MAX_K, SRX_EVAL_MAX_GAIN = 8, 2048, 8, 32                  # pinned to the header by tests/test_eval_cpu.py
+SRX_EVAL_WAVE_M, SRX_EVAL_LDS_ROW, SRX_EVAL_MEAN_CHUNK = 256, 1024, 1024                              # the kernel's size constants, and the means' chunk
+
 
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
@@ -331,7 +342,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "ext", "sparse_rx_feedback.h"),
                                                             os.path.join(INCLUDE_DIR, "order", "sparse_rx_order.h"),
                                                             os.path.join(INCLUDE_DIR, "boost", "sparse_rx_boost.h"),
-                                                            os.path.join(INCLUDE_DIR, "ltr", "sparse_rx_ltr.h")]
+                                                            os.path.join(INCLUDE_DIR, "ltr", "sparse_rx_ltr.h"),
+                                                            os.path.join(INCLUDE_DIR, "eval", "sparse_rx_eval.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -381,7 +393,7 @@ def lib() -> ctypes.CDLL:
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
-                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS}.items():
+                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -1473,3 +1473,36 @@ class SparseIndexViews:
         index."""
         self._need_index()
         return self._be.rerank_model_results(results, top_k, extra, mode, "rerank_model")
+
+    search_door = "search"  # the class's own batched search: what :meth:`rank_eval` runs
+
+    def evaluate(self, qrels, results, k_values=(1, 3, 5, 10, 100), *, gain: str = "linear", rel_level: int = 1, per_query: bool = False,
+                 complete: bool = False, ignore_identical_ids: bool = False):
+        """Ranking quality of result lists (the reference's ``EvaluateRetrieval.evaluate(qrels, results, k_values)`` step, which it
+        takes from BEIR / pytrec_eval on the host): ``qrels`` = ``{qid: {doc_id: int grade}}`` (or a :class:`~.evaluate.Judgments`
+        built once by ``Judgments.from_qrels(qrels, None, self.doc_ids, device=...)``), ``results`` = ``{qid: {doc_id: score}}`` as any
+        search of this object, a reranker or a fusion returns it -> ``{"NDCG@k", "MAP@k", "Recall@k", "P@k", "MRR@k", "Success@k",
+        "Judged@k" for every k of k_values, "n_queries"}``, the means over the queries that are judged and have an entry in
+        ``results`` (``complete``: every judged query; one without an entry scores zeros), computed on the GPU (``srx_eval_lists``,
+        include/eval/sparse_rx_eval.h).  ``per_query`` also returns ``{qid: {...}}``.  A list is ranked by (score descending, doc id
+        ascending in corpus order), cut at 2 048; ``gain`` "linear" (trec_eval) | "exp2"; relevant = grade >= ``rel_level``;
+        ``ignore_identical_ids`` drops ``doc_id == qid``.  Global doc ids only: a SHARDED index is evaluated like any other.
+        ``ValueError``: no index, 0 or more than 8 cutoffs, not ascending, one above 2 048, a grade that is no int."""
+        self._need_index()
+        from .evaluate import evaluate_results
+        device = self._be.dev.device if self._be.dev is not None else self._be.device
+        return evaluate_results(qrels, results, self.host.doc_ids, device, k_values, gain=gain, rel_level=rel_level, per_query=per_query,
+                                complete=complete, ignore_identical_ids=ignore_identical_ids)
+
+    def rank_eval(self, queries: Dict[str, str], qrels, k_values=(1, 3, 5, 10, 100), **search_keywords):
+        """Search, then :meth:`evaluate` (Elasticsearch's ``_rank_eval``): this object's own search at ``top_k = max(k_values)`` with
+        ``search_keywords`` passed through (the filter, collapse, boost, rank-model keywords; ``gain``, ``rel_level``, ``per_query``,
+        ``complete`` and ``ignore_identical_ids`` go to :meth:`evaluate`).  No search path of its own."""
+        from .evaluate import check_cutoffs
+        from . import _capi
+        ks = check_cutoffs(k_values, cap=_capi.SRX_EVAL_MAX_M)
+        eval_keywords = {k: search_keywords.pop(k) for k in ("gain", "rel_level", "per_query", "complete", "ignore_identical_ids") if k in search_keywords}
+        if "top_k" in search_keywords:
+            raise ValueError("rank_eval searches at top_k = max(k_values): give no top_k")
+        results = getattr(self, self.search_door)(queries, top_k=ks[-1], **search_keywords)
+        return self.evaluate(qrels, results, ks, **eval_keywords)

@@ -43,6 +43,7 @@ class RetrievalService(SparseIndexViews):
     """BM25 retrieval with the reference's API; scoring + top-k run on the GPU."""
 
     not_built = "BM25 index not built. Call build_bm25_index() first."  # mode "bm25", term_order "term": backend.SparseIndexViews
+    search_door = "search_bm25"
 
     def __init__(self, index_path=None, embedding_path=None, num_workers: int = 4, cache_size: int = 1000, *,
                  device: Optional[str] = None, tile_log2: int = 14, group=None, sharded: Optional[bool] = None,
