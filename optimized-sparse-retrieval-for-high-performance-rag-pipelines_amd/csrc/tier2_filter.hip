@@ -9,8 +9,10 @@
 //   * the predicate.  tier2_kernel.hip funnels every candidate (score bits, local doc) through after_bound<AFTER>(const
 //     ScoreShared &, ...).  Declared BEFORE the include, the overload below takes ScoreShared & -- every call site holds a
 //     non-const S, so overload resolution picks it there -- and is: the file's own test, then the doc's filter bit.  Were a call
-//     site ever to pass a const S it would silently lose the filter: tests/test_filter_gpu.py runs every site (hash units, flat
-//     tiles, the append scan, the general selection, the term passes) against the oracle.
+//     site ever to pass a const S it would silently lose the filter.  tests/test_filter_gpu.py runs sampled corpora and masks
+//     against the oracle; tests/test_tier2_filter_routes_cpu.py / _gpu.py run the directed route cases (every path, every
+//     selection edge, all four instances) under masks built so that, per step of the restated route, losing the filter inside
+//     that step's doc range alone changes the expected rows -- and more work items than workgroups, for the row below.
 //   * the work item's filter row, in a workgroup-shared word pair of this unit (FilterItem); srx_filtered_score_kernel resolves
 //     it (q_filter, -1, NULL) once per item and calls the file's score_block<VT, true, CP>, whose open_item publishes it with its
 //     barriers and sets the bound to "none" (0xFFFFFFFF) when the search carries none.

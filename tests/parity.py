@@ -562,18 +562,22 @@ class _T2List:
     """The work item's running list, simulated exactly: the docs on it, tau, and the cut every selection site shares (the k
     best in (score desc, doc asc) order, tau = the k-th score)."""
 
-    def __init__(self, s, tau0, k, bound):
-        self.s, self.tau, self.k, self.bound = s, np.float32(tau0), k, bound
+    def __init__(self, s, tau0, k, bound, allowed=None):
+        self.s, self.tau, self.k, self.bound, self.allowed = s, np.float32(tau0), k, bound, allowed
         self.docs = np.zeros(0, np.int64)
+        self.log = []  # per fold / dense_group call: (outcome, the docs it counted: the list's, then the candidates)
 
     def cand(self, docs):
-        """The docs of `docs` that can enter: score > 0, bits >= tau (float order for positive scores), after the bound."""
+        """The docs of `docs` that can enter: score > 0, bits >= tau (float order for positive scores), after the bound, then
+        the filter bit (tier2_filter.hip's predicate: the bound first, then the row)."""
         docs = np.asarray(docs, np.int64)
         sc = self.s[docs]
         ok = (sc > 0) & (sc >= self.tau)
         if self.bound is not None:
             ub, ud = self.bound
             ok &= (sc < ub) | ((sc == ub) & (docs > ud))
+        if self.allowed is not None:
+            ok &= self.allowed[docs]
         return docs[ok]
 
     def select(self, extra=()):
@@ -581,8 +585,16 @@ class _T2List:
         d = d[np.lexsort((d, -self.s[d].astype(np.float64)))][: self.k]
         self.docs, self.tau = d, self.s[d[-1]]
 
+    def _logged(self, c, outcome):
+        self.log.append((outcome, np.concatenate([self._before, c])))
+        return outcome
+
     def fold(self, docs, cap=KMAX):
         """topk_fold<N, LAZY>: nothing / append while the list has room / the selection."""
+        self._before = self.docs
+        return self._logged(self.cand(docs), self._fold(docs, cap))
+
+    def _fold(self, docs, cap):
         c = self.cand(docs)
         n_old, n_new = len(self.docs), len(c)
         if n_new == 0 and n_old <= self.k:
@@ -595,6 +607,10 @@ class _T2List:
 
     def dense_group(self, lo, hi, n_docs, append_scan, ovf_cap):
         """One dense group [lo, hi) of docs: dense_tile_append, then dense_tile_general when it refuses."""
+        self._before = self.docs
+        return self._logged(self.cand(np.arange(lo, min(hi, n_docs))), self._dense_group(lo, hi, n_docs, append_scan, ovf_cap))
+
+    def _dense_group(self, lo, hi, n_docs, append_scan, ovf_cap):
         rng = np.arange(lo, min(hi, n_docs))
         if append_scan:
             n_old = len(self.docs)
@@ -620,7 +636,7 @@ class _T2List:
 
 
 def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_tiles, k, p, debug, flags, tps=None, mode="bm25",
-                 val_dtype="f32", k1=1.2, b=0.75, avgdl=1.0, post16=True, after=None, layout=None):
+                 val_dtype="f32", k1=1.2, b=0.75, avgdl=1.0, post16=True, after=None, layout=None, allowed=None):
     """What score_block does for every work item of one search, as an ordered list of steps per item.
     unit_tiles = the unit the index was built (padded) for, tps = tiles per unit of the search (the plan's; default the same),
     p = plan(n_tiles, tps, ...), debug = the search's debug bits, flags = bool[items, >= n_super] tier 1's flag bits (from
@@ -637,7 +653,12 @@ def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_til
                                                              many reach tier 2's tau, the fold's outcome (before "emit")
       ("emit", entries, shrunk)                              topk_shrink ran a selection or not
     A selection outcome is (name, n) with the names of _T2List; `compact` says whether list_compact_select ran at the end of
-    dense_quads.  Also returned per item: tau0 and all_units."""
+    dense_quads.  Also returned per item: tau0 and all_units.
+    allowed = None, or one entry per query -- None (the query's filter row is -1) or bool[n_docs] over local docs -- of a
+    FILTERED search: search_impl then sends everything to tier 2 and drops the term bounds for every query of the batch
+    (tau0 = 0), and the mask joins the candidate predicate (_T2List.cand) and nothing else: P, M, n_steps, the packer's groups
+    and `masked` are functions of the postings.  With `allowed` the result also carries "sel_docs": per item, for every
+    selection outcome in step order, (outcome, the docs the decision counted: those on the list, then the candidates)."""
     from scipy.sparse import csr_matrix
     import oracle
     f = np.float32
@@ -658,12 +679,16 @@ def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_til
     post_doc = post[:, :4].reshape(-1)  # the doc of posting position g (negative: run padding)
     csc = csr_matrix((sv, indices, indptr), shape=(n_docs, V)).tocsc()
     sdata = sv if mode == "dot" else data
-    dbg = debug | (SRX_DBG_TIER2_ONLY if (after is not None or tps != unit_tiles) else 0)
+    filtered = allowed is not None
+    assert not filtered or len(allowed) == nq, "one mask (or None) per query"
+    dbg = debug | (SRX_DBG_TIER2_ONLY if (after is not None or filtered or tps != unit_tiles) else 0)  # search_impl: restricted
     col = bound_column_of(k)
-    bounds_on = not (dbg & SRX_DBG_NO_TERM_BOUND) and after is None and col >= 0 and not np.any(sv < 0)
+    bounds_on = not (dbg & SRX_DBG_NO_TERM_BOUND) and after is None and not filtered and col >= 0 and not np.any(sv < 0)  # index_view
     q_of, split_of, nsq_of = item_queries(p, nq)
     flags = np.asarray(flags, bool)
     out = {"steps": [], "tau0": [], "all_units": []}
+    if filtered:
+        out["sel_docs"] = []
     per_q = {}
     for it in range(p["items"]):
         qi, split, nsq = int(q_of[it]), int(split_of[it]), int(nsq_of[it])
@@ -679,6 +704,8 @@ def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_til
         if not any_:
             out["steps"].append([("skip",)])
             out["tau0"].append(f(0))
+            if filtered:
+                out["sel_docs"].append([])
             continue
         if qi not in per_q:  # open_item's tau0, the exact scores in the kernel's order, postings per doc
             tau0, neg, nonfinite = f(0), False, False
@@ -701,7 +728,8 @@ def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_til
             per_q[qi] = (tau0, nonfinite, s, m)
         tau0, nonfinite, s, m = per_q[qi]
         out["tau0"].append(tau0)
-        L = _T2List(s, tau0, k, None if after is None else (f(max(after[0][qi], 0)), int(after[1][qi])))
+        L = _T2List(s, tau0, k, None if after is None else (f(max(after[0][qi], 0)), int(after[1][qi])),
+                    None if not filtered or allowed[qi] is None else np.asarray(allowed[qi], bool))
         append_scan = not (dbg & SRX_DBG_WAVE_DENSE_GENERAL)
         steps = []
 
@@ -722,6 +750,8 @@ def tier2_routes(indptr, indices, data, doc_lengths, idf, q, tile_log2, unit_til
                 steps.append(("t1_fold", len(d1), len(ok), float(tau_emit), L.fold(ok, cap=k)[0]))
             steps.append(("emit", n, n > k))
             out["steps"].append(steps)
+            if filtered:
+                out["sel_docs"].append(L.log)
 
         if nt > MAXT:
             ja, jb = su_lo * tps, min(su_hi * tps, n_tiles)
