@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .boost import boost_deep  # beside collapse_deep: the same search_fn contract
-from .index import DeviceIndex, HostIndex, build_host_index, encode_queries, parse_operators, pool_depth, score_host_batch, search_host_batch, tokenize
+from .index import DeviceIndex, HostIndex, build_host_index, deep_reduce, encode_queries, parse_operators, pool_depth, score_host_batch, search_host_batch, tokenize
 
 
 class SparseBackend:
@@ -272,34 +272,6 @@ class SparseBackend:
             out[qid] = [results[qid][p] for p in kept] if as_rows[qid] else {cands[p]: results[qid][cands[p]] for p in kept}
         return out
 
-    def collapsed_search_arrays(self, q_ptr, q_term, q_weight, k: int, collapse: "CollapseSpec", filter=None, q_filter=None):
-        """Host CSR batch -> host rows (doc, score, count) of the top ``k`` of the COLLAPSED complete ranking, exact:
-        :func:`collapse_deep` over this index's device search (under ``filter`` / ``q_filter``, a DocFilter and the host row
-        numbers, when given) and the field table's ``collapse_device``.  ``first`` = min(max(4 k, 64), 1024, n_docs)."""
-        import torch
-        from . import _capi
-        from .filter import q_filter_to_device
-        from .index import _batch_to_device, _to_host, validate_query_batch
-        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
-        nq = len(q_ptr) - 1
-        if nq == 0:
-            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
-        dev, table = self.dev, self.field_table()
-        flt = {}
-        if filter is not None:
-            flt = {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
-
-        def search_fn(qp, qt, qw, kk, after=None):
-            return dev.search_device(qp, qt, qw, kk, after=after, **flt)
-
-        def collapse_fn(d, s, c, kk):
-            return table.collapse_device(collapse.by, d, s, c, kk, collapse.per_group, collapse.nulls)
-
-        first = min(max(4 * k, 64), _capi.SRX_MAX_K, self.n_docs_total)
-        out = collapse_deep(search_fn, collapse_fn, *_batch_to_device(torch, q_ptr, q_term, q_weight, dev.device), k, first,
-                            page=_capi.SRX_MAX_K, max_depth=collapse.depth)
-        return _to_host(torch, dev.device, out)
-
     # -- boosts by field values (include/boost/sparse_rx_boost.h) ---------------------------------------------------------------
     boost_page = 1024  # rows per page of the exact boosted search (the engine's list depth; a test may lower it)
 
@@ -331,31 +303,6 @@ class SparseBackend:
         res.depth = None if depth is None else int(depth)
         return res
 
-    def _boost_deep(self, batch, k: int, boost, flt):
-        """:func:`~.boost.boost_deep` over this index's device search (``flt``: its filter keywords) -> device rows"""
-        from . import _capi
-        from .boost import BoostFn
-        dev = self.dev
-        page = min(int(self.boost_page), _capi.SRX_MAX_K)
-        first = min(max(4 * k, 64), max(page, k), self.n_docs_total)
-        return boost_deep(lambda qp, qt, qw, kk, after=None: dev.search_device(qp, qt, qw, kk, after=after, **flt),
-                          BoostFn(self.field_table(), boost), *batch, k, first, page=page, max_depth=boost.depth)
-
-    def boosted_search_arrays(self, q_ptr, q_term, q_weight, k: int, boost, filter=None, q_filter=None):
-        """Host CSR batch -> host rows (doc, score, count) of the top ``k`` of the BOOSTED complete ranking, exact:
-        :func:`~.boost.boost_deep` over this index's device search (under ``filter`` / ``q_filter`` when given) and the field
-        table's ``boost_device``.  ``first`` = min(max(4 k, 64), 1024, n_docs); the scores are the boosted ones."""
-        import torch
-        from .filter import q_filter_to_device
-        from .index import _batch_to_device, _to_host, validate_query_batch
-        validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
-        nq = len(q_ptr) - 1
-        if nq == 0:
-            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
-        dev = self.dev
-        flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
-        return _to_host(torch, dev.device, self._boost_deep(_batch_to_device(torch, q_ptr, q_term, q_weight, dev.device), k, boost, flt))
-
     def boost_results(self, results, boost, top_k=None, call: str = "boost_results"):
         """Result lists re-scored and re-ranked by a boost (``srx_boost_topk``): ``results`` = ``{qid: {doc_id: score}}`` as any
         search returns it (or ``search_by_vector``'s lists of ``{"doc_id", "score"}`` dicts) -> ``{qid: {doc_id: new score}}``,
@@ -363,28 +310,41 @@ class SparseBackend:
         ``boost_mode`` is allowed.  One upload, one launch, one copy back.  ValueError: a list deeper than 2048, an unknown doc
         id, and what :meth:`boost_spec` refuses of ``boost``."""
         from . import _capi
+        from .boost import BoostFn
         res = self.boost_spec(boost, None, 1, call, exact=False)
         if res is None:
             raise ValueError(f"{call} needs a boost")
+        return self._rerank_lists(results, call, _capi.SRX_BOOST_MAX_M, top_k, self.field_table,
+                                  lambda table, k, upload, pairs, live: BoostFn(table, res)(*upload(), k, want_pos=True)[1:])
+
+    def _rerank_lists(self, results, call: str, cap: int, top_k, table, run, new_scores: bool = True):
+        """The door of the list operators that reorder: ``results`` (what :meth:`result_lists` takes, at most ``cap`` docs a list)
+        -> ``{qid: {doc_id: score}}``, the first ``top_k`` (None: all) in the order ``run`` gives.  ``table()`` -> the field table
+        (made only when a list has a doc); ``run(table, k, upload, pairs, live) -> (score [nq, k] | None, count [nq] or [nq, c] with
+        the count in column 0, pos [nq, k])`` launches once on ``upload()``, the (doc, score, count) triple on the table's device,
+        k = min(top_k, the deepest list).  The scores returned are ``run``'s (``new_scores``) or the ones given.  One upload of the
+        triple, one copy back.  ValueError: ``top_k`` below 1, then what :meth:`result_lists` refuses."""
         if top_k is not None and int(top_k) < 1:
             raise ValueError(f"top_k must be >= 1, got {top_k}")
         out = {qid: {} for qid in (results or {})}
         if not results:
             return out
-        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, _capi.SRX_BOOST_MAX_M)
+        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, cap)
         if not live:
             return out
         import torch
-        from .boost import BoostFn
-        table = self.field_table()
+        table = table()
         m = cand_doc.shape[1]
         k = m if top_k is None else min(int(top_k), m)
-        _, ns, cnt, pos = BoostFn(table, res)(*(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k, want_pos=True)
-        block = torch.cat([pos, cnt.reshape(-1, 1), ns.view(torch.int32)], dim=1).cpu().numpy()
+        ns, cnt, pos = run(table, k, lambda: tuple(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), pairs, live)
+        block = torch.cat([pos, cnt.reshape(len(live), -1)] + ([ns.view(torch.int32)] if new_scores else []), dim=1).cpu().numpy()
         for i, (qid, _, _) in enumerate(live):
             n = int(block[i, k])
-            new = block[i, k + 1: k + 1 + n].copy().view(np.float32)
-            out[qid] = {pairs[qid][int(p)][0]: float(v) for p, v in zip(block[i, :n], new)}
+            given = [pairs[qid][int(p)] for p in block[i, :n]]
+            if new_scores:  # the last k columns
+                new = block[i, block.shape[1] - k:][:n].copy().view(np.float32)
+                given = [(d, float(v)) for (d, _), v in zip(given, new)]
+            out[qid] = dict(given)
         return out
 
     # -- reranking with a tree-ensemble model (include/ltr/sparse_rx_ltr.h) -------------------------------------------------------
@@ -441,36 +401,23 @@ class SparseBackend:
         from .ltr import check_mode
         fn = self.rank_spec(True, None, 1, call)
         check_mode(mode)
-        if top_k is not None and int(top_k) < 1:
-            raise ValueError(f"top_k must be >= 1, got {top_k}")
-        out = {qid: {} for qid in (results or {})}
-        if not results:
-            return out
-        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, _capi.SRX_LTR_MAX_M)
-        if not live:
-            return out
-        import torch
-        from .ltr import resolve_features
-        table = fn.table
-        n_extra = resolve_features(table.columns, fn.features, fn.model)[2]
-        m = cand_doc.shape[1]
-        plane = None
-        if n_extra:
-            host = np.full((len(live), m, n_extra), np.nan, dtype=np.float32)
-            for i, (qid, _, _) in enumerate(live):
-                row = (extra or {}).get(qid, {})
-                for c, (doc_id, _) in enumerate(pairs[qid]):
-                    vals = np.asarray(row.get(doc_id, ()), dtype=np.float32).reshape(-1)[:n_extra]
-                    host[i, c, : len(vals)] = vals
-            plane = torch.as_tensor(host, device=table.device)
-        k = m if top_k is None else min(int(top_k), m)
-        _, ns, cnt, pos = fn(*(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k, extra=plane, mode=mode, want_pos=True)
-        block = torch.cat([pos, cnt.reshape(-1, 1), ns.view(torch.int32)], dim=1).cpu().numpy()
-        for i, (qid, _, _) in enumerate(live):
-            n = int(block[i, k])
-            new = block[i, k + 1: k + 1 + n].copy().view(np.float32)
-            out[qid] = {pairs[qid][int(p)][0]: float(v) for p, v in zip(block[i, :n], new)}
-        return out
+
+        def run(table, k, upload, pairs, live):
+            import torch
+            from .ltr import resolve_features
+            n_extra = resolve_features(table.columns, fn.features, fn.model)[2]
+            plane = None
+            if n_extra:
+                host = np.full((len(live), max(len(pairs[qid]) for qid, _, _ in live), n_extra), np.nan, dtype=np.float32)
+                for i, (qid, _, _) in enumerate(live):
+                    row = (extra or {}).get(qid, {})
+                    for c, (doc_id, _) in enumerate(pairs[qid]):
+                        vals = np.asarray(row.get(doc_id, ()), dtype=np.float32).reshape(-1)[:n_extra]
+                        host[i, c, : len(vals)] = vals
+                plane = torch.as_tensor(host, device=table.device)
+            return fn(*upload(), k, extra=plane, mode=mode, want_pos=True)[1:]
+
+        return self._rerank_lists(results, call, _capi.SRX_LTR_MAX_M, top_k, lambda: fn.table, run)
 
     def facet_specs(self, fields, call: str = "facets"):
         """``fields`` of a facet door -- one name, a sequence of names, or a dict name -> binning spec (None: the column's own
@@ -639,24 +586,9 @@ class SparseBackend:
         id, and what :meth:`search_sorted` refuses of ``by`` / ``order`` / ``nulls``."""
         from . import _capi
         self._order_column(by, order, nulls, call)
-        if top_k is not None and int(top_k) < 1:
-            raise ValueError(f"top_k must be >= 1, got {top_k}")
-        out = {qid: {} for qid in (results or {})}
-        if not results:
-            return out
-        pairs, live, cand_doc, cand_count, score = self.result_lists(results, call, _capi.SRX_ORDER_MAX_M)
-        if not live:
-            return out
-        import torch
-        table = self.field_table()
-        m = cand_doc.shape[1]
-        k = m if top_k is None else min(int(top_k), m)
-        _, _, _, extra, pos = table.sort_lists_device(by, *(torch.as_tensor(a, device=table.device) for a in (cand_doc, score, cand_count)), k,
-                                                      order, nulls, want_pos=True)
-        block = torch.cat([pos, extra], dim=1).cpu().numpy()
-        for i, (qid, _, _) in enumerate(live):
-            out[qid] = {pairs[qid][int(p)][0]: pairs[qid][int(p)][1] for p in block[i, : int(block[i, k])]}
-        return out
+        return self._rerank_lists(results, call, _capi.SRX_ORDER_MAX_M, top_k, self.field_table,
+                                  lambda table, k, upload, pairs, live: (None,) + table.sort_lists_device(by, *upload(), k, order, nulls, want_pos=True)[3:],
+                                  new_scores=False)
 
     # -- relevance feedback (include/ext/sparse_rx_feedback.h) ----------------------------------------------------------------
     def enable_feedback(self, mode: str = "bm25") -> None:
@@ -700,52 +632,69 @@ class SparseBackend:
         self._need_forward(call, "expand_docs=...")
         return spec
 
-    def _search_expanded(self, batch, k: int, filter=None, q_filter=None, collapse=None, boost=None):
-        """The second pass: an expanded batch still on the device -> host rows.  k <= 1024: nothing is copied back in between;
-        deeper: the batch goes to the host once and takes the paged route of :meth:`~.index.DeviceIndex.search`."""
-        import torch
-        from . import _capi
-        from .filter import q_filter_to_device
-        from .index import _to_host
-        e_ptr, e_term, e_weight, _ = batch
-        dev = self.dev
-        nq = e_ptr.numel() - 1
-        if k > _capi.SRX_MAX_K:
-            p = e_ptr.cpu().numpy()
-            n = int(p[-1])
-            return dev.search(p, e_term[:n].cpu().numpy(), e_weight[:n].cpu().numpy(), k, filter=filter, q_filter=q_filter)
-        flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
-        if boost is not None:
-            return _to_host(torch, dev.device, self._boost_deep((e_ptr, e_term, e_weight), k, boost, flt))
-        if collapse is None:
-            return _to_host(torch, dev.device, dev.search_device(e_ptr, e_term, e_weight, k, **flt))
-        table = self.field_table()
-        first = min(max(4 * k, 64), _capi.SRX_MAX_K, self.n_docs_total)
-        out = collapse_deep(lambda qp, qt, qw, kk, after=None: dev.search_device(qp, qt, qw, kk, after=after, **flt),
-                            lambda d, s, c, kk: table.collapse_device(collapse.by, d, s, c, kk, collapse.per_group, collapse.nulls),
-                            e_ptr, e_term, e_weight, k, first, page=_capi.SRX_MAX_K, max_depth=collapse.depth)
-        return _to_host(torch, dev.device, out)
+    def search_rows(self, q_ptr, q_term, q_weight, k: int, filter=None, q_filter=None, collapse=None, expand=None, boost=None):
+        """Host CSR batch -> host rows (doc i32[nq, k] GLOBAL row ids, score f32[nq, k], count i32[nq]): the one route of the
+        optional stages.  ``filter`` / ``q_filter``: a DocFilter and the host row numbers.  Without a staged keyword the call is
+        :meth:`search_arrays` or, filtered, the index's ``search`` -- any k, nothing else runs.  Otherwise the batch goes to the
+        device once and
 
-    def expanded_search_arrays(self, q_ptr, q_term, q_weight, k: int, expand: "ExpandSpec", filter=None, q_filter=None, collapse=None, boost=None):
-        """Host CSR batch -> host rows (doc, score, count) of the search of the EXPANDED batch: a first pass ``expand.docs`` deep
-        (under ``filter`` / ``q_filter``, never collapsed), ``srx_feedback_expand`` with alpha = 1 - weight, beta = weight and
-        row_cap = min(max_row_terms, 4096 // expand.docs), then the existing search of the expanded batch at ``k`` under the same
-        filter, collapsed when ``collapse`` is given, boosted (exact) when ``boost`` is.  The lists of the first pass and the expanded
-        batch stay on the device."""
+          * ``expand`` (:class:`ExpandSpec`): a first pass ``min(expand.docs, n_docs)`` deep under the filter, never collapsed, then
+            ``srx_feedback_expand`` with alpha = 1 - weight, beta = weight; its lists and the expanded batch stay on the device;
+          * :meth:`_second_pass` searches the batch under the filter: collapsed (``collapse``, a :class:`CollapseSpec`), boosted
+            (``boost``, a resolver of :meth:`boost_spec`), or plain."""
+        if collapse is None and expand is None and boost is None:
+            if filter is None:
+                return self.search_arrays(q_ptr, q_term, q_weight, k)
+            return self.dev.search(q_ptr, q_term, q_weight, k, filter=filter, q_filter=q_filter)
         import torch
-        from .filter import q_filter_to_device
         from .index import _batch_to_device, validate_query_batch
         validate_query_batch(q_ptr, q_term, q_weight, self.host.vocab_size)
         nq = len(q_ptr) - 1
         if nq == 0:
             return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), np.zeros(0, np.int32)
-        dev, fwd = self.dev, self._forward
-        flt = {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(dev), q_filter, nq)}
-        qp, qt, qw = _batch_to_device(torch, q_ptr, q_term, q_weight, dev.device)
-        d, s, c = dev.search_device(qp, qt, qw, min(expand.docs, self.n_docs_total), **flt)
-        batch = fwd.expand_device(qp, qt, qw, d, s, c, fb_docs=expand.docs, n_terms=expand.terms, alpha=1.0 - expand.weight, beta=expand.weight,
-                                  doc_weight=expand.by, term_weight=self._fb_term_weight, term_gain=self._fb_gain)
-        return self._search_expanded(batch, k, filter, q_filter, collapse, boost)
+        flt = self._device_filter(filter, q_filter, nq)
+        batch = _batch_to_device(torch, q_ptr, q_term, q_weight, self.dev.device)
+        if expand is not None:
+            d, s, c = self.dev.search_device(*batch, min(expand.docs, self.n_docs_total), **flt)
+            batch = self._forward.expand_device(*batch, d, s, c, fb_docs=expand.docs, n_terms=expand.terms, alpha=1.0 - expand.weight,
+                                                beta=expand.weight, doc_weight=expand.by, term_weight=self._fb_term_weight,
+                                                term_gain=self._fb_gain)[:3]
+        return self._second_pass(batch, k, filter, q_filter, collapse, boost, flt)
+
+    def _device_filter(self, filter, q_filter, nq: int) -> dict:
+        """The filter keywords of ``search_device``: none, or the DocFilter and its host row numbers, checked and uploaded"""
+        from .filter import q_filter_to_device
+        return {} if filter is None else {"filter": filter, "q_filter": q_filter_to_device(filter.for_index(self.dev), q_filter, nq)}
+
+    def _second_pass(self, batch, k: int, filter=None, q_filter=None, collapse=None, boost=None, flt: Optional[dict] = None):
+        """A batch on the device -> host rows, one copy back: the plain ``search_device``, :func:`collapse_deep` (``first`` =
+        min(max(4 k, 64), 1024, n_docs), pages of 1 024) or :func:`~.boost.boost_deep` (pages of min(``boost_page``, 1 024), ``first``
+        = min(max(4 k, 64), max(page, k), n_docs)) over it, under ``filter`` / ``q_filter`` (``flt``: their :meth:`_device_filter`,
+        when the caller has it).  k > 1024 (never collapsed or boosted): the batch goes to the host once and takes the paged route
+        of :meth:`~.index.DeviceIndex.search`."""
+        import torch
+        from . import _capi
+        from .boost import BoostFn
+        from .index import _to_host
+        dev = self.dev
+        if k > _capi.SRX_MAX_K:
+            p = batch[0].cpu().numpy()
+            n = int(p[-1])
+            return dev.search(p, batch[1][:n].cpu().numpy(), batch[2][:n].cpu().numpy(), k, filter=filter, q_filter=q_filter)
+        if flt is None:
+            flt = self._device_filter(filter, q_filter, batch[0].numel() - 1)
+        search_fn = lambda qp, qt, qw, kk, after=None: dev.search_device(qp, qt, qw, kk, after=after, **flt)
+        if boost is not None:
+            page = min(int(self.boost_page), _capi.SRX_MAX_K)
+            out = boost_deep(search_fn, BoostFn(self.field_table(), boost), *batch, k, min(max(4 * k, 64), max(page, k), self.n_docs_total),
+                             page=page, max_depth=boost.depth)
+        elif collapse is not None:
+            table = self.field_table()
+            out = collapse_deep(search_fn, lambda d, s, c, kk: table.collapse_device(collapse.by, d, s, c, kk, collapse.per_group, collapse.nulls),
+                                *batch, k, min(max(4 * k, 64), _capi.SRX_MAX_K, self.n_docs_total), page=_capi.SRX_MAX_K, max_depth=collapse.depth)
+        else:
+            out = dev.search_device(*batch, k, **flt)
+        return _to_host(torch, dev.device, out)
 
     def _seed_block(self, lists, call: str, what: str):
         """{qid: sequence of doc ids} -> (qids, doc i32[nq, m] GLOBAL row ids padded with -1, count i32[nq]); at most 32 per qid"""
@@ -798,7 +747,7 @@ class SparseBackend:
                                   fb_docs=max(1, int(doc.shape[1])), n_terms=int(terms), alpha=0.0, beta=1.0, doc_weight="uniform",
                                   term_weight=self._fb_term_weight, term_gain=self._fb_gain)
         rows = None if spec is None else np.asarray([spec.row_of_qid[qid] for qid in qids], dtype=np.int32)
-        docs, scores, counts = self._search_expanded(batch, k_eff, None if spec is None else spec.on_device(dev), rows)
+        docs, scores, counts = self._second_pass(batch[:3], k_eff, None if spec is None else spec.on_device(dev), rows)
         for i, qid in enumerate(qids):
             c = int(counts[i])
             out[qid] = self.to_dict(docs[i, :c].astype(np.int64), scores[i, :c])
@@ -855,14 +804,14 @@ class SparseBackend:
         A filtered call neither reads nor writes the cache -- its key is the query text --, and equal texts share a row only
         under the same filter row.
 
-        ``collapse`` (:meth:`collapse_spec`): every row is the top ``top_k`` of the COLLAPSED complete ranking
-        (:meth:`collapsed_search_arrays`), under ``filter`` when given; such a call bypasses the cache as a filtered one does.
+        ``collapse`` (:meth:`collapse_spec`): every row is the top ``top_k`` of the COLLAPSED complete ranking, under ``filter``
+        when given; such a call bypasses the cache as a filtered one does.
 
-        ``expand`` (:meth:`expand_spec`): every row is the search of the query EXPANDED from its own first results
-        (:meth:`expanded_search_arrays`), under ``filter`` and ``collapse`` when given; such a call bypasses the cache too.
+        ``expand`` (:meth:`expand_spec`): every row is the search of the query EXPANDED from its own first results, under
+        ``filter`` and ``collapse`` when given; such a call bypasses the cache too.
 
-        ``boost`` (:meth:`boost_spec`): every row is the top ``top_k`` of the BOOSTED complete ranking with its boosted scores
-        (:meth:`boosted_search_arrays`), under ``filter`` and ``expand`` when given; such a call bypasses the cache too."""
+        ``boost`` (:meth:`boost_spec`): every row is the top ``top_k`` of the BOOSTED complete ranking with its boosted scores,
+        under ``filter`` and ``expand`` when given; such a call bypasses the cache too.  :meth:`search_rows` is the route of all four."""
         if filter is not None or collapse is not None or expand is not None or boost is not None:
             cache = None
         k_eff = min(int(top_k), self.n_docs_total)  # any depth: search_arrays pages past the engine's 1024-row lists
@@ -895,24 +844,8 @@ class SparseBackend:
             pending[key].append(qid)
         if texts and k_eff > 0:
             q_ptr, q_term, q_weight = encode_queries(texts, self.host.vocabulary, order=order)
-            if expand is not None:
-                docs, scores, counts = self.expanded_search_arrays(q_ptr, q_term, q_weight, k_eff, expand,
-                                                                   filter=None if filter is None else filter.on_device(self.dev),
-                                                                   q_filter=None if filter is None else np.asarray(frows, dtype=np.int32),
-                                                                   collapse=collapse, boost=boost)
-            elif boost is not None:
-                docs, scores, counts = self.boosted_search_arrays(q_ptr, q_term, q_weight, k_eff, boost,
-                                                                  filter=None if filter is None else filter.on_device(self.dev),
-                                                                  q_filter=None if filter is None else np.asarray(frows, dtype=np.int32))
-            elif collapse is not None:
-                docs, scores, counts = self.collapsed_search_arrays(q_ptr, q_term, q_weight, k_eff, collapse,
-                                                                    filter=None if filter is None else filter.on_device(self.dev),
-                                                                    q_filter=None if filter is None else np.asarray(frows, dtype=np.int32))
-            elif filter is None:
-                docs, scores, counts = self.search_arrays(q_ptr, q_term, q_weight, k_eff)
-            else:
-                docs, scores, counts = self.dev.search(q_ptr, q_term, q_weight, k_eff, filter=filter.on_device(self.dev),
-                                                       q_filter=np.asarray(frows, dtype=np.int32))
+            docs, scores, counts = self.search_rows(q_ptr, q_term, q_weight, k_eff, None if filter is None else filter.on_device(self.dev),
+                                                    None if filter is None else np.asarray(frows, dtype=np.int32), collapse, expand, boost)
             for i, key in enumerate(keys):
                 if q_ptr[i + 1] == q_ptr[i]:
                     continue
@@ -1016,32 +949,17 @@ def collapse_deep(search_fn, collapse_fn, q_ptr, q_term, q_weight, k: int, first
     then come back with FEWER than ``k`` rows although more groups exist further down: that is the caller's trade, not an error.
     ``m`` stays below ``k + page`` <= 2048 for k, page <= 1024."""
     import torch
-    first = int(first) if max_depth is None else min(int(first), int(max_depth))
 
-    def collapsed(d, s, c):  # k columns, whatever the list's depth
-        kk = min(k, int(d.shape[1]))
-        od, os_, oc = collapse_fn(d, s, c, kk)[:3]
-        if kk < k:
-            od = torch.cat([od, torch.full((od.shape[0], k - kk), -1, dtype=od.dtype, device=od.device)], dim=1)
-            os_ = torch.cat([os_, torch.zeros((os_.shape[0], k - kk), dtype=os_.dtype, device=os_.device)], dim=1)
-        return od, os_, oc
-
-    d, s, c = search_fn(q_ptr, q_term, q_weight, first)
-    kd, ks, kc = collapsed(d, s, c)
-    active = (kc < k) & (c == first)
-    depth, kk = first, first
-    while max_depth is None or depth < max_depth:
-        if int(active.sum().item()) == 0:  # every query done: one sync per page
-            break
-        a_doc = torch.where(active, d[:, kk - 1], torch.zeros_like(c, dtype=torch.int32)).to(torch.int32).contiguous()
-        a_score = torch.where(active, s[:, kk - 1], torch.zeros_like(c, dtype=torch.float32)).contiguous()
-        kk = page if max_depth is None else min(page, max_depth - depth)
-        d, s, c = search_fn(q_ptr, q_term, q_weight, kk, after=(a_doc, a_score))
-        depth += kk
+    def reduce(d, s, c, kept, kk):
+        if kept is None:
+            return collapse_fn(d, s, c, kk)
         # the padding of the kept rows lies in front of the page: no count, a doc id of -1 is dead
-        kd, ks, kc = collapsed(torch.cat([kd, d], dim=1).contiguous(), torch.cat([ks, s], dim=1).contiguous(), None)
-        active = active & (kc < k) & (c == kk)
-    return kd, ks, kc
+        return collapse_fn(torch.cat([kept[0], d], dim=1).contiguous(), torch.cat([kept[1], s], dim=1).contiguous(), None, kk)
+
+    def unfinished(d, s, c, kk, ks, kc):
+        return (kc < k) & (c == kk)
+
+    return deep_reduce(search_fn, reduce, unfinished, q_ptr, q_term, q_weight, k, first, page, max_depth)
 
 
 def facet_dict(spec, counts, extra, top=None) -> dict:
@@ -1474,7 +1392,39 @@ class SparseIndexViews:
         self._need_index()
         return self._be.rerank_model_results(results, top_k, extra, mode, "rerank_model")
 
-    search_door = "search"  # the class's own batched search: what :meth:`rank_eval` runs
+    search_door = "search"  # the class's own batched search: what :meth:`rank_eval` runs, and its name in the messages
+    blank = "empty"  # which texts are answered {} unsearched (search_dicts): a false one; the service: "whitespace"
+    strip_cache_key = True  # the cache key is the stripped text; OptimizedRetriever: the text as it is
+
+    def _search(self, queries, top_k, filters, collapse, expand, boost=None, boost_depth=None, rank_model=False, rank_pool=None):
+        """The body of the class's batched search (its docstring names the keywords): ``filters`` = (allowed_docs, excluded_docs,
+        must_terms, any_terms, must_not_terms, operators, where), ``collapse`` = (collapse_by, per_group, collapse_nulls,
+        collapse_depth), ``expand`` = (expand_docs, expand_terms, expand_weight, expand_by).  With a rank model the search runs at
+        ``top_k`` = the pool, its specs checked against the pool, and :meth:`SparseBackend.rerank_model_results` cuts it to the
+        caller's ``top_k``.  The checks come in one order: the index, the model, the filter chain, collapse, expand, boost."""
+        be, call = self._be, self.search_door
+        self._need_index()
+        ranked = be.rank_spec(rank_model, rank_pool, top_k, call, boost)
+        if ranked is not None:
+            if min(int(top_k), be.n_docs_total) <= 0:
+                return {qid: {} for qid in queries}
+            return be.rerank_model_results(self._search(queries, ranked.pool, filters, collapse, expand), top_k, call=call)
+        allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, operators, where = filters
+        if operators:
+            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
+        spec = be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, call)
+        collapse = be.collapse_spec(*collapse, top_k, call)
+        expand = be.expand_spec(*expand, call)
+        boosted = be.boost_spec(boost, boost_depth, top_k, call, collapse)
+        if not self._before_search(top_k, expand):
+            return {qid: {} for qid in queries}
+        # search_dicts leaves the cache alone when one of the four specs is given
+        return be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock, strip_key=self.strip_cache_key,
+                               blank=self.blank, filter=spec, collapse=collapse, expand=expand, boost=boosted)
+
+    def _before_search(self, top_k, expand) -> bool:
+        """What a class does between the checks and the search; False: every query is answered {} unsearched"""
+        return True
 
     def evaluate(self, qrels, results, k_values=(1, 3, 5, 10, 100), *, gain: str = "linear", rel_level: int = 1, per_query: bool = False,
                  complete: bool = False, ignore_identical_ids: bool = False):

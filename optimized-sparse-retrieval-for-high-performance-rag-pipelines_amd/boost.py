@@ -15,6 +15,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import _capi
+from .index import deep_reduce
 
 SCORE_MODES = {"multiply": _capi.SRX_BOOST_SCORE_MULTIPLY, "sum": _capi.SRX_BOOST_SCORE_SUM, "max": _capi.SRX_BOOST_SCORE_MAX,
                "min": _capi.SRX_BOOST_SCORE_MIN}
@@ -342,39 +343,18 @@ def boost_deep(search_fn, boost_fn, q_ptr, q_term, q_weight, k: int, first: int,
         raise ValueError(f"boost_mode \"multiply\" with a factor that can be negative (F_lo = {float(boost_fn.F_lo)!r}) has no bound on an "
                          "unseen doc: the exact door refuses it")
     k = int(k)
-    first = int(first) if max_depth is None else min(int(first), int(max_depth))
     f_hi = float(boost_fn.F_hi)
 
     def bound(s_last):  # fp32, one rounding: what the device computes for (s_last, F_hi)
         hi = torch.full_like(s_last, f_hi)
         return s_last * hi if mode == "multiply" else s_last + hi
 
-    def boosted(d, s, c, carry):  # k columns, whatever the list's depth
-        total = int(d.shape[1]) + (0 if carry is None else int(carry[0].shape[1]))
-        kk = min(k, total)
-        od, os_, oc = boost_fn(d, s, c, kk, carry=carry)[:3]
-        if kk < k:
-            od = torch.cat([od, torch.full((od.shape[0], k - kk), -1, dtype=od.dtype, device=od.device)], dim=1)
-            os_ = torch.cat([os_, torch.zeros((os_.shape[0], k - kk), dtype=os_.dtype, device=os_.device)], dim=1)
-        return od, os_, oc
+    def reduce(d, s, c, kept, kk):  # the kept rows are the carry: their scores are final
+        return boost_fn(d, s, c, kk, carry=None if kept is None else (kept[0].contiguous(), kept[1].contiguous(), kept[2]))
 
     def unfinished(d, s, c, kk, ks, kc):
         full = c == kk
         settled = (kc == k) & (bound(s[:, kk - 1]) < ks[:, k - 1])
         return full & ~settled
 
-    d, s, c = search_fn(q_ptr, q_term, q_weight, first)
-    kd, ks, kc = boosted(d, s, c, None)
-    active = unfinished(d, s, c, first, ks, kc)
-    depth, kk = first, first
-    while max_depth is None or depth < max_depth:
-        if int(active.sum().item()) == 0:  # every query done: one sync per page
-            break
-        a_doc = torch.where(active, d[:, kk - 1], torch.zeros_like(c, dtype=torch.int32)).to(torch.int32).contiguous()
-        a_score = torch.where(active, s[:, kk - 1], torch.zeros_like(c, dtype=torch.float32)).contiguous()
-        kk = page if max_depth is None else min(page, max_depth - depth)
-        d, s, c = search_fn(q_ptr, q_term, q_weight, kk, after=(a_doc, a_score))
-        depth += kk
-        kd, ks, kc = boosted(d, s, c, (kd.contiguous(), ks.contiguous(), kc))
-        active = active & unfinished(d, s, c, kk, ks, kc)
-    return kd, ks, kc
+    return deep_reduce(search_fn, reduce, unfinished, q_ptr, q_term, q_weight, k, first, page, max_depth)

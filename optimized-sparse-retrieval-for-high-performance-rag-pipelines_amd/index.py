@@ -955,12 +955,57 @@ def deep_search(search_fn, q_ptr, q_term, q_weight, k: int, page: int):
         got += kk
         if got >= k or int((c == kk).sum().item()) == 0:  # every query exhausted: one sync per page, pages are rare
             break
-        last = (c.long() - 1).clamp(min=0).unsqueeze(1)
-        full = c == kk
-        a_doc = torch.where(full, d.gather(1, last).squeeze(1), torch.zeros_like(c, dtype=torch.int32)).to(torch.int32).contiguous()
-        a_score = torch.where(full, s.gather(1, last).squeeze(1), torch.zeros_like(c, dtype=torch.float32)).contiguous()
-        after = (a_doc, a_score)
+        after = page_cursor(torch, c == kk, d, s, c, kk)
     return out_d, out_s, out_c
+
+
+def page_cursor(torch, goes_on, d, s, c, kk: int):
+    """The ``after`` of the page behind the page ``(d, s, c)`` of ``kk`` rows, for every pager: the page's last row for a query
+    that ``goes_on`` (bool[nq]; such a query's page is full, so its last row is column ``kk - 1``), else (0, 0.0) -- nothing
+    ranks after score 0, the query's next page comes back empty."""
+    a_doc = torch.where(goes_on, d[:, kk - 1], torch.zeros_like(c, dtype=torch.int32)).to(torch.int32).contiguous()
+    a_score = torch.where(goes_on, s[:, kk - 1], torch.zeros_like(c, dtype=torch.float32)).contiguous()
+    return a_doc, a_score
+
+
+def deep_reduce(search_fn, reduce, unfinished, q_ptr, q_term, q_weight, k: int, first: int, page: int, max_depth: Optional[int] = None):
+    """The paged reader under ``collapse_deep`` and ``boost_deep``: the top ``k`` of a ranking that is REDUCED as it is read, on top
+    of a search limited to ``page`` rows per call (``search_fn`` as :func:`deep_search` takes it; torch tensors throughout).
+
+      * ``reduce(d, s, c, kept, kk) -> (doc [nq, kk], score [nq, kk], count [nq], ...)``: the page ``(d, s, c)`` reduced together
+        with ``kept``, the ``k``-column rows held so far (None on page 1); ``kk`` = min(k, columns of the page and of ``kept``).
+        The reader pads the answer to ``k`` columns (doc -1, score 0).
+      * ``unfinished(d, s, c, kk, ks, kc) -> bool[nq]``: the queries that, after the page ``(d, s, c)`` of ``kk`` rows and with the
+        rows ``ks`` / ``kc`` kept, want the next page.  A query that was finished once stays finished.
+
+    Page 1 has ``first`` rows (at most ``max_depth``), every further one ``page`` (the last one what ``max_depth`` leaves).  Before
+    every further page: one synchronisation, the "is anyone left" test; then the cursor (:func:`page_cursor`) of the queries still
+    active.  ``max_depth`` None reads until nobody is left."""
+    torch = _torch()
+    first = int(first) if max_depth is None else min(int(first), int(max_depth))
+
+    def at_k(d, s, c, kept):  # k columns, whatever the list's depth
+        kk = min(k, int(d.shape[1]) + (0 if kept is None else int(kept[0].shape[1])))
+        od, os_, oc = reduce(d, s, c, kept, kk)[:3]
+        if kk < k:
+            od = torch.cat([od, torch.full((od.shape[0], k - kk), -1, dtype=od.dtype, device=od.device)], dim=1)
+            os_ = torch.cat([os_, torch.zeros((os_.shape[0], k - kk), dtype=os_.dtype, device=os_.device)], dim=1)
+        return od, os_, oc
+
+    d, s, c = search_fn(q_ptr, q_term, q_weight, first)
+    kd, ks, kc = at_k(d, s, c, None)
+    active = unfinished(d, s, c, first, ks, kc)
+    depth, kk = first, first
+    while max_depth is None or depth < max_depth:
+        if int(active.sum().item()) == 0:  # every query done: one sync per page
+            break
+        after = page_cursor(torch, active, d, s, c, kk)
+        kk = page if max_depth is None else min(page, max_depth - depth)
+        d, s, c = search_fn(q_ptr, q_term, q_weight, kk, after=after)
+        depth += kk
+        kd, ks, kc = at_k(d, s, c, (kd, ks, kc))
+        active = active & unfinished(d, s, c, kk, ks, kc)
+    return kd, ks, kc
 
 
 def merge_topk_device(in_doc, in_score, in_count, k: int, gathered: bool = False):

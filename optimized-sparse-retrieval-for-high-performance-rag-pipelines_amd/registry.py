@@ -21,7 +21,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .backend import SparseBackend, SparseIndexViews, apply_operators
+from .backend import SparseBackend, SparseIndexViews
 from .index import HostIndex, check_fuse_args, check_rescore_args, encode_queries, hybrid_depths, hybrid_search, rows_to_dict
 
 _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
@@ -30,7 +30,7 @@ _BM25_TYPES = ("bm25", "bm25_retriever", "bm25_custom")
 class _SparseRetrieverBase(SparseIndexViews):
     """Shared batched search: cache semantics of the reference call sites, one srx_search per call."""
 
-    strip_cache_key = True  # mode, term_order and the doors that only hand on to the backend: backend.SparseIndexViews
+    # mode, term_order, strip_cache_key, blank, the body of search and the doors that only hand on to the backend: backend.SparseIndexViews
 
     def __init__(self, k1: float, b: float, device: Optional[str], tile_log2: int, use_cache: bool = True, group=None,
                  shard_searcher_factory=None, sharded: Optional[bool] = None, one_copy: bool = True):
@@ -65,26 +65,10 @@ class _SparseRetrieverBase(SparseIndexViews):
         ``RetrievalService.search_bm25`` (needs raw scores > 0, which the search guarantees; not with ``collapse_by``; no cache).
         ``rank_model`` / ``rank_pool``: the first ``rank_pool`` rows of this search re-scored by the model of :meth:`set_rank_model`
         and cut to ``top_k``, as ``RetrievalService.search_bm25`` (pool-relative; not with ``boost``)."""
-        self._need_index()
-        ranked = self._be.rank_spec(rank_model, rank_pool, top_k, "search", boost)
-        if ranked is not None:
-            if min(int(top_k), self._be.n_docs_total) <= 0:
-                return {qid: {} for qid in queries}
-            pooled = self.search(queries, ranked.pool, allowed_docs=allowed_docs, excluded_docs=excluded_docs, must_terms=must_terms, any_terms=any_terms,
-                                 must_not_terms=must_not_terms, operators=operators, where=where, collapse_by=collapse_by, per_group=per_group,
-                                 collapse_nulls=collapse_nulls, collapse_depth=collapse_depth, expand_docs=expand_docs, expand_terms=expand_terms,
-                                 expand_weight=expand_weight, expand_by=expand_by)
-            return self._be.rerank_model_results(pooled, top_k, call="search")
-        if operators:
-            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
-        spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search")
-        collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search")
-        expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search")
-        boosted = self._be.boost_spec(boost, boost_depth, top_k, "search", collapse)
-        # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional, and
-        # search_dicts leaves it alone when one of the four specs is given
-        return self._be.search_dicts(queries, top_k, order=self.term_order, cache=self.query_cache, lock=self.cache_lock,
-                                     strip_key=self.strip_cache_key, blank="empty", filter=spec, collapse=collapse, expand=expand, boost=boosted)
+        # blank = no text (retriever_registry.py:237-239): white space is searched as an empty row; the cache is optional
+        return self._search(queries, top_k, (allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, operators, where),
+                            (collapse_by, per_group, collapse_nulls, collapse_depth), (expand_docs, expand_terms, expand_weight, expand_by),
+                            boost, boost_depth, rank_model, rank_pool)
 
     def score(self, queries: Dict[str, str], candidates: Dict[str, Any]) -> Dict[str, Dict[str, float]]:
         """The exact score of caller-named documents: ``{qid: {doc_id: score}}`` with every doc of ``candidates[qid]`` in

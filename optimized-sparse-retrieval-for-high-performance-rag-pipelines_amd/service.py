@@ -44,6 +44,7 @@ class RetrievalService(SparseIndexViews):
 
     not_built = "BM25 index not built. Call build_bm25_index() first."  # mode "bm25", term_order "term": backend.SparseIndexViews
     search_door = "search_bm25"
+    blank = "whitespace"  # no text or white space only is answered {} (:211-213); the cache key is the stripped text (:216), the cache always on
 
     def __init__(self, index_path=None, embedding_path=None, num_workers: int = 4, cache_size: int = 1000, *,
                  device: Optional[str] = None, tile_log2: int = 14, group=None, sharded: Optional[bool] = None,
@@ -169,32 +170,18 @@ class RetrievalService(SparseIndexViews):
         model's scores.  ``ValueError``: no :meth:`set_rank_model`, a feature that names a column without :meth:`set_doc_fields`,
         a set column, "sparse_score" / "dense_score" (:meth:`search_hybrid` only), ``rank_pool`` above 1 024, ``boost=`` in the same
         call (chain :meth:`boost_results`), a sharded index."""
-        self._need_index()  # :205-206
-        ranked = self._be.rank_spec(rank_model, rank_pool, top_k, "search_bm25", boost)
-        if ranked is not None:
-            if min(int(top_k), self._be.n_docs_total) <= 0:
-                return {qid: {} for qid in queries}
-            pooled = self.search_bm25(queries, ranked.pool, allowed_docs=allowed_docs, excluded_docs=excluded_docs, must_terms=must_terms,
-                                      any_terms=any_terms, must_not_terms=must_not_terms, operators=operators, where=where, collapse_by=collapse_by,
-                                      per_group=per_group, collapse_nulls=collapse_nulls, collapse_depth=collapse_depth, expand_docs=expand_docs,
-                                      expand_terms=expand_terms, expand_weight=expand_weight, expand_by=expand_by)
-            return self._be.rerank_model_results(pooled, top_k, call="search_bm25")
-        if operators:
-            queries, must_terms, must_not_terms = apply_operators(queries, must_terms, must_not_terms)
-        spec = self._be.filter_spec(queries, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where, "search_bm25")
-        collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, collapse_depth, top_k, "search_bm25")
-        expand = self._be.expand_spec(expand_docs, expand_terms, expand_weight, expand_by, "search_bm25")
-        boosted = self._be.boost_spec(boost, boost_depth, top_k, "search_bm25", collapse)
+        return self._search(queries, top_k, (allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, operators, where),
+                            (collapse_by, per_group, collapse_nulls, collapse_depth), (expand_docs, expand_terms, expand_weight, expand_by),
+                            boost, boost_depth, rank_model, rank_pool)
+
+    def _before_search(self, top_k, expand) -> bool:
         if min(int(top_k), self._be.n_docs_total) <= 0:  # the reference's argpartition(-scores, 0)[:0] keeps nothing (:276-279)
-            return {qid: {} for qid in queries}
+            return False
         if (self.k1, self.b) != self._built_k1b:
             self._upload()  # k1 / b are plain attributes on the reference (:116-117): impacts depend on them
             if expand is not None:
                 self._be.enable_feedback("bm25")  # the upload dropped the forward index; its rows do not depend on k1 / b
-        # blank = no text or white space only (:211-213); cache key = the stripped text (:216); the cache is always on, and
-        # search_dicts leaves it alone when one of the four specs is given
-        return self._be.search_dicts(queries, top_k, order="term", cache=self.query_cache, lock=self.cache_lock, strip_key=True,
-                                     blank="whitespace", filter=spec, collapse=collapse, expand=expand, boost=boosted)
+        return True
 
     def score_bm25(self, queries: Dict[str, str], candidates: Dict[str, Sequence[str]]) -> Dict[str, Dict[str, float]]:
         """The exact BM25 score of caller-named documents (no reference counterpart: it can only rank):
