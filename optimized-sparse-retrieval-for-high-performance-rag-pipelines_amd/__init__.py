@@ -21,6 +21,8 @@ from . import ltr
 from .ltr import ForestModel, RankFn
 from . import evaluate
 from .evaluate import Judgments
+from . import binary
+from .binary import DenseBinaryIndex, ScreenedDenseIndex
 
 __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", "build_host_index", "encode_queries", "merge_topk_device", "fuse_topk_device", "fuse_scored_device", "validate_candidates", "HybridRetriever",
            "tokenize", "build_library", "SparseRxError", "SparseRxUnavailable", "_capi", "ShardedSearcher", "shard_range",
@@ -30,4 +32,5 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
            "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape",
            "late_pool_depth", "FieldTable", "columns_from_metadata", "collapse_deep", "collapse_pool_depth", "ForwardIndex",
-           "boost", "BoostFn", "BoostResolver", "boost_deep", "ltr", "ForestModel", "RankFn", "evaluate", "Judgments"]
+           "boost", "BoostFn", "BoostResolver", "boost_deep", "ltr", "ForestModel", "RankFn", "evaluate", "Judgments",
+           "binary", "DenseBinaryIndex", "ScreenedDenseIndex"]

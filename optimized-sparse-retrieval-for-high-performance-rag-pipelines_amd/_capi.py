@@ -2,7 +2,7 @@
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
 include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
-include/ltr/sparse_rx_ltr.h and include/eval/sparse_rx_eval.h).
+include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h and include/binary/sparse_rx_binary.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -22,7 +22,7 @@ CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
            "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
-           "eval.hip"]  # one translation unit each, compiled in parallel
+           "eval.hip", "dense_binary.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -299,6 +299,17 @@ SRX_EVAL_NDCG, SRX_EVAL_AP, SRX_EVAL_RECALL, SRX_EVAL_P, SRX_EVAL_RR, SRX_EVAL_S
 SRX_EVAL_METRICS, SRX_EVAL_MAX_M, SRX_EVAL_MAX_K, SRX_EVAL_MAX_GAIN = 8, 2048, 8, 32                  # pinned to the header by tests/test_eval_cpu.py
 SRX_EVAL_WAVE_M, SRX_EVAL_LDS_ROW, SRX_EVAL_MEAN_CHUNK = 256, 1024, 1024                              # the kernel's size constants, and the means' chunk
 
+# every symbol include/binary/sparse_rx_binary.h declares (the seventeenth header of the same library)
+BINARY_SYMBOLS = {
+    "srx_binary_bytes": (_I64, [_I64, _I32, _I32]),
+    "srx_binary_encode": (ctypes.c_int, [_I32, _VP, _I64, _I64, _I32, _I32, _I64, _I64, _VP, _I32, _VP, _VP]),
+    "srx_binary_workspace_bytes": (_I64, [_I32, _I64, _I32]),
+    "srx_binary_search": (ctypes.c_int, [_I32, _VP, _I64, _I32, _VP, _I32, _I32, _I64, _FP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "srx_binary_dist_docs": (ctypes.c_int, [_I32, _VP, _I64, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _VP]),
+}
+SRX_BINARY_TILE, SRX_BINARY_QTILE, SRX_BINARY_PASS = 64, 128, 1024                                    # rows per tile, queries per wave walk and per pass
+SRX_BINARY_RANK_CHUNK, SRX_BINARY_SPLIT_DOCS, SRX_BINARY_BLOCK_DOCS = 4096, 16384, 256                # the rank kernel's step, docs per row split, docs per workgroup
+
 
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
@@ -343,7 +354,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "order", "sparse_rx_order.h"),
                                                             os.path.join(INCLUDE_DIR, "boost", "sparse_rx_boost.h"),
                                                             os.path.join(INCLUDE_DIR, "ltr", "sparse_rx_ltr.h"),
-                                                            os.path.join(INCLUDE_DIR, "eval", "sparse_rx_eval.h")]
+                                                            os.path.join(INCLUDE_DIR, "eval", "sparse_rx_eval.h"),
+                                                            os.path.join(INCLUDE_DIR, "binary", "sparse_rx_binary.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -393,7 +405,7 @@ def lib() -> ctypes.CDLL:
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
-                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS}.items():
+                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -197,7 +197,7 @@ class RetrievalService(SparseIndexViews):
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
-    def set_embeddings(self, embeddings, storage: str = "f32") -> None:
+    def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4) -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
@@ -207,11 +207,26 @@ class RetrievalService(SparseIndexViews):
         pass of four queries).  "f16" / "bf16" (no reference counterpart): rounded to half precision and searched a whole
         query batch at a time by MFMA (``DenseHalfIndex``, include/sparse_rx_half.h); :meth:`search_by_vector`,
         :meth:`search_hybrid` and :meth:`score_by_vector` then return the scores OF THE ROUNDED ROWS (and rounded query
-        vectors).  Any other value raises ``ValueError``."""
+        vectors).  Any other value raises ``ValueError``.
+
+        ``screen``: None (default: every search reads every row) or "binary" (no reference counterpart): 1-bit codes of the rows
+        (``DenseBinaryIndex``, include/binary/sparse_rx_binary.h; centred on the column means) screen the corpus by Hamming
+        distance under the search's filter, and the rows above are read only for the ``min(k * oversample, 1024)`` nearest
+        (``ScreenedDenseIndex``).  :meth:`search_by_vector` and the dense side of :meth:`search_hybrid` then return the best of
+        that pool -- approximate unless the pool covers the allowed docs; the scores are those of the storage.  The rows stay
+        resident: the screen saves bandwidth, not memory.  Not offered with a sharded index.  Any other value raises
+        ``ValueError``, as does ``oversample < 1``."""
         from .dense import DenseF32Index, DenseHalfIndex
         storage = str(storage).lower()
         if storage not in ("f32", "f16", "bf16"):
             raise ValueError(f"storage must be 'f32', 'f16' or 'bf16', got {storage!r}")
+        if screen is not None:
+            from .binary import check_oversample
+            if screen != "binary":
+                raise ValueError(f"screen must be None or 'binary', got {screen!r}")
+            oversample = check_oversample(oversample)
+            if self._be.sharded():
+                raise ValueError("screen='binary' is not offered with a sharded index")
         e = np.asarray(embeddings, dtype=np.float32)
         if e.ndim != 2 or (self.doc_ids and e.shape[0] != len(self.doc_ids)):
             raise ValueError("embeddings must be [n_docs, dim] with one row per document")
@@ -219,6 +234,10 @@ class RetrievalService(SparseIndexViews):
         # either index streams a memory map to the device in <= 64 MB chunks
         self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
         self.embedding_storage = storage
+        self.embedding_screen, self.embedding_oversample = screen, (oversample if screen is not None else None)
+        if screen is not None:
+            from .binary import DenseBinaryIndex, ScreenedDenseIndex
+            self._dense = ScreenedDenseIndex(self._dense, DenseBinaryIndex(e, center="mean", device=self.device), oversample)
 
     def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
                          excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> List[Dict]:
@@ -656,6 +675,8 @@ class RetrievalService(SparseIndexViews):
             stats["device_index_mb"] = self.dev.device_bytes() / (1024 * 1024)
         if getattr(self, "_dense", None) is not None:
             stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16" or "bf16" (set_embeddings)
+            stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None or "binary"
+            stats["embedding_oversample"] = getattr(self, "embedding_oversample", None)
         return stats
 
     def __enter__(self):
