@@ -297,7 +297,12 @@ int srx_memcpy_async(void *dst, const void *src, int64_t bytes, void *stream);
  *   scaled in fp64 like the reference's NumPy scalars), results = the k largest scores > 0 per query, ranked
  *   (score desc, doc asc), ids = doc_base + row, rows padded with -1 / 0, counts in out_count.
  * corpus i8[n_docs][dim], queries i8[nq][dim] row-major, 16-byte aligned, dim in {32,64,96,128,192,256,384,512,768,1024}
- * (pad rows with zeros otherwise); all pointers are device pointers; asynchronous on `stream`. */
+ * (pad rows with zeros otherwise); all pointers are device pointers; asynchronous on `stream`.
+ * Queries run in passes of QB = clamp(floor(2^32 / (4 ld) / 32) * 32, 32, 1024), ld = n_docs rounded up to 64: as many as keep
+ * the fp32 score matrix of a pass (QB x ld, the largest part of the workspace) within 4 GiB, but never fewer than 32.  So the
+ * matrix is within 4 GiB only up to 2^25 docs; beyond that the floor of 32 holds and it is 128 bytes per doc -- past 2^32
+ * bytes above 2^25 docs, past 2^31 cells above 2^26 docs (256 GiB at 2^31 docs).  srx_dense_workspace_bytes returns the size;
+ * the caller decides. */
 int64_t srx_dense_workspace_bytes(int32_t nq, int64_t n_docs, int32_t k);
 int srx_dense_search_i8(int32_t device, const int8_t *corpus, const float *corpus_scale, int64_t n_docs, int32_t dim,
                         const int8_t *queries, const float *query_scale, int32_t nq, int32_t k, int64_t doc_base,
