@@ -2,7 +2,7 @@
 include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h, include/sparse_rx_mmr.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
 include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
-include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h and include/binary/sparse_rx_binary.h).
+include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h, include/binary/sparse_rx_binary.h and include/mx/sparse_rx_mx.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -22,12 +22,15 @@ CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
            "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
-           "eval.hip", "dense_binary.hip"]  # one translation unit each, compiled in parallel
+           "eval.hip", "dense_binary.hip", "dense_mx.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-std=c++17"]
+# flags of single units, behind HIPCC_FLAGS.  dense_mx.hip: its fp32 arithmetic (the quantiser) is compiled to scalar-per-lane VALU
+# instructions only, never to the packed two-float forms
+UNIT_FLAGS = {"dense_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 SRX_VAL_F32, SRX_VAL_F16 = 0, 1
 SRX_FUSE_WEIGHTED, SRX_FUSE_RRF = 0, 1
@@ -310,6 +313,16 @@ BINARY_SYMBOLS = {
 SRX_BINARY_TILE, SRX_BINARY_QTILE, SRX_BINARY_PASS = 64, 128, 1024                                    # rows per tile, queries per wave walk and per pass
 SRX_BINARY_RANK_CHUNK, SRX_BINARY_SPLIT_DOCS, SRX_BINARY_BLOCK_DOCS = 4096, 16384, 256                # the rank kernel's step, docs per row split, docs per workgroup
 
+# every symbol include/mx/sparse_rx_mx.h declares (the eighteenth header of the same library); the argument lists after `type` are the half index's
+MX_SYMBOLS = {
+    "srx_mx_bytes": (_I64, [_I32, _I64, _I32]),
+    "srx_mx_convert": (ctypes.c_int, [_I32, _I32, _VP, _I64, _I64, _I32, _I32, _I64, _I64, _VP, _VP, _VP]),
+    "srx_mx_workspace_bytes": (_I64, [_I32, _I64, _I32]),
+    "srx_mx_search": (ctypes.c_int, [_I32, _I32, _VP, _I64, _I32, _VP, _I32, _I32, _I64, _FP, _VP, _VP, _VP, _VP, _I64, _VP, ctypes.c_float]),
+    "srx_mx_score_docs": (ctypes.c_int, [_I32, _I32, _VP, _I64, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _VP]),
+}
+SRX_MX_FP8, SRX_MX_FP4 = 0, 1  # srx_mx_type
+
 
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
@@ -355,7 +368,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "boost", "sparse_rx_boost.h"),
                                                             os.path.join(INCLUDE_DIR, "ltr", "sparse_rx_ltr.h"),
                                                             os.path.join(INCLUDE_DIR, "eval", "sparse_rx_eval.h"),
-                                                            os.path.join(INCLUDE_DIR, "binary", "sparse_rx_binary.h")]
+                                                            os.path.join(INCLUDE_DIR, "binary", "sparse_rx_binary.h"),
+                                                            os.path.join(INCLUDE_DIR, "mx", "sparse_rx_mx.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -376,7 +390,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         newest_src = max(os.path.getmtime(os.path.join(CSRC_DIR, x)) for x in [f, *INCLUDED_SOURCES.get(f, [])])
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(newest_src, newest_hdr):
             continue
-        cmd = [hipcc, *HIPCC_FLAGS, f"-I{INCLUDE_DIR}", f"-I{CSRC_DIR}", "-c", "-o", obj, src]
+        cmd = [hipcc, *HIPCC_FLAGS, *UNIT_FLAGS.get(f, []), f"-I{INCLUDE_DIR}", f"-I{CSRC_DIR}", "-c", "-o", obj, src]
         if verbose:
             print(" ".join(cmd))
         procs.append((f, subprocess.Popen(cmd)))
@@ -405,7 +419,7 @@ def lib() -> ctypes.CDLL:
         raise SparseRxUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
-                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS}.items():
+                                   **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS, **MX_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -207,7 +207,11 @@ class RetrievalService(SparseIndexViews):
         pass of four queries).  "f16" / "bf16" (no reference counterpart): rounded to half precision and searched a whole
         query batch at a time by MFMA (``DenseHalfIndex``, include/sparse_rx_half.h); :meth:`search_by_vector`,
         :meth:`search_hybrid` and :meth:`score_by_vector` then return the scores OF THE ROUNDED ROWS (and rounded query
-        vectors).  Any other value raises ``ValueError``.
+        vectors).  "mxfp8" / "mxfp4" (no reference counterpart): OCP microscaling codes with a power-of-two scale per 32 columns,
+        searched by the block-scaled MFMA (``DenseMxIndex``, include/mx/sparse_rx_mx.h; about 1 and 1/2 byte per dim); the same
+        three calls, filter / term / ``where`` keywords and ``rescore=True`` included, then return the scores OF THE DEQUANTISED
+        ROWS (and MXFP8 query vectors).  Not offered with ``screen="binary"``, with ``mmr_lambda`` / :meth:`diversify` or with a
+        sharded index: each raises ``ValueError``.  Any other value raises ``ValueError``.
 
         ``screen``: None (default: every search reads every row) or "binary" (no reference counterpart): 1-bit codes of the rows
         (``DenseBinaryIndex``, include/binary/sparse_rx_binary.h; centred on the column means) screen the corpus by Hamming
@@ -218,8 +222,13 @@ class RetrievalService(SparseIndexViews):
         ``ValueError``, as does ``oversample < 1``."""
         from .dense import DenseF32Index, DenseHalfIndex
         storage = str(storage).lower()
-        if storage not in ("f32", "f16", "bf16"):
-            raise ValueError(f"storage must be 'f32', 'f16' or 'bf16', got {storage!r}")
+        if storage not in ("f32", "f16", "bf16", "mxfp8", "mxfp4"):
+            raise ValueError(f"storage must be 'f32', 'f16', 'bf16', 'mxfp8' or 'mxfp4', got {storage!r}")
+        mx = storage.startswith("mx")
+        if mx and screen is not None:
+            raise ValueError(f"screen={screen!r} is not offered with storage={storage!r}")
+        if mx and self._be.sharded():
+            raise ValueError(f"storage={storage!r} is not offered with a sharded index")
         if screen is not None:
             from .binary import check_oversample
             if screen != "binary":
@@ -232,7 +241,11 @@ class RetrievalService(SparseIndexViews):
             raise ValueError("embeddings must be [n_docs, dim] with one row per document")
         self.embedding_index = e
         # either index streams a memory map to the device in <= 64 MB chunks
-        self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
+        if mx:
+            from .mx import DenseMxIndex
+            self._dense = DenseMxIndex(e, dtype=storage, device=self.device)
+        else:
+            self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
         self.embedding_storage = storage
         self.embedding_screen, self.embedding_oversample = screen, (oversample if screen is not None else None)
         if screen is not None:
@@ -282,7 +295,9 @@ class RetrievalService(SparseIndexViews):
             bound = float(np.linalg.norm(q.astype(np.float64))) * self._dense.max_row_norm()
             # half storage scores the ROUNDED query: rounding raises a component by up to 2^-9 (bf16) / 2^-12 (f16) of itself,
             # so its norm can exceed |q|_2 by 0.2 %: the margin covers that (max_row_norm is already that of the rounded rows)
-            offset = bound * (1.001 if getattr(self, "embedding_storage", "f32") == "f32" else 1.01) + 1e-30
+            # MX storage scores the MXFP8 query: e4m3 rounding raises a component by at most 2^-4 of itself, a norm of at most 1.0625 |q|_2
+            storage = getattr(self, "embedding_storage", "f32")
+            offset = bound * (1.001 if storage == "f32" else 1.07 if storage.startswith("mx") else 1.01) + 1e-30
             d, s, n = self._dense.search(q, kk, score_offset=offset, **flt)
             idx = d[0, : int(n[0])].astype(np.int64)
             sc = np.dot(self.embedding_index[idx], q).astype(np.float32)  # the reference's fp32 expression on the k rows
@@ -316,6 +331,10 @@ class RetrievalService(SparseIndexViews):
         if spec is None:
             return None
         return spec.on_device(self._dense).for_index(self._dense), spec
+
+    def _need_mmr_rows(self, call: str) -> None:
+        if not hasattr(self._dense, "mmr_device"):
+            raise ValueError(f"{call} is not offered with storage={getattr(self, 'embedding_storage', 'f32')!r}: MMR reads f32 or half-precision rows")
 
     def _ensure_dense(self) -> None:
         if getattr(self, "_dense", None) is None and self.embedding_path and os.path.exists(str(self.embedding_path)) and self.doc_ids:
@@ -423,6 +442,8 @@ class RetrievalService(SparseIndexViews):
             raise ValueError("hybrid search needs the whole index on one GPU (the dense corpus is not sharded)")
         self._need_index()
         self._ensure_dense()
+        if mmr_lambda is not None:
+            self._need_mmr_rows("search_hybrid(mmr_lambda=...)")
         collapse = self._be.collapse_spec(collapse_by, per_group, collapse_nulls, None, top_k, "search_hybrid")
         if collapse is not None and late_query_tokens is None:
             pools["collapse"] = collapse_pool_depth(top_k, collapse_pool, n_docs)
@@ -548,6 +569,7 @@ class RetrievalService(SparseIndexViews):
         if not results:
             return {}
         self._ensure_dense()
+        self._need_mmr_rows("diversify()")
         lists = {qid: list(row) for qid, row in results.items()}
         if self.host is not None:
             out, live, cand_doc, cand_count = self._be.candidate_block(results, lists)
@@ -674,7 +696,7 @@ class RetrievalService(SparseIndexViews):
         if self.dev is not None:
             stats["device_index_mb"] = self.dev.device_bytes() / (1024 * 1024)
         if getattr(self, "_dense", None) is not None:
-            stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16" or "bf16" (set_embeddings)
+            stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16", "bf16", "mxfp8" or "mxfp4" (set_embeddings)
             stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None or "binary"
             stats["embedding_oversample"] = getattr(self, "embedding_oversample", None)
         return stats
