@@ -197,7 +197,7 @@ class RetrievalService(SparseIndexViews):
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
-    def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4) -> None:
+    def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4, ann=None, nlist=None, nprobe=None) -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
@@ -219,8 +219,29 @@ class RetrievalService(SparseIndexViews):
         (``ScreenedDenseIndex``).  :meth:`search_by_vector` and the dense side of :meth:`search_hybrid` then return the best of
         that pool -- approximate unless the pool covers the allowed docs; the scores are those of the storage.  The rows stay
         resident: the screen saves bandwidth, not memory.  Not offered with a sharded index.  Any other value raises
-        ``ValueError``, as does ``oversample < 1``."""
+        ``ValueError``, as does ``oversample < 1``.
+
+        ``ann``: None (default: nothing changes) or "ivf" (no reference counterpart): the "f16" / "bf16" rows partitioned into
+        ``nlist`` k-means lists (``IvfHalfIndex``, include/ivf/sparse_rx_ivf.h); :meth:`search_by_vector` and the dense side of
+        :meth:`search_hybrid` read the ``nprobe`` lists whose centroids score highest and return the exact top k of those lists
+        with the storage's score bits -- approximate unless ``nprobe == nlist``; :meth:`score_by_vector` is unchanged.  Not
+        offered with f32 or MX storage, with ``screen="binary"``, with ``mmr_lambda`` / :meth:`diversify` or with a sharded
+        index, and ``nlist`` / ``nprobe`` must be in [1, min(n_docs, 65536)] / [1, min(nlist, 1024)]: each raises ``ValueError``."""
         from .dense import DenseF32Index, DenseHalfIndex
+        if ann is None and (nlist is not None or nprobe is not None):
+            raise ValueError("nlist= / nprobe= need ann='ivf'")
+        if ann is not None:
+            if ann != "ivf":
+                raise ValueError(f"ann must be None or 'ivf', got {ann!r}")
+            if str(storage).lower() not in ("f16", "bf16"):
+                raise ValueError(f"ann='ivf' needs storage 'f16' or 'bf16', got {storage!r}")
+            if screen is not None:
+                raise ValueError(f"screen={screen!r} is not offered with ann='ivf'")
+            if self._be.sharded():
+                raise ValueError("ann='ivf' is not offered with a sharded index")
+            from .ivf import check_nlist, check_nprobe
+            nlist = check_nlist(0 if nlist is None else nlist, int(np.shape(embeddings)[0]))
+            nprobe = check_nprobe(0 if nprobe is None else nprobe, nlist)
         storage = str(storage).lower()
         if storage not in ("f32", "f16", "bf16", "mxfp8", "mxfp4"):
             raise ValueError(f"storage must be 'f32', 'f16', 'bf16', 'mxfp8' or 'mxfp4', got {storage!r}")
@@ -244,10 +265,15 @@ class RetrievalService(SparseIndexViews):
         if mx:
             from .mx import DenseMxIndex
             self._dense = DenseMxIndex(e, dtype=storage, device=self.device)
+        elif ann is not None:
+            from .ivf import IvfHalfIndex
+            self._dense = IvfHalfIndex(e, nlist, dtype=storage, device=self.device)
+            self._dense.default_nprobe = nprobe
         else:
             self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
         self.embedding_storage = storage
         self.embedding_screen, self.embedding_oversample = screen, (oversample if screen is not None else None)
+        self.embedding_ann = ann
         if screen is not None:
             from .binary import DenseBinaryIndex, ScreenedDenseIndex
             self._dense = ScreenedDenseIndex(self._dense, DenseBinaryIndex(e, center="mean", device=self.device), oversample)
@@ -334,7 +360,8 @@ class RetrievalService(SparseIndexViews):
 
     def _need_mmr_rows(self, call: str) -> None:
         if not hasattr(self._dense, "mmr_device"):
-            raise ValueError(f"{call} is not offered with storage={getattr(self, 'embedding_storage', 'f32')!r}: MMR reads f32 or half-precision rows")
+            raise ValueError(f"{call} is not offered with storage={getattr(self, 'embedding_storage', 'f32')!r}, ann={getattr(self, 'embedding_ann', None)!r}: "
+                             "MMR reads f32 or half-precision rows in doc order")
 
     def _ensure_dense(self) -> None:
         if getattr(self, "_dense", None) is None and self.embedding_path and os.path.exists(str(self.embedding_path)) and self.doc_ids:
@@ -699,6 +726,9 @@ class RetrievalService(SparseIndexViews):
             stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16", "bf16", "mxfp8" or "mxfp4" (set_embeddings)
             stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None or "binary"
             stats["embedding_oversample"] = getattr(self, "embedding_oversample", None)
+            stats["embedding_ann"] = getattr(self, "embedding_ann", None)            # None or "ivf"
+            stats["nlist"] = getattr(self._dense, "nlist", None)
+            stats["nprobe"] = getattr(self._dense, "default_nprobe", None)
         return stats
 
     def __enter__(self):
