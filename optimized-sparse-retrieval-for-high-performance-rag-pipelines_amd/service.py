@@ -197,7 +197,8 @@ class RetrievalService(SparseIndexViews):
 
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
-    def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4, ann=None, nlist=None, nprobe=None) -> None:
+    def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4, ann=None, nlist=None, nprobe=None,
+                       pq_dsub: int = 8) -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
@@ -211,15 +212,21 @@ class RetrievalService(SparseIndexViews):
         searched by the block-scaled MFMA (``DenseMxIndex``, include/mx/sparse_rx_mx.h; about 1 and 1/2 byte per dim); the same
         three calls, filter / term / ``where`` keywords and ``rescore=True`` included, then return the scores OF THE DEQUANTISED
         ROWS (and MXFP8 query vectors).  Not offered with ``screen="binary"``, with ``mmr_lambda`` / :meth:`diversify` or with a
-        sharded index: each raises ``ValueError``.  Any other value raises ``ValueError``.
+        sharded index: each raises ``ValueError``.  "pq" (no reference counterpart): 8-bit product codes, one byte per ``pq_dsub``
+        (4, 8 or 16) dimensions, with codebooks trained at this call (``DensePqIndex``, include/pq/sparse_rx_pq.h; 96 bytes per
+        768-dim row at the default 8); the same three calls, filter / term / ``where`` keywords and ``rescore=True`` included,
+        then return the scores OF THE RECONSTRUCTED ROWS -- approximate, and the only storage that keeps no row.  Not offered
+        with ``screen=``, ``ann=``, ``mmr_lambda`` / :meth:`diversify` or a sharded index: each raises ``ValueError``.  Any other
+        value raises ``ValueError``.
 
         ``screen``: None (default: every search reads every row) or "binary" (no reference counterpart): 1-bit codes of the rows
         (``DenseBinaryIndex``, include/binary/sparse_rx_binary.h; centred on the column means) screen the corpus by Hamming
         distance under the search's filter, and the rows above are read only for the ``min(k * oversample, 1024)`` nearest
         (``ScreenedDenseIndex``).  :meth:`search_by_vector` and the dense side of :meth:`search_hybrid` then return the best of
         that pool -- approximate unless the pool covers the allowed docs; the scores are those of the storage.  The rows stay
-        resident: the screen saves bandwidth, not memory.  Not offered with a sharded index.  Any other value raises
-        ``ValueError``, as does ``oversample < 1``.
+        resident: the screen saves bandwidth, not memory.  Not offered with a sharded index.  "pq" (f32 / f16 / bf16 storage):
+        the same two steps with a ``DensePqIndex`` (``pq_dsub``) as the screen: the pool is its top ``k * oversample`` by PQ
+        score.  Any other value raises ``ValueError``, as does ``oversample < 1``.
 
         ``ann``: None (default: nothing changes) or "ivf" (no reference counterpart): the "f16" / "bf16" rows partitioned into
         ``nlist`` k-means lists (``IvfHalfIndex``, include/ivf/sparse_rx_ivf.h); :meth:`search_by_vector` and the dense side of
@@ -233,6 +240,8 @@ class RetrievalService(SparseIndexViews):
         if ann is not None:
             if ann != "ivf":
                 raise ValueError(f"ann must be None or 'ivf', got {ann!r}")
+            if str(storage).lower() == "pq" or screen == "pq":
+                raise ValueError("ann='ivf' is not offered with storage='pq' or screen='pq' (there are no product-quantised lists)")
             if str(storage).lower() not in ("f16", "bf16"):
                 raise ValueError(f"ann='ivf' needs storage 'f16' or 'bf16', got {storage!r}")
             if screen is not None:
@@ -243,20 +252,24 @@ class RetrievalService(SparseIndexViews):
             nlist = check_nlist(0 if nlist is None else nlist, int(np.shape(embeddings)[0]))
             nprobe = check_nprobe(0 if nprobe is None else nprobe, nlist)
         storage = str(storage).lower()
-        if storage not in ("f32", "f16", "bf16", "mxfp8", "mxfp4"):
-            raise ValueError(f"storage must be 'f32', 'f16', 'bf16', 'mxfp8' or 'mxfp4', got {storage!r}")
-        mx = storage.startswith("mx")
-        if mx and screen is not None:
+        if storage not in ("f32", "f16", "bf16", "mxfp8", "mxfp4", "pq"):
+            raise ValueError(f"storage must be 'f32', 'f16', 'bf16', 'mxfp8', 'mxfp4' or 'pq', got {storage!r}")
+        mx, pq = storage.startswith("mx"), storage == "pq"
+        if (mx or pq) and screen is not None:
             raise ValueError(f"screen={screen!r} is not offered with storage={storage!r}")
-        if mx and self._be.sharded():
+        if (mx or pq) and self._be.sharded():
             raise ValueError(f"storage={storage!r} is not offered with a sharded index")
         if screen is not None:
             from .binary import check_oversample
-            if screen != "binary":
-                raise ValueError(f"screen must be None or 'binary', got {screen!r}")
+            if screen not in ("binary", "pq"):
+                raise ValueError(f"screen must be None or 'binary' or 'pq', got {screen!r}")
             oversample = check_oversample(oversample)
             if self._be.sharded():
-                raise ValueError("screen='binary' is not offered with a sharded index")
+                raise ValueError(f"screen={screen!r} is not offered with a sharded index")
+        if pq or screen == "pq":
+            from .pq import subspaces
+            if np.ndim(embeddings) == 2:
+                subspaces(int(np.shape(embeddings)[1]), pq_dsub)
         e = np.asarray(embeddings, dtype=np.float32)
         if e.ndim != 2 or (self.doc_ids and e.shape[0] != len(self.doc_ids)):
             raise ValueError("embeddings must be [n_docs, dim] with one row per document")
@@ -265,6 +278,9 @@ class RetrievalService(SparseIndexViews):
         if mx:
             from .mx import DenseMxIndex
             self._dense = DenseMxIndex(e, dtype=storage, device=self.device)
+        elif pq:
+            from .pq import DensePqIndex
+            self._dense = DensePqIndex(e, dsub=pq_dsub, device=self.device)
         elif ann is not None:
             from .ivf import IvfHalfIndex
             self._dense = IvfHalfIndex(e, nlist, dtype=storage, device=self.device)
@@ -274,9 +290,15 @@ class RetrievalService(SparseIndexViews):
         self.embedding_storage = storage
         self.embedding_screen, self.embedding_oversample = screen, (oversample if screen is not None else None)
         self.embedding_ann = ann
+        self.embedding_pq_dsub = int(pq_dsub) if pq or screen == "pq" else None
         if screen is not None:
             from .binary import DenseBinaryIndex, ScreenedDenseIndex
-            self._dense = ScreenedDenseIndex(self._dense, DenseBinaryIndex(e, center="mean", device=self.device), oversample)
+            if screen == "pq":
+                from .pq import DensePqIndex
+                coarse = DensePqIndex(e, dsub=pq_dsub, device=self.device)
+            else:
+                coarse = DenseBinaryIndex(e, center="mean", device=self.device)
+            self._dense = ScreenedDenseIndex(self._dense, coarse, oversample)
 
     def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
                          excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> List[Dict]:
@@ -322,6 +344,7 @@ class RetrievalService(SparseIndexViews):
             # half storage scores the ROUNDED query: rounding raises a component by up to 2^-9 (bf16) / 2^-12 (f16) of itself,
             # so its norm can exceed |q|_2 by 0.2 %: the margin covers that (max_row_norm is already that of the rounded rows)
             # MX storage scores the MXFP8 query: e4m3 rounding raises a component by at most 2^-4 of itself, a norm of at most 1.0625 |q|_2
+            # PQ storage scores the f32 query against the reconstructed rows (max_row_norm is theirs): the margin covers the fp32 sums
             storage = getattr(self, "embedding_storage", "f32")
             offset = bound * (1.001 if storage == "f32" else 1.07 if storage.startswith("mx") else 1.01) + 1e-30
             d, s, n = self._dense.search(q, kk, score_offset=offset, **flt)
@@ -641,6 +664,8 @@ class RetrievalService(SparseIndexViews):
         shape mismatch, no token at all or a non-finite value."""
         from .dense import check_half_dtype
         from .late import TokenIndex
+        if str(storage).lower() == "pq":
+            raise ValueError("storage='pq' is not offered for token embeddings (MaxSim reads half-precision rows): use 'f16' or 'bf16'")
         storage = check_half_dtype(storage)
         if self._be.sharded():
             raise ValueError("late interaction needs the whole index on one GPU (the token store is not sharded)")
@@ -723,8 +748,9 @@ class RetrievalService(SparseIndexViews):
         if self.dev is not None:
             stats["device_index_mb"] = self.dev.device_bytes() / (1024 * 1024)
         if getattr(self, "_dense", None) is not None:
-            stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16", "bf16", "mxfp8" or "mxfp4" (set_embeddings)
-            stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None or "binary"
+            stats["embedding_storage"] = getattr(self, "embedding_storage", "f32")  # "f32", "f16", "bf16", "mxfp8", "mxfp4" or "pq" (set_embeddings)
+            stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None, "binary" or "pq"
+            stats["pq_dsub"] = getattr(self, "embedding_pq_dsub", None)             # with storage or screen "pq"
             stats["embedding_oversample"] = getattr(self, "embedding_oversample", None)
             stats["embedding_ann"] = getattr(self, "embedding_ann", None)            # None or "ivf"
             stats["nlist"] = getattr(self._dense, "nlist", None)
