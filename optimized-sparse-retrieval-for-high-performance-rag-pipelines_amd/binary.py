@@ -287,14 +287,16 @@ class ScreenedDenseIndex:
     ``binary`` may also be a :class:`~.pq.DensePqIndex`: the pool is then the PQ search's top ``pool`` under the caller's filter,
     taken with ``score_offset = max|q|_2 * max_row_norm * 1.01`` so that every allowed doc is rankable.  That offset coarsens
     the SCREEN's order to ulp(offset): docs whose PQ scores differ by less can swap places at the pool's edge.  The pool is
-    rescored and cut exactly as above."""
+    rescored and cut exactly as above.  An :class:`~.ivfpq.IvfPqIndex` screens the same way over the ``default_nprobe`` lists it
+    probes: the pool holds docs of those lists only."""
 
     def __init__(self, exact, binary, oversample: int = 4):
         if not isinstance(exact, (DenseF32Index, DenseHalfIndex)):
             raise ValueError(f"the exact index of a screened search must be a DenseF32Index or a DenseHalfIndex, got {type(exact).__name__}")
+        from .ivfpq import IvfPqIndex
         from .pq import DensePqIndex
-        if not isinstance(binary, (DenseBinaryIndex, DensePqIndex)):
-            raise ValueError(f"the screen must be a DenseBinaryIndex or a DensePqIndex, got {type(binary).__name__}")
+        if not isinstance(binary, (DenseBinaryIndex, DensePqIndex, IvfPqIndex)):
+            raise ValueError(f"the screen must be a DenseBinaryIndex or a DensePqIndex (or an IvfPqIndex), got {type(binary).__name__}")
         if (exact.n_docs, exact.dim, exact.doc_base) != (binary.n_docs, binary.dim, binary.doc_base) or exact.device != binary.device:
             raise ValueError(f"the screen speaks of {binary.n_docs} x {binary.dim} rows from id {binary.doc_base} on {binary.device}, the exact "
                              f"index of {exact.n_docs} x {exact.dim} from {exact.doc_base} on {exact.device}")
@@ -317,7 +319,7 @@ class ScreenedDenseIndex:
         else:  # a PQ screen: every allowed doc rankable (the one synchronisation of this door: the largest query norm)
             from .pq import OFFSET_MARGIN
             bound = float(queries.double().norm(dim=1).max().item()) * self.binary.max_row_norm() * OFFSET_MARGIN + 1e-30
-            pool_doc, _, pool_count = self.binary.search_device(queries, self.pool(k), bound, filter=filter, q_filter=q_filter)
+            pool_doc, _, pool_count = self.binary.search_device(queries, self.pool(k), score_offset=bound, filter=filter, q_filter=q_filter)
         score = self.exact.score_docs_device(queries, pool_doc, pool_count)
         if score_offset != 0.0:
             score = score + torch.tensor(float(score_offset), dtype=torch.float32, device=self.device)  # fl32(score + offset)

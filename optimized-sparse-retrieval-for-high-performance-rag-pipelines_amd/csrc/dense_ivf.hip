@@ -18,6 +18,7 @@
 //             group of 32 queries) work items, found by a binary search of the group offsets -> rank each pair's strip ->
 //             srx_merge_impl.
 #include "half_common.h"
+#include "ivf_probe.h"
 #include "ivf/sparse_rx_ivf.h"
 
 namespace {
@@ -567,27 +568,27 @@ int check_desc(const char *who, const srx_ivf_desc *d, int32_t nq, const float *
     return SRX_OK;
 }
 
-// the probe of one pass of <= 1024 queries
-int probe_pass(const srx_ivf_desc *d, const float *queries, int nq, int nprobe, int32_t *probe_list, float *probe_score, float *cscores,
-               int64_t ldc, hipStream_t stream) {
-    const int ks = d->dim_pad / 16;
-    const int qblocks = (nq + 31) / 32, n_ct = (d->nlist + 31) / 32;
+}  // namespace
+
+// the probe of one pass of <= 1024 queries (ivf_probe.h): shared with dense_ivfpq.hip, whose lists have the same centroids
+int srx_ivf_probe_pass(const void *centroids, int nlist, int type, int dim_pad, const float *queries, int nq, int nprobe, int32_t *probe_list,
+                       float *probe_score, float *cscores, int64_t ldc, hipStream_t stream) {
+    const int ks = dim_pad / 16;
+    const int qblocks = (nq + 31) / 32, n_ct = (nlist + 31) / 32;
     int slices = 512 / qblocks < n_ct / 4 ? 512 / qblocks : n_ct / 4;  // >= 512 workgroups while a slice keeps a tile per wave
     const dim3 grid((unsigned)qblocks, (unsigned)(slices < 1 ? 1 : slices));
-    const size_t lds = (size_t)d->dim_pad * 64;
-    if (d->type == SRX_HALF_F16)
-        hipLaunchKernelGGL(srx_ivf_centroid_scores_kernel<SRX_HALF_F16>, grid, dim3(THREADS), lds, stream, (const hf_v4i *)d->centroids, d->nlist, ks,
-                           queries, nq, cscores, ldc);
+    const size_t lds = (size_t)dim_pad * 64;
+    if (type == SRX_HALF_F16)
+        hipLaunchKernelGGL(srx_ivf_centroid_scores_kernel<SRX_HALF_F16>, grid, dim3(THREADS), lds, stream, (const hf_v4i *)centroids, nlist, ks, queries,
+                           nq, cscores, ldc);
     else
-        hipLaunchKernelGGL(srx_ivf_centroid_scores_kernel<SRX_HALF_BF16>, grid, dim3(THREADS), lds, stream, (const hf_v4i *)d->centroids, d->nlist, ks,
-                           queries, nq, cscores, ldc);
-    hipLaunchKernelGGL(srx_ivf_probe_select_kernel, dim3((unsigned)nq), dim3(THREADS), 0, stream, (const float *)cscores, ldc, d->nlist, nprobe,
-                       probe_list, probe_score);
+        hipLaunchKernelGGL(srx_ivf_centroid_scores_kernel<SRX_HALF_BF16>, grid, dim3(THREADS), lds, stream, (const hf_v4i *)centroids, nlist, ks, queries,
+                           nq, cscores, ldc);
+    hipLaunchKernelGGL(srx_ivf_probe_select_kernel, dim3((unsigned)nq), dim3(THREADS), 0, stream, (const float *)cscores, ldc, nlist, nprobe, probe_list,
+                       probe_score);
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }
-
-}  // namespace
 
 SRX_API int srx_ivf_assign(int32_t device, int32_t type, const void *centroids_packed, int32_t nlist, int32_t dim, int32_t dim_pad,
                            const float *rows, int64_t ld, int64_t n, int32_t *out_list, float *out_score, void *stream_v) {
@@ -658,8 +659,9 @@ SRX_API int srx_ivf_probe(const srx_ivf_desc *desc, const float *queries, int32_
     HIP_TRY(hipSetDevice(desc->device));
     for (int q0 = 0; q0 < nq; q0 += IVF_PASS) {
         const int qb = nq - q0 < IVF_PASS ? nq - q0 : IVF_PASS;
-        const int prc = probe_pass(desc, queries + (int64_t)q0 * desc->dim_pad, qb, nprobe, probe_list + (int64_t)q0 * nprobe,
-                                   probe_score + (int64_t)q0 * nprobe, (float *)workspace, ldc, (hipStream_t)stream_v);
+        const int prc = srx_ivf_probe_pass(desc->centroids, desc->nlist, desc->type, desc->dim_pad, queries + (int64_t)q0 * desc->dim_pad, qb, nprobe,
+                                           probe_list + (int64_t)q0 * nprobe, probe_score + (int64_t)q0 * nprobe, (float *)workspace, ldc,
+                                           (hipStream_t)stream_v);
         if (prc != SRX_OK) return prc;
     }
     return SRX_OK;
@@ -692,7 +694,7 @@ SRX_API int srx_ivf_search(const srx_ivf_desc *desc, const float *queries, int32
         const float *qsrc = queries + (int64_t)q0 * d.dim_pad;
         const int32_t *plist = probe_list != nullptr ? probe_list + (int64_t)q0 * nprobe : w.probe_list;
         if (probe_list == nullptr) {
-            rc = probe_pass(desc, qsrc, qb, nprobe, w.probe_list, w.probe_score, w.cscores, pl.ldc, stream);
+            rc = srx_ivf_probe_pass(d.centroids, d.nlist, d.type, d.dim_pad, qsrc, qb, nprobe, w.probe_list, w.probe_score, w.cscores, pl.ldc, stream);
             if (rc != SRX_OK) return rc;
         }
         hipLaunchKernelGGL(srx_ivf_zero_kernel, dim3((unsigned)((d.nlist + THREADS) / THREADS)), dim3(THREADS), 0, stream, w.count, d.nlist + 1);

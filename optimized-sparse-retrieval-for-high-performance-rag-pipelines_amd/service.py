@@ -233,13 +233,33 @@ class RetrievalService(SparseIndexViews):
         :meth:`search_hybrid` read the ``nprobe`` lists whose centroids score highest and return the exact top k of those lists
         with the storage's score bits -- approximate unless ``nprobe == nlist``; :meth:`score_by_vector` is unchanged.  Not
         offered with f32 or MX storage, with ``screen="binary"``, with ``mmr_lambda`` / :meth:`diversify` or with a sharded
-        index, and ``nlist`` / ``nprobe`` must be in [1, min(n_docs, 65536)] / [1, min(nlist, 1024)]: each raises ``ValueError``."""
+        index, and ``nlist`` / ``nprobe`` must be in [1, min(n_docs, 65536)] / [1, min(nlist, 1024)]: each raises ``ValueError``.
+        "ivfpq" (no reference counterpart): the same lists holding 8-bit product codes of the residual ``row - centroid``
+        (``IvfPqIndex``, include/ivfpq/sparse_rx_ivfpq.h; ``pq_dsub``, f16 centroids).  With ``storage="pq"`` the index stands alone
+        and keeps no row: the three calls return ``coarse + code sum`` scores of the probed lists' docs (:meth:`score_by_vector`:
+        of any doc).  With ``storage`` "f32" / "f16" / "bf16" and ``screen="pq"`` it is the screen of the exact rows: the pool is
+        its top ``k * oversample`` of the ``nprobe`` probed lists.  Not offered with MX storage, ``screen="binary"``,
+        ``storage="pq"`` together with ``screen=``, ``mmr_lambda`` / :meth:`diversify` with ``storage="pq"``, a sharded index or
+        token embeddings."""
         from .dense import DenseF32Index, DenseHalfIndex
         if ann is None and (nlist is not None or nprobe is not None):
             raise ValueError("nlist= / nprobe= need ann='ivf'")
-        if ann is not None:
+        ivfpq = ann == "ivfpq"
+        if ivfpq:
+            lowered = str(storage).lower()
+            if lowered.startswith("mx"):
+                raise ValueError(f"ann='ivfpq' is not offered with storage={storage!r}")
+            if screen == "binary":
+                raise ValueError("screen='binary' is not offered with ann='ivfpq'")
+            if lowered == "pq" and screen is not None:
+                raise ValueError(f"screen={screen!r} is not offered with storage='pq'")
+            if lowered in ("f32", "f16", "bf16") and screen != "pq":
+                raise ValueError("ann='ivfpq' needs storage='pq' (the index alone) or screen='pq' (the screen of the exact rows)")
+            if self._be.sharded():
+                raise ValueError("ann='ivfpq' is not offered with a sharded index")
+        elif ann is not None:
             if ann != "ivf":
-                raise ValueError(f"ann must be None or 'ivf', got {ann!r}")
+                raise ValueError(f"ann must be None, 'ivf' or 'ivfpq', got {ann!r}")
             if str(storage).lower() == "pq" or screen == "pq":
                 raise ValueError("ann='ivf' is not offered with storage='pq' or screen='pq' (there are no product-quantised lists)")
             if str(storage).lower() not in ("f16", "bf16"):
@@ -248,6 +268,7 @@ class RetrievalService(SparseIndexViews):
                 raise ValueError(f"screen={screen!r} is not offered with ann='ivf'")
             if self._be.sharded():
                 raise ValueError("ann='ivf' is not offered with a sharded index")
+        if ann is not None and str(storage).lower() in ("f32", "f16", "bf16", "pq"):
             from .ivf import check_nlist, check_nprobe
             nlist = check_nlist(0 if nlist is None else nlist, int(np.shape(embeddings)[0]))
             nprobe = check_nprobe(0 if nprobe is None else nprobe, nlist)
@@ -278,10 +299,14 @@ class RetrievalService(SparseIndexViews):
         if mx:
             from .mx import DenseMxIndex
             self._dense = DenseMxIndex(e, dtype=storage, device=self.device)
+        elif pq and ivfpq:
+            from .ivfpq import IvfPqIndex
+            self._dense = IvfPqIndex(e, nlist, dsub=pq_dsub, device=self.device)
+            self._dense.default_nprobe = nprobe
         elif pq:
             from .pq import DensePqIndex
             self._dense = DensePqIndex(e, dsub=pq_dsub, device=self.device)
-        elif ann is not None:
+        elif ann is not None and not ivfpq:
             from .ivf import IvfHalfIndex
             self._dense = IvfHalfIndex(e, nlist, dtype=storage, device=self.device)
             self._dense.default_nprobe = nprobe
@@ -293,7 +318,11 @@ class RetrievalService(SparseIndexViews):
         self.embedding_pq_dsub = int(pq_dsub) if pq or screen == "pq" else None
         if screen is not None:
             from .binary import DenseBinaryIndex, ScreenedDenseIndex
-            if screen == "pq":
+            if screen == "pq" and ivfpq:
+                from .ivfpq import IvfPqIndex
+                coarse = IvfPqIndex(e, nlist, dsub=pq_dsub, device=self.device)
+                coarse.default_nprobe = nprobe
+            elif screen == "pq":
                 from .pq import DensePqIndex
                 coarse = DensePqIndex(e, dsub=pq_dsub, device=self.device)
             else:
@@ -656,7 +685,7 @@ class RetrievalService(SparseIndexViews):
         return self._be.collapse_results(results, by, top_k, per_group, nulls, "collapse")
 
     # -- late interaction (no reference counterpart) -----------------------------------------------------------
-    def set_token_embeddings(self, token_embeddings, storage: str = "f16") -> None:
+    def set_token_embeddings(self, token_embeddings, storage: str = "f16", ann=None) -> None:
         """Put the TOKEN vectors of the docs on the GPU for :meth:`rerank_late` (:class:`~.late.TokenIndex`; rounded to
         ``storage`` "f16" or "bf16").  ``token_embeddings``: ``{doc_id: f32[t_d, dim]}`` with every indexed doc present (``t_d``
         may be 0), or ``(matrix f32[n_tok, dim], counts)`` with the docs' tokens in ``doc_ids`` order.  Needs the BM25 index
@@ -664,6 +693,8 @@ class RetrievalService(SparseIndexViews):
         shape mismatch, no token at all or a non-finite value."""
         from .dense import check_half_dtype
         from .late import TokenIndex
+        if ann is not None:
+            raise ValueError(f"ann={ann!r} is not offered for token embeddings (MaxSim reads half-precision rows by doc, not lists of codes)")
         if str(storage).lower() == "pq":
             raise ValueError("storage='pq' is not offered for token embeddings (MaxSim reads half-precision rows): use 'f16' or 'bf16'")
         storage = check_half_dtype(storage)
@@ -752,9 +783,10 @@ class RetrievalService(SparseIndexViews):
             stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None, "binary" or "pq"
             stats["pq_dsub"] = getattr(self, "embedding_pq_dsub", None)             # with storage or screen "pq"
             stats["embedding_oversample"] = getattr(self, "embedding_oversample", None)
-            stats["embedding_ann"] = getattr(self, "embedding_ann", None)            # None or "ivf"
-            stats["nlist"] = getattr(self._dense, "nlist", None)
-            stats["nprobe"] = getattr(self._dense, "default_nprobe", None)
+            stats["embedding_ann"] = getattr(self, "embedding_ann", None)            # None, "ivf" or "ivfpq"
+            lists = getattr(self._dense, "binary", self._dense)                     # an IVF-PQ screen holds the lists of the pair
+            stats["nlist"] = getattr(lists, "nlist", None)
+            stats["nprobe"] = getattr(lists, "default_nprobe", None)
         return stats
 
     def __enter__(self):
