@@ -31,6 +31,8 @@ from . import pq
 from .pq import DensePqIndex
 from . import ivfpq
 from .ivfpq import IvfPqIndex
+from . import graph
+from .graph import GraphHalfIndex
 
 __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", "build_host_index", "encode_queries", "merge_topk_device", "fuse_topk_device", "fuse_scored_device", "validate_candidates", "HybridRetriever",
            "tokenize", "build_library", "SparseRxError", "SparseRxUnavailable", "_capi", "ShardedSearcher", "shard_range",
@@ -41,4 +43,4 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape",
            "late_pool_depth", "FieldTable", "columns_from_metadata", "collapse_deep", "collapse_pool_depth", "ForwardIndex",
            "boost", "BoostFn", "BoostResolver", "boost_deep", "ltr", "ForestModel", "RankFn", "evaluate", "Judgments",
-           "binary", "DenseBinaryIndex", "ScreenedDenseIndex", "mx", "DenseMxIndex", "ivf", "IvfHalfIndex", "pq", "DensePqIndex", "ivfpq", "IvfPqIndex"]
+           "binary", "DenseBinaryIndex", "ScreenedDenseIndex", "mx", "DenseMxIndex", "ivf", "IvfHalfIndex", "pq", "DensePqIndex", "ivfpq", "IvfPqIndex", "graph", "GraphHalfIndex"]

@@ -3,7 +3,7 @@ include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
 include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
 include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h, include/binary/sparse_rx_binary.h, include/mx/sparse_rx_mx.h,
-include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h and include/ivfpq/sparse_rx_ivfpq.h).
+include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h, include/ivfpq/sparse_rx_ivfpq.h and include/graph/sparse_rx_graph.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -23,7 +23,7 @@ CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
            "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
-           "eval.hip", "dense_binary.hip", "dense_mx.hip", "dense_ivf.hip", "dense_pq.hip", "dense_ivfpq.hip"]  # one translation unit each, compiled in parallel
+           "eval.hip", "dense_binary.hip", "dense_mx.hip", "dense_ivf.hip", "dense_pq.hip", "dense_ivfpq.hip", "dense_graph.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -31,10 +31,11 @@ INCLUDE_DIR = os.path.join(_ROOT, "include")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-std=c++17"]
 # flags of single units, behind HIPCC_FLAGS.  dense_mx.hip: its fp32 arithmetic (the quantiser) is compiled to scalar-per-lane VALU
 # instructions only, never to the packed two-float forms; dense_ivf.hip: the same for the centroid sums, whose order is a contract;
-# dense_pq.hip: the same for the distance, table and score chains, each one fp32 operation at a time; dense_ivfpq.hip: its residuals and sums likewise
+# dense_pq.hip: the same for the distance, table and score chains, each one fp32 operation at a time; dense_ivfpq.hip: its residuals and sums likewise;
+# dense_graph.hip: the same for the one fp32 addition of the score offset
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"dense_mx.hip": _NO_PACKED_F32, "dense_ivf.hip": _NO_PACKED_F32, "dense_pq.hip": _NO_PACKED_F32,
-              "dense_ivfpq.hip": _NO_PACKED_F32}
+              "dense_ivfpq.hip": _NO_PACKED_F32, "dense_graph.hip": _NO_PACKED_F32}
 
 SRX_VAL_F32, SRX_VAL_F16 = 0, 1
 SRX_FUSE_WEIGHTED, SRX_FUSE_RRF = 0, 1
@@ -380,6 +381,23 @@ IVFPQ_SYMBOLS = {
 SRX_IVFPQ_PASS, SRX_IVFPQ_TARGET_ITEMS, SRX_IVFPQ_MAX_SLICES, SRX_IVFPQ_SLICE_TILES = 1024, 512, 64, 16  # the plan's constants
 
 
+class GraphDesc(ctypes.Structure):
+    """``srx_graph_desc`` (include/graph/sparse_rx_graph.h): a host struct of device pointers"""
+    _fields_ = [("device", ctypes.c_int32), ("type", ctypes.c_int32), ("n_docs", ctypes.c_int64), ("doc_base", ctypes.c_int64),
+                ("dim_pad", ctypes.c_int32), ("degree", ctypes.c_int32), ("corpus", ctypes.c_void_p), ("graph", ctypes.c_void_p)]
+
+
+# every symbol include/graph/sparse_rx_graph.h declares (the twenty-second header of the same library)
+_GP = ctypes.POINTER(GraphDesc)
+GRAPH_SYMBOLS = {
+    "srx_graph_search": (ctypes.c_int, [_GP, _VP, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _FP, _VP, _VP, _VP, _VP, _VP, ctypes.c_float]),
+    "srx_graph_prune": (ctypes.c_int, [_I32, _VP, _I64, _I32, _I32, _VP, _VP]),
+    "srx_graph_merge": (ctypes.c_int, [_I32, _VP, _I64, _I32, _VP, _VP, _VP, _VP]),
+}
+SRX_GRAPH_DEGREES, SRX_GRAPH_MAX_ITOPK, SRX_GRAPH_MAX_WIDTH, SRX_GRAPH_MAX_ITER = (16, 32, 64), 512, 8, 1024  # the limits of the header
+SRX_GRAPH_MAX_SEED, SRX_GRAPH_MAX_NEW, SRX_GRAPH_BUDGET, SRX_GRAPH_MAX_D0 = 512, 512, 8192, 128
+
+
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
     ``srx_order_workspace_bytes`` by tests/test_order_cpu.py).  A segment is what one workgroup scans for one row."""
@@ -429,7 +447,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "ivf", "sparse_rx_ivf.h"),
                                                             os.path.join(INCLUDE_DIR, "pq", "sparse_rx_pq.h"),
                                                             os.path.join(CSRC_DIR, "ivf_probe.h"),
-                                                            os.path.join(INCLUDE_DIR, "ivfpq", "sparse_rx_ivfpq.h")]
+                                                            os.path.join(INCLUDE_DIR, "ivfpq", "sparse_rx_ivfpq.h"),
+                                                            os.path.join(INCLUDE_DIR, "graph", "sparse_rx_graph.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -480,7 +499,7 @@ def lib() -> ctypes.CDLL:
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
                                    **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS, **MX_SYMBOLS, **IVF_SYMBOLS,
-                                   **PQ_SYMBOLS, **IVFPQ_SYMBOLS}.items():
+                                   **PQ_SYMBOLS, **IVFPQ_SYMBOLS, **GRAPH_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

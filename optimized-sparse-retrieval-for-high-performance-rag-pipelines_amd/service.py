@@ -198,7 +198,7 @@ class RetrievalService(SparseIndexViews):
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
     def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4, ann=None, nlist=None, nprobe=None,
-                       pq_dsub: int = 8) -> None:
+                       pq_dsub: int = 8, graph_degree=None, itopk=None, search_width=None) -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
@@ -240,10 +240,20 @@ class RetrievalService(SparseIndexViews):
         of any doc).  With ``storage`` "f32" / "f16" / "bf16" and ``screen="pq"`` it is the screen of the exact rows: the pool is
         its top ``k * oversample`` of the ``nprobe`` probed lists.  Not offered with MX storage, ``screen="binary"``,
         ``storage="pq"`` together with ``screen=``, ``mmr_lambda`` / :meth:`diversify` with ``storage="pq"``, a sharded index or
-        token embeddings."""
+        token embeddings.
+        "graph" (no reference counterpart): a neighbour graph of ``graph_degree`` (16, 32 or 64; default 32) edges per row over the
+        "f16" / "bf16" rows (``GraphHalfIndex``, include/graph/sparse_rx_graph.h), built at this call; :meth:`search_by_vector` and
+        the dense side of :meth:`search_hybrid` walk it with a beam of ``itopk`` (a multiple of 32 in [32, 512], default 64; raised
+        to the depth a call asks for) and ``search_width`` parents per step (default 4) in one launch, and return the best docs
+        the walk reached with the storage's score bits -- approximate; :meth:`score_by_vector` is unchanged.  The metric is the
+        inner product: normalise the rows for cosine.  Not offered with f32, MX or PQ storage, ``screen=``, ``nlist=`` /
+        ``nprobe=``, ``mmr_lambda`` / :meth:`diversify`, a sharded index or token embeddings."""
         from .dense import DenseF32Index, DenseHalfIndex
         if ann is None and (nlist is not None or nprobe is not None):
             raise ValueError("nlist= / nprobe= need ann='ivf'")
+        graph = ann == "graph"
+        if not graph and not (graph_degree is None and itopk is None and search_width is None):
+            raise ValueError("graph_degree= / itopk= / search_width= need ann='graph'")
         ivfpq = ann == "ivfpq"
         if ivfpq:
             lowered = str(storage).lower()
@@ -257,9 +267,27 @@ class RetrievalService(SparseIndexViews):
                 raise ValueError("ann='ivfpq' needs storage='pq' (the index alone) or screen='pq' (the screen of the exact rows)")
             if self._be.sharded():
                 raise ValueError("ann='ivfpq' is not offered with a sharded index")
+        elif graph:
+            from .graph import check_degree
+            if nlist is not None or nprobe is not None:
+                raise ValueError("nlist= / nprobe= are not offered with ann='graph' (there are no lists)")
+            if str(storage).lower() == "pq" or screen == "pq":
+                raise ValueError("ann='graph' is not offered with storage='pq' or screen='pq' (the walk scores half-precision rows)")
+            if str(storage).lower() not in ("f16", "bf16"):
+                raise ValueError(f"ann='graph' needs storage 'f16' or 'bf16', got {storage!r}")
+            if screen is not None:
+                raise ValueError(f"screen={screen!r} is not offered with ann='graph'")
+            if self._be.sharded():
+                raise ValueError("ann='graph' is not offered with a sharded index")
+            graph_degree = check_degree(32 if graph_degree is None else graph_degree)
+            itopk, search_width = int(64 if itopk is None else itopk), int(4 if search_width is None else search_width)
+            if not (32 <= itopk <= 512 and itopk % 32 == 0):
+                raise ValueError(f"itopk must be a multiple of 32 in [32, 512], got {itopk}")
+            if not (1 <= search_width <= 8 and search_width * graph_degree <= 512):
+                raise ValueError(f"search_width must be in [1, 8] with search_width * graph_degree <= 512, got {search_width}")
         elif ann is not None:
             if ann != "ivf":
-                raise ValueError(f"ann must be None, 'ivf' or 'ivfpq', got {ann!r}")
+                raise ValueError(f"ann must be None, 'ivf', 'ivfpq' or 'graph', got {ann!r}")
             if str(storage).lower() == "pq" or screen == "pq":
                 raise ValueError("ann='ivf' is not offered with storage='pq' or screen='pq' (there are no product-quantised lists)")
             if str(storage).lower() not in ("f16", "bf16"):
@@ -268,7 +296,7 @@ class RetrievalService(SparseIndexViews):
                 raise ValueError(f"screen={screen!r} is not offered with ann='ivf'")
             if self._be.sharded():
                 raise ValueError("ann='ivf' is not offered with a sharded index")
-        if ann is not None and str(storage).lower() in ("f32", "f16", "bf16", "pq"):
+        if ann is not None and not graph and str(storage).lower() in ("f32", "f16", "bf16", "pq"):
             from .ivf import check_nlist, check_nprobe
             nlist = check_nlist(0 if nlist is None else nlist, int(np.shape(embeddings)[0]))
             nprobe = check_nprobe(0 if nprobe is None else nprobe, nlist)
@@ -306,6 +334,10 @@ class RetrievalService(SparseIndexViews):
         elif pq:
             from .pq import DensePqIndex
             self._dense = DensePqIndex(e, dsub=pq_dsub, device=self.device)
+        elif graph:
+            from .graph import GraphHalfIndex
+            self._dense = GraphHalfIndex(e, degree=graph_degree, dtype=storage, device=self.device)
+            self._dense.default_itopk, self._dense.default_width = itopk, search_width
         elif ann is not None and not ivfpq:
             from .ivf import IvfHalfIndex
             self._dense = IvfHalfIndex(e, nlist, dtype=storage, device=self.device)
@@ -783,10 +815,12 @@ class RetrievalService(SparseIndexViews):
             stats["embedding_screen"] = getattr(self, "embedding_screen", None)     # None, "binary" or "pq"
             stats["pq_dsub"] = getattr(self, "embedding_pq_dsub", None)             # with storage or screen "pq"
             stats["embedding_oversample"] = getattr(self, "embedding_oversample", None)
-            stats["embedding_ann"] = getattr(self, "embedding_ann", None)            # None, "ivf" or "ivfpq"
+            stats["embedding_ann"] = getattr(self, "embedding_ann", None)            # None, "ivf", "ivfpq" or "graph"
             lists = getattr(self._dense, "binary", self._dense)                     # an IVF-PQ screen holds the lists of the pair
             stats["nlist"] = getattr(lists, "nlist", None)
             stats["nprobe"] = getattr(lists, "default_nprobe", None)
+            stats["graph_degree"] = getattr(self._dense, "degree", None)             # with ann "graph"
+            stats["itopk"] = getattr(self._dense, "default_itopk", None)
         return stats
 
     def __enter__(self):
