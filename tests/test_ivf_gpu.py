@@ -125,7 +125,7 @@ def test_assign_is_the_argmax_of_the_scorer_bits(case):
 def test_update_in_the_stated_order():
     import sparse_rx.ivf as ivf
     rng = np.random.default_rng(9)
-    lens = [0, 1, 255, 256, 257, 513, 0, 5]
+    lens = [0, 1, 255, 256, 257, 513, 0, 5, 1023, 1024, 1025, 2305]  # up to three rounds of four chunks, the last one ragged
     n, dim = sum(lens) + 17, 200
     rows = (rng.standard_normal((n, dim)) * np.exp2(rng.integers(-8, 9, (n, 1)))).astype(np.float32)
     member = np.concatenate([np.sort(m) for m in np.split(rng.permutation(n)[: sum(lens)], np.cumsum(lens)[:-1])]).astype(np.int32)
