@@ -3,7 +3,8 @@ include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
 include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
 include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h, include/binary/sparse_rx_binary.h, include/mx/sparse_rx_mx.h,
-include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h, include/ivfpq/sparse_rx_ivfpq.h and include/graph/sparse_rx_graph.h).
+include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h, include/ivfpq/sparse_rx_ivfpq.h, include/graph/sparse_rx_graph.h and
+include/fused/sparse_rx_half_fused.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -23,8 +24,9 @@ CSRC_DIR = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "sparse_rx.hip", "dense.hip", "fuse.hip",
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
            "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
-           "eval.hip", "dense_binary.hip", "dense_mx.hip", "dense_ivf.hip", "dense_pq.hip", "dense_ivfpq.hip", "dense_graph.hip"]  # one translation unit each, compiled in parallel
-INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"]}  # a unit that compiles another source file as part of itself
+           "eval.hip", "dense_binary.hip", "dense_mx.hip", "dense_ivf.hip", "dense_pq.hip", "dense_ivfpq.hip", "dense_graph.hip",
+           "dense_half_fused.hip"]  # one translation unit each, compiled in parallel
+INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"], "dense_half_fused.hip": ["dense_half.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
 
@@ -398,6 +400,25 @@ SRX_GRAPH_DEGREES, SRX_GRAPH_MAX_ITOPK, SRX_GRAPH_MAX_WIDTH, SRX_GRAPH_MAX_ITER 
 SRX_GRAPH_MAX_SEED, SRX_GRAPH_MAX_NEW, SRX_GRAPH_BUDGET, SRX_GRAPH_MAX_D0 = 512, 512, 8192, 128
 
 
+# every symbol include/fused/sparse_rx_half_fused.h declares (the twenty-third header of the same library); the argument lists are the half index's
+HALF_FUSED_SYMBOLS = {
+    "srx_dense_half_fused_workspace_bytes": HALF_SYMBOLS["srx_dense_half_workspace_bytes"],
+    "srx_dense_search_half_fused": HALF_SYMBOLS["srx_dense_search_half"],
+}
+SRX_HALF_FUSED_CAP, SRX_HALF_FUSED_MIN_DOCS, SRX_HALF_FUSED_PASS = 65536, 65536, 1024  # pinned to the header by tests/test_half_fused_cpu.py
+
+
+def half_fused_sample(n_docs: int, k: int) -> int:
+    """Docs of the threshold sample of ``srx_dense_search_half_fused`` (0: none): the rule of include/fused/sparse_rx_half_fused.h
+    restated, so a caller can tell which side of it a corpus is on."""
+    n_docs, k = int(n_docs), int(k)
+    if n_docs < SRX_HALF_FUSED_MIN_DOCS:
+        return 0
+    s = max(-(-3 * k * n_docs // SRX_HALF_FUSED_CAP), min(max(164 * k, 4096), 16384))
+    s = -(-s // 128) * 128
+    return s if 4 * s <= n_docs else 0
+
+
 def order_plan(n_docs: int, n_rows: int, k: int):
     """``(segments, workspace bytes)`` of ``srx_order_topk``: the formula of include/order/sparse_rx_order.h restated (pinned to
     ``srx_order_workspace_bytes`` by tests/test_order_cpu.py).  A segment is what one workgroup scans for one row."""
@@ -448,7 +469,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "pq", "sparse_rx_pq.h"),
                                                             os.path.join(CSRC_DIR, "ivf_probe.h"),
                                                             os.path.join(INCLUDE_DIR, "ivfpq", "sparse_rx_ivfpq.h"),
-                                                            os.path.join(INCLUDE_DIR, "graph", "sparse_rx_graph.h")]
+                                                            os.path.join(INCLUDE_DIR, "graph", "sparse_rx_graph.h"),
+                                                            os.path.join(INCLUDE_DIR, "fused", "sparse_rx_half_fused.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -499,7 +521,7 @@ def lib() -> ctypes.CDLL:
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
                                    **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS, **MX_SYMBOLS, **IVF_SYMBOLS,
-                                   **PQ_SYMBOLS, **IVFPQ_SYMBOLS, **GRAPH_SYMBOLS}.items():
+                                   **PQ_SYMBOLS, **IVFPQ_SYMBOLS, **GRAPH_SYMBOLS, **HALF_FUSED_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

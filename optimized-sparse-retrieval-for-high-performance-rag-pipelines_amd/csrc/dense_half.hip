@@ -25,6 +25,174 @@ constexpr int HG_KB = 4;  // k-steps per stage of the GEMM's K loop (dim_pad is 
 static_assert(THREADS == HG_KB * 64, "the GEMM's staging moves piece threadIdx.x of each tile's HG_KB KiB: one piece per thread");
 static_assert(WAVES == 4 && HF_QTILE == 128, "the GEMM lays its four waves out 2 x 2 over 128 queries x 128 docs");
 
+// ================================================================================================ query pack
+// qpack[(tile * ks + s) * 64 + lane] = the rounded columns 16 s + 8 (lane >> 5) .. + 7 of query tile * 32 + (lane & 31);
+// n_tiles tiles are written, queries at or past nq as zeros
+template <int TYPE>
+__global__ __launch_bounds__(THREADS) void srx_dense_half_pack_queries_kernel(const float *__restrict__ queries, int nq, int ks, int n_tiles,
+                                                                              hf_v4i *__restrict__ qpack) {
+    const int64_t n = (int64_t)n_tiles * ks * 64;
+    for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
+        const int lane = (int)(i & 63);
+        const int64_t ts = i >> 6;
+        const int s = (int)(ts % ks);
+        const int64_t q = (ts / ks) * 32 + (lane & 31);
+        hf_v4i p = {0, 0, 0, 0};
+        if (q < nq) {
+            const hf_v4f *src = reinterpret_cast<const hf_v4f *>(queries + q * (int64_t)(ks * 16) + 16 * s + 8 * (lane >> 5));
+            p = hf_round8<TYPE>(src[0], src[1]);
+        }
+        qpack[i] = p;
+    }
+}
+
+// ================================================================================================ GEMM
+// D[row = query][col = doc]: lane l holds doc l & 31, rows (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
+typedef hf_v4i hg_stage_t[2][2][4][HG_KB * 64];  // [buffer][queries / docs][tile of 32][k-step of the stage][lane]: 64 KiB of LDS
+
+// The chain of one workgroup: query tiles qt0 .. qt0 + 3 (all exist in qpack) x doc tiles dt0 .. dt0 + 3 (those at or past
+// n_dtiles read as zeros), the wave's 2 x 2 tiles of 32 x 32 left in acc.  Ends behind a barrier: `stage` is free again.
+template <int TYPE>
+__device__ __forceinline__ void hg_block_chain(const hf_v4i *__restrict__ corpus, int64_t n_dtiles, int ks, const hf_v4i *__restrict__ qpack,
+                                               int64_t qt0, int64_t dt0, hg_stage_t &stage, hf_v16f (&acc)[2][2]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wq = wave >> 1, wd = wave & 1;  // the wave's 64 queries and 64 docs of the block
+    hf_v4i ga[4], gb[4];
+    // thread t moves piece t of each tile's HG_KB KiB of the stage: (tile * ks + s0) * 64 + t, t < HG_KB * 64 = 256
+    auto load_stage = [&](int st) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ga[i] = qpack[((qt0 + i) * ks + st * HG_KB) * 64 + tid];
+            gb[i] = (hf_v4i){0, 0, 0, 0};
+            if (dt0 + i < n_dtiles) gb[i] = corpus[((dt0 + i) * ks + st * HG_KB) * 64 + tid];
+        }
+    };
+    auto store_stage = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            stage[buf][0][i][tid] = ga[i];
+            stage[buf][1][i][tid] = gb[i];
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+    const int n_stages = ks / HG_KB;
+    load_stage(0);
+    store_stage(0);
+    __syncthreads();
+    for (int st = 0; st < n_stages; ++st) {
+        const int buf = st & 1;
+        const bool more = st + 1 < n_stages;  // uniform
+        if (more) load_stage(st + 1);         // in flight over this stage's MFMAs
+#pragma unroll
+        for (int kk = 0; kk < HG_KB; ++kk) {  // ascending k: one chain per output element
+            hf_v4i A[2], B[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                A[i] = stage[buf][0][2 * wq + i][kk * 64 + lane];
+                B[i] = stage[buf][1][2 * wd + i][kk * 64 + lane];
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = hf_mfma<TYPE>(A[i], B[j], acc[i][j]);
+        }
+        if (more) store_stage(buf ^ 1);  // that buffer was last read in stage st - 1: one barrier ago
+        __syncthreads();
+    }
+}
+
+// Workgroup b serves query block b % n_qblocks and doc block b / n_qblocks: the workgroups that read one block of docs run
+// together.  The scores go to a [queries][ld] fp32 matrix.
+template <int TYPE>
+__global__ __launch_bounds__(THREADS) void srx_dense_half_scores_kernel(const hf_v4i *__restrict__ corpus, int64_t n_docs, int ks,
+                                                                        const hf_v4i *__restrict__ qpack, int nq, int n_qblocks,
+                                                                        float *__restrict__ scores, int64_t ld) {
+    __shared__ hg_stage_t stage;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int qblock = (int)(blockIdx.x % (unsigned)n_qblocks);
+    const int64_t dblock = blockIdx.x / (unsigned)n_qblocks;
+    const int64_t qt0 = (int64_t)qblock * 4, dt0 = dblock * 4;  // first tiles of 32
+    hf_v16f acc[2][2];
+    hg_block_chain<TYPE>(corpus, (n_docs + 31) / 32, ks, qpack, qt0, dt0, stage, acc);  // nothing is read past the corpus's tiles
+    const int64_t q0 = (qt0 + 2 * (wave >> 1)) * 32, d0 = (dt0 + 2 * (wave & 1)) * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int64_t d = d0 + 32 * j + r;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int64_t q = q0 + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                if (q < nq && d < n_docs) scores[q * ld + d] = acc[i][j][reg];
+            }
+        }
+}
+
+// ================================================================================================ rank
+// One workgroup per (query, split of the columns) folds its slice of the score row into an exact lazy top-k list: the ranked
+// value of column c is fl32(score + offset), a result iff > 0 and (with a filter row) bit c of the row is set.
+__global__ __launch_bounds__(THREADS) void srx_dense_half_topk_kernel(const float *__restrict__ scores, int64_t ld, int64_t n_docs, int nq,
+                                                                      int k, int n_splits, int64_t doc_base, float score_offset,
+                                                                      const uint32_t *__restrict__ filter_bits, int64_t filter_words,
+                                                                      const int32_t *__restrict__ q_filter, int q0,
+                                                                      int32_t *__restrict__ cand_doc, float *__restrict__ cand_score,
+                                                                      int32_t *__restrict__ cand_count) {
+    __shared__ MergeShared M;
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x / n_splits, split = blockIdx.x - q * n_splits;
+    if (q >= nq) return;
+    const int64_t lo = n_docs * split / n_splits, hi = n_docs * (split + 1) / n_splits;
+    const uint32_t *frow = nullptr;  // null: this query is not filtered
+    if (filter_bits != nullptr) {
+        const int fr = q_filter != nullptr ? q_filter[q0 + q] : 0;
+        if (fr >= 0) frow = filter_bits + (int64_t)fr * filter_words;
+    }
+    if (tid == 0) {
+        M.tk.count = 0;
+        M.tk.tau = 0;
+    }
+    __syncthreads();
+    const float *row = scores + (int64_t)q * ld;
+    for (int64_t c0 = lo; c0 < hi; c0 += (int64_t)THREADS * HF_NPT) {
+        unsigned ubits[HF_NPT];
+        int udoc[HF_NPT];
+        const unsigned tau = M.tk.tau;
+#pragma unroll
+        for (int n = 0; n < HF_NPT; ++n) {
+            const int64_t c = c0 + (int64_t)n * THREADS + tid;
+            float x = 0.0f;
+            bool allowed = false;
+            if (c < hi) {  // c < n_docs: the filter row has a word for it
+                x = row[c] + score_offset;  // + 0.0f by default (exact)
+                allowed = frow == nullptr || ((frow[c >> 5] >> (c & 31)) & 1u) != 0u;
+            }
+            const unsigned b = __float_as_uint(x);
+            ubits[n] = (allowed && x > 0.0f && b >= tau) ? b : 0u;
+            udoc[n] = (int)(doc_base + c);
+        }
+        topk_fold<HF_NPT, true>(ubits, udoc, k, M.tk, M.hist);
+    }
+    __syncthreads();
+    topk_shrink(k, M.tk, M.hist);
+    const unsigned cnt = M.tk.count;
+    const int64_t o = (int64_t)blockIdx.x * k;
+    for (unsigned i = tid; i < cnt; i += THREADS) {
+        cand_doc[o + i] = M.tk.doc[i];
+        cand_score[o + i] = __uint_as_float(M.tk.bits[i]);
+    }
+    if (tid == 0) cand_count[blockIdx.x] = (int)cnt;
+}
+
+}  // namespace
+
+#ifndef SRX_HALF_SHARED_KERNELS_ONLY  // dense_half_fused.hip compiles the kernels above a second time and nothing below
+namespace {
+
 // ================================================================================================ convert
 constexpr int HC_TILE = 32;               // rows per workgroup
 constexpr int HC_ROWS = HC_TILE / WAVES;  // rows per wave
@@ -105,158 +273,6 @@ void hc_launch(const HalfConvertArgs &a, bool vec, hipStream_t stream) {
     }
     SRX_HC(1) SRX_HC(2) SRX_HC(3) SRX_HC(4)
 #undef SRX_HC
-}
-
-// ================================================================================================ query pack
-// qpack[(tile * ks + s) * 64 + lane] = the rounded columns 16 s + 8 (lane >> 5) .. + 7 of query tile * 32 + (lane & 31);
-// n_tiles tiles are written, queries at or past nq as zeros
-template <int TYPE>
-__global__ __launch_bounds__(THREADS) void srx_dense_half_pack_queries_kernel(const float *__restrict__ queries, int nq, int ks, int n_tiles,
-                                                                              hf_v4i *__restrict__ qpack) {
-    const int64_t n = (int64_t)n_tiles * ks * 64;
-    for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
-        const int lane = (int)(i & 63);
-        const int64_t ts = i >> 6;
-        const int s = (int)(ts % ks);
-        const int64_t q = (ts / ks) * 32 + (lane & 31);
-        hf_v4i p = {0, 0, 0, 0};
-        if (q < nq) {
-            const hf_v4f *src = reinterpret_cast<const hf_v4f *>(queries + q * (int64_t)(ks * 16) + 16 * s + 8 * (lane >> 5));
-            p = hf_round8<TYPE>(src[0], src[1]);
-        }
-        qpack[i] = p;
-    }
-}
-
-// ================================================================================================ GEMM
-// D[row = query][col = doc]: lane l holds doc l & 31, rows (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  Workgroup b serves query
-// block b % n_qblocks and doc block b / n_qblocks: the workgroups that read one block of docs run together.
-template <int TYPE>
-__global__ __launch_bounds__(THREADS) void srx_dense_half_scores_kernel(const hf_v4i *__restrict__ corpus, int64_t n_docs, int ks,
-                                                                        const hf_v4i *__restrict__ qpack, int nq, int n_qblocks,
-                                                                        float *__restrict__ scores, int64_t ld) {
-    __shared__ hf_v4i stage[2][2][4][HG_KB * 64];  // [buffer][queries / docs][tile of 32][k-step of the stage][lane]: 64 KiB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int qblock = (int)(blockIdx.x % (unsigned)n_qblocks);
-    const int64_t dblock = blockIdx.x / (unsigned)n_qblocks;
-    const int64_t qt0 = (int64_t)qblock * 4, dt0 = dblock * 4;  // first tiles of 32; the query tiles all exist in qpack
-    const int64_t n_dtiles = (n_docs + 31) / 32;                // tiles the corpus holds: nothing is read past them
-    const int wq = wave >> 1, wd = wave & 1;                    // the wave's 64 queries and 64 docs of the block
-    hf_v4i ga[4], gb[4];
-    // thread t moves piece t of each tile's HG_KB KiB of the stage: (tile * ks + s0) * 64 + t, t < HG_KB * 64 = 256
-    auto load_stage = [&](int st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ga[i] = qpack[((qt0 + i) * ks + st * HG_KB) * 64 + tid];
-            gb[i] = (hf_v4i){0, 0, 0, 0};
-            if (dt0 + i < n_dtiles) gb[i] = corpus[((dt0 + i) * ks + st * HG_KB) * 64 + tid];
-        }
-    };
-    auto store_stage = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            stage[buf][0][i][tid] = ga[i];
-            stage[buf][1][i][tid] = gb[i];
-        }
-    };
-    hf_v16f acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    const int n_stages = ks / HG_KB;
-    load_stage(0);
-    store_stage(0);
-    __syncthreads();
-    for (int st = 0; st < n_stages; ++st) {
-        const int buf = st & 1;
-        const bool more = st + 1 < n_stages;  // uniform
-        if (more) load_stage(st + 1);         // in flight over this stage's MFMAs
-#pragma unroll
-        for (int kk = 0; kk < HG_KB; ++kk) {  // ascending k: one chain per output element
-            hf_v4i A[2], B[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                A[i] = stage[buf][0][2 * wq + i][kk * 64 + lane];
-                B[i] = stage[buf][1][2 * wd + i][kk * 64 + lane];
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = hf_mfma<TYPE>(A[i], B[j], acc[i][j]);
-        }
-        if (more) store_stage(buf ^ 1);  // that buffer was last read in stage st - 1: one barrier ago
-        __syncthreads();
-    }
-    const int64_t q0 = (qt0 + 2 * wq) * 32, d0 = (dt0 + 2 * wd) * 32;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int64_t d = d0 + 32 * j + r;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int64_t q = q0 + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (q < nq && d < n_docs) scores[q * ld + d] = acc[i][j][reg];
-            }
-        }
-}
-
-// ================================================================================================ rank
-// One workgroup per (query, split of the columns) folds its slice of the score row into an exact lazy top-k list: the ranked
-// value of column c is fl32(score + offset), a result iff > 0 and (with a filter row) bit c of the row is set.
-__global__ __launch_bounds__(THREADS) void srx_dense_half_topk_kernel(const float *__restrict__ scores, int64_t ld, int64_t n_docs, int nq,
-                                                                      int k, int n_splits, int64_t doc_base, float score_offset,
-                                                                      const uint32_t *__restrict__ filter_bits, int64_t filter_words,
-                                                                      const int32_t *__restrict__ q_filter, int q0,
-                                                                      int32_t *__restrict__ cand_doc, float *__restrict__ cand_score,
-                                                                      int32_t *__restrict__ cand_count) {
-    __shared__ MergeShared M;
-    const int tid = threadIdx.x;
-    const int q = blockIdx.x / n_splits, split = blockIdx.x - q * n_splits;
-    if (q >= nq) return;
-    const int64_t lo = n_docs * split / n_splits, hi = n_docs * (split + 1) / n_splits;
-    const uint32_t *frow = nullptr;  // null: this query is not filtered
-    if (filter_bits != nullptr) {
-        const int fr = q_filter != nullptr ? q_filter[q0 + q] : 0;
-        if (fr >= 0) frow = filter_bits + (int64_t)fr * filter_words;
-    }
-    if (tid == 0) {
-        M.tk.count = 0;
-        M.tk.tau = 0;
-    }
-    __syncthreads();
-    const float *row = scores + (int64_t)q * ld;
-    for (int64_t c0 = lo; c0 < hi; c0 += (int64_t)THREADS * HF_NPT) {
-        unsigned ubits[HF_NPT];
-        int udoc[HF_NPT];
-        const unsigned tau = M.tk.tau;
-#pragma unroll
-        for (int n = 0; n < HF_NPT; ++n) {
-            const int64_t c = c0 + (int64_t)n * THREADS + tid;
-            float x = 0.0f;
-            bool allowed = false;
-            if (c < hi) {  // c < n_docs: the filter row has a word for it
-                x = row[c] + score_offset;  // + 0.0f by default (exact)
-                allowed = frow == nullptr || ((frow[c >> 5] >> (c & 31)) & 1u) != 0u;
-            }
-            const unsigned b = __float_as_uint(x);
-            ubits[n] = (allowed && x > 0.0f && b >= tau) ? b : 0u;
-            udoc[n] = (int)(doc_base + c);
-        }
-        topk_fold<HF_NPT, true>(ubits, udoc, k, M.tk, M.hist);
-    }
-    __syncthreads();
-    topk_shrink(k, M.tk, M.hist);
-    const unsigned cnt = M.tk.count;
-    const int64_t o = (int64_t)blockIdx.x * k;
-    for (unsigned i = tid; i < cnt; i += THREADS) {
-        cand_doc[o + i] = M.tk.doc[i];
-        cand_score[o + i] = __uint_as_float(M.tk.bits[i]);
-    }
-    if (tid == 0) cand_count[blockIdx.x] = (int)cnt;
 }
 
 // ================================================================================================ scorer of given docs
@@ -421,3 +437,4 @@ SRX_API int srx_dense_score_docs_half(int32_t device, int32_t type, const void *
     HIP_TRY(hipGetLastError());
     return SRX_OK;
 }
+#endif  // SRX_HALF_SHARED_KERNELS_ONLY

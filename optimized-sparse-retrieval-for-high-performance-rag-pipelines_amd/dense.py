@@ -242,11 +242,14 @@ class _DenseIndex:
         """Row length rounded up to the 64 columns the f32 / uint8 kernels step by."""
         return _pad64(self.dim, engine)
 
-    def _search_device(self, queries, dtype, k: int, *extra, filter=None, q_filter=None):
+    def _search_device(self, queries, dtype, k: int, *extra, filter=None, q_filter=None, workspace_fn=None, entry=None):
         """k check, the query block zero-padded to ``dim_pad``, the output triple and the workspace, then the class's
         ``_launch(L, q, nq, k, out, ws, stream, *extra)`` -> the entry point's return code.  An empty batch launches nothing.
         With a ``filter`` (a :class:`~.filter.DocFilter` over this index's rows; ``q_filter`` int32 device tensor [nq] or None)
-        the class's ``_launch_filtered(L, q, nq, k, out, ws, stream, fdesc, *extra)`` (include/sparse_rx_filter.h)."""
+        the class's ``_launch_filtered(L, q, nq, k, out, ws, stream, fdesc, *extra)`` (include/sparse_rx_filter.h).
+        ``workspace_fn`` / ``entry``: the workspace call of a second route of the class and the name its failures are reported
+        under (defaults: ``_workspace_fn``, ``_entry`` / ``_filtered_entry``)."""
+        workspace_fn = workspace_fn or self._workspace_fn
         torch = _torch()
         _check_k(k)
         nq = int(queries.shape[0])
@@ -256,13 +259,13 @@ class _DenseIndex:
             out = _empty_topk(torch, nq, k, self.device)
             if nq == 0:
                 return out
-            ws = _grow_ws(torch, self, _capi.check(getattr(L, self._workspace_fn)(nq, self.n_docs, k), self._workspace_fn))
+            ws = _grow_ws(torch, self, _capi.check(getattr(L, workspace_fn)(nq, self.n_docs, k), workspace_fn))
             fdesc, keep = resolve_filter(self, filter, q_filter, nq)  # keep: alive until the call has been issued
             if fdesc is None:
-                _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), self._entry)
+                _capi.check(self._launch(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), *extra), entry or self._entry)
             else:
                 _capi.check(self._launch_filtered(L, q, nq, k, out, ws, _stream_ptr(torch, self.device), fdesc, *extra),
-                            self._filtered_entry or self._entry + "_filtered")
+                            entry or self._filtered_entry or self._entry + "_filtered")
         return out
 
     def _launch_filtered(self, *args):
@@ -758,6 +761,7 @@ class DenseHalfIndex(_DenseIndex, _MmrSelect):
     _workspace_fn, _entry, _score_entry = "srx_dense_half_workspace_bytes", "srx_dense_search_half", "srx_dense_score_docs_half"
     _filtered_entry = "srx_dense_search_half"  # one entry point, the filter optional
     _mmr_entry = "srx_mmr_select_half"
+    fused = False  # what ``fused=False`` of a search means: True puts every search of this index on srx_dense_search_half_fused
 
     def _launch_mmr(self, L, *tail):
         return L.srx_mmr_select_half(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(self.corpus), self.n_docs, self.dim_pad, self.doc_base, *tail)
@@ -817,24 +821,31 @@ class DenseHalfIndex(_DenseIndex, _MmrSelect):
             self._max_norm = best ** 0.5
         return self._max_norm
 
-    def search_device(self, queries_f32, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+    def search_device(self, queries_f32, k: int, score_offset: float = 0.0, filter=None, q_filter=None, fused: bool = False):
         """f32[nq, dim] queries on the device (rounded to the index's type by the search) -> (doc i32[nq,k], score f32[nq,k],
         count i32[nq]); asynchronous.  Top-k of (score + score_offset) > 0, the returned scores carry the offset; ``filter`` /
-        ``q_filter`` as ``DeviceIndex.search_device``."""
+        ``q_filter`` as ``DeviceIndex.search_device``.  ``fused=True`` (or the index's ``fused`` attribute): the same words from
+        ``srx_dense_search_half_fused`` (include/fused/sparse_rx_half_fused.h), which screens the top k inside the GEMM and keeps
+        no nq x n_docs score matrix; its workspace is ``srx_dense_half_fused_workspace_bytes``."""
+        if fused or self.fused:
+            return self._search_device(queries_f32, _torch().float32, k, score_offset, True, filter=filter, q_filter=q_filter,
+                                       workspace_fn="srx_dense_half_fused_workspace_bytes", entry="srx_dense_search_half_fused")
         return self._search_device(queries_f32, _torch().float32, k, score_offset, filter=filter, q_filter=q_filter)
 
-    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc, score_offset):
-        return L.srx_dense_search_half(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(self.corpus), self.n_docs, self.dim_pad, _ptr(q), nq, k,
-                                       self.doc_base, fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream,
-                                       float(score_offset))
+    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc, score_offset, fused=False):
+        entry = L.srx_dense_search_half_fused if fused else L.srx_dense_search_half
+        return entry(self.device.index or 0, HALF_TYPES[self.dtype], _ptr(self.corpus), self.n_docs, self.dim_pad, _ptr(q), nq, k,
+                     self.doc_base, fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream, float(score_offset))
 
-    def _launch(self, L, q, nq, k, out, ws, stream, score_offset):
-        return self._launch_filtered(L, q, nq, k, out, ws, stream, None, score_offset)
+    def _launch(self, L, q, nq, k, out, ws, stream, score_offset, fused=False):
+        return self._launch_filtered(L, q, nq, k, out, ws, stream, None, score_offset, fused)
 
-    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
-        """Host arrays in, host arrays out; ``q_filter``: a host sequence of row numbers, validated here."""
+    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None, fused: bool = False):
+        """Host arrays in, host arrays out; ``q_filter``: a host sequence of row numbers, validated here; ``fused`` as
+        :meth:`search_device`."""
         q = self._queries_to_device(queries)
-        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0]))))
+        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0])),
+                                             fused=fused))
 
     def _queries_to_device(self, queries):
         q = np.ascontiguousarray(queries, dtype=np.float32)

@@ -198,7 +198,7 @@ class RetrievalService(SparseIndexViews):
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
     def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4, ann=None, nlist=None, nprobe=None,
-                       pq_dsub: int = 8, graph_degree=None, itopk=None, search_width=None) -> None:
+                       pq_dsub: int = 8, graph_degree=None, itopk=None, search_width=None, fused: bool = False) -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
@@ -247,8 +247,19 @@ class RetrievalService(SparseIndexViews):
         to the depth a call asks for) and ``search_width`` parents per step (default 4) in one launch, and return the best docs
         the walk reached with the storage's score bits -- approximate; :meth:`score_by_vector` is unchanged.  The metric is the
         inner product: normalise the rows for cosine.  Not offered with f32, MX or PQ storage, ``screen=``, ``nlist=`` /
-        ``nprobe=``, ``mmr_lambda`` / :meth:`diversify`, a sharded index or token embeddings."""
+        ``nprobe=``, ``mmr_lambda`` / :meth:`diversify`, a sharded index or token embeddings.
+
+        ``fused``: False (default: nothing changes) or True ("f16" / "bf16" storage; no reference counterpart): :meth:`search_by_vector`
+        and the dense side of :meth:`search_hybrid` call ``srx_dense_search_half_fused`` (include/fused/sparse_rx_half_fused.h), which
+        returns the words of ``srx_dense_search_half`` without its nq x n_docs score matrix; filter / term / ``where`` keywords and
+        ``rescore=True`` ride along unchanged.  Not offered with f32, MX or PQ storage, ``ann=`` or ``screen=``: each raises
+        ``ValueError``."""
         from .dense import DenseF32Index, DenseHalfIndex
+        if fused:
+            if str(storage).lower() not in ("f16", "bf16"):
+                raise ValueError(f"fused=True needs storage 'f16' or 'bf16', got {storage!r}")
+            if ann is not None or screen is not None:
+                raise ValueError(f"fused=True is not offered with ann={ann!r} / screen={screen!r} (it is the exact search of the half rows)")
         if ann is None and (nlist is not None or nprobe is not None):
             raise ValueError("nlist= / nprobe= need ann='ivf'")
         graph = ann == "graph"
@@ -344,7 +355,9 @@ class RetrievalService(SparseIndexViews):
             self._dense.default_nprobe = nprobe
         else:
             self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
-        self.embedding_storage = storage
+        if fused:
+            self._dense.fused = True
+        self.embedding_storage, self.embedding_fused = storage, bool(fused)
         self.embedding_screen, self.embedding_oversample = screen, (oversample if screen is not None else None)
         self.embedding_ann = ann
         self.embedding_pq_dsub = int(pq_dsub) if pq or screen == "pq" else None
