@@ -3,8 +3,8 @@ include/sparse_rx_quant.h, include/sparse_rx_filter.h, include/sparse_rx_half.h,
 include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.h, include/sparse_rx_collapse.h,
 include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
 include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h, include/binary/sparse_rx_binary.h, include/mx/sparse_rx_mx.h,
-include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h, include/ivfpq/sparse_rx_ivfpq.h, include/graph/sparse_rx_graph.h and
-include/fused/sparse_rx_half_fused.h).
+include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h, include/ivfpq/sparse_rx_ivfpq.h, include/graph/sparse_rx_graph.h,
+include/fused/sparse_rx_half_fused.h and include/batched/sparse_rx_f32_batched.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -25,7 +25,7 @@ SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "spa
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
            "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
            "eval.hip", "dense_binary.hip", "dense_mx.hip", "dense_ivf.hip", "dense_pq.hip", "dense_ivfpq.hip", "dense_graph.hip",
-           "dense_half_fused.hip"]  # one translation unit each, compiled in parallel
+           "dense_half_fused.hip", "dense_f32_batched.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"], "dense_half_fused.hip": ["dense_half.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -408,6 +408,37 @@ HALF_FUSED_SYMBOLS = {
 SRX_HALF_FUSED_CAP, SRX_HALF_FUSED_MIN_DOCS, SRX_HALF_FUSED_PASS = 65536, 65536, 1024  # pinned to the header by tests/test_half_fused_cpu.py
 
 
+# every symbol include/batched/sparse_rx_f32_batched.h declares (the twenty-fourth header of the same library); the search takes the
+# argument list of srx_dense_search_f32_filtered.  The unit is compiled with HIPCC_FLAGS alone, as dense.hip and dense_score.hip are:
+# -ffp-contract=off keeps its rescoring chain the bits of theirs
+F32_BATCHED_SYMBOLS = {
+    "srx_dense_f32_batched_workspace_bytes": SYMBOLS["srx_dense_f32_workspace_bytes"],
+    "srx_dense_search_f32_batched": FILTER_SYMBOLS["srx_dense_search_f32_filtered"],
+}
+SRX_F32_BATCHED_CAP, SRX_F32_BATCHED_MIN_DOCS, SRX_F32_BATCHED_PASS = 65536, 65536, 1024  # pinned to the header by tests/test_f32_batched_cpu.py
+SRX_F32_BATCHED_TARGET, SRX_F32_BATCHED_MAX_SAMPLE = 8192, 262144
+
+
+def f32_batched_sample(n_docs: int, k: int) -> int:
+    """Docs of the threshold sample of ``srx_dense_search_f32_batched`` (0: none): the rule of include/batched/sparse_rx_f32_batched.h
+    restated."""
+    n_docs, k = int(n_docs), int(k)
+    if n_docs < SRX_F32_BATCHED_MIN_DOCS:
+        return 0
+    s = min(max(-(-k * n_docs // SRX_F32_BATCHED_TARGET), min(max(164 * k, 4096), 16384)), SRX_F32_BATCHED_MAX_SAMPLE)
+    s = -(-s // 128) * 128
+    return s if 4 * s <= n_docs else 0
+
+
+def f32_batched_workspace(nq: int, n_docs: int, k: int) -> int:
+    """``srx_dense_f32_batched_workspace_bytes`` restated from the header's formula."""
+    r = lambda b: -(-b // 256) * 256
+    qb, S = min(int(nq), SRX_F32_BATCHED_PASS), f32_batched_sample(n_docs, k)
+    lists = qb * max(1, min(-(-int(n_docs) // 256) // 16, 4096 // int(k), 64))
+    return (256 + r(qb * 8) + r(qb * 4) + r(qb * S * 4) + 2 * r(lists * k * 4) + r(lists * 4) + r((qb * 33 + 1) * 4)
+            + 2 * r(qb * SRX_F32_BATCHED_CAP * 4) + 256)
+
+
 def half_fused_sample(n_docs: int, k: int) -> int:
     """Docs of the threshold sample of ``srx_dense_search_half_fused`` (0: none): the rule of include/fused/sparse_rx_half_fused.h
     restated, so a caller can tell which side of it a corpus is on."""
@@ -470,7 +501,8 @@ def _deps():
                                                             os.path.join(CSRC_DIR, "ivf_probe.h"),
                                                             os.path.join(INCLUDE_DIR, "ivfpq", "sparse_rx_ivfpq.h"),
                                                             os.path.join(INCLUDE_DIR, "graph", "sparse_rx_graph.h"),
-                                                            os.path.join(INCLUDE_DIR, "fused", "sparse_rx_half_fused.h")]
+                                                            os.path.join(INCLUDE_DIR, "fused", "sparse_rx_half_fused.h"),
+                                                            os.path.join(INCLUDE_DIR, "batched", "sparse_rx_f32_batched.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -521,7 +553,7 @@ def lib() -> ctypes.CDLL:
     for name, (res, args) in {**SYMBOLS, **RESCORE_SYMBOLS, **QUANT_SYMBOLS, **FILTER_SYMBOLS, **HALF_SYMBOLS, **MMR_SYMBOLS,
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
                                    **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS, **MX_SYMBOLS, **IVF_SYMBOLS,
-                                   **PQ_SYMBOLS, **IVFPQ_SYMBOLS, **GRAPH_SYMBOLS, **HALF_FUSED_SYMBOLS}.items():
+                                   **PQ_SYMBOLS, **IVFPQ_SYMBOLS, **GRAPH_SYMBOLS, **HALF_FUSED_SYMBOLS, **F32_BATCHED_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -664,6 +664,7 @@ class DenseF32Index(_DenseIndex, _MmrSelect):
     batch of query vectors (``srx_dense_search_f32``)."""
 
     _entry, _score_entry, _mmr_entry = "srx_dense_search_f32", "srx_dense_score_docs_f32", "srx_mmr_select_f32"
+    batched = False  # what ``batched=False`` of a search means: True puts every search of this index on srx_dense_search_f32_batched
 
     def _launch_mmr(self, L, *tail):
         return L.srx_mmr_select_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, self.doc_base, *tail)
@@ -703,23 +704,32 @@ class DenseF32Index(_DenseIndex, _MmrSelect):
             self._max_norm = best ** 0.5
         return self._max_norm
 
-    def search_device(self, queries, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+    def search_device(self, queries, k: int, score_offset: float = 0.0, filter=None, q_filter=None, batched: bool = False):
         """Top-k of (score + score_offset) > 0 per query (include/sparse_rx.h); the returned scores carry the offset.
-        ``filter`` / ``q_filter`` as ``DeviceIndex.search_device`` (``srx_dense_search_f32_filtered``)."""
+        ``filter`` / ``q_filter`` as ``DeviceIndex.search_device`` (``srx_dense_search_f32_filtered``).  ``batched=True`` (or the
+        index's ``batched`` attribute): the same words from ``srx_dense_search_f32_batched`` (include/batched/sparse_rx_f32_batched.h),
+        which screens a whole query batch by an fp32 MFMA GEMM and scores only the surviving pairs with the exact arithmetic; its
+        workspace is ``srx_dense_f32_batched_workspace_bytes``."""
+        if batched or self.batched:
+            return self._search_device(queries, _torch().float32, k, score_offset, True, filter=filter, q_filter=q_filter,
+                                       workspace_fn="srx_dense_f32_batched_workspace_bytes", entry="srx_dense_search_f32_batched")
         return self._search_device(queries, _torch().float32, k, score_offset, filter=filter, q_filter=q_filter)
 
-    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc, score_offset):
-        return L.srx_dense_search_f32_filtered(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k,
-                                               self.doc_base, fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream,
-                                               float(score_offset))
+    def _launch_filtered(self, L, q, nq, k, out, ws, stream, fdesc, score_offset, batched=False):
+        entry = L.srx_dense_search_f32_batched if batched else L.srx_dense_search_f32_filtered
+        return entry(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k, self.doc_base, fdesc,
+                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream, float(score_offset))
 
-    def _launch(self, L, q, nq, k, out, ws, stream, score_offset):
+    def _launch(self, L, q, nq, k, out, ws, stream, score_offset, batched=False):
+        if batched:
+            return self._launch_filtered(L, q, nq, k, out, ws, stream, None, score_offset, True)
         return L.srx_dense_search_f32(self.device.index or 0, _ptr(self.emb), self.n_docs, self.dim_pad, _ptr(q), nq, k, self.doc_base,
                                       _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), stream, float(score_offset))
 
-    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None):
+    def search(self, queries: np.ndarray, k: int, score_offset: float = 0.0, filter=None, q_filter=None, batched: bool = False):
         q = self._queries_to_device(queries)
-        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0]))))
+        return self._host(self.search_device(q, k, score_offset, filter=filter, q_filter=host_q_filter(self, filter, q_filter, int(q.shape[0])),
+                                             batched=batched))
 
     def _queries_to_device(self, queries):
         q = np.ascontiguousarray(queries, dtype=np.float32)

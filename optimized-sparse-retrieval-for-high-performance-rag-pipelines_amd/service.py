@@ -198,7 +198,7 @@ class RetrievalService(SparseIndexViews):
     # -- misc -------------------------------------------------------------------------------------------
     # -- dense side (retrieval.py:320-339, 402-436) ----------------------------------------------------------
     def set_embeddings(self, embeddings, storage: str = "f32", screen=None, oversample: int = 4, ann=None, nlist=None, nprobe=None,
-                       pq_dsub: int = 8, graph_degree=None, itopk=None, search_width=None, fused: bool = False) -> None:
+                       pq_dsub: int = 8, graph_degree=None, itopk=None, search_width=None, fused: bool = False, batched: bool = False) -> None:
         """Make a [n_docs, dim] float32 matrix (row i = doc_ids[i]) the ``embedding_index`` and put it on the GPU.  The
         reference memory-maps ``embedding_path`` with the row count of its document store (``_load_embeddings``,
         retrieval.py:320-339); the store is out of scope here, so the rows come from the caller or, in
@@ -253,8 +253,19 @@ class RetrievalService(SparseIndexViews):
         and the dense side of :meth:`search_hybrid` call ``srx_dense_search_half_fused`` (include/fused/sparse_rx_half_fused.h), which
         returns the words of ``srx_dense_search_half`` without its nq x n_docs score matrix; filter / term / ``where`` keywords and
         ``rescore=True`` ride along unchanged.  Not offered with f32, MX or PQ storage, ``ann=`` or ``screen=``: each raises
-        ``ValueError``."""
+        ``ValueError``.
+
+        ``batched``: False (default: nothing changes) or True ("f32" storage; no reference counterpart): :meth:`search_by_vector` and
+        the dense side of :meth:`search_hybrid` call ``srx_dense_search_f32_batched`` (include/batched/sparse_rx_f32_batched.h), which
+        returns the words of ``srx_dense_search_f32`` / ``_filtered`` from an fp32 MFMA screen of the whole batch and exact rescoring
+        of the survivors; filter / term / ``where`` keywords, ``rescore=True`` and ``mmr_lambda`` ride along unchanged.  Not offered with
+        any other storage, ``ann=`` or ``screen=``: each raises ``ValueError``."""
         from .dense import DenseF32Index, DenseHalfIndex
+        if batched:
+            if str(storage).lower() != "f32":
+                raise ValueError(f"batched=True needs storage 'f32', got {storage!r}")
+            if ann is not None or screen is not None:
+                raise ValueError(f"batched=True is not offered with ann={ann!r} / screen={screen!r} (it is the exact search of the f32 rows)")
         if fused:
             if str(storage).lower() not in ("f16", "bf16"):
                 raise ValueError(f"fused=True needs storage 'f16' or 'bf16', got {storage!r}")
@@ -357,7 +368,9 @@ class RetrievalService(SparseIndexViews):
             self._dense = DenseF32Index(e, device=self.device) if storage == "f32" else DenseHalfIndex(e, dtype=storage, device=self.device)
         if fused:
             self._dense.fused = True
-        self.embedding_storage, self.embedding_fused = storage, bool(fused)
+        if batched:
+            self._dense.batched = True
+        self.embedding_storage, self.embedding_fused, self.embedding_batched = storage, bool(fused), bool(batched)
         self.embedding_screen, self.embedding_oversample = screen, (oversample if screen is not None else None)
         self.embedding_ann = ann
         self.embedding_pq_dsub = int(pq_dsub) if pq or screen == "pq" else None
