@@ -53,6 +53,15 @@ def search_plan(nq: int, n_docs: int, m: int):
     return QB, ns, r256(2 * qb * ld) + 2 * r256(4 * qb * ns * m) + r256(4 * qb * ns) + r256(4 * qb * m) + 256
 
 
+def asym_search_plan(nq: int, n_docs: int, m: int, dim_pad: int):
+    """``(queries per pass, row splits, workspace bytes)`` of ``srx_binary_asym_search``: the pass plan of :func:`search_plan` plus
+    the pass's prepared queries and their code sums (the formula of include/asym/sparse_rx_binary_asym.h restated)."""
+    QB, ns, nbytes = search_plan(nq, n_docs, m)
+    q32 = -(-min(int(nq), QB) // 32) * 32
+    r256 = lambda x: -(-x // 256) * 256
+    return QB, ns, nbytes + r256(q32 * int(dim_pad)) + r256(4 * q32)
+
+
 def tiled_word_index(row, word, words: int):
     """Index of word ``word`` of row ``row`` in the tiled corpus (u32 units), for rows of ``words`` words."""
     return (((row >> 6) * (words // 4) + (word >> 2)) * 64 + (row & 63)) * 4 + (word & 3)
@@ -276,6 +285,98 @@ class DenseBinaryIndex:
         return _to_host(torch, self.device, (self.hamming_docs_device(q, cd, cc),))[0]
 
 
+    # -- asymmetric scores: 4-bit query codes against the same 1-bit corpus (include/asym/sparse_rx_binary_asym.h) ----------
+    def asym_search_plan(self, nq: int, m: int):
+        """:func:`asym_search_plan` for this index."""
+        return asym_search_plan(nq, self.n_docs, m, self.dim_pad)
+
+    def quantize_queries_device(self, queries_f32):
+        """f32[nq, dim] on the device -> i8[nq, dim_pad]: ``srx_binary_asym_quantize`` against the index's centre (codes in
+        [-7, 7], zeros at and above dim); asynchronous."""
+        torch = _torch()
+        _require_f32(queries_f32, "queries")
+        if int(queries_f32.shape[1]) != self.dim:
+            raise ValueError(f"queries have {int(queries_f32.shape[1])} columns, the index {self.dim}")
+        nq = int(queries_f32.shape[0])
+        with torch.cuda.device(self.device):
+            out = torch.empty((nq, self.dim_pad), dtype=torch.int8, device=self.device)
+            if nq > 0:
+                x, ld = _f32_rows(torch, queries_f32.to(self.device), "queries")
+                _capi.check(_capi.lib().srx_binary_asym_quantize(self.device.index or 0, _ptr(x), ld, nq, self.dim, self.dim_pad, _ptr(self.center),
+                                                                 _ptr(out), _stream_ptr(torch, self.device)), "srx_binary_asym_quantize")
+        return out
+
+    def _query_codes(self, torch, queries_f32, q_codes):
+        if (queries_f32 is None) == (q_codes is None):
+            raise ValueError("give the queries either as f32 rows or as q_codes=, not both")
+        if q_codes is None:
+            return self.quantize_queries_device(queries_f32)
+        if not isinstance(q_codes, torch.Tensor) or q_codes.dtype != torch.int8 or q_codes.dim() != 2 or int(q_codes.shape[1]) != self.dim_pad \
+                or q_codes.device != self.device:
+            raise ValueError(f"q_codes must be an int8 tensor [nq, {self.dim_pad}] on {self.device}")
+        return q_codes.contiguous()
+
+    def asym_search_device(self, queries_f32, m: int, q_codes=None, filter=None, q_filter=None, route: int = 0):
+        """``srx_binary_asym_search``: (doc i32[nq, m], score i32[nq, m], count i32[nq]), asynchronous.  Row q holds the
+        ``count[q] = min(m, allowed docs)`` best allowed docs by (score descending, doc ascending), then -1 / INT32_MIN.
+        ``route``: 0 (the library chooses by nq), 1 (bit planes) or 2 (MFMA); the words do not depend on it."""
+        torch = _torch()
+        _check_k(m)
+        L = _capi.lib()
+        with torch.cuda.device(self.device):
+            qc = self._query_codes(torch, queries_f32, q_codes)
+            nq = int(qc.shape[0])
+            out = (torch.empty((nq, m), dtype=torch.int32, device=self.device), torch.empty((nq, m), dtype=torch.int32, device=self.device),
+                   torch.empty((nq,), dtype=torch.int32, device=self.device))
+            if nq == 0:
+                return out
+            ws = _grow_ws(torch, self, _capi.check(L.srx_binary_asym_workspace_bytes(nq, self.n_docs, m, self.dim_pad),
+                                                   "srx_binary_asym_workspace_bytes"))
+            fdesc, keep = resolve_filter(self, filter, q_filter, nq)  # keep: alive until the call has been issued
+            _capi.check(L.srx_binary_asym_search(self.device.index or 0, _ptr(self.bits), self.n_docs, self.dim_pad, _ptr(qc), nq, m, self.doc_base,
+                                                 fdesc, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(),
+                                                 _stream_ptr(torch, self.device), int(route)), "srx_binary_asym_search")
+            del keep
+        return out
+
+    def asym_search(self, queries, m: int, filter=None, q_filter=None, route: int = 0):
+        """Host arrays in, host arrays out; ``q_filter``: a host sequence of row numbers, validated here."""
+        q = self._queries_to_device(queries)
+        qf = host_q_filter(self, filter, q_filter, int(q.shape[0]))
+        return _to_host(_torch(), self.device, self.asym_search_device(q, m, filter=filter, q_filter=qf, route=route))
+
+    def asym_docs_device(self, queries_f32, cand_doc, cand_count=None, q_codes=None):
+        """``srx_binary_asym_score_docs``: i32[nq, m], the scores of the given GLOBAL ids; INT32_MIN for padding (-1, entries at or
+        beyond ``cand_count[q]``) and ids outside the index; duplicates are legal.  Asynchronous."""
+        torch = _torch()
+        L = _capi.lib()
+        with torch.cuda.device(self.device):
+            qc = self._query_codes(torch, queries_f32, q_codes)
+            nq = int(qc.shape[0])
+            if cand_doc.dim() != 2 or int(cand_doc.shape[0]) != nq or cand_doc.dtype != torch.int32 or int(cand_doc.shape[1]) < 1:
+                raise ValueError("asym_docs_device: cand_doc must be an int32 tensor [nq, m] with m >= 1")
+            if cand_count is not None and (cand_count.dtype != torch.int32 or cand_count.numel() != nq):
+                raise ValueError("asym_docs_device: cand_count must be an int32 tensor [nq]")
+            m = int(cand_doc.shape[1])
+            cand_doc = cand_doc.contiguous()
+            cand_count = None if cand_count is None else cand_count.contiguous()
+            out = torch.empty((nq, m), dtype=torch.int32, device=self.device)
+            if nq > 0:
+                _capi.check(L.srx_binary_asym_score_docs(self.device.index or 0, _ptr(self.bits), self.n_docs, self.dim_pad, _ptr(qc), nq,
+                                                         self.doc_base, _ptr(cand_doc), _ptr(cand_count), m, _ptr(out),
+                                                         _stream_ptr(torch, self.device)), "srx_binary_asym_score_docs")
+        return out
+
+    def asym_docs(self, queries, cand_doc, cand_count=None) -> np.ndarray:
+        """Host arrays in (the candidates validated by :func:`validate_candidates`), i32[nq, m] out."""
+        torch = _torch()
+        q = self._queries_to_device(queries)
+        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, int(q.shape[0]))
+        cd = torch.as_tensor(cand_doc, device=self.device)
+        cc = None if cand_count is None else torch.as_tensor(cand_count, device=self.device)
+        return _to_host(torch, self.device, (self.asym_docs_device(q, cd, cc),))[0]
+
+
 class ScreenedDenseIndex:
     """A dense index searched in two steps: the Hamming screen of ``binary`` picks
     ``pool = min(max(k, k * oversample), 1024, n_docs)`` docs under the caller's filter, ``exact.score_docs_device`` scores them
@@ -288,9 +389,13 @@ class ScreenedDenseIndex:
     taken with ``score_offset = max|q|_2 * max_row_norm * 1.01`` so that every allowed doc is rankable.  That offset coarsens
     the SCREEN's order to ulp(offset): docs whose PQ scores differ by less can swap places at the pool's edge.  The pool is
     rescored and cut exactly as above.  An :class:`~.ivfpq.IvfPqIndex` screens the same way over the ``default_nprobe`` lists it
-    probes: the pool holds docs of those lists only."""
+    probes: the pool holds docs of those lists only.
 
-    def __init__(self, exact, binary, oversample: int = 4):
+    ``asymmetric=True`` (a :class:`DenseBinaryIndex` screen only): the pool is the top ``pool`` of ``asym_search_device``, the
+    4-bit-query scores of include/asym/sparse_rx_binary_asym.h, instead of the Hamming search's; everything after the pool is
+    unchanged."""
+
+    def __init__(self, exact, binary, oversample: int = 4, asymmetric: bool = False):
         if not isinstance(exact, (DenseF32Index, DenseHalfIndex)):
             raise ValueError(f"the exact index of a screened search must be a DenseF32Index or a DenseHalfIndex, got {type(exact).__name__}")
         from .ivfpq import IvfPqIndex
@@ -300,7 +405,9 @@ class ScreenedDenseIndex:
         if (exact.n_docs, exact.dim, exact.doc_base) != (binary.n_docs, binary.dim, binary.doc_base) or exact.device != binary.device:
             raise ValueError(f"the screen speaks of {binary.n_docs} x {binary.dim} rows from id {binary.doc_base} on {binary.device}, the exact "
                              f"index of {exact.n_docs} x {exact.dim} from {exact.doc_base} on {exact.device}")
-        self.exact, self.binary, self.oversample = exact, binary, check_oversample(oversample)
+        if asymmetric and not isinstance(binary, DenseBinaryIndex):
+            raise ValueError(f"asymmetric=True needs a DenseBinaryIndex as the screen, got {type(binary).__name__}")
+        self.exact, self.binary, self.oversample, self.asymmetric = exact, binary, check_oversample(oversample), bool(asymmetric)
         self.n_docs, self.dim, self.doc_base, self.device = exact.n_docs, exact.dim, exact.doc_base, exact.device
 
     def pool(self, k: int) -> int:
@@ -314,7 +421,9 @@ class ScreenedDenseIndex:
         queries = queries.to(self.device)
         if int(queries.shape[0]) == 0:
             return self.exact.search_device(queries, k, score_offset, filter=filter, q_filter=q_filter)
-        if isinstance(self.binary, DenseBinaryIndex):
+        if self.asymmetric:
+            pool_doc, _, pool_count = self.binary.asym_search_device(queries, self.pool(k), filter=filter, q_filter=q_filter)
+        elif isinstance(self.binary, DenseBinaryIndex):
             pool_doc, _, pool_count = self.binary.hamming_search_device(queries, self.pool(k), filter=filter, q_filter=q_filter)
         else:  # a PQ screen: every allowed doc rankable (the one synchronisation of this door: the largest query norm)
             from .pq import OFFSET_MARGIN

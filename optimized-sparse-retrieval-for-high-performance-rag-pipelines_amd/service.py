@@ -226,7 +226,9 @@ class RetrievalService(SparseIndexViews):
         that pool -- approximate unless the pool covers the allowed docs; the scores are those of the storage.  The rows stay
         resident: the screen saves bandwidth, not memory.  Not offered with a sharded index.  "pq" (f32 / f16 / bf16 storage):
         the same two steps with a ``DensePqIndex`` (``pq_dsub``) as the screen: the pool is its top ``k * oversample`` by PQ
-        score.  Any other value raises ``ValueError``, as does ``oversample < 1``.
+        score.  "binary_asym": the codes, the pool size and every restriction of "binary", but the pool is ranked by the
+        asymmetric score of include/asym/sparse_rx_binary_asym.h (the query keeps 4 bits per dimension) instead of the Hamming
+        distance.  Any other value raises ``ValueError``, as does ``oversample < 1``.
 
         ``ann``: None (default: nothing changes) or "ivf" (no reference counterpart): the "f16" / "bf16" rows partitioned into
         ``nlist`` k-means lists (``IvfHalfIndex``, include/ivf/sparse_rx_ivf.h); :meth:`search_by_vector` and the dense side of
@@ -283,6 +285,8 @@ class RetrievalService(SparseIndexViews):
                 raise ValueError(f"ann='ivfpq' is not offered with storage={storage!r}")
             if screen == "binary":
                 raise ValueError("screen='binary' is not offered with ann='ivfpq'")
+            if screen == "binary_asym":
+                raise ValueError("screen='binary_asym' is not offered with ann='ivfpq'")
             if lowered == "pq" and screen is not None:
                 raise ValueError(f"screen={screen!r} is not offered with storage='pq'")
             if lowered in ("f32", "f16", "bf16") and screen != "pq":
@@ -332,8 +336,8 @@ class RetrievalService(SparseIndexViews):
             raise ValueError(f"storage={storage!r} is not offered with a sharded index")
         if screen is not None:
             from .binary import check_oversample
-            if screen not in ("binary", "pq"):
-                raise ValueError(f"screen must be None or 'binary' or 'pq', got {screen!r}")
+            if screen not in ("binary", "pq", "binary_asym"):
+                raise ValueError(f"screen must be None or 'binary' or 'pq' or 'binary_asym', got {screen!r}")
             oversample = check_oversample(oversample)
             if self._be.sharded():
                 raise ValueError(f"screen={screen!r} is not offered with a sharded index")
@@ -385,7 +389,7 @@ class RetrievalService(SparseIndexViews):
                 coarse = DensePqIndex(e, dsub=pq_dsub, device=self.device)
             else:
                 coarse = DenseBinaryIndex(e, center="mean", device=self.device)
-            self._dense = ScreenedDenseIndex(self._dense, coarse, oversample)
+            self._dense = ScreenedDenseIndex(self._dense, coarse, oversample, asymmetric=screen == "binary_asym")
 
     def search_by_vector(self, query_vector: np.ndarray, k: int = 10, min_score: float = 0.0, *, allowed_docs=None,
                          excluded_docs=None, must_terms=None, any_terms=None, must_not_terms=None, where=None) -> List[Dict]:
