@@ -12,7 +12,7 @@ from .distributed import (ShardedSearcher, shard_range, global_df, global_avgdl,
                           build_sharded_host_index)
 from .backend import SparseBackend, collapse_deep, collapse_pool_depth
 from .filter import DocFilter
-from .late import TokenIndex, check_late_shape, late_pool_depth
+from .late import TokenIndex, check_late_search, check_late_shape, late_pool_depth, late_search_plan
 from .fields import FieldTable, columns_from_metadata
 from .feedback import ForwardIndex
 from . import boost
@@ -40,7 +40,7 @@ __all__ = ["RetrievalService", "DeviceIndex", "HostBatchPipeline", "HostIndex", 
            "load_index_npz", "save_index_npz", "DenseF32Index", "DenseHalfIndex", "DenseInt8Index", "DenseUint8Index", "QuantizedEmbeddingIndex", "quantize_symmetric",
            "quantize_asymmetric", "quantize_query_asymmetric",
            "quantize_query_symmetric", "quantize_symmetric_device", "quantize_asymmetric_device", "quantize_queries_symmetric_device",
-           "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape",
+           "quantize_queries_asymmetric_device", "check_mmr_args", "mmr_pool_depth", "parse_operators", "TokenIndex", "check_late_shape", "check_late_search", "late_search_plan",
            "late_pool_depth", "FieldTable", "columns_from_metadata", "collapse_deep", "collapse_pool_depth", "ForwardIndex",
            "boost", "BoostFn", "BoostResolver", "boost_deep", "ltr", "ForestModel", "RankFn", "evaluate", "Judgments",
            "binary", "DenseBinaryIndex", "ScreenedDenseIndex", "mx", "DenseMxIndex", "ivf", "IvfHalfIndex", "pq", "DensePqIndex", "ivfpq", "IvfPqIndex", "graph", "GraphHalfIndex"]

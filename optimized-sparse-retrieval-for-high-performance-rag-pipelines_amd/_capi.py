@@ -4,7 +4,8 @@ include/sparse_rx_terms.h, include/sparse_rx_maxsim.h, include/sparse_rx_fields.
 include/sparse_rx_facets.h, include/ext/sparse_rx_feedback.h, include/order/sparse_rx_order.h, include/boost/sparse_rx_boost.h,
 include/ltr/sparse_rx_ltr.h, include/eval/sparse_rx_eval.h, include/binary/sparse_rx_binary.h, include/mx/sparse_rx_mx.h,
 include/ivf/sparse_rx_ivf.h, include/pq/sparse_rx_pq.h, include/ivfpq/sparse_rx_ivfpq.h, include/graph/sparse_rx_graph.h,
-include/fused/sparse_rx_half_fused.h, include/batched/sparse_rx_f32_batched.h and include/asym/sparse_rx_binary_asym.h).
+include/fused/sparse_rx_half_fused.h, include/batched/sparse_rx_f32_batched.h, include/asym/sparse_rx_binary_asym.h and
+include/late/sparse_rx_maxsim_search.h).
 
 The library is the product: there is no CPU fallback.  If it is missing or cannot be loaded every entry point
 raises ``SparseRxUnavailable`` -- loudly, never a silent eager path.
@@ -25,7 +26,7 @@ SOURCES = ["wave_kernel.hip", "tier2_kernel.hip", "merge.hip", "build.hip", "spa
            "score_docs.hip", "dense_score.hip", "dense_quant.hip", "filter.hip", "tier2_filter.hip", "dense_half.hip", "mmr.hip",
            "terms.hip", "maxsim.hip", "fields.hip", "collapse.hip", "facets.hip", "feedback.hip", "order.hip", "boost.hip", "ltr.hip",
            "eval.hip", "dense_binary.hip", "dense_mx.hip", "dense_ivf.hip", "dense_pq.hip", "dense_ivfpq.hip", "dense_graph.hip",
-           "dense_half_fused.hip", "dense_f32_batched.hip", "dense_binary_asym.hip"]  # one translation unit each, compiled in parallel
+           "dense_half_fused.hip", "dense_f32_batched.hip", "dense_binary_asym.hip", "maxsim_search.hip"]  # one translation unit each, compiled in parallel
 INCLUDED_SOURCES = {"tier2_filter.hip": ["tier2_kernel.hip"], "dense_half_fused.hip": ["dense_half.hip"]}  # a unit that compiles another source file as part of itself
 SRC_PATH = os.path.join(CSRC_DIR, "wave_kernel.hip")            # the dominant kernel's source (bench.py hashes it)
 INCLUDE_DIR = os.path.join(_ROOT, "include")
@@ -430,6 +431,13 @@ BINARY_ASYM_SYMBOLS = {
 SRX_BINARY_ASYM_ROUTE_NQ = 16                                   # route 0 takes the MFMA route from this many queries
 SRX_BINARY_ASYM_ROUTE_PLANES, SRX_BINARY_ASYM_ROUTE_MFMA = 1, 2  # the forced routes
 
+# every symbol include/late/sparse_rx_maxsim_search.h declares (the twenty-sixth header of the same library); the search takes the head
+# of the reranker's argument list up to tq, then k and the filter where that has its candidates
+MAXSIM_SEARCH_SYMBOLS = {
+    "srx_maxsim_search_workspace_bytes": (_I64, [_I32, _I32, _I32, _I64, _I32]),
+    "srx_maxsim_search_half": (ctypes.c_int, [*_MAXSIM_HEAD[:12], _I32, _FP, _VP, _VP, _VP, _VP, _I64, _VP]),
+}
+
 
 def f32_batched_sample(n_docs: int, k: int) -> int:
     """Docs of the threshold sample of ``srx_dense_search_f32_batched`` (0: none): the rule of include/batched/sparse_rx_f32_batched.h
@@ -490,6 +498,7 @@ def _deps():
                                                             os.path.join(CSRC_DIR, "field_common.h"),
                                                             os.path.join(CSRC_DIR, "half_common.h"),
                                                             os.path.join(CSRC_DIR, "mmr_common.h"),
+                                                            os.path.join(CSRC_DIR, "maxsim_common.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_rescore.h"),
                                                             os.path.join(INCLUDE_DIR, "sparse_rx_quant.h"),
@@ -515,7 +524,8 @@ def _deps():
                                                             os.path.join(INCLUDE_DIR, "graph", "sparse_rx_graph.h"),
                                                             os.path.join(INCLUDE_DIR, "fused", "sparse_rx_half_fused.h"),
                                                             os.path.join(INCLUDE_DIR, "batched", "sparse_rx_f32_batched.h"),
-                                                            os.path.join(INCLUDE_DIR, "asym", "sparse_rx_binary_asym.h")]
+                                                            os.path.join(INCLUDE_DIR, "asym", "sparse_rx_binary_asym.h"),
+                                                            os.path.join(INCLUDE_DIR, "late", "sparse_rx_maxsim_search.h")]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -567,7 +577,7 @@ def lib() -> ctypes.CDLL:
                                    **TERMS_SYMBOLS, **MAXSIM_SYMBOLS, **FIELDS_SYMBOLS, **COLLAPSE_SYMBOLS, **FACET_SYMBOLS, **FEEDBACK_SYMBOLS,
                                    **ORDER_SYMBOLS, **BOOST_SYMBOLS, **LTR_SYMBOLS, **EVAL_SYMBOLS, **BINARY_SYMBOLS, **MX_SYMBOLS, **IVF_SYMBOLS,
                                    **PQ_SYMBOLS, **IVFPQ_SYMBOLS, **GRAPH_SYMBOLS, **HALF_FUSED_SYMBOLS, **F32_BATCHED_SYMBOLS,
-                                   **BINARY_ASYM_SYMBOLS}.items():
+                                   **BINARY_ASYM_SYMBOLS, **MAXSIM_SEARCH_SYMBOLS}.items():
         try:
             f = getattr(L, name)
         except AttributeError as e:

@@ -1,6 +1,7 @@
 """Late-interaction reranking (include/sparse_rx_maxsim.h): a token-vector store resident in HBM and the MaxSim scores of
 given (query, doc) pairs over it -- ``score = sum over the live query tokens of the largest similarity to any token of the
-doc`` -- with the top-k of a candidate list by them.  No reference counterpart: it has no reranker.
+doc`` -- with the top-k of a candidate list by them, and the exhaustive search of the whole store by the same scores
+(include/late/sparse_rx_maxsim_search.h).  No reference counterpart: it has no reranker and no multi-vector index.
 
 The token rows of all docs are the rows of ONE :class:`~.dense.DenseHalfIndex` (``TokenIndex.tokens``): its
 ``score_docs_device`` of a query token against a token row IS the similarity the MaxSim kernel computes, bit for bit.
@@ -13,6 +14,7 @@ import numpy as np
 
 from . import _capi
 from .dense import HALF_TYPES, DenseHalfIndex, _require_f32, check_half_dtype
+from .filter import host_q_filter, resolve_filter
 from .index import _candidate_block, _empty_topk, _grow_ws, _ptr, _stream_ptr, _to_host, _torch, pool_depth, validate_candidates
 
 LATE_MAX_M = _capi.SRX_MAX_K  # candidates per list of the rerank form
@@ -35,6 +37,31 @@ def check_late_shape(tq: int, dim_pad: int, m: Optional[int] = None, k=None) -> 
     if not (1 <= k <= m):
         raise ValueError(f"k must be in [1, m={m}] for the rerank, got {k}")
     return k
+
+
+def check_late_search(tq: int, dim_pad: int, k) -> int:
+    """The shape rules of include/late/sparse_rx_maxsim_search.h on the host, or ``ValueError``: :func:`check_late_shape`'s limits
+    of ``tq`` and 1 <= k <= 1024 (no silent truncation).  Returns ``k`` as an int."""
+    check_late_shape(tq, dim_pad)
+    k = int(k)
+    if not (1 <= k <= LATE_MAX_M):
+        raise ValueError(f"a late-interaction search returns 1 .. {LATE_MAX_M} docs per query, got k={k} (no silent truncation)")
+    return k
+
+
+def late_search_plan(nq: int, tq: int, dim_pad: int, n_docs: int, k: int):
+    """``(queries per group, minimum workspace bytes, preferred workspace bytes)`` of ``srx_maxsim_search_half``: the formulas of
+    include/late/sparse_rx_maxsim_search.h restated (the preferred size is pinned to ``srx_maxsim_search_workspace_bytes`` by
+    tests/test_late_search_cpu.py)."""
+    nq, n_docs, k = int(nq), int(n_docs), int(k)
+    nab, ks = (tq + 31) // 32, dim_pad // 16
+    qg = next((g for g in (4, 2) if g * nab <= 4 and g * nab * ks <= 64 and g < 2 * nq), 1)
+    ld = -(-n_docs // 64) * 64
+    rows = min(nq, min(max((1 << 30) // (ld * 4) // 4 * 4, 4), 1024))
+    splits = min(-(-n_docs // 8192), max(2048 // rows, 1)) if rows else 1
+    qbytes = -(-nq * nab * 32 * dim_pad * 2 // 256) * 256
+    lists = -(-rows * splits * k * 8 // 256) * 256 if splits > 1 else 0
+    return qg, qbytes + min(nq, qg) * ld * 4 + 512, qbytes + rows * ld * 4 + lists + 512
 
 
 def late_pool_depth(top_k: int, late_pool, n_docs: int) -> int:
@@ -165,8 +192,34 @@ class TokenIndex:
                                                      _ptr(out[2]), _ptr(ws), ws.numel(), _stream_ptr(torch, self.device)), "srx_maxsim_rerank_half")
         return out
 
+    def search_device(self, q_tok, q_tok_count, k: int, filter=None, q_filter=None, workspace_bytes=None):
+        """``srx_maxsim_search_half``: the ``k <= 1024`` docs of the WHOLE store with the best MaxSim score per query -- row q is
+        what :meth:`rerank_device` returns for the list of all docs the query's filter row allows, whatever ``n_docs`` is.
+        ``q_tok`` / ``q_tok_count`` as :meth:`score_docs_device`; ``filter`` / ``q_filter`` as ``DeviceIndex.search_device`` (rows
+        over this store's docs).  ``workspace_bytes``: run with a workspace of this size instead of the preferred one (at least
+        :func:`late_search_plan`'s minimum: more passes, the same words).  Returns the device triple (doc i32[nq, k], score
+        f32[nq, k], count i32[nq]), rows padded with -1 / 0; asynchronous on the current stream."""
+        torch = _torch()
+        L = _capi.lib()
+        nq, tq = self._check_queries(torch, q_tok, q_tok_count)
+        k = check_late_search(tq, self.dim_pad, k)
+        fdesc, keep = resolve_filter(self, filter, q_filter, nq)  # keep: alive until the call below has been issued
+        with torch.cuda.device(self.device):
+            q, qc = self._padded(torch, q_tok, q_tok_count)
+            out = _empty_topk(torch, nq, k, self.device)
+            if nq > 0:
+                need = _capi.check(L.srx_maxsim_search_workspace_bytes(nq, tq, self.dim_pad, self.n_docs, k), "srx_maxsim_search_workspace_bytes")
+                if workspace_bytes is None:
+                    ws = _grow_ws(torch, self, need)
+                else:
+                    ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
+                _capi.check(L.srx_maxsim_search_half(*self._head(q, qc, nq, tq, None, None, 0)[:12], k, fdesc, _ptr(out[0]), _ptr(out[1]),
+                                                     _ptr(out[2]), _ptr(ws), ws.numel(), _stream_ptr(torch, self.device)), "srx_maxsim_search_half")
+        del keep
+        return out
+
     # -- host arrays in, host arrays out ----------------------------------------------------------------------------------
-    def _host_inputs(self, q_tok, q_tok_count, cand_doc, cand_count):
+    def _host_queries(self, q_tok, q_tok_count):
         torch = _torch()
         q = np.ascontiguousarray(q_tok, dtype=np.float32)
         if q.ndim != 3:
@@ -178,9 +231,14 @@ class TokenIndex:
             if qc.ndim != 1 or qc.dtype.kind not in "iu" or len(qc) != nq:
                 raise ValueError(f"q_tok_count must be a 1-D integer array of length {nq}")
             qc = torch.as_tensor(np.ascontiguousarray(qc, dtype=np.int32), device=self.device)
-        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, nq)
+        return torch.as_tensor(q, device=self.device), qc
+
+    def _host_inputs(self, q_tok, q_tok_count, cand_doc, cand_count):
+        torch = _torch()
+        q, qc = self._host_queries(q_tok, q_tok_count)
+        cand_doc, cand_count = validate_candidates(cand_doc, cand_count, int(q.shape[0]))
         cc = None if cand_count is None else torch.as_tensor(cand_count, device=self.device)
-        return torch.as_tensor(q, device=self.device), qc, torch.as_tensor(cand_doc, device=self.device), cc
+        return q, qc, torch.as_tensor(cand_doc, device=self.device), cc
 
     def score_docs(self, q_tok, q_tok_count, cand_doc, cand_count=None) -> np.ndarray:
         """:meth:`score_docs_device` on host arrays: one synchronisation, one copy.  Returns f32[nq, m]."""
@@ -189,6 +247,14 @@ class TokenIndex:
     def rerank(self, q_tok, q_tok_count, cand_doc, cand_count, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """:meth:`rerank_device` on host arrays: one synchronisation, one copy.  Returns host (doc, score, count)."""
         return _to_host(_torch(), self.device, self.rerank_device(*self._host_inputs(q_tok, q_tok_count, cand_doc, cand_count), k))
+
+
+    def search(self, q_tok, q_tok_count, k: int, filter=None, q_filter=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search_device` on host arrays (``q_filter``: a host sequence of row numbers, validated here): one synchronisation,
+        one copy.  Returns host (doc, score, count)."""
+        q, qc = self._host_queries(q_tok, q_tok_count)
+        qf = host_q_filter(self, filter, q_filter, int(q.shape[0]))
+        return _to_host(_torch(), self.device, self.search_device(q, qc, k, filter=filter, q_filter=qf))
 
 
 def stack_query_tokens(query_tokens, qids, dim: int) -> Tuple[np.ndarray, np.ndarray]:

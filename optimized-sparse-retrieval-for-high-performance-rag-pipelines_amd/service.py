@@ -454,8 +454,10 @@ class RetrievalService(SparseIndexViews):
         return results
 
     def _dense_filter(self, queries, allowed_docs, excluded_docs, must_terms=None, any_terms=None, must_not_terms=None, where=None,
-                      call: str = "search_hybrid"):
-        """The filter keywords as (DocFilter over the embedding rows, spec), or None when none constrains a query"""
+                      call: str = "search_hybrid", index=None):
+        """The filter keywords as (DocFilter over the embedding rows -- or the docs of ``index``, the token store --, spec), or None
+        when none constrains a query"""
+        index = self._dense if index is None else index
         terms = not (must_terms is None and any_terms is None and must_not_terms is None)
         if allowed_docs is None and excluded_docs is None and not terms and where is None:
             return None
@@ -467,10 +469,10 @@ class RetrievalService(SparseIndexViews):
             raise ValueError("must_terms / any_terms / must_not_terms need the BM25 index (its posting lists): call build_bm25_index() first")
         else:  # embeddings without a BM25 index: docs are named by their row number
             from .backend import RowOfIds, doc_filter_spec
-            spec = doc_filter_spec(RowOfIds.numbered(self._dense.n_docs).row_of, queries, allowed_docs, excluded_docs)
+            spec = doc_filter_spec(RowOfIds.numbered(index.n_docs).row_of, queries, allowed_docs, excluded_docs)
         if spec is None:
             return None
-        return spec.on_device(self._dense).for_index(self._dense), spec
+        return spec.on_device(index).for_index(index), spec
 
     def _need_mmr_rows(self, call: str) -> None:
         if not hasattr(self._dense, "mmr_device"):
@@ -818,6 +820,38 @@ class RetrievalService(SparseIndexViews):
             return out
         doc, score, count = tokens.rerank(q_tok, q_cnt, cand_doc, cand_count, min(int(top_k), m))
         for i, (qid, _, _) in enumerate(live):
+            out[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
+        return out
+
+    def search_late(self, query_tokens, top_k: int = 10, *, allowed_docs=None, excluded_docs=None, must_terms=None, any_terms=None,
+                    must_not_terms=None, where=None) -> Dict[str, Dict[str, float]]:
+        """Late-interaction SEARCH (no reference counterpart): the ``top_k`` docs of the whole token index of
+        :meth:`set_token_embeddings` with the best MaxSim score for every query of ``query_tokens`` = ``{qid: f32[t_q, dim]}``
+        (what :meth:`rerank_late` takes), on the GPU (``srx_maxsim_search_half``, include/late/sparse_rx_maxsim_search.h): what
+        :meth:`rerank_late` returns given ALL docs, without the 1 024-doc limit of its lists.  All queries run as one batch.
+
+        ``allowed_docs`` / ``excluded_docs`` / ``must_terms`` / ``any_terms`` / ``must_not_terms`` / ``where`` as in
+        :meth:`search_bm25`: the search ranks the allowed docs alone.
+
+        Returns ``{qid: {doc_id: maxsim_score}}`` by (score descending, row of the doc ascending); scores may be negative or 0 (a
+        doc without tokens scores 0).  ``{}`` stays ``{}``, ``top_k <= 0`` gives ``{}`` per query.  ``ValueError``: no token
+        index, a sharded index, more than 128 query tokens, a wrong shape, ``top_k`` above 1024 (no silent truncation)."""
+        from .late import LATE_MAX_M, stack_query_tokens
+        if self._be.sharded():
+            raise ValueError("late interaction needs the whole index on one GPU (the token store is not sharded)")
+        tokens = self._ensure_late()
+        if int(top_k) > LATE_MAX_M:
+            raise ValueError(f"search_late returns at most {LATE_MAX_M} docs per query, got top_k={top_k} (no silent truncation)")
+        qids = list(query_tokens)
+        q_tok, q_cnt = stack_query_tokens(query_tokens, qids, tokens.dim)
+        out = {qid: {} for qid in qids}
+        if not qids or int(top_k) <= 0:
+            return out
+        fs = self._dense_filter({qid: None for qid in qids}, allowed_docs, excluded_docs, must_terms, any_terms, must_not_terms, where,
+                                "search_late", index=tokens)
+        flt = {} if fs is None else {"filter": fs[0], "q_filter": np.asarray([fs[1].row_of_qid[qid] for qid in qids], dtype=np.int32)}
+        doc, score, count = tokens.search(q_tok, q_cnt, int(top_k), **flt)
+        for i, qid in enumerate(qids):
             out[qid] = rows_to_dict(self.host.doc_ids, doc, score, count, i)
         return out
 
